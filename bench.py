@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the EDVR hot path on MI355X (contract: see the task statement / DESIGN.md §5).
 
-  python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N>1: launched by torch.distributed.run)
 
 `value` -- one step = one pass of the hot path over one synthetic clip per GPU: EDVR-M x4 forward,
 1x5x3x180x320 -> 3x720x1280, fp32 (BASELINE.json configs[1], the configuration the metric is quoted on).
 Clips are independent work items, so ranks shard clips with no data-path collective:
-"scaling": "weak".  Rank 0 prints ONE JSON line.  Beside the headline the line carries:
+"scaling": "weak".  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the last step's
+outputs with --dump-outputs and prints the headline line (metric, value, unit, ms_per_step = one timed step, ...).
+With --full the line also carries:
+  value_one_clip_in_flight  the same clips one at a time on one stream
   roofline           dominant kernel of the headline forward, hipEvents around every launch
   inner_step         (ii) one inner MAML step at LR 176x320 (MFDN fwd+bwd, EDVR fwd+bwd on the SLR clip, losses,
                      Adam) over >= 50 steps, with its own roofline object and the launches per step
@@ -15,6 +18,7 @@ Clips are independent work items, so ranks shard clips with no 
                      the meta-gradient is all-reduced over RCCL (the one real exchange step of the method)
   edvr_l_bf16        configs[4]: EDVR-L x4 1x7x3x64x64 on the three MFMA modes
   cpu_baseline       the CPU oracle on this box's host cores (a reported baseline, not the target)
+(the --no-* switches drop single legs of a --full run).
 """
 import argparse
 import hashlib
@@ -37,6 +41,7 @@ dynavsr_amd.configure_runtime()   # six hardware queues unless the user chose (D
 FP32_MFMA_PEAK_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md, "Peak FP32 (matrix)"
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # same guide, dense bf16
 HBM_PEAK_GBS = 8000.0           # same guide, HBM3E peak
+DUMP_BUDGET_BYTES = 64 << 20    # --dump-outputs: all arrays of all ranks together
 
 # Algorithmic work (probe-derived; scales linearly in H*W)
 F_EDVR_M_180 = 973.6e9          # EDVR-M x4 forward, 1x5x3x180x320
@@ -636,6 +641,20 @@ def split_mode_rate(cfg, h, w, x, y_fp32, steps, warmup):
             "note": "opt-in (bf16_mfma = 2), held to the fp32 parity bars by tests/test_gpu_edvr.py"}
 
 
+def dump_outputs(d, arrays, n_arrays):
+    """--dump-outputs: every (name, tensor) as d/<name>.npy in float32.  The `n_arrays` arrays of all ranks share
+    DUMP_BUDGET_BYTES; an array over its share is written as a fixed sample of its flattened elements (the same seeded,
+    sorted index set for every array of that size), so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // max(1, n_arrays)
+    for name, t in arrays:
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def _merge_rank_leg(per_rank, value_key="value"):
     """A leg every rank ran on its own frames (independent work, no collective): rank 0's full object, with `value` = the SUM
     over the ranks and the per-rank figures beside it (the driver derives scaling efficiency from its own N = 1 run)."""
@@ -679,7 +698,8 @@ def _dry_run(rank, world, args):
     where the GPU run creates the RCCL one (here gloo as well) for the flat meta-gradient all-reduce
     (dist.allreduce_meta_gradients on a tensor list of the real size: 15.0 MB for EDVR-M + MFDN) and the round-robin frame
     shards with their metric reduction (dist.shard_indices / reduce_metric_vectors).  Rank 0 returns a JSON line with the key
-    set of the GPU line at the same world size (tests/test_host_logic.py compares it with a recorded GPU line)."""
+    set of the GPU line at the same world size (tests/test_host_logic.py compares the --full form with a recorded GPU line);
+    without --full only the timed skeleton runs, as in a plain GPU run."""
     import torch.distributed as tdist
     from dynavsr_amd import dist as D
     dist, coll = None, None
@@ -706,6 +726,16 @@ def _dry_run(rank, world, args):
     if grouped:
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
     elapsed = float(t)
+    base = {"metric": "dry run: launcher and process-group plumbing only (gloo, CPU, no kernels)", "value": None,
+            "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / max(args.steps, 1), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "dry_run": True,
+            "config": {"workload": "none (dry run)", "clips_per_step": world}, "protocol": None}
+    if not args.full:
+        if grouped:
+            tdist.barrier()
+            tdist.destroy_process_group()
+        return base if rank == 0 else None
     # the legs every rank runs on its own frames: stand-ins with the rank in their value (sum = world (world + 1) / 2)
     mine = ({"value": float(rank + 1), "unit": "clips/s", "ms_per_step": None},
             {"value": float(rank + 1), "unit": "frames/s", "ms_per_frame": None})
@@ -729,21 +759,17 @@ def _dry_run(rank, world, args):
         tdist.destroy_process_group()
     if rank != 0:
         return None
-    line = {"metric": "dry run: launcher and process-group plumbing only (gloo, CPU, no kernels)", "value": None,
-            "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / max(args.steps, 1), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "dry_run": True,
-            "config": {"workload": "none (dry run)", "clips_per_step": world},
-            "protocol": None, "value_one_clip_in_flight": None, "runtime": None,
-            "one_clip_in_flight": None, "roofline": None, "kernel_breakdown_ms_per_step": None, "end_to_end_tflops": None,
-            "inner_step": _merge_rank_leg([b_[0] for b_ in both]),
-            "per_frame_pipeline": _merge_rank_leg([b_[1] for b_ in both]),
-            "inner_step_clips_per_s": _merge_rank_leg([b_[0] for b_ in both]).get("value"),
-            "per_frame_pipeline_frames_per_s": _merge_rank_leg([b_[1] for b_ in both]).get("value"),
-            "meta_step": {"ranks": world, "allreduce": {"backend": "gloo", "bytes": nbytes, "executed": grouped,
-                                                         "averaged_correctly": ok}},
-            "validation": {"frames": frames, "sharding": "range(rank, frames, world)",
-                           "psnr_vector_complete": bool((vec == torch.arange(frames, dtype=torch.float64) + 30.0).all())}}
+    line = dict(base)
+    line.update({"value_one_clip_in_flight": None, "runtime": None,
+                 "one_clip_in_flight": None, "roofline": None, "kernel_breakdown_ms_per_step": None, "end_to_end_tflops": None,
+                 "inner_step": _merge_rank_leg([b_[0] for b_ in both]),
+                 "per_frame_pipeline": _merge_rank_leg([b_[1] for b_ in both]),
+                 "inner_step_clips_per_s": _merge_rank_leg([b_[0] for b_ in both]).get("value"),
+                 "per_frame_pipeline_frames_per_s": _merge_rank_leg([b_[1] for b_ in both]).get("value"),
+                 "meta_step": {"ranks": world, "allreduce": {"backend": "gloo", "bytes": nbytes, "executed": grouped,
+                                                              "averaged_correctly": ok}},
+                 "validation": {"frames": frames, "sharding": "range(rank, frames, world)",
+                                "psnr_vector_complete": bool((vec == torch.arange(frames, dtype=torch.float64) + 30.0).all())}})
     if world == 1:   # legs of the one-GPU line only
         line.update({"experimental_bf16_split": None, "edvr_l_bf16": None, "other_backbones": None, "cpu_baseline": None})
     return line
@@ -774,11 +800,15 @@ def main():
     ap.add_argument("--width", type=int, default=320)
     ap.add_argument("--clips-in-flight", type=int, default=2,
                     help="clips of the forward leg on the GPU at a time, one HIP stream each (1: one clip per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-inner-step", action="store_true", help="skip the inner-step and per-frame-pipeline legs")
-    ap.add_argument("--no-split", action="store_true", help="skip the bf16 legs (split-mode forward, EDVR-L)")
-    ap.add_argument("--no-meta", action="store_true", help="skip the meta-training iteration with the RCCL all-reduce")
-    ap.add_argument("--no-validation", action="store_true", help="skip the sharded validation leg (frames over ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the one-clip-in-flight protocol, the roofline pass and every other leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the SR frames of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle leg")
+    ap.add_argument("--no-inner-step", action="store_true", help="with --full: skip the inner-step and per-frame-pipeline legs")
+    ap.add_argument("--no-split", action="store_true", help="with --full: skip the bf16 legs (split-mode forward, EDVR-L)")
+    ap.add_argument("--no-meta", action="store_true", help="with --full: skip the meta-training iteration with the RCCL all-reduce")
+    ap.add_argument("--no-validation", action="store_true", help="with --full: skip the sharded validation leg (frames over ranks)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group plumbing only, on the CPU over gloo (no kernels): what tests/ run here")
     args = ap.parse_args()
@@ -843,29 +873,37 @@ def main():
     opt_fwd = _opt()
 
     def run_clips(n, in_flight):
-        y_ = None
-        for y_ in super_resolve_video(opt_fwd, net, repeat(x, n), in_flight=in_flight):
-            pass
-        return y_
+        """The SR frames of the last `in_flight` clips (the last step)."""
+        last = []
+        for i, y_ in enumerate(super_resolve_video(opt_fwd, net, repeat(x, n), in_flight=in_flight)):
+            if i >= n - in_flight:
+                last.append(y_)
+        return last
 
     run_clips(S * args.warmup, S)
     barrier()
     t0 = time.perf_counter()
-    y = run_clips(S * args.steps, S)
+    ys = run_clips(S * args.steps, S)
     barrier()
     elapsed = time.perf_counter() - t0
-    # ... and the same clips one at a time on one stream (the figure of rounds 1-3), rank-local
-    run_clips(max(3, args.warmup // 2), 1)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    run_clips(args.steps, 1)
-    torch.cuda.synchronize()
-    ms_one = 1e3 * (time.perf_counter() - t1) / args.steps
+    y = ys[-1]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [(("sr_rank%d_clip%d" % (rank, j)) if world > 1 else ("sr_clip%d" % j), y_)
+                                         for j, y_ in enumerate(ys)], world * len(ys))
+    ms_one = None
+    if args.full:
+        # ... and the same clips one at a time on one stream (the figure of rounds 1-3), rank-local
+        run_clips(max(3, args.warmup // 2), 1)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        run_clips(args.steps, 1)
+        torch.cuda.synchronize()
+        ms_one = 1e3 * (time.perf_counter() - t1) / args.steps
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
-    assert torch.isfinite(y).all()
+    assert all(bool(torch.isfinite(y_).all()) for y_ in ys)
 
     line = None
     if rank == 0:
@@ -877,20 +915,20 @@ def main():
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             # (`value` counts S clips in flight per GPU since round 4; rounds 1-3 measured one at a time: compare like with like)
-            "protocol": "%d clip(s) in flight per GPU, one HIP stream each; value_one_clip_in_flight = the one-at-a-time "
-                        "protocol of rounds 1-3" % S,
-            "value_one_clip_in_flight": 1e3 / ms_one,
+            "protocol": "%d clip(s) in flight per GPU, one HIP stream each" % S,
             "config": {"workload": "EDVR-M x4 forward (PCD deformable alignment + TSA fusion + "
                                    "reconstruction), clips of 1x5x3x%dx%d -> 3x%dx%d (BASELINE.json configs[1]); one step = "
                                    "%d clip(s) per GPU, one per HIP stream (adapt.super_resolve_video)"
                                    % (h, w, 4 * h, 4 * w, S),
                        "clips_per_step": world * S, "clips_in_flight_per_gpu": S,
-                       "value_one_clip_in_flight": 1e3 / ms_one,
                        "sharding": "independent clips per rank, no collective"},
-            "one_clip_in_flight": {"value": 1e3 / ms_one, "unit": "frames/s", "ms_per_clip": ms_one,
-                                   "note": "the same clips one at a time on one stream (rank 0): the protocol of rounds 1-3 "
-                                           "and the latency of one forward"},
         }
+    if rank == 0 and args.full:
+        line["protocol"] += "; value_one_clip_in_flight = the one-at-a-time protocol of rounds 1-3"
+        line["value_one_clip_in_flight"] = line["config"]["value_one_clip_in_flight"] = 1e3 / ms_one
+        line["one_clip_in_flight"] = {"value": 1e3 / ms_one, "unit": "frames/s", "ms_per_clip": ms_one,
+                                      "note": "the same clips one at a time on one stream (rank 0): the protocol of rounds 1-3 "
+                                              "and the latency of one forward"}
         # ---- roofline of the dominant kernel: separate pass, hipEvents around every launch
         plan = engine.get_plan(net._cfg(), 1, h, w)
         params = [p.detach().contiguous() for p in net.ordered_parameters()]
@@ -1009,7 +1047,7 @@ def main():
                 line["other_backbones"] = {"error": "%s: %s" % (type(e).__name__, e)}
     # The legs the metric is named after run on EVERY rank, each on its own frames (independent work items, no collective:
     # north_star asks for the inner step at 1/2/4/8 GPUs): rank 0 reports the sum and the per-rank figures.
-    if not args.no_inner_step:
+    if args.full and not args.no_inner_step:
         barrier()
         mine = (inner_step_rate(dev), per_frame_pipeline_rate(dev))
         barrier()
@@ -1025,14 +1063,14 @@ def main():
             line["config"]["inner_step_clips_per_s"] = line["inner_step_clips_per_s"]
             line["config"]["per_frame_pipeline_frames_per_s"] = line["per_frame_pipeline_frames_per_s"]
             line["config"]["three_inner_steps_ms_per_frame"] = (line["inner_step"].get("three_inner_steps") or {}).get("ms_per_frame")
-    if rank == 0:
+    if rank == 0 and args.full:
         # what the process got from the runtime: the hardware-queue setting and the MEASURED overlap of the weight-gradient
         # side stream with the launch stream (dvsr_side_stream_overlaps), before any RCCL communicator exists
         line["runtime"] = dict(_rt_report(dev), probed="before the RCCL group")
     # The RCCL communicator is created only now: once it exists, its helper threads slow host-bound launch sequences down
     # (EDVR-L bf16 forward+backward, ~700 launches in 10.5 ms, measured 14.1 ms when the meta leg ran first; the inner-step
     # per-frame loop 8.2 -> 10.0 ms; the GPU-bound legs do not move).
-    if not (args.no_meta and args.no_validation):
+    if args.full and not (args.no_meta and args.no_validation):
         try:
             if dist is not None:
                 rccl = tdist.new_group(backend="nccl")
@@ -1047,7 +1085,7 @@ def main():
     if rank == 0 and line is not None and rccl is not None:
         line["runtime"]["side_stream_overlaps_with_rccl_group"] = _rt_report(dev)["side_stream_overlaps_fresh_stream"]
     meta = None
-    if not args.no_meta:   # every rank takes part (the collective)
+    if args.full and not args.no_meta:   # every rank takes part (the collective)
         try:
             meta = meta_step_rate(dev, world, tdist if rccl is not None else None, rccl, cpu_group=dist is not None)
         except Exception as e:
@@ -1057,7 +1095,7 @@ def main():
         if dist_err:
             meta["process_group_error"] = dist_err
     val = None
-    if not args.no_validation:   # every rank takes part (its shard of the frames, the metric reduction)
+    if args.full and not args.no_validation:   # every rank takes part (its shard of the frames, the metric reduction)
         try:
             val = validation_rate(dev, world, tdist if (world > 1 and rccl is not None) else None, rccl)
         except Exception as e:
@@ -1070,7 +1108,7 @@ def main():
             line["meta_step"] = meta
         if val is not None:
             line["validation"] = val
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, h, w, 0, y)   # same clip (seed 1 + rank 0), same weights
     if tdist.is_initialized():
         tdist.barrier(group=None if dist is not None else rccl)

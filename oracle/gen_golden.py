@@ -604,11 +604,99 @@ def degradation_cases():
     save("degradation", **out)
 
 
+# AST walk of the two reference drivers under INTEGRATION.md's Level-1 PYTHONPATH (<repo>/dynavsr_amd:<repo>:<codes>):
+# every project-local import with the file it resolves to, every util.X / option.X and every attribute used on the model
+# wrappers.  Only names and line numbers leave this walk (tests/golden/dropin_drivers.json); tests/test_dropin.py resolves
+# them against this build.
+_DRIVER_WALK = r"""
+import ast, importlib, importlib.machinery, importlib.util, json, sys
+codes, drivers = sys.argv[1], sys.argv[2:]
+LOCAL = {"data", "utils", "options", "models"}
+ALIAS = ("util", "option")
+WRAPPERS = ("model", "modelcp", "est_model", "est_modelcp", "est_model_fixed")
+out = {}
+for path in drivers:
+    tree = ast.parse(open(path).read(), path)
+    imports, attrs, methods = {}, {}, {}
+    for node in ast.walk(tree):
+        mods = []
+        if isinstance(node, ast.Import):
+            mods = [a.name for a in node.names]
+        elif isinstance(node, ast.ImportFrom) and node.level == 0:
+            mods = [node.module]
+            for a in node.names:    # `from data.meta_learner import loader` may name a submodule
+                if node.module.split(".")[0] in LOCAL and importlib.util.find_spec(node.module) and \
+                        getattr(importlib.util.find_spec(node.module), "submodule_search_locations", None) and \
+                        importlib.machinery.PathFinder.find_spec(
+                            node.module + "." + a.name, importlib.util.find_spec(node.module).submodule_search_locations):
+                    mods.append(node.module + "." + a.name)
+        for m in mods:
+            if m.split(".")[0] not in LOCAL:
+                continue
+            spec = importlib.util.find_spec(m)
+            origin = spec.origin if spec is not None else None
+            if origin and origin.startswith(codes):
+                imports[m] = {"provider": "codes", "file": origin[len(codes):].lstrip("/")}
+            else:
+                imports[m] = {"provider": "repo" if origin else None, "file": None}
+        if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name):
+            if node.value.id in ALIAS:
+                attrs.setdefault((node.value.id, node.attr), node.lineno)
+            elif node.value.id in WRAPPERS:
+                methods.setdefault((node.value.id, node.attr), node.lineno)
+    out[path[len(codes):].lstrip("/")] = {
+        "imports": imports,
+        "attrs": sorted([a, b, n] for (a, b), n in attrs.items()),
+        "methods": sorted([a, b, n] for (a, b), n in methods.items())}
+print(json.dumps(out))
+"""
+
+
+def dropin_cases():
+    """What tests/test_dropin.py checks this build against, recorded from the reference as names only: (1) the uses of the
+    two drivers (see _DRIVER_WALK), (2) the state-dict keys and shapes of the reference's three video backbones at every
+    configuration networks.define_G builds (TOFlow, DUF 16L / 28L / 52L x2 / x3 / x4, EDVR-M x2 / x4)."""
+    import json
+    import subprocess
+    import tempfile
+    env = dict(os.environ)
+    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "dynavsr_amd"), ROOT, REF])
+    env["PYTHONDONTWRITEBYTECODE"] = "1"
+    drivers = [os.path.join(REF, "test_dynavsr.py"), os.path.join(REF, "train_dynavsr.py")]
+    with tempfile.TemporaryDirectory() as tmp:
+        r = subprocess.run([sys.executable, "-c", _DRIVER_WALK, REF] + drivers, env=env, cwd=tmp,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, check=True)
+    uses = json.loads(r.stdout.strip().splitlines()[-1])
+    path = os.path.join(OUT, "dropin_drivers.json")
+    with open(path, "w") as f:
+        json.dump({"source": "the reference's codes/test_dynavsr.py and codes/train_dynavsr.py, walked by "
+                             "oracle/gen_golden.py:_DRIVER_WALK under the Level-1 PYTHONPATH", "drivers": uses},
+                  f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote %-28s %7.1f KB" % ("dropin_drivers.json", os.path.getsize(path) / 1024))
+    import models.archs.DUF_arch as RD
+    import models.archs.EDVR_arch as RE
+    import models.archs.TOF_arch as RT
+    nets = [("TOF", RT.TOFlow(adapt_official=True))]
+    for n in ("DUF_16L", "DUF_28L", "DUF_52L"):
+        for s in (2, 3, 4):
+            nets.append(("%sx%d" % (n, s), getattr(RD, n)(scale=s, adapt_official=True)))
+    for s in (2, 4):
+        nets.append(("EDVR-Mx%d" % s, RE.EDVR(nf=64, nframes=5, groups=8, front_RBs=5, back_RBs=10, scale=s)))
+    sds = {name: [[k, list(v.shape)] for k, v in net.state_dict().items()] for name, net in nets}
+    path = os.path.join(OUT, "backbone_state_dicts.json")
+    with open(path, "w") as f:
+        json.dump({"source": "state_dict() of the reference's TOF_arch / DUF_arch / EDVR_arch modules, in order",
+                   "networks": sds}, f, separators=(",", ":"))
+        f.write("\n")
+    print("wrote %-28s %7.1f KB" % ("backbone_state_dicts.json", os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     os.makedirs(OUT, exist_ok=True)
     E, L, models, U = import_reference()
-    which = sys.argv[1:] or ["dcn", "pcd", "edvr", "mfdn", "estimators", "inner", "degradation", "meta", "tof", "duf", "crop"]
+    which = sys.argv[1:] or ["dcn", "pcd", "edvr", "mfdn", "estimators", "inner", "degradation", "meta", "tof", "duf", "crop", "dropin"]
     if "dcn" in which: dcn_cases()
     if "pcd" in which: pcd_tsa(E)
     if "edvr" in which: edvr_full(E)
@@ -622,3 +710,4 @@ if __name__ == "__main__":
     if "inner" in which: inner_step(models, U)
     if "degradation" in which: degradation_cases()
     if "meta" in which: meta_step(models)
+    if "dropin" in which: dropin_cases()

@@ -1,12 +1,12 @@
-"""CPU: the Level-1 drop-in recipe of INTEGRATION.md, checked against the reference drivers themselves.
+"""CPU: the Level-1 drop-in recipe of INTEGRATION.md, checked against what the reference drivers use.
 
 With INTEGRATION's exact PYTHONPATH (dynavsr_amd first, then the repo, then codes/) a fresh interpreter
-AST-walks codes/test_dynavsr.py and codes/train_dynavsr.py and resolves
+resolves what codes/test_dynavsr.py and codes/train_dynavsr.py use:
   * every project-local import (``data.*``, ``utils.*``, ``options.*``, ``models.*``) to a module file,
   * every ``util.X`` / ``option.X`` attribute the drivers touch, on THIS build's modules,
   * every method the drivers call on the model wrappers, on this build's wrapper classes.
-Nothing of the reference is copied or shipped: the drivers are only parsed, and the whole file is skipped where
-/root/reference does not exist (the GPU box).  The host helpers of utils/util.py are also checked here
+Nothing of the reference is copied or shipped: the drivers were parsed once by oracle/gen_golden.py, which recorded
+the names they use (tests/golden/dropin_drivers.json).  The host helpers of utils/util.py are also checked here
 against the oracle's independent restatements (tests may import oracle/)."""
 import json
 import os
@@ -17,23 +17,21 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
-REF = "/root/reference/codes"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree only exists in the build container")
-
-_WALKER = r"""
-import ast, importlib, importlib.machinery, importlib.util, json, sys
-drivers, report = sys.argv[1:], {"imports": {}, "missing_modules": [], "missing_attrs": [], "missing_methods": []}
-LOCAL = {"data", "utils", "options", "models"}
-OURS = ("/dynavsr_amd/",)
+# What the reference's two drivers use, recorded as names and line numbers by oracle/gen_golden.py (dropin): every
+# project-local import with the provider the Level-1 recipe resolved it to ("codes": the reference's own file, relative to
+# codes/; "repo": this build), every util.X / option.X, every attribute used on the model wrappers.
+_RESOLVER = r"""
+import ast, importlib.util, inspect, json, sys
+uses = json.load(open(sys.argv[1]))["drivers"]
+report = {"imports": {}, "missing_modules": [], "missing_attrs": [], "missing_methods": []}
 import options.options as option
 from utils import util
 import models
 from models.Video_base_model import VideoBaseModel
 from models.LRestimator_model import LRimgestimator_Model
 alias = {"util": util, "option": option}
-import inspect
 def provides(cls, name):     # a method, or an attribute some method of the class (or a base) assigns on self
     if callable(getattr(cls, name, None)):
         return True
@@ -45,61 +43,64 @@ def provides(cls, name):     # a method, or an attribute some method of the clas
     return False
 wrappers = {"model": VideoBaseModel, "modelcp": VideoBaseModel, "est_model": LRimgestimator_Model,
             "est_modelcp": LRimgestimator_Model, "est_model_fixed": LRimgestimator_Model}
-for path in drivers:
-    tree = ast.parse(open(path).read(), path)
-    for node in ast.walk(tree):
-        mods = []
-        if isinstance(node, ast.Import):
-            mods = [a.name for a in node.names]
-        elif isinstance(node, ast.ImportFrom) and node.level == 0:
-            mods = [node.module]
-            for a in node.names:    # `from data.meta_learner import loader` may name a submodule
-                if node.module.split(".")[0] in LOCAL and importlib.util.find_spec(node.module) and \
-                        getattr(importlib.util.find_spec(node.module), "submodule_search_locations", None) and \
-                        importlib.machinery.PathFinder.find_spec(
-                            node.module + "." + a.name, importlib.util.find_spec(node.module).submodule_search_locations):
-                    mods.append(node.module + "." + a.name)
-        for m in mods:
-            if m.split(".")[0] not in LOCAL:
-                continue
-            try:
-                spec = importlib.util.find_spec(m)
-            except Exception as e:
-                spec = None
-            if spec is None or not spec.origin:
-                report["missing_modules"].append([path, m])
-            else:
-                report["imports"][m] = spec.origin
-        if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in alias:
-            if not hasattr(alias[node.value.id], node.attr):
-                report["missing_attrs"].append([path, node.value.id + "." + node.attr, node.lineno])
-        if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in wrappers:
-            if not provides(wrappers[node.value.id], node.attr):     # methods called and attributes read / written
-                report["missing_methods"].append([path, node.value.id + "." + node.attr, node.lineno])
+for path, u in sorted(uses.items()):
+    for m in sorted(u["imports"]):
+        try:
+            spec = importlib.util.find_spec(m)
+        except Exception as e:
+            spec = None
+        if spec is None or not spec.origin:
+            report["missing_modules"].append([path, m])
+        else:
+            report["imports"][m] = spec.origin
+    for name, attr, line in u["attrs"]:
+        if not hasattr(alias[name], attr):
+            report["missing_attrs"].append([path, name + "." + attr, line])
+    for name, attr, line in u["methods"]:
+        if not provides(wrappers[name], attr):     # methods called and attributes read / written
+            report["missing_methods"].append([path, name + "." + attr, line])
 report["util_file"], report["option_file"], report["models_file"] = util.__file__, option.__file__, models.__file__
 print(json.dumps(report))
 """
 
 
-@needs_ref
 def test_level1_recipe_resolves_everything_the_drivers_use(tmp_path):
+    rec_path = os.path.join(GOLDEN, "dropin_drivers.json")
+    with open(rec_path) as f:
+        uses = json.load(f)["drivers"]
+    assert sorted(uses) == ["test_dynavsr.py", "train_dynavsr.py"]
+    # a stand-in codes/ tree holding (empty) the reference files the recipe resolved the dataset imports to
+    codes = tmp_path / "codes"
+    theirs = {}
+    for u in uses.values():
+        for m, where in u["imports"].items():
+            if where["provider"] == "codes":
+                f = codes / where["file"]
+                f.parent.mkdir(parents=True, exist_ok=True)
+                f.write_text("")
+                theirs[m] = str(f)
+    assert {"data.data_sampler", "data.meta_learner"} <= set(theirs)
     env = dict(os.environ)
     # INTEGRATION.md, Level 1: PYTHONPATH=<repo>/dynavsr_amd:<repo>:<codes>
-    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "dynavsr_amd"), ROOT, REF])
-    env["PYTHONDONTWRITEBYTECODE"] = "1"                 # the reference tree is read-only by contract
-    drivers = [os.path.join(REF, "test_dynavsr.py"), os.path.join(REF, "train_dynavsr.py")]
-    r = subprocess.run([sys.executable, "-c", _WALKER] + drivers, env=env, cwd=str(tmp_path),
+    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "dynavsr_amd"), ROOT, str(codes)])
+    env["PYTHONDONTWRITEBYTECODE"] = "1"
+    r = subprocess.run([sys.executable, "-c", _RESOLVER, rec_path], env=env, cwd=str(tmp_path),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     rep = json.loads(r.stdout.strip().splitlines()[-1])
     assert rep["missing_modules"] == [], rep["missing_modules"]
     assert rep["missing_attrs"] == [], rep["missing_attrs"]
     assert rep["missing_methods"] == [], rep["missing_methods"]
-    # who provides what: models / options / utils.util are this build's, the dataset code is the reference's
+    # who provides what: models / options / utils.util are this build's, the dataset code is the codes/ tree's
     for k in ("util_file", "option_file", "models_file"):
         assert os.path.join(ROOT, "dynavsr_amd") in rep[k], rep[k]
     imp = rep["imports"]
-    assert imp["data.data_sampler"].startswith(REF) and imp["data.meta_learner"].startswith(REF)
+    for m, f in theirs.items():
+        assert imp[m] == f, (m, imp[m])
+    for u in uses.values():
+        for m, where in u["imports"].items():
+            if where["provider"] == "repo":
+                assert imp[m].startswith(os.path.join(ROOT, "dynavsr_amd")), (m, imp[m])
     assert imp["options.options"].startswith(ROOT) and imp["models"].startswith(ROOT) and imp["utils"].startswith(ROOT)
 
 
@@ -215,41 +216,27 @@ def test_util_duf_downsample_and_flip_forward():
     assert torch.allclose(sym, inp * 2, atol=1e-7)
 
 
-@needs_ref
 def test_backbone_state_dicts_match_the_reference_modules():
-    """networks.define_G's three video backbones expose exactly the reference modules' state-dict keys and shapes, so
-    reference checkpoints load with strict=True.  The reference modules are only constructed (CPU, plain torch; EDVR's
-    CUDA extension import is stubbed like oracle/gen_golden.py does), nothing is copied."""
-    code = r'''
-import importlib.util, json, sys, types
-sys.dont_write_bytecode = True
-repo, ref = sys.argv[1], sys.argv[2]
-sys.path.insert(0, repo)
-from dynavsr_amd.models.archs import DUF_arch, EDVR_arch, TOF_arch
-sys.path.insert(0, ref)
-sys.modules["models.archs.dcn.deform_conv_cuda"] = types.ModuleType("deform_conv_cuda")
-import models.archs.DUF_arch as RD, models.archs.EDVR_arch as RE, models.archs.TOF_arch as RT
-bad = []
-pairs = [("TOF", TOF_arch.TOFlow(adapt_official=True), RT.TOFlow(adapt_official=True))]
-for n in ("DUF_16L", "DUF_28L", "DUF_52L"):
-    for s in (2, 3, 4):
-        pairs.append((n + "x%d" % s, getattr(DUF_arch, n)(scale=s, adapt_official=True), getattr(RD, n)(scale=s, adapt_official=True)))
-for s in (2, 4):
-    cfg = dict(nf=64, nframes=5, groups=8, front_RBs=5, back_RBs=10, scale=s)
-    pairs.append(("EDVR-Mx%d" % s, EDVR_arch.EDVR(**cfg), RE.EDVR(**cfg)))
-for name, a, b in pairs:
-    sa, sb = a.state_dict(), b.state_dict()
-    if list(sa) != list(sb) or any(tuple(sa[k].shape) != tuple(sb[k].shape) for k in sa):
-        bad.append(name)
-print(json.dumps({"checked": len(pairs), "bad": bad}))
-'''
-    env = dict(os.environ)
-    env["PYTHONDONTWRITEBYTECODE"] = "1"
-    r = subprocess.run([sys.executable, "-c", code, ROOT, REF], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    rep = json.loads(r.stdout.strip().splitlines()[-1])
-    assert rep["checked"] == 12 and rep["bad"] == [], rep
+    """networks.define_G's three video backbones expose exactly the reference modules' state-dict keys and shapes (in order),
+    so reference checkpoints load with strict=True.  The reference's keys and shapes are recorded by oracle/gen_golden.py
+    (dropin) in tests/golden/backbone_state_dicts.json; nothing else of the reference is used."""
+    from dynavsr_amd.models.archs import DUF_arch, EDVR_arch, TOF_arch
+    with open(os.path.join(GOLDEN, "backbone_state_dicts.json")) as f:
+        rec = json.load(f)["networks"]
+    nets = {"TOF": lambda: TOF_arch.TOFlow(adapt_official=True)}
+    for n in ("DUF_16L", "DUF_28L", "DUF_52L"):
+        for s in (2, 3, 4):
+            nets[n + "x%d" % s] = (lambda n=n, s=s: getattr(DUF_arch, n)(scale=s, adapt_official=True))
+    for s in (2, 4):
+        cfg = dict(nf=64, nframes=5, groups=8, front_RBs=5, back_RBs=10, scale=s)
+        nets["EDVR-Mx%d" % s] = (lambda cfg=cfg: EDVR_arch.EDVR(**cfg))
+    assert len(nets) == 12 and sorted(nets) == sorted(rec)
+    bad = []
+    for name, make in nets.items():
+        sd = make().state_dict()
+        if [[k, list(v.shape)] for k, v in sd.items()] != rec[name]:
+            bad.append(name)
+    assert bad == [], bad
 
 
 def test_async_png_writer(tmp_path):

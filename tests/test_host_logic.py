@@ -361,7 +361,7 @@ def test_bench_two_ranks_dry_run(launcher):
     """`python bench.py --gpus 2` must start its own ranks (no launcher: README.md:92-96 starts the reference's trainer
     as one process per GPU; train_dynavsr.py:23-30), and the torch.distributed.run form the driver uses for N > 1 must
     keep working.  --dry-run runs the N-rank skeleton over gloo on the CPU: barriers, MAX of the elapsed time, the flat
-    15 MB meta-gradient all-reduce, the frame shards + metric reduction; rank 0 prints ONE JSON line."""
+    15 MB meta-gradient all-reduce, the frame shards + metric reduction (the legs of --full); rank 0 prints ONE JSON line."""
     import json
     import socket
     import subprocess
@@ -369,7 +369,7 @@ def test_bench_two_ranks_dry_run(launcher):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     bench = os.path.join(root, "bench.py")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    args = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"]
+    args = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run", "--full"]
     if launcher == "self":
         cmd = [sys.executable, bench] + args
     else:
@@ -399,6 +399,58 @@ def test_bench_two_ranks_dry_run(launcher):
         assert set(line) - {"dry_run"} == set(rec) - one_gpu_only, (sorted(set(line) ^ set(rec)))
         for leg in ("inner_step", "per_frame_pipeline"):
             assert {"value", "unit", "ranks", "per_rank_value", "min_rank_value", "max_rank_value"} <= set(rec[leg]) & set(line[leg])
+
+
+def test_bench_plain_dry_run_is_the_headline_only():
+    """Without --full a run is the timed skeleton and the headline line: no leg, no second protocol, no roofline pass."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+                        "--dry-run"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                         "vs_baseline", "dtype", "data", "protocol", "config", "dry_run"}, sorted(line)
+    assert line["n_gpus"] == 2 and line["steps"] == 4 and line["ms_per_step"] >= 0.0
+
+
+def test_bench_dump_outputs_sizes_and_sample():
+    """--dump-outputs: float32 .npy files; arrays within their share of the 64 MB budget are written whole, larger ones as
+    the same seeded sample in every run."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = r'''
+import os, sys
+import numpy as np
+import torch
+sys.path.insert(0, sys.argv[1])
+import bench
+d = sys.argv[2]
+small = torch.arange(12, dtype=torch.float64).view(3, 4)
+big = torch.arange(3 * 720 * 1280, dtype=torch.float32).view(1, 3, 720, 1280)
+for sub in ("a", "b"):
+    bench.dump_outputs(os.path.join(d, sub), [("small", small), ("big0", big), ("big1", big + 1)], 8)
+share = bench.DUMP_BUDGET_BYTES // 4 // 8
+s = np.load(os.path.join(d, "a", "small.npy"))
+assert s.dtype == np.float32 and s.shape == (3, 4) and np.array_equal(s, small.numpy())
+b0, b1 = np.load(os.path.join(d, "a", "big0.npy")), np.load(os.path.join(d, "a", "big1.npy"))
+assert b0.dtype == np.float32 and b0.shape == (share,) and np.array_equal(b1, b0 + 1)
+assert np.all(np.diff(b0) > 0) and np.array_equal(np.load(os.path.join(d, "b", "big0.npy")), b0)
+total = sum(os.path.getsize(os.path.join(d, "a", f)) for f in os.listdir(os.path.join(d, "a")))
+assert total <= bench.DUMP_BUDGET_BYTES + 3 * 1024, total
+print("ok")
+'''
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        r = subprocess.run([sys.executable, "-c", code, root, d], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           timeout=600)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
 
 
 def _val_worker(rank, world, port, q):

@@ -9,9 +9,9 @@ cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$tag; rm -rf "$out"; mkdir -p "$out"
 B="--no-cpu-baseline --no-inner-step --no-split --no-meta --no-validation"
 # 1. the driver's bench line (all legs)
-python bench.py > $out/${tag}_bench_line.json 2> $out/${tag}_bench_stderr.txt
+python bench.py --full > $out/${tag}_bench_line.json 2> $out/${tag}_bench_stderr.txt
 # 2. kernel trace of the headline forward
-rocprofv3 --kernel-trace --stats -d $out/db1 -o r -- python bench.py --steps 10 --warmup 3 $B > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $out/db1 -o r -- python bench.py --full --steps 10 --warmup 3 $B > /dev/null 2>&1
 python tools/rocprof_summary.py $out/db1/r_results.db > $out/${tag}_kernel_trace_bench_fwd180x320.txt; rm -rf $out/db1
 # 3. inner step: timings, kernel table, launch timeline of one EDVR fwd+bwd at the SLR size
 rocprofv3 --kernel-trace --stats -d $out/db2 -o r -- python tools/inner_bench.py 176 320 6 2>&1 | grep -E "inner|EDVR|MFDN|full|LR|adapt_video|overlapped" > $out/${tag}_inner_step_176x320.txt
@@ -24,7 +24,7 @@ python tools/op_profile.py 180 320 5 2>&1 | grep -v amdgpu > $out/${tag}_per_lau
 python tools/op_profile.py 44 80 10 2>&1 | grep -v amdgpu > $out/${tag}_per_launch_fwd44x80.txt
 # 5. PMC: HBM traffic (FETCH_SIZE / WRITE_SIZE in separate passes) and matrix-pipe utilisation
 for c in FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE; do
-  rocprofv3 --pmc $c --kernel-trace -d $out/db_$c -o p -- python bench.py --steps 3 --warmup 1 $B > /dev/null 2>&1
+  rocprofv3 --pmc $c --kernel-trace -d $out/db_$c -o p -- python bench.py --full --steps 3 --warmup 1 $B > /dev/null 2>&1
 done
 python tools/pmc_traffic.py $out/db_FETCH_SIZE/p_results.db $out/db_WRITE_SIZE/p_results.db $out/${tag}_pmc_hbm_traffic.txt $out/pmc_traffic.json
 python tools/pmc_mfma.py $out/db_SQ_VALU_MFMA_BUSY_CYCLES/p_results.db $out/db_GRBM_GUI_ACTIVE/p_results.db > $out/${tag}_pmc_mfma_util.txt
@@ -149,7 +149,7 @@ done
 python tools/graph_fwd_bench.py 2>&1 | grep -v amdgpu > $out/${tag}_graph_vs_eager_fwd.txt
 for sw in "DVSR_CONV_WINO5=0" "DVSR_CONV_WINO=0"; do
 echo "== forward 180x320 with $sw" >> $out/${tag}_wino_vs_direct.txt
-env $sw python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inner-step --no-split --no-meta --no-validation 2>/dev/null | tail -1 | python -c "
+env $sw python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-inner-step --no-split --no-meta --no-validation 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print({k: d[k] for k in ('value','ms_per_step','value_one_clip_in_flight')}, d['roofline']['kernel'], d['roofline']['frac'])" >> $out/${tag}_wino_vs_direct.txt
 done
