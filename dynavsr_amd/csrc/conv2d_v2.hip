@@ -69,19 +69,13 @@ struct Conv2Shape {
   static constexpr size_t LDS_BYTES = (size_t)2 * BUF_FLOATS * sizeof(float);
 };
 
-// channels per chunk: enough k-steps per barrier (72 MFMAs per wave for 3x3, 64 for 2x2 and 1x1)
-int conv2_cc(int ks, int stride) { (void)stride; return ks == 1 ? 32 : (ks == 2 ? 16 : 8); }
-int conv2_pch(int ks, int stride) {  // packed floats per (64-cout block, chunk): two halves
-  return 2 * ks * ks * (conv2_cc(ks, stride) / 8) * 2 * 32 * 4;
-}
-
 // ---- weight packing ---------------------------------------------------------------------------
 // P[cb][k][((((mt*KK + tap)*KQ4 + q)*2 + hi)*32 + lo)*4 + j] = W(cout = cb*64 + mt*32 + lo,
 //   cin = k*CC + 2*(4q + j) + hi, tap), zero outside.
 // wt = 1 (data gradient): this conv's (cin, cout, tap) = original (cout, cin slice, mirrored tap).
 __global__ void pack_weights_kernel(PackTable t) {
   const PackEntry& e = t.e[blockIdx.y];
-  if (e.bf || e.perm >= 3) return;  // packed by pack_weights_bf16_kernel / pack_weights_wino(3)_kernel / pack_weights_dcn3_kernel
+  if (e.bf || has_own_pack_kernel(e.layout)) return;  // packed by pack_weights_bf16_kernel / pack_weights_wino(3)_kernel / pack_weights_dcn3_kernel
   const int kq4 = e.CC / 8;
   const size_t per_chunk = (size_t)e.pch;
   const size_t total = (size_t)e.ncb * e.nchunks * per_chunk;
@@ -98,7 +92,7 @@ __global__ void pack_weights_kernel(PackTable t) {
     const int mt = r / e.KK;
     // channel of (operand group q, lane half hi, k-step j): interleaved for the register-staged halo image,
     // 4 consecutive channels per lane half for the DMA-staged planar one (conv2d_dma_item)
-    const int co = cb * 64 + mt * 32 + lo, ci = k * e.CC + (e.perm ? 8 * q + 4 * hi + j : 2 * (4 * q + j) + hi);
+    const int co = cb * 64 + mt * 32 + lo, ci = k * e.CC + (e.layout != PackLayout::INTERLEAVED ? 8 * q + 4 * hi + j : 2 * (4 * q + j) + hi);
     float v = 0.f;
     if (co < e.Cout && ci < e.Ctot) {
       if (!e.wt) v = e.w[((size_t)co * e.Ctot + ci) * e.KK + tap];
@@ -146,32 +140,24 @@ __global__ void pack_weights_bf16_kernel(PackTable t) {
 }
 
 int pack_weights_run(const PackTable& t, hipStream_t st) {
-  if (t.n <= 0) return DVSR_OK;
-  bool any_f32 = false, any_bf = false, any_wino = false, any_wino3 = false, any_wino5 = false, any_dcn3 = false;
-  for (int i = 0; i < t.n; ++i)
-    (t.e[i].bf ? any_bf : (t.e[i].perm == 3 ? any_wino : (t.e[i].perm == 4 ? any_wino3 : (t.e[i].perm == 5 ? any_wino5 : (t.e[i].perm == 6 ? any_dcn3 : any_f32))))) = true;
-  if (any_dcn3) {
-    int rc = pack_weights_dcn3_run(t, st);
-    if (rc) return rc;
-  }
-  if (any_wino) {
-    int rc = pack_weights_wino_run(t, st);
-    if (rc) return rc;
-  }
-  if (any_wino3) {
-    int rc = pack_weights_wino3_run(t, st);
-    if (rc) return rc;
-  }
-  if (any_wino5) {
-    int rc = pack_weights_wino5_run(t, st);
-    if (rc) return rc;
-  }
-  if (any_f32) {
+  auto any = [&](auto pred) {   // (a kernel is launched only if an entry of the table is its to pack)
+    for (int i = 0; i < t.n; ++i) if (pred(t.e[i])) return true;
+    return false;
+  };
+  const struct { PackLayout layout; int (*run)(const PackTable&, hipStream_t); } own[] = {
+      {PackLayout::DCN_SPLIT, pack_weights_dcn3_run}, {PackLayout::WINO_F2, pack_weights_wino_run},
+      {PackLayout::WINO_F2_BF16, pack_weights_wino3_run}, {PackLayout::WINO_F4, pack_weights_wino5_run}};
+  for (const auto& o : own)
+    if (any([&](const PackEntry& e) { return !e.bf && e.layout == o.layout; })) {
+      int rc = o.run(t, st);
+      if (rc) return rc;
+    }
+  if (any([](const PackEntry& e) { return !e.bf && !has_own_pack_kernel(e.layout); })) {
     hipLaunchKernelGGL(pack_weights_kernel, dim3(48, t.n), dim3(256), 0, st, t);
     int rc = check_launch("pack_weights_kernel");
     if (rc) return rc;
   }
-  if (any_bf) {
+  if (any([](const PackEntry& e) { return e.bf != 0; })) {
     hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(48, t.n), dim3(256), 0, st, t);
     return check_launch("pack_weights_bf16_kernel");
   }
@@ -548,7 +534,7 @@ static int launch_conv2(ConvK2 k, hipStream_t st) {
 // groups per (channel, row), so one global_load_lds_dwordx4 moves 64 groups = 1 KiB and a chunk
 // (8 channels x 6 rows x 10 groups = 480 groups) is TWO instructions per wave instead of eight, with no staging
 // registers, no masking and no ds_write.  The LDS image is planar, [channel][row][40 columns]; a B operand is four
-// ds_read_b32 (channels 4*hi + j, the order pack_weights_kernel uses with perm = 1), conflict-free: the 32 lanes
+// ds_read_b32 (channels 4*hi + j, the order pack_weights_kernel uses with PackLayout::DMA_ORDER), conflict-free: the 32 lanes
 // of a half read 32 consecutive dwords.
 // Groups outside the image are never written by the DMA (their lanes are masked off); the prologue zeroes them
 // once in both buffers -- validity depends on the position only, not on the chunk.
@@ -724,7 +710,7 @@ static int launch_dma(ConvK2 k, hipStream_t st) {
 // weights per 32-cout half by LDS-DMA into one of two buffers, while the chunk's halo tile ((TH + KS - 1) rows x the
 // aligned columns [ox0 - 4, ox0 + 36), which cover a pad of up to 4) stays in LDS for its KS steps and the next chunk's
 // arrives in the other halo buffer.  One barrier per step, KS x 4 x MT x NT MFMAs between barriers.  The packed image is
-// the ordinary one (KK = KS * KS taps, `perm` channel order): the taps of a kernel row are contiguous in it.
+// the ordinary one (KK = KS * KS taps, PackLayout::DMA_ORDER channels): the taps of a kernel row are contiguous in it.
 // Channel counts that are not a multiple of 8 (the 21-channel 9x9 conv) multiply stale-but-finite LDS contents by the
 // pack's zero weights; both halo buffers are cleared once for that.
 // (TOFlow spends 96 % of its forward in these convolutions: 17.7 ms on the single-buffered conv2d_mfma_kernel.)
@@ -912,7 +898,13 @@ static int launch_ksplit(ConvK2 k, hipStream_t st) {
   return check_launch("conv2d_ksplit_kernel");
 }
 
-// Launch geometry.  Calibrated on MI355X per-layer timings of all five candidate geometries
+// ---- launch geometry ----------------------------------------------------------------------------------------
+// One function per decision; conv2_choose below lists them in priority order.
+namespace {
+struct ConvShape { int ks, stride, N, Ho, Wo, Cout, Ctot; };
+int int_or(const char* v, int dflt) { return v ? atoi(v) : dflt; }   // of a getenv() result
+
+// Calibrated on MI355X per-layer timings of all five candidate geometries
 // (profiles/r01_conv_geometry_sweep.txt): the 4x32-pixel tile beats 8x32 on every EDVR layer, 16-channel
 // chunks never beat 8, and between 64 (MT=2) and 32 (MT=1) output channels per workgroup the winner is
 // the one with the smaller MFMA time on the busiest CU,
@@ -920,151 +912,137 @@ static int launch_ksplit(ConvK2 k, hipStream_t st) {
 // i.e. pure tile quantisation (e.g. Cout = 216 wastes 18 % of a 64-wide block but 4 % of 32-wide ones;
 // 575 tiles are 3 rounds of 64-wide but 5 half-size rounds of 32-wide blocks).  Ties go to MT=2 (half
 // the workgroups, half the weight traffic).
-// cycles of a conv2d_wino5_kernel workgroup (32 tiles of 4x4 outputs x 64 couts): per 8-channel chunk and fixed (prologue +
-// epilogue), from the op-level times of the 8- and 16-chunk layers at 5x180x320 (profiles/r06_wino5_layers.txt)
-static constexpr double W5_CHUNK_CYC = 4300.0, W5_FIXED_CYC = 17500.0;
-static double conv2_pipe_cost(int TH, int MT, int KK, int CC, int N, int Ho, int Wo, int Cout) {
-  const double wgs = (double)ceil_div(Wo, 32) * ceil_div(Ho, TH) * N * ceil_div(Cout, 32 * MT);
-  return ceil(wgs / 256.0) * 64.0 * KK * (CC / 2) * (TH / 4) * MT;
+double conv2_pipe_cost(int TH, int MT, int CC, const ConvShape& s) {
+  const double wgs = (double)ceil_div(s.Wo, 32) * ceil_div(s.Ho, TH) * s.N * ceil_div(s.Cout, 32 * MT);
+  return ceil(wgs / 256.0) * 64.0 * (s.ks * s.ks) * (CC / 2) * (TH / 4) * MT;
 }
+bool mt1_wins(int cc, const ConvShape& s) { return conv2_pipe_cost(4, 1, cc, s) < 0.97 * conv2_pipe_cost(4, 2, cc, s); }
 
-ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ctot, int allow_ksplit) {
-  if (ks == 7 || ks == 9) {  // row-split DMA kernel (conv2d_dmarow_kernel) or nothing: dma = 2 when it applies
-    ConvGeo g{8, 4, 2};
-    const double c42 = conv2_pipe_cost(4, 2, ks * ks, 8, N, Ho, Wo, Cout);
-    const double c41 = conv2_pipe_cost(4, 1, ks * ks, 8, N, Ho, Wo, Cout);
-    if (c41 < 0.97 * c42) g.mt = 1;
-    static int row_on = -1;  // DVSR_CONV_DMAROW=0: the caller falls back to the single-buffered kernel (A/B aid)
-    if (row_on < 0) {
-      const char* v = getenv("DVSR_CONV_DMAROW");
-      row_on = v ? atoi(v) : 1;
-    }
-    // (any Cout: even the 16 -> 2 flow head, 2 of 32 tile rows used, gains over the single-buffered kernel:
-    // TOFlow forward 6.8 -> 6.1 ms, forward+backward 48.3 -> 45.0 ms with it)
-    if (row_on && (allow_ksplit & 2) && stride == 1 && Wo % 4 == 0) g.dma = 2;
-    return g;
-  }
-  // Small grids: the K-split kernel (geo {32, NT, MT} with ks == 3).  DVSR_CONV_KSPLIT_BELOW=<workgroups of the
-  // 4x32x32 geometry> moves the threshold (0 disables); DVSR_CONV_KSPLIT_NT=1|2 pins the tile shape.
-  // Threshold from profiles/r02_small_grid_ab.txt: below ~700 such workgroups (the 44x80 levels: 66..330) the K-split
-  // kernel wins (rc_rb 19.2 -> 14.8 us, fe_rb 30 -> 26 us); at 900 (the 180x320 trunk) and 1155 (L1_om at 5x44x80) the
-  // pipelined 4-row kernel is faster again (47.5 vs 52.6 us, 65 vs 72 us): three times the halo and unshared weights.
-  if (ks == 3 && stride == 1 && (allow_ksplit & 1) && Ctot >= 32 && Cout >= 32) {
-    static int below = -1, pin_nt = -1;
-    if (below < 0) {
-      const char* v = getenv("DVSR_CONV_KSPLIT_BELOW");
-      below = v ? atoi(v) : 700;
-      const char* n = getenv("DVSR_CONV_KSPLIT_NT");
-      pin_nt = n ? atoi(n) : 0;
-    }
-    const long long wg41 = (long long)ceil_div(Wo, 32) * ceil_div(Ho, 4) * N * ceil_div(Cout, 32);
-    if (wg41 < below) {
-      // 1 row x 64 couts (even row count not needed) or 2 rows x 32 couts: the latter halves the weight traffic
-      // per workgroup but needs an even split of the rows and Cout in 32-blocks; 64-wide blocks waste less when
-      // Cout % 64 == 0
-      const bool nt2 = pin_nt ? pin_nt == 2 : (Cout % 64 != 0 && Ho % 2 == 0);
-      return nt2 ? ConvGeo{32, 2, 1} : ConvGeo{32, 1, 2};
-    }
-  }
-  static int force = -2;  // DVSR_CONV_TILE=0|1|2 pins (8,2)/(4,2)/(4,1) tiles (A/B aid); default: model
-  if (force == -2) {
-    const char* v = getenv("DVSR_CONV_TILE");
-    force = (v && v[0] >= '0' && v[0] <= '2') ? v[0] - '0' : -1;
-  }
-  const int cc = conv2_cc(ks, stride);
-  if (ks == 3 && stride == 2) {  // the two pyramid convs: few tiles, pick by tile quantisation alone
-    const double c82 = conv2_pipe_cost(8, 2, 9, cc, N, Ho, Wo, Cout);
-    const double c42 = conv2_pipe_cost(4, 2, 9, cc, N, Ho, Wo, Cout);
-    const double c41 = conv2_pipe_cost(4, 1, 9, cc, N, Ho, Wo, Cout);
-    if (force == 0 || (force < 0 && c82 <= c42 && c82 <= c41)) return ConvGeo{cc, 8, 2};
-    if (force == 2 || (force < 0 && c41 < 0.97 * c42)) return ConvGeo{cc, 4, 1};
-    return ConvGeo{cc, 4, 2};
-  }
-  const double c42 = conv2_pipe_cost(4, 2, ks * ks, cc, N, Ho, Wo, Cout);
-  const double c41 = conv2_pipe_cost(4, 1, ks * ks, cc, N, Ho, Wo, Cout);
-  ConvGeo g = c41 < 0.97 * c42 ? ConvGeo{cc, 4, 1} : ConvGeo{cc, 4, 2};
-  if (force == 0 && ks != 2) g = ConvGeo{cc, 8, 2};
-  if (force == 1) g = ConvGeo{cc, 4, 2};
-  if (force == 2) g = ConvGeo{cc, 4, 1};
-  // halo by DMA (conv2d_dma_item): plain pad-1 inputs on a 16-byte column grid, whole 8-channel chunks.
-  // DVSR_CONV_DMA=0 keeps the register-staged kernel (A/B aid).
-  static int dma_on = -1;
-  if (dma_on < 0) {
-    const char* v = getenv("DVSR_CONV_DMA");
-    dma_on = v ? atoi(v) : 1;
-  }
-  if (dma_on && (allow_ksplit & 2) && ks == 3 && stride == 1 && Wo % 4 == 0 && Ctot % 8 == 0) g.dma = 1;
-  if (force >= 0) return g;
-  // Winograd F(2x2, 3x3) (conv2d_wino.hip): one workgroup per CU, 64 couts x 64 2x2-pixel tiles, 4/9 of the MFMAs plus the
-  // transforms.  Model: rounds over the 256 CUs x (MFMA cycles of a workgroup's chunks + transform / epilogue overhead)
-  // against the direct kernel's rounds x MFMA cycles at its measured 0.78 efficiency.  DVSR_CONV_WINO=0 disables,
-  // =2 takes it wherever it is eligible (A/B aid).
-  int wino_on = 1;   // (read per call: plans are built once, and the tests switch it at run time)
-  if (const char* v = getenv("DVSR_CONV_WINO")) wino_on = atoi(v);
-  if (wino_on && g.dma == 1 && (allow_ksplit & 4) && Cout >= 32 && Ctot >= 16) {
-    const int nch = Ctot / 8;
-    // (one workgroup per CU: rounds over the device's CUs; cycle figures measured on MI355X: tools/wino_trace.py, 2.07 GHz
-    // under this kernel)
-    const double cus = (double)device_cus();
-    auto wino_cost = [&](int oh, int ow) {
-      const double wgs = (double)ceil_div(Wo, ow) * ceil_div(Ho, oh) * N * ceil_div(Cout, 64);
-      return ceil(wgs / cus) * (nch * 5100.0 + 12500.0) / 2.07;
-    };
-    const double w4 = wino_cost(4, 64), w8 = wino_cost(8, 32);
-    // (the direct kernels reach 0.78 of their MFMA time only over many rounds of workgroups; on grids of a few rounds their
-    // prologue / epilogue is exposed: L2_fea 5x64->64 @90x160 measures 0.60 -- profiles/r03_c_per_launch_fwd180x320.txt)
-    const double dcyc = std::min(c42, c41);
-    const double drounds = dcyc / (64.0 * 9 * 4 * (c41 < 0.97 * c42 ? 1 : 2));
-    const double direct = dcyc * nch / (drounds <= 6.0 ? 0.60 : 0.78) / 2.4;
-    // DVSR_CONV_WINO3 (default 1): the same GEMMs on the bf16 pipe with the exact 3-way operand split (conv2d_wino3.hip)
-    int wino3_on = 1;
-    if (const char* v = getenv("DVSR_CONV_WINO3")) wino3_on = atoi(v);
-    // ... which also has a 16 x 16-pixel tile (th = 16): the 44x80 levels of the batched inner step fill 92 % of its tiles
-    // against 72 % of the 8 x 32 ones (DVSR_CONV_WINO_T16=0: off)
-    static const bool t16_on = [] { const char* v = getenv("DVSR_CONV_WINO_T16"); return !(v && v[0] == '0'); }();
-    const double w16 = (wino3_on && t16_on) ? wino_cost(16, 16) : 1e300;
-    const double best = std::min(std::min(w4, w8), w16);
-    // (both Winograd kernels hold a workgroup's whole working set in ~150 KB of LDS: gfx950's 160 KB, checked, not assumed)
-    // DVSR_CONV_WINO5 (read per call): Winograd F(4x4, 3x3) on the bf16 pipe (conv2d_wino5.hip: 32 tiles of 4x4 outputs x 64
-    // couts per workgroup, 1024 threads, 156 KB of LDS).  Forward launches only (allow bit 3: plain / residual / PixelShuffle(2)
-    // stores of 4-pixel tile rows -- Wo % 4 == 0 --, no accumulate / gradient mask).  0: off, 1: where the model says it is faster (default),
-    // 2: wherever it is eligible (A/B aid), 3: eligible and 16x32-pixel workgroup tiles (A/B aid).
-    int wino5_on = 1;
-    if (const char* v = getenv("DVSR_CONV_WINO5")) wino5_on = atoi(v);
-    if (wino5_on && wino3_on && (allow_ksplit & 8) && Wo % 4 == 0 && device_lds_optin() >= (size_t)156 * 1024) {
-      auto w5_cost = [&](int oh, int ow) {
-        const double wgs = (double)ceil_div(Wo, ow) * ceil_div(Ho, oh) * N * ceil_div(Cout, 64);
-        return ceil(wgs / cus) * (nch * W5_CHUNK_CYC + W5_FIXED_CYC) / 2.07;
-      };
-      const double f8 = w5_cost(8, 64), f16 = w5_cost(16, 32);
-      const double best5 = std::min(f8, f16);
-      // (the model flatters this kernel on grids of one round -- the N = 1 trunk at 180x320 measures 31 us against 26 --: it has
-      // to win by 15 %)
-      if (wino5_on >= 2 || (1.15 * best5 < best && best5 < direct)) return ConvGeo{8, wino5_on == 3 ? 16 : (f16 < f8 ? 16 : 8), 2, 0, 5};
-    }
-    if ((wino_on == 2 || best < direct) && device_lds_optin() >= (size_t)155 * 1024)
-      return ConvGeo{8, (w16 < w4 && w16 < w8) ? 16 : (w8 < w4 ? 8 : 4), 2, 0, wino3_on ? 4 : 3};
-  }
-  // Small grids (every workgroup resident at once) are bound by one memory latency per chunk, not by the
-  // matrix pipe: 16-channel chunks halve the number of exposed latencies.  DVSR_CONV_CC16_BELOW=<workgroups>
-  // moves the threshold (0 disables).
-  static int cc16_below = -1;
-  if (cc16_below < 0) {
-    const char* v = getenv("DVSR_CONV_CC16_BELOW");
-    cc16_below = v ? atoi(v) : 0;
-  }
-  if (ks == 3 && stride == 1 && Ctot >= 32) {
-    const long long wgs = (long long)ceil_div(Wo, 32) * ceil_div(Ho, 4) * N * ceil_div(Cout, 32 * g.mt);
-    if (wgs <= cc16_below) g.cc = 16;
-  }
+// 7x7 / 9x9: the row-split DMA kernel (conv2d_dmarow_kernel), or no packed kernel at all (callers use the single-buffered one)
+// (any Cout: even the 16 -> 2 flow head, 2 of 32 tile rows used, gains over the single-buffered kernel:
+// TOFlow forward 6.8 -> 6.1 ms, forward+backward 48.3 -> 45.0 ms with it)
+ConvGeo choose_row_split(const ConvShape& s, ConvAllow allow) {
+  ConvGeo g{8, 4, mt1_wins(8, s) ? 1 : 2};
+  if ((allow & ALLOW_DMA_HALO) && s.stride == 1 && s.Wo % 4 == 0) g.kernel = ConvKernel::ROW_SPLIT;
   return g;
 }
 
-int conv2_pch_cc(int ks, int cc, int bf, int dma) {
-  if (dma == 3) return 16 * 2 * 64 * 4;   // Winograd image: 16 transformed taps x 8 channels x 64 couts
-  if (dma == 4) return 2 * 6144;          // the same as three bf16 pieces: 2 phases x 24 KB
-  if (dma == 5) return 18 * 2 * 3 * 256;  // F(4x4, 3x3): 18 point pairs x 2 cout halves x 3 fragments of 1 KB (X, X', L)
-  return (bf == 2 ? 3 : 1) * 2 * ks * ks * (bf ? cc / 16 : cc / 8) * 2 * 32 * 4;
+// Small grids: the K-split kernel (geo {32, NT, MT} with ks == 3).
+// Threshold from profiles/r02_small_grid_ab.txt: below ~700 workgroups of the 4x32x32 geometry (the 44x80 levels: 66..330) the
+// K-split kernel wins (rc_rb 19.2 -> 14.8 us, fe_rb 30 -> 26 us); at 900 (the 180x320 trunk) and 1155 (L1_om at 5x44x80) the
+// pipelined 4-row kernel is faster again (47.5 vs 52.6 us, 65 vs 72 us): three times the halo and unshared weights.
+constexpr long long KSPLIT_BELOW_WGS = 700;
+bool choose_ksplit(const ConvShape& s, ConvAllow allow, ConvGeo* g) {
+  if (!(s.ks == 3 && s.stride == 1 && (allow & ALLOW_KSPLIT) && s.Ctot >= 32 && s.Cout >= 32)) return false;
+  const long long wg41 = (long long)ceil_div(s.Wo, 32) * ceil_div(s.Ho, 4) * s.N * ceil_div(s.Cout, 32);
+  if (wg41 >= KSPLIT_BELOW_WGS) return false;
+  // 1 row x 64 couts (even row count not needed) or 2 rows x 32 couts: the latter halves the weight traffic
+  // per workgroup but needs an even split of the rows and Cout in 32-blocks; 64-wide blocks waste less when
+  // Cout % 64 == 0
+  *g = (s.Cout % 64 != 0 && s.Ho % 2 == 0) ? ConvGeo{32, 2, 1} : ConvGeo{32, 1, 2};
+  return true;
+}
+
+// channels per chunk: enough k-steps per barrier (72 MFMAs per wave for 3x3, 64 for 2x2 and 1x1)
+int chunk_channels(int ks) { return ks == 1 ? 32 : (ks == 2 ? 16 : 8); }
+// The direct kernel's tile, by tile quantisation alone.  The 8-row tile only for the two stride-2 pyramid convs (few tiles).
+ConvGeo choose_direct_tile(const ConvShape& s) {
+  const int cc = chunk_channels(s.ks);
+  if (s.ks == 3 && s.stride == 2) {
+    const double c82 = conv2_pipe_cost(8, 2, cc, s);
+    if (c82 <= conv2_pipe_cost(4, 2, cc, s) && c82 <= conv2_pipe_cost(4, 1, cc, s)) return ConvGeo{cc, 8, 2};
+  }
+  return ConvGeo{cc, 4, mt1_wins(cc, s) ? 1 : 2};
+}
+
+// Time models of a 3x3 layer in whole 8-channel chunks, all in the same unit.  The Winograd kernels run one workgroup per CU:
+// rounds over the device's CUs x (cycles of a workgroup's chunks + transform / epilogue overhead); cycle figures measured on
+// MI355X (tools/wino_trace.py), 2.07 GHz under these kernels.
+struct WinoPick { int th; double cost; };
+double wino_rounds_cost(const ConvShape& s, double cus, int oh, int ow, double chunk_cyc, double fixed_cyc) {
+  const double wgs = (double)ceil_div(s.Wo, ow) * ceil_div(s.Ho, oh) * s.N * ceil_div(s.Cout, 64);
+  return ceil(wgs / cus) * ((s.Ctot / 8) * chunk_cyc + fixed_cyc) / 2.07;
+}
+// ... the direct kernel: rounds x MFMA cycles at its measured 0.78 efficiency
+// (the direct kernels reach 0.78 of their MFMA time only over many rounds of workgroups; on grids of a few rounds their
+// prologue / epilogue is exposed: L2_fea 5x64->64 @90x160 measures 0.60 -- profiles/r03_c_per_launch_fwd180x320.txt)
+double direct_cost(const ConvShape& s) {
+  const double dcyc = std::min(conv2_pipe_cost(4, 2, 8, s), conv2_pipe_cost(4, 1, 8, s));
+  const double drounds = dcyc / (64.0 * 9 * 4 * (mt1_wins(8, s) ? 1 : 2));
+  return dcyc * (s.Ctot / 8) / (drounds <= 6.0 ? 0.60 : 0.78) / 2.4;
+}
+// Winograd F(2x2, 3x3) (conv2d_wino.hip): 64 couts x 64 2x2-pixel tiles per workgroup, 4/9 of the MFMAs plus the transforms.
+// The bf16x3 form (conv2d_wino3.hip) also has a 16 x 16-pixel tile (th = 16): the 44x80 levels of the batched inner step fill
+// 92 % of its tiles against 72 % of the 8 x 32 ones.
+WinoPick wino_f2_cost(const ConvShape& s, double cus, bool tile16) {
+  const double w4 = wino_rounds_cost(s, cus, 4, 64, 5100.0, 12500.0), w8 = wino_rounds_cost(s, cus, 8, 32, 5100.0, 12500.0);
+  const double w16 = tile16 ? wino_rounds_cost(s, cus, 16, 16, 5100.0, 12500.0) : 1e300;
+  return {(w16 < w4 && w16 < w8) ? 16 : (w8 < w4 ? 8 : 4), std::min(std::min(w4, w8), w16)};
+}
+// Winograd F(4x4, 3x3) on the bf16 pipe (conv2d_wino5.hip: 32 tiles of 4x4 outputs x 64 couts per workgroup, 1024 threads,
+// 156 KB of LDS).  Cycles of a workgroup per 8-channel chunk and fixed (prologue + epilogue): fitted in round 6 to op-level
+// times of the 8- and 16-chunk layers at 5x180x320 from a table that was not kept.  The kept one, profiles/r06_wino_vs_direct.txt
+// (fe_rb_a 80.1 us, L1_offset_conv1 132.2 us, three rounds each), gives 4500 and 19300: the constants are 5-10 % below it.
+constexpr double W5_CHUNK_CYC = 4300.0, W5_FIXED_CYC = 17500.0;
+WinoPick wino_f4_cost(const ConvShape& s, double cus) {
+  const double f8 = wino_rounds_cost(s, cus, 8, 64, W5_CHUNK_CYC, W5_FIXED_CYC), f16 = wino_rounds_cost(s, cus, 16, 32, W5_CHUNK_CYC, W5_FIXED_CYC);
+  return {f16 < f8 ? 16 : 8, std::min(f8, f16)};
+}
+}  // namespace
+
+ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ctot, ConvAllow allow) {
+  const ConvShape s{ks, stride, N, Ho, Wo, Cout, Ctot};
+  if (ks == 7 || ks == 9) return choose_row_split(s, allow);
+  ConvGeo g;
+  if (choose_ksplit(s, allow, &g)) return g;
+  g = choose_direct_tile(s);
+  // halo by DMA (conv2d_dma_item): plain pad-1 inputs on a 16-byte column grid, whole 8-channel chunks
+  if ((allow & ALLOW_DMA_HALO) && ks == 3 && stride == 1 && Wo % 4 == 0 && Ctot % 8 == 0) g.kernel = ConvKernel::DMA_HALO;
+  // Winograd, where the DMA-halo kernel could run.  The switches are read per call: plans are built once, and the tests switch
+  // them at run time.  DVSR_CONV_WINO=0 disables, =2 takes F(2x2) wherever it is eligible (A/B aid); DVSR_CONV_WINO3 (default 1):
+  // F(2x2) on the bf16 pipe with the exact 3-way operand split, 0: on the fp32 pipe and no F(4x4); DVSR_CONV_WINO5: 0 no F(4x4),
+  // 1 where the model says it is faster (default), 2 wherever it is eligible, 3 eligible and 16x32-pixel workgroup tiles (A/B aids).
+  const int wino_on = int_or(getenv("DVSR_CONV_WINO"), 1);
+  if (!(wino_on && g.kernel == ConvKernel::DMA_HALO && (allow & ALLOW_WINO) && Cout >= 32 && Ctot >= 16)) return g;
+  const int wino3_on = int_or(getenv("DVSR_CONV_WINO3"), 1), wino5_on = int_or(getenv("DVSR_CONV_WINO5"), 1);
+  const double direct = direct_cost(s), cus = (double)device_cus();
+  const WinoPick f2 = wino_f2_cost(s, cus, wino3_on != 0);
+  // (both Winograd kernels hold a workgroup's whole working set in ~150 KB of LDS: gfx950's 160 KB, checked, not assumed)
+  // F(4x4): launches whose epilogue it implements (ALLOW_WINO_F4: plain / residual / PixelShuffle(2) stores of 4-pixel tile rows
+  // -- Wo % 4 == 0 --, no accumulate / gradient mask).  Callers: the engine's no-grad forward slot and the op-level packed
+  // entries, which pass the flag for every aligned 3x3 whether or not autograd records the call.
+  if (wino5_on && wino3_on && (allow & ALLOW_WINO_F4) && Wo % 4 == 0 && device_lds_optin() >= (size_t)156 * 1024) {
+    const WinoPick f4 = wino_f4_cost(s, cus);
+    // (the model flatters this kernel on grids of one round -- the N = 1 trunk at 180x320 measures 31 us against 26 --: it has
+    // to win by 15 %)
+    if (wino5_on >= 2 || (1.15 * f4.cost < f2.cost && f4.cost < direct)) return ConvGeo{8, wino5_on == 3 ? 16 : f4.th, 2, 0, ConvKernel::WINO_F4};
+  }
+  if ((wino_on == 2 || f2.cost < direct) && device_lds_optin() >= (size_t)155 * 1024)
+    return ConvGeo{8, f2.th, 2, 0, wino3_on ? ConvKernel::WINO_F2_BF16 : ConvKernel::WINO_F2};
+  return g;
+}
+
+// ---- the rule for a weight pack -----------------------------------------------------------------------------
+// fp32-sized slots per packed (64-cout block, chunk of cc channels)
+static int pack_chunk_floats(int ks, int cc, int bf, PackLayout layout) {
+  switch (layout) {
+    case PackLayout::WINO_F2: return 16 * 2 * 64 * 4;       // Winograd image: 16 transformed taps x 8 channels x 64 couts
+    case PackLayout::WINO_F2_BF16: return 2 * 6144;         // the same as three bf16 pieces: 2 phases x 24 KB
+    case PackLayout::WINO_F4: return 18 * 2 * 3 * 256;      // F(4x4, 3x3): 18 point pairs x 2 cout halves x 3 fragments of 1 KB (X, X', L)
+    case PackLayout::DCN_SPLIT: return mdcn_pack_floats();
+    default: return (bf == 2 ? 3 : 1) * 2 * ks * ks * (bf ? cc / 16 : cc / 8) * 2 * 32 * 4;   // two 32-cout halves (per piece)
+  }
+}
+size_t conv2_pack_floats(int ks, int Cout, int Ctot, int cc, int bf, PackLayout layout) {
+  return (size_t)ceil_div(Cout, 64) * ceil_div(Ctot, cc) * pack_chunk_floats(ks, cc, bf, layout);
+}
+PackEntry conv2_pack_entry(const float* w, float* P, int ks, int Cout, int Ctot, int cc, int bf, PackLayout layout, int wt, int w_ctot,
+                           int w_coff) {
+  PackEntry e{};
+  e.w = w; e.P = P; e.Cout = Cout; e.Ctot = Ctot; e.KK = ks * ks; e.CC = cc; e.wt = wt; e.w_ctot = w_ctot; e.w_coff = w_coff;
+  e.ncb = ceil_div(Cout, 64); e.nchunks = ceil_div(Ctot, cc); e.pch = pack_chunk_floats(ks, cc, bf, layout);
+  e.bf = bf; e.layout = layout;
+  return e;
 }
 
 // `wp` = weights packed by pack_weights_kernel for this (ks, wt, geo.cc) combination.
@@ -1082,7 +1060,7 @@ extern "C" int dvsr_debug_conv_trace(void* buf, int launch_index) {
 int conv2d_packed_prepare(const dvsr_conv2d_desc& d, const float* wp, const ConvExtra& ex, const ConvGeo& geo, ConvK2* out) {
   DVSR_REQUIRE(d.x0 && wp && d.y, DVSR_ERR_INVALID, "conv2d_packed: null x0/wp/y");
   DVSR_REQUIRE(((d.ks == 1 || d.ks == 2) && d.stride == 1) || (d.ks == 3 && (d.stride == 1 || d.stride == 2)) ||
-                   ((d.ks == 7 || d.ks == 9) && d.stride == 1 && geo.dma == 2),
+                   ((d.ks == 7 || d.ks == 9) && d.stride == 1 && geo.kernel == ConvKernel::ROW_SPLIT),
                DVSR_ERR_UNSUPPORTED, "conv2d_packed: ks=%d stride=%d", d.ks, d.stride);
   DVSR_REQUIRE(d.c1 == 0 || (d.c0 % geo.cc == 0 && !ex.in_ps && !ex.in_dil), DVSR_ERR_UNSUPPORTED,
                "conv2d_packed: two inputs need c0 %% %d == 0 and a plain first input (c0=%d)", geo.cc, d.c0);
@@ -1116,19 +1094,19 @@ int conv2d_packed_prepare(const dvsr_conv2d_desc& d, const float* wp, const Conv
   k.trace = (g_trace_countdown == 0) ? g_trace_buf : nullptr;
   if (g_trace_countdown >= 0) --g_trace_countdown;
 #endif
-  if (geo.dma == 2) {
+  if (geo.kernel == ConvKernel::ROW_SPLIT) {
     DVSR_REQUIRE((d.ks == 7 || d.ks == 9) && d.stride == 1 && d.pad == d.ks / 2 && !ex.in_ps && !ex.in_dil && geo.cc == 8 &&
                      geo.th == 4 && d.W % 4 == 0 && (d.c1 == 0 || d.c0 % 8 == 0) && k.x0_bs % 4 == 0 && k.x1_bs % 4 == 0 &&
                      ((uintptr_t)d.x0 & 15) == 0 && ((uintptr_t)d.x1 & 15) == 0,
                  DVSR_ERR_UNSUPPORTED, "conv2d_packed: the row-split DMA kernel needs 7x7 / 9x9, stride 1, pad ks/2, plain "
                  "16-byte aligned inputs and W %% 4 == 0 (W=%d c0=%d c1=%d)", d.W, d.c0, d.c1);
-  } else if (geo.dma) {
-    DVSR_REQUIRE(geo.dma < 3 || d.c0 + d.c1 >= 16, DVSR_ERR_UNSUPPORTED, "conv2d_packed: the Winograd kernel needs two 8-channel chunks");
-    DVSR_REQUIRE(geo.dma != 5 || (!ex.accum && !ex.gmask && d.W % 4 == 0 && (geo.th == 8 || geo.th == 16)), DVSR_ERR_UNSUPPORTED,
+  } else if (needs_dma_halo_inputs(geo.kernel)) {
+    DVSR_REQUIRE(!is_winograd(geo.kernel) || d.c0 + d.c1 >= 16, DVSR_ERR_UNSUPPORTED, "conv2d_packed: the Winograd kernel needs two 8-channel chunks");
+    DVSR_REQUIRE(geo.kernel != ConvKernel::WINO_F4 || (!ex.accum && !ex.gmask && d.W % 4 == 0 && (geo.th == 8 || geo.th == 16)), DVSR_ERR_UNSUPPORTED,
                  "conv2d_packed: the F(4x4, 3x3) kernel stores whole tile columns of forward launches (W=%d th=%d)", d.W, geo.th);
-    DVSR_REQUIRE(geo.dma < 3 || d.pixel_shuffle == 0 || (d.pixel_shuffle == 2 && d.Cout % 4 == 0 && !d.res && !ex.accum && !ex.gmask),
+    DVSR_REQUIRE(!is_winograd(geo.kernel) || d.pixel_shuffle == 0 || (d.pixel_shuffle == 2 && d.Cout % 4 == 0 && !d.res && !ex.accum && !ex.gmask),
                  DVSR_ERR_UNSUPPORTED, "conv2d_packed: the Winograd kernel stores plain or PixelShuffle(2) tiles (ps=%d)", d.pixel_shuffle);
-    DVSR_REQUIRE(d.ks == 3 && d.stride == 1 && d.pad == 1 && !ex.in_ps && !ex.in_dil && geo.cc == 8 && (geo.th == 4 || geo.th == 8 || (geo.th == 16 && geo.dma >= 4)) &&
+    DVSR_REQUIRE(d.ks == 3 && d.stride == 1 && d.pad == 1 && !ex.in_ps && !ex.in_dil && geo.cc == 8 && (geo.th == 4 || geo.th == 8 || (geo.th == 16 && on_bf16_split(geo.kernel))) &&
                      d.W % 4 == 0 && d.c0 % 8 == 0 && d.c1 % 8 == 0 && k.x0_bs % 4 == 0 && k.x1_bs % 4 == 0 &&
                      ((uintptr_t)d.x0 & 15) == 0 && ((uintptr_t)d.x1 & 15) == 0,
                  DVSR_ERR_UNSUPPORTED, "conv2d_packed: the DMA-halo kernel needs 3x3/s1/pad 1, plain 16-byte aligned inputs, "
@@ -1147,76 +1125,50 @@ int conv2d_packed_prepare(const dvsr_conv2d_desc& d, const float* wp, const Conv
   return DVSR_OK;
 }
 
+template <int KS, int S, int CC, int TH, int BF>   // both widths of a bf16 tile shape
+static int launch_conv2_mt(int mt, const ConvK2& k, hipStream_t st) {
+  return mt == 2 ? launch_conv2<KS, S, CC, TH, 2, BF>(k, st) : launch_conv2<KS, S, CC, TH, 1, BF>(k, st);
+}
+
 int conv2d_packed_run(const dvsr_conv2d_desc& d, const float* wp, const ConvExtra& ex, const ConvGeo& geo,
                       hipStream_t st) {
   ConvK2 k;
   int rc = conv2d_packed_prepare(d, wp, ex, geo, &k);
   if (rc) return rc;
-  const int code = geo.cc * 100 + geo.th * 10 + geo.mt;
   if (geo.bf) {
     DVSR_REQUIRE((d.ks == 3 || (d.ks == 2 && geo.bf == 2)) && d.stride == 1 && geo.cc == 16 && (geo.th == 4 || (geo.bf == 2 && geo.th == 8)),
                  DVSR_ERR_UNSUPPORTED,
                  "conv2d_packed: the bf16 kernel exists for 3x3 (split: also 2x2) stride-1 convs with 16-channel chunks");
-    if (geo.bf == 2 && d.ks == 2) {   // the estimators' 4x4 stride-2 convolutions in their 2x2 space-to-depth form
-      if (geo.th == 8) {
-        if (geo.mt == 2) return launch_conv2<2, 1, 16, 8, 2, 2>(k, st);
-        return launch_conv2<2, 1, 16, 8, 1, 2>(k, st);
+    const bool th8 = geo.th == 8;
+    if (geo.bf == 2 && d.ks == 2)   // the estimators' 4x4 stride-2 convolutions in their 2x2 space-to-depth form
+      return th8 ? launch_conv2_mt<2, 1, 16, 8, 2>(geo.mt, k, st) : launch_conv2_mt<2, 1, 16, 4, 2>(geo.mt, k, st);
+    if (geo.bf == 2) return th8 ? launch_conv2_mt<3, 1, 16, 8, 2>(geo.mt, k, st) : launch_conv2_mt<3, 1, 16, 4, 2>(geo.mt, k, st);
+    return launch_conv2_mt<3, 1, 16, 4, 1>(geo.mt, k, st);
+  }
+  switch (geo.kernel) {
+    case ConvKernel::WINO_F2: return conv2d_wino_launch(k, geo.th, st);
+    case ConvKernel::WINO_F2_BF16: return conv2d_wino3_launch(k, geo.th, st);
+    case ConvKernel::WINO_F4: return conv2d_wino5_launch(k, geo.th, st);
+    case ConvKernel::ROW_SPLIT:
+      if (d.ks == 7) return geo.mt == 2 ? launch_dmarow<7, 4, 2>(k, st) : launch_dmarow<7, 4, 1>(k, st);
+      return geo.mt == 2 ? launch_dmarow<9, 4, 2>(k, st) : launch_dmarow<9, 4, 1>(k, st);
+    case ConvKernel::DMA_HALO:
+      if (geo.th != 4) break;
+      return geo.mt == 2 ? launch_dma<4, 2>(k, st) : launch_dma<4, 1>(k, st);
+    case ConvKernel::REG:
+      if (d.ks == 3 && geo.cc == 32) return geo.mt == 2 ? launch_ksplit<2, 1>(k, st) : launch_ksplit<1, 2>(k, st);   // K-split small-grid kernel
+      switch (((d.ks * 10 + d.stride) * 100 + geo.cc) * 100 + geo.th * 10 + geo.mt) {   // the digits of KS, S, CC (two), TH, MT
+        case 320882: return launch_conv2<3, 2, 8, 8, 2>(k, st);
+        case 320842: return launch_conv2<3, 2, 8, 4, 2>(k, st);
+        case 320841: return launch_conv2<3, 2, 8, 4, 1>(k, st);
+        case 310842: return launch_conv2<3, 1, 8, 4, 2>(k, st);
+        case 310841: return launch_conv2<3, 1, 8, 4, 1>(k, st);
+        case 211642: return launch_conv2<2, 1, 16, 4, 2>(k, st);   // the estimator's 4x4 stride-2 convs, re-expressed over a
+        case 211641: return launch_conv2<2, 1, 16, 4, 1>(k, st);   // space-to-depth input
+        case 113242: return launch_conv2<1, 1, 32, 4, 2>(k, st);
+        case 113241: return launch_conv2<1, 1, 32, 4, 1>(k, st);
       }
-      if (geo.mt == 2) return launch_conv2<2, 1, 16, 4, 2, 2>(k, st);
-      return launch_conv2<2, 1, 16, 4, 1, 2>(k, st);
-    }
-    if (geo.bf == 2) {
-      if (geo.th == 8) {
-        if (geo.mt == 2) return launch_conv2<3, 1, 16, 8, 2, 2>(k, st);
-        return launch_conv2<3, 1, 16, 8, 1, 2>(k, st);
-      }
-      if (geo.mt == 2) return launch_conv2<3, 1, 16, 4, 2, 2>(k, st);
-      return launch_conv2<3, 1, 16, 4, 1, 2>(k, st);
-    }
-    if (geo.mt == 2) return launch_conv2<3, 1, 16, 4, 2, 1>(k, st);
-    return launch_conv2<3, 1, 16, 4, 1, 1>(k, st);
-  }
-  if (geo.dma == 3) return conv2d_wino_launch(k, geo.th, st);
-  if (geo.dma == 4) return conv2d_wino3_launch(k, geo.th, st);
-  if (geo.dma == 5) return conv2d_wino5_launch(k, geo.th, st);
-  if (geo.dma == 2) {
-    if (d.ks == 7) return geo.mt == 2 ? launch_dmarow<7, 4, 2>(k, st) : launch_dmarow<7, 4, 1>(k, st);
-    return geo.mt == 2 ? launch_dmarow<9, 4, 2>(k, st) : launch_dmarow<9, 4, 1>(k, st);
-  }
-  if (geo.dma) {
-    if (geo.th == 8) return geo.mt == 2 ? launch_dma<8, 2>(k, st) : launch_dma<8, 1>(k, st);
-    return geo.mt == 2 ? launch_dma<4, 2>(k, st) : launch_dma<4, 1>(k, st);
-  }
-  if (d.ks == 3 && geo.cc == 32) {  // K-split small-grid kernel
-    if (geo.mt == 2) return launch_ksplit<2, 1>(k, st);
-    return launch_ksplit<1, 2>(k, st);
-  }
-  if (d.ks == 3 && d.stride == 2) {
-    switch (code) {
-      case 882: return launch_conv2<3, 2, 8, 8, 2>(k, st);
-      case 842: return launch_conv2<3, 2, 8, 4, 2>(k, st);
-      case 841: return launch_conv2<3, 2, 8, 4, 1>(k, st);
-    }
-  } else
-  if (d.ks == 3) {
-    switch (code) {
-      case 882: return launch_conv2<3, 1, 8, 8, 2>(k, st);
-      case 842: return launch_conv2<3, 1, 8, 4, 2>(k, st);
-      case 841: return launch_conv2<3, 1, 8, 4, 1>(k, st);
-      case 1642: return launch_conv2<3, 1, 16, 4, 2>(k, st);
-      case 1641: return launch_conv2<3, 1, 16, 4, 1>(k, st);
-    }
-  } else if (d.ks == 2) {  // the estimator's 4x4 stride-2 convs, re-expressed over a space-to-depth input
-    switch (code) {
-      case 1642: return launch_conv2<2, 1, 16, 4, 2>(k, st);
-      case 1641: return launch_conv2<2, 1, 16, 4, 1>(k, st);
-    }
-  } else {
-    switch (code) {
-      case 3282: return launch_conv2<1, 1, 32, 8, 2>(k, st);
-      case 3242: return launch_conv2<1, 1, 32, 4, 2>(k, st);
-      case 3241: return launch_conv2<1, 1, 32, 4, 1>(k, st);
-    }
+      break;
   }
   DVSR_REQUIRE(false, DVSR_ERR_INVALID, "conv2d_packed: no kernel for ks=%d cc=%d th=%d mt=%d", d.ks, geo.cc, geo.th,
                geo.mt);
@@ -1237,8 +1189,11 @@ OpPack op_pack(int ks, int stride, int pad, int N, int Ho, int Wo, int Cout, int
   using namespace dvsr;
   OpPack o;
   const bool k3 = ks == 3 && stride == 1 && pad == 1, kbig = (ks == 7 || ks == 9) && stride == 1 && pad == ks / 2;
-  o.geo = conv2_choose(ks, stride, N, Ho, Wo, Cout, Ctot, (k3 && plain ? 1 : 0) | ((k3 || kbig) && aligned ? 2 : 0) | (k3 && aligned ? 4 | 8 : 0));
-  o.floats = (size_t)ceil_div(Cout, 64) * ceil_div(Ctot, o.geo.cc) * conv2_pch_cc(ks, o.geo.cc, 0, o.geo.dma);
+  // (every aligned 3x3 may take the Winograd kernels, F(4x4) included, whether or not autograd records the caller: these entries
+  // run plain forward-style epilogues only -- no accumulate, no gradient mask)
+  o.geo = conv2_choose(ks, stride, N, Ho, Wo, Cout, Ctot, (k3 && plain ? ALLOW_KSPLIT : ALLOW_NONE) | ((k3 || kbig) && aligned ? ALLOW_DMA_HALO : ALLOW_NONE) |
+                                                              (k3 && aligned ? ALLOW_WINO | ALLOW_WINO_F4 : ALLOW_NONE));
+  o.floats = conv2_pack_floats(ks, Cout, Ctot, o.geo);
   return o;
 }
 OpPack op_pack_for(const dvsr_conv2d_desc& d, int Cout, int Ctot) {
@@ -1253,17 +1208,13 @@ int op_run(const dvsr_conv2d_desc& d, const dvsr::ConvExtra& ex, int Cout, int C
   DVSR_REQUIRE((d.ks == 1 || d.ks == 3 || d.ks == 7 || d.ks == 9) && d.stride == 1 && d.pad == d.ks / 2, DVSR_ERR_UNSUPPORTED,
                "conv2d (packed): ks=%d stride=%d pad=%d (1x1 / 3x3 / 7x7 / 9x9, stride 1, pad ks/2)", d.ks, d.stride, d.pad);
   const OpPack o = op_pack_for(d, Cout, Ctot);
-  DVSR_REQUIRE(d.ks <= 3 || o.geo.dma == 2, DVSR_ERR_UNSUPPORTED, "conv2d (packed): this %dx%d convolution is not eligible for the "
+  DVSR_REQUIRE(d.ks <= 3 || o.geo.kernel == ConvKernel::ROW_SPLIT, DVSR_ERR_UNSUPPORTED, "conv2d (packed): this %dx%d convolution is not eligible for the "
                "row-split kernel (dvsr_conv2d_packed_geometry): use dvsr_conv2d_forward / _backward", d.ks, d.ks);
   DVSR_REQUIRE(ws && bytes >= o.floats * sizeof(float), DVSR_ERR_WORKSPACE, "conv2d (packed): workspace %zu < %zu bytes", bytes,
                o.floats * sizeof(float));
   PackTable t;
   t.n = 1;
-  PackEntry& e = t.e[0];
-  e.w = d.w; e.P = (float*)ws; e.Cout = Cout; e.Ctot = Ctot; e.KK = d.ks * d.ks; e.CC = o.geo.cc; e.wt = ex.wt;
-  e.w_ctot = ex.w_ctot; e.w_coff = ex.w_coff; e.ncb = ceil_div(Cout, 64); e.nchunks = ceil_div(Ctot, e.CC); e.bf = 0;
-  e.perm = o.geo.dma;
-  e.pch = conv2_pch_cc(d.ks, e.CC, 0, o.geo.dma);
+  t.e[0] = conv2_pack_entry(d.w, (float*)ws, d.ks, Cout, Ctot, o.geo, ex.wt, ex.w_ctot, ex.w_coff);
   int rc = pack_weights_run(t, st);
   if (rc) return rc;
   return conv2d_packed_run(d, (const float*)ws, ex, o.geo, st);
@@ -1278,8 +1229,10 @@ extern "C" size_t dvsr_conv2d_packed_workspace_bytes(const dvsr_conv2d_desc* d) 
   const size_t b = op_pack(d->ks, 1, d->ks / 2, d->N, d->H, d->W, ctot, d->Cout, true).floats;
   const size_t c = op_pack(d->ks, 1, d->ks / 2, d->N, d->H, d->W, d->Cout, ctot, false).floats;
   // (the Winograd images of a 3x3 layer: 16 transformed taps instead of 9 -- F(4x4, 3x3): 36, as two fragments each)
-  const size_t w = d->ks == 3 ? (size_t)std::max(dvsr::ceil_div(d->Cout, 64) * dvsr::ceil_div(ctot, 8), dvsr::ceil_div(ctot, 64) * dvsr::ceil_div(d->Cout, 8)) *
-                                    std::max(dvsr::conv2_pch_cc(3, 8, 0, 4), dvsr::conv2_pch_cc(3, 8, 0, 5)) : 0;
+  size_t w = 0;
+  if (d->ks == 3)
+    for (const dvsr::PackLayout l : {dvsr::PackLayout::WINO_F2_BF16, dvsr::PackLayout::WINO_F4})
+      w = std::max(w, std::max(dvsr::conv2_pack_floats(3, d->Cout, ctot, 8, 0, l), dvsr::conv2_pack_floats(3, ctot, d->Cout, 8, 0, l)));
   return std::max(std::max(a, b), std::max(c, w)) * sizeof(float);
 }
 
@@ -1287,7 +1240,7 @@ extern "C" int dvsr_conv2d_packed_geometry(const dvsr_conv2d_desc* d, int geo[4]
   DVSR_REQUIRE(d && geo && (d->ks == 1 || d->ks == 3 || d->ks == 7 || d->ks == 9) && d->stride == 1 && d->pad == d->ks / 2,
                DVSR_ERR_INVALID, "conv2d_packed_geometry: 1x1 / 3x3 / 7x7 / 9x9 stride-1 descriptors only");
   const OpPack o = op_pack_for(*d, d->Cout, d->c0 + d->c1);
-  geo[0] = o.geo.cc; geo[1] = o.geo.th; geo[2] = o.geo.mt; geo[3] = o.geo.dma;
+  geo[0] = o.geo.cc; geo[1] = o.geo.th; geo[2] = o.geo.mt; geo[3] = static_cast<int>(o.geo.kernel);
   return DVSR_OK;
 }
 

@@ -61,7 +61,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // channels writes two 128-byte runs per xn).
 __global__ void pack_weights_wino_kernel(PackTable t) {
   const PackEntry& e = t.e[blockIdx.y];
-  if (e.perm != 3) return;
+  if (e.layout != PackLayout::WINO_F2) return;
   const size_t total = (size_t)e.ncb * e.nchunks * 512;   // (cout, cin) pairs incl. padding
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int c8 = (int)(i & 7), col = (int)((i >> 3) & 63);

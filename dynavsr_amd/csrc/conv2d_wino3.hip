@@ -4,7 +4,7 @@
 //     hi*hi + hi*mid + mid*hi + hi*lo + lo*hi + mid*mid,
 // are accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (EDVR_arch.py:254-313 is what is being computed).
 //
-// History.  Round 4 built four forms of the kernel in this file (DVSR_CONV_WINO3_BLK = 0..3: V through the LDS; DESIGN 3.1f keeps
+// History.  Round 4 built four forms of the kernel in this file (a run-time switch, since removed, chose among them: V through the LDS; DESIGN 3.1f keeps
 // their description and measurements, profiles/r04_wino3_variants.txt the numbers); round 5's form 4 (conv2d_wino4.hip: the B
 // operand built in registers) replaced them as the default and round 6 RETIRED them -- two rounds without a layer on which any
 // of them won.  What remains here is what form 4 reads: the weight pack.
@@ -27,7 +27,7 @@ typedef __bf16 w3bf2 __attribute__((ext_vector_type(2)));
 // cin = k*8 + slot).  One thread = one (cout, cin) pair, as pack_weights_wino_kernel.
 __global__ void pack_weights_wino3_kernel(PackTable t) {
   const PackEntry& e = t.e[blockIdx.y];
-  if (e.perm != 4) return;
+  if (e.layout != PackLayout::WINO_F2_BF16) return;
   __bf16* const P16 = reinterpret_cast<__bf16*>(e.P);
   const size_t total = (size_t)e.ncb * e.nchunks * 512;   // (cout, cin) pairs incl. padding
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {

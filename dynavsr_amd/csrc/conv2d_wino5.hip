@@ -40,7 +40,11 @@
 // Epilogue.  Y = A^T M A.  The six nu of a row are in one wave: the column transform (6 -> 4 values) is done in registers,
 // then per cout half one exchange round through the LDS ([xi][j][register quad][lane] x 16 B = 96 KB), eight reader waves
 // (tile, 2 couts) apply the row transform, bias, activation, residual and store 16-byte output rows (PixelShuffle(2): 32);
-// a ragged last tile row stores only its rows inside the image.  Used for NO-GRAD forwards only (engine.hip: Op::geo_ng).
+// a ragged last tile row stores only its rows inside the image.
+//
+// Who runs it.  Launches that pass ALLOW_WINO_F4 to conv2_choose: the engine's NO-GRAD forward slot (engine.hip: Op::fwd[1]; a
+// training tape keeps F(2x2)) and the op-level packed entries (dvsr_conv2d_forward_packed / _dgrad_packed), which pass it for
+// every aligned 3x3 -- the TOFlow and DUF modules call those with autograd recording.
 #include <type_traits>
 
 #include "common.h"
@@ -100,7 +104,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t w5_rsrc(const float* base, int
 // (cout, cin) pair.
 __global__ void pack_weights_wino5_kernel(PackTable t) {
   const PackEntry& e = t.e[blockIdx.y];
-  if (e.perm != 5) return;
+  if (e.layout != PackLayout::WINO_F4) return;
   __bf16* const P16 = reinterpret_cast<__bf16*>(e.P);
   const size_t total = (size_t)e.ncb * e.nchunks * 512;   // (cout, cin) pairs incl. padding
   constexpr double G[6][3] = {{1.0 / 4, 0, 0},          {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},

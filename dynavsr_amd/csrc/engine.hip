@@ -66,17 +66,15 @@ struct Op {
   size_t planes = 0;
   int gB = 0, gN = 0, gC = 0;
   size_t gHW = 0;
-  // packed-weight slots (conv2d_v2.hip): forward pack in the activation arena, the two
-  // data-gradient packs in the backward-only region
-  size_t wp_off = 0, dpk_off[2] = {0, 0};
-  size_t wp_floats = 0, dpk_floats[2] = {0, 0};
-  ConvGeo geo = {8, 8, 2}, dgeo[2] = {{8, 8, 2}, {8, 8, 2}};  // launch geometry chosen at plan time
-  // NO-GRAD forwards (a workspace without the gradient region: test(), the baseline / adapted forwards of the per-frame
-  // pipeline -- Video_base_model.py:197-201) may take another kernel for the same layer: the F(4x4, 3x3) Winograd kernel
-  // (conv2d_wino5.hip).  Training tapes keep `geo`, so that everything the backward re-reads, the batched == per-frame
-  // identities and the goldens of the inner step are what they were.  ng_off == wp_off: same geometry, same pack.
-  ConvGeo geo_ng = {8, 8, 2};
-  size_t wp_ng_off = 0, wp_ng_floats = 0;
+  // packed-weight slots (conv2d_v2.hip): a launch geometry chosen at plan time and where its pack lives (floats: of ONE weight
+  // set).  Forward packs in the activation arena, the two data-gradient packs (per input) in the backward-only region.
+  struct PackSlot { ConvGeo geo = {8, 8, 2}; size_t off = 0, floats = 0; };
+  // fwd[nograd].  NO-GRAD forwards (a workspace without the gradient region: test(), the baseline / adapted forwards of the
+  // per-frame pipeline -- Video_base_model.py:197-201) may take another kernel for the same layer: the F(4x4, 3x3) Winograd
+  // kernel (conv2d_wino5.hip).  Training tapes keep fwd[0], so that everything the backward re-reads, the batched == per-frame
+  // identities and the goldens of the inner step are what they were.  fwd[1] == fwd[0] elsewhere: same geometry, same pack.
+  // (OP_DCN: fwd[0] alone, floats == 0 without a pack)
+  PackSlot fwd[2], dgrad[2];
 };
 
 // ---- backward tape -------------------------------------------------------------------------
@@ -198,24 +196,24 @@ struct Builder {
           g.th = 8;
         return g;
       };
-      // the K-split small-grid kernel takes plain inputs with an explicit pad of 1 and 32-channel chunks
-      // (bit 0), the DMA-halo kernel plain inputs in whole 8-channel chunks (bit 1)
+      // the K-split small-grid kernel takes plain inputs with an explicit pad of 1 and 32-channel chunks, the DMA-halo kernel
+      // plain inputs in whole 8-channel chunks
       const bool plain = pad < 0 && !wmap && !p.cfg.bf16_mfma;
-      // ... and the Winograd kernel where the DMA-halo kernel could run (bit 2; its epilogue stores plain or
-      // PixelShuffle(2) tiles)
-      const int ks_ok = (plain && (c1 == 0 || c0 % 32 == 0) ? 1 : 0) | (plain && c0 % 8 == 0 && c1 % 8 == 0 ? 2 | 4 : 0);
-      const int fwd_ok = (ps == 0 || (ps == 2 && !res.valid())) ? ks_ok : (ks_ok & ~4);
-      o.geo = as_bf(conv2_choose(ks, stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok), Ho, Wo, Cout);
-      o.wp_floats = (size_t)ceil_div(Cout, 64) * ceil_div(c0 + c1, o.geo.cc) * conv2_pch_cc(ks, o.geo.cc, o.geo.bf, o.geo.dma);
-      o.wp_off = alloc("", o.wp_floats * p.wsets).off;   // one pack per weight set, consecutive
-      // bit 3: the NO-GRAD forward may take the F(4x4, 3x3) kernel (never the data gradients: accumulate / mask epilogues)
-      o.geo_ng = o.geo; o.wp_ng_off = o.wp_off; o.wp_ng_floats = o.wp_floats;
-      if ((fwd_ok & 4) && !o.geo.bf) {
-        const ConvGeo g5 = conv2_choose(ks, stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok | 8);
-        if (g5.dma == 5) {
-          o.geo_ng = g5;
-          o.wp_ng_floats = (size_t)ceil_div(Cout, 64) * ceil_div(c0 + c1, g5.cc) * conv2_pch_cc(ks, g5.cc, 0, 5);
-          o.wp_ng_off = alloc("", o.wp_ng_floats * p.wsets).off;
+      // ... and the Winograd kernel where the DMA-halo kernel could run (its epilogue stores plain or PixelShuffle(2) tiles)
+      const ConvAllow ks_ok = (plain && (c1 == 0 || c0 % 32 == 0) ? ALLOW_KSPLIT : ALLOW_NONE) |
+                              (plain && c0 % 8 == 0 && c1 % 8 == 0 ? ALLOW_DMA_HALO | ALLOW_WINO : ALLOW_NONE);
+      const ConvAllow fwd_ok = (ps == 0 || (ps == 2 && !res.valid())) ? ks_ok : without(ks_ok, ALLOW_WINO);
+      o.fwd[0].geo = as_bf(conv2_choose(ks, stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok), Ho, Wo, Cout);
+      o.fwd[0].floats = conv2_pack_floats(ks, Cout, c0 + c1, o.fwd[0].geo);
+      o.fwd[0].off = alloc("", o.fwd[0].floats * p.wsets).off;   // one pack per weight set, consecutive
+      // the NO-GRAD forward may take the F(4x4, 3x3) kernel (never the data gradients: accumulate / mask epilogues)
+      o.fwd[1] = o.fwd[0];
+      if ((fwd_ok & ALLOW_WINO) && !o.fwd[0].geo.bf) {
+        const ConvGeo g5 = conv2_choose(ks, stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok | ALLOW_WINO_F4);
+        if (g5.kernel == ConvKernel::WINO_F4) {
+          o.fwd[1].geo = g5;
+          o.fwd[1].floats = conv2_pack_floats(ks, Cout, c0 + c1, g5);
+          o.fwd[1].off = alloc("", o.fwd[1].floats * p.wsets).off;
         }
       }
       for (int which = 0; which < 2; ++which) {
@@ -223,11 +221,11 @@ struct Builder {
         if (!ci) continue;
         // dgrad = stride-1 conv over the input grid with Cout' = ci, Ctot' = Cout
         // (data gradient: the gradient tensor is the plain input unless it is pixel-shuffled or zero-dilated)
-        o.dgeo[which] = as_bf(conv2_choose(ks, 1, N, H, W, ci, Cout, (!ps && stride == 1) ? ks_ok : 0), H, W, ci, true);
-        o.dpk_floats[which] = (size_t)ceil_div(ci, 64) * ceil_div(Cout, o.dgeo[which].cc) *
-                              conv2_pch_cc(ks, o.dgeo[which].cc, o.dgeo[which].bf, o.dgeo[which].dma);
-        o.dpk_off[which] = p.dpack_floats;
-        p.dpack_floats += o.dpk_floats[which] * p.wsets;
+        Op::PackSlot& dg = o.dgrad[which];
+        dg.geo = as_bf(conv2_choose(ks, 1, N, H, W, ci, Cout, (!ps && stride == 1) ? ks_ok : ALLOW_NONE), H, W, ci, true);
+        dg.floats = conv2_pack_floats(ks, ci, Cout, dg.geo);
+        dg.off = p.dpack_floats;
+        p.dpack_floats += dg.floats * p.wsets;
       }
     }
     p.ops.push_back(o);
@@ -239,8 +237,8 @@ struct Builder {
     o.N = N; o.c0 = C; o.H = H; o.W = W; o.Cout = C; o.dg = dg; o.act = act;
     o.y = alloc(name, (size_t)N * C * H * W);
     if (C % (dg * 8) == 0) {  // LDS-sampler kernel: weights packed like a conv with 8-channel chunks
-      o.wp_floats = (size_t)ceil_div(C, 64) * (C / 8) * mdcn_pack_floats();
-      o.wp_off = alloc("", o.wp_floats * p.wsets).off;
+      o.fwd[0].floats = conv2_pack_floats(3, C, C, 8, 0, PackLayout::DCN_SPLIT);   // (the larger layout: the slot fits either)
+      o.fwd[0].off = alloc("", o.fwd[0].floats * p.wsets).off;
     }
     p.ops.push_back(o);
     return o.y;
@@ -738,7 +736,7 @@ static void dgrad_desc(const dvsr_edvr_plan& p, const BOp& b, const float* const
   if (b.mask_op >= 0 && !bs.use_v1) { ex.gmask = bs.arena + p.ops[b.mask_op].y.off; ex.gmask_act = p.ops[b.mask_op].act; }
   if (o->stride == 2) { ex.in_dil = 2; ex.Hs = Ho; ex.Ws = Wo; g.H = o->H; g.W = o->W; }
   else { g.H = Ho; g.W = Wo; }
-  set_wsets(p, o->N, o->dpk_floats[b.which], 0, &ex);
+  set_wsets(p, o->N, o->dgrad[b.which].floats, 0, &ex);
   *gd = g; *exd = ex;
 }
 
@@ -790,7 +788,7 @@ static int run_backward_op(const dvsr_edvr_plan& p, const BOp& b, const float* c
       ConvExtra ex;
       dgrad_desc(p, b, P, bs, &g, &ex);
       if (bs.use_v1) return conv2d_run(g, ex, st);
-      return conv2d_packed_run(g, bs.dpack + o->dpk_off[b.which], ex, o->dgeo[b.which], st);
+      return conv2d_packed_run(g, bs.dpack + o->dgrad[b.which].off, ex, o->dgrad[b.which].geo, st);
     }
     case B_REDUCE: {
       float* dst = bs.at(b.a);
@@ -828,7 +826,7 @@ static int run_backward_op(const dvsr_edvr_plan& p, const BOp& b, const float* c
 
 struct Bases {
   float* arena; const float* x; float* out; bool use_v1;
-  bool nograd = false;   // the workspace has no gradient region: the forward may run the no-grad geometries (Op::geo_ng)
+  bool nograd = false;   // the workspace has no gradient region: the forward may run the no-grad geometries (Op::fwd[1])
   float* at(const T& t) const {
     if (t.space == SP_ARENA) return arena + t.off;
     if (t.space == SP_INPUT) return const_cast<float*>(x) + t.off;
@@ -958,14 +956,11 @@ static int pack_all(const dvsr_edvr_plan& p, const float* const* P, float* arena
   auto flush = [&]() { int rc = pack_weights_run(t, st); t.n = 0; return rc; };
   const int S = p.wsets;   // weight sets: params are [S][numel], every pack slot holds S consecutive packs
   for (const Op& o : p.ops) {
-    if (o.type == OP_DCN && fwd_base && o.wp_floats) {
+    // (table entries are reused after a flush: conv2_pack_entry writes every field)
+    if (o.type == OP_DCN && fwd_base && o.fwd[0].floats) {
       for (int ws = 0; ws < S; ++ws) {
-        PackEntry& e = t.e[t.n++];
-        e = PackEntry{};   // (slots are reused after a flush: no field may keep the previous occupant's value -- perm!)
-        e.w = P[o.pw] + (size_t)ws * o.Cout * o.c0 * 9; e.P = fwd_base + o.wp_off + (size_t)ws * o.wp_floats;
-        e.Cout = o.Cout; e.Ctot = o.c0; e.KK = 9; e.CC = 8; e.wt = 0;
-        e.w_ctot = 0; e.w_coff = 0; e.ncb = ceil_div(o.Cout, 64); e.nchunks = o.c0 / 8; e.bf = 0; e.perm = mdcn_pack_perm(o.W);
-        e.pch = e.perm == 6 ? mdcn_pack_floats() : conv2_pch(3, 1);   // (the chunk pitch of the layout; the slot fits either)
+        t.e[t.n++] = conv2_pack_entry(P[o.pw] + (size_t)ws * o.Cout * o.c0 * 9, fwd_base + o.fwd[0].off + (size_t)ws * o.fwd[0].floats,
+                                      3, o.Cout, o.c0, 8, 0, mdcn_pack_layout(o.W));
         if (t.n == 48) { int rc = flush(); if (rc) return rc; }
       }
     }
@@ -982,26 +977,17 @@ static int pack_all(const dvsr_edvr_plan& p, const float* const* P, float* arena
     }
     for (int ws = 0; ws < S; ++ws) {
       if (fwd_base) {
-        PackEntry& e = t.e[t.n++];
-        e = PackEntry{};
-        const ConvGeo& fg = nograd ? o.geo_ng : o.geo;
-        e.w = wsrc + ws * wnum; e.Cout = o.Cout; e.Ctot = ctot; e.KK = KK;
-        e.P = nograd ? fwd_base + o.wp_ng_off + (size_t)ws * o.wp_ng_floats : fwd_base + o.wp_off + (size_t)ws * o.wp_floats;
-        e.CC = fg.cc; e.wt = 0; e.w_ctot = 0; e.w_coff = 0; e.ncb = ceil_div(o.Cout, 64);
-        e.nchunks = ceil_div(ctot, e.CC); e.bf = fg.bf; e.perm = fg.dma; e.pch = conv2_pch_cc(o.ks, e.CC, e.bf, fg.dma);
+        const Op::PackSlot& f = o.fwd[nograd];
+        t.e[t.n++] = conv2_pack_entry(wsrc + ws * wnum, fwd_base + f.off + (size_t)ws * f.floats, o.ks, o.Cout, ctot, f.geo);
         if (t.n == 48) { int rc = flush(); if (rc) return rc; }
       }
       if (bwd_base) {
         for (int which = 0; which < 2; ++which) {
           const int ci = which ? o.c1 : o.c0;
           if (!ci) continue;
-          PackEntry& e = t.e[t.n++];
-          e = PackEntry{};
-          e.w = wsrc + ws * wnum; e.P = bwd_base + o.dpk_off[which] + (size_t)ws * o.dpk_floats[which]; e.Cout = ci; e.Ctot = o.Cout;
-          e.KK = KK;
-          e.CC = o.dgeo[which].cc; e.wt = 1; e.w_ctot = ctot; e.w_coff = which ? o.c0 : 0;
-          e.ncb = ceil_div(ci, 64); e.nchunks = ceil_div(o.Cout, e.CC); e.bf = o.dgeo[which].bf;
-          e.pch = conv2_pch_cc(o.ks, e.CC, e.bf, o.dgeo[which].dma); e.perm = o.dgeo[which].dma;
+          const Op::PackSlot& dg = o.dgrad[which];
+          t.e[t.n++] = conv2_pack_entry(wsrc + ws * wnum, bwd_base + dg.off + (size_t)ws * dg.floats, o.ks, ci, o.Cout, dg.geo, 1, ctot,
+                                        which ? o.c0 : 0);
           if (t.n == 48) { int rc = flush(); if (rc) return rc; }
         }
       }
@@ -1045,21 +1031,18 @@ static int run_forward_op(const dvsr_edvr_plan& p, const Op& o, const float* con
                                       p.wsets > 1 ? o.N / p.wsets : 1, p.wsets > 1 ? (long long)o.Cout * o.c0 * 9 : 0,
                                       p.wsets > 1 ? o.Cout : 0);
       ConvExtra ex;
-      if (bs.nograd) {
-        set_wsets(p, o.N, o.wp_ng_floats, o.Cout, &ex);
-        return conv2d_packed_run(d, bs.arena + o.wp_ng_off, ex, o.geo_ng, st);
-      }
-      set_wsets(p, o.N, o.wp_floats, o.Cout, &ex);
-      return conv2d_packed_run(d, bs.arena + o.wp_off, ex, o.geo, st);
+      const Op::PackSlot& f = o.fwd[bs.nograd];
+      set_wsets(p, o.N, f.floats, o.Cout, &ex);
+      return conv2d_packed_run(d, bs.arena + f.off, ex, f.geo, st);
     }
     case OP_DCN: {
       const float* om = bs.at(o.x1);
       const long long bstride = (long long)o.dg * 27 * o.H * o.W;
-      if (!bs.use_v1 && o.wp_floats)
+      if (!bs.use_v1 && o.fwd[0].floats)
         return mdcn_forward_packed_run(bs.at(o.x0), om, bstride, om + (size_t)o.dg * 18 * o.H * o.W, bstride, 1,
-                                       bs.arena + o.wp_off, P[o.pb], bs.at(o.y), o.N, o.c0, o.H, o.W, o.Cout,
+                                       bs.arena + o.fwd[0].off, P[o.pb], bs.at(o.y), o.N, o.c0, o.H, o.W, o.Cout,
                                        o.dg, o.act, st, p.wsets > 1 ? o.N / p.wsets : 1,
-                                       p.wsets > 1 ? (long long)o.wp_floats : 0, p.wsets > 1 ? o.Cout : 0, mdcn_pack_perm(o.W));
+                                       p.wsets > 1 ? (long long)o.fwd[0].floats : 0, p.wsets > 1 ? o.Cout : 0, mdcn_pack_layout(o.W));
       return mdcn_forward_run(bs.at(o.x0), om, bstride, om + (size_t)o.dg * 18 * o.H * o.W, bstride, 1,
                               P[o.pw], P[o.pb], bs.at(o.y), o.N, o.c0, o.H, o.W, o.Cout, 3, 3, 1, 1,
                               1, 1, o.dg, o.act, st);
@@ -1361,10 +1344,9 @@ extern "C" int dvsr_edvr_op_info(const dvsr_edvr_plan* p, int index, char* kind,
   if (p->ops[index].type == OP_CONV)
   {
     // (the geometry of the NO-GRAD forward -- what dvsr_edvr_forward_timed's workspace runs; a training tape's forward runs
-    // Op::geo, which differs only where the tag ends in "w5": those layers are "w3" there)
-    const ConvGeo& g = p->ops[index].geo_ng;
-    snprintf(name, name_cap, "%s[%d/%d/%d%s]", p->ops[index].name, g.cc, g.th, g.mt,
-             g.dma == 5 ? "w5" : (g.dma == 4 ? "w3" : (g.dma == 3 ? "w" : (g.dma ? "d" : ""))));
+    // Op::fwd[0], which differs only where the tag ends in "w5": those layers are "w3" there)
+    const ConvGeo& g = p->ops[index].fwd[1].geo;
+    snprintf(name, name_cap, "%s[%d/%d/%d%s]", p->ops[index].name, g.cc, g.th, g.mt, kernel_tag(g.kernel));
   }
   else
     snprintf(name, name_cap, "%s", p->ops[index].name);
@@ -1373,12 +1355,11 @@ extern "C" int dvsr_edvr_op_info(const dvsr_edvr_plan* p, int index, char* kind,
 
 // Contraction work of a whole plan, forward and backward tapes (out: NINE doubles): out[0] / out[2] = algorithmic FLOPs (2 x MACs of the direct
 // sums: convolutions and the DCN contraction; weight + data gradients for the backward), out[1] / out[3] = the same work as
-// the kernels shape it, in fp32 products -- launches on the Winograd F(2x2, 3x3) kernels (geo.dma 3, 4) do 16/36 of theirs, on
-// the F(4x4, 3x3) kernel (geo.dma 5) 36/144;
+// the kernels shape it, in fp32 products -- launches on the Winograd kernels do multiplies_per_output_ratio() of theirs;
 // out[4] = algorithmic bytes of the forward tape.  out[5] / out[7] = FLOPs ISSUED to the fp32 matrix pipe
 // (v_mfma_f32_32x32x2_f32), out[6] / out[8] = FLOPs ISSUED to the bf16 matrix pipe (v_mfma_f32_32x32x16_bf16) by the forward /
 // backward tape: a launch on the exact 3-way operand split issues SIX bf16 products per fp32 product (geo.bf == 2, the
-// Winograd bf16x3 kernels geo.dma == 4 / 5, the split3 weight gradient), a plain bf16 launch (geo.bf == 1) one.  bench.py prices
+// Winograd bf16x3 kernels -- on_bf16_split() --, the split3 weight gradient), a plain bf16 launch (geo.bf == 1) one.  bench.py prices
 // every roofline fraction with the issued figures against the peak of the pipe they were issued to.
 static int plan_work(const dvsr_edvr_plan* p, double* out9, bool nograd) {
   DVSR_REQUIRE(p && out9, DVSR_ERR_INVALID, "edvr_plan_work: null argument");
@@ -1388,10 +1369,9 @@ static int plan_work(const dvsr_edvr_plan* p, double* out9, bool nograd) {
   };
   // one conv-shaped launch: f algorithmic FLOPs on geometry g -> (fp32 products done, pipe they go to)
   auto issue = [&](const ConvGeo& g, double f, double* ex, int pass) {
-    // (F(2x2, 3x3): 16 multiplies per 2x2 outputs instead of 36; F(4x4, 3x3), geo.dma == 5: 36 per 4x4 outputs instead of 144)
-    const double shaped = g.dma == 5 ? f * 0.25 : (g.dma >= 3 ? f * (16.0 / 36.0) : f);
+    const double shaped = f * multiplies_per_output_ratio(g.kernel);
     *ex += shaped;
-    if (g.dma == 4 || g.dma == 5 || g.bf == 2) bfp[pass] += 6.0 * shaped;
+    if (on_bf16_split(g.kernel) || g.bf == 2) bfp[pass] += 6.0 * shaped;
     else if (g.bf == 1) bfp[pass] += shaped;
     else f32p[pass] += shaped;
   };
@@ -1403,7 +1383,7 @@ static int plan_work(const dvsr_edvr_plan* p, double* out9, bool nograd) {
     }
     if (o.type == OP_CONV) {
       const double f = conv_part(o, o.c0 + o.c1);
-      fa += f; issue(nograd ? o.geo_ng : o.geo, f, &fe, 0);
+      fa += f; issue(o.fwd[nograd].geo, f, &fe, 0);
     } else if (o.type == OP_DCN) {
       const double f = 2.0 * (double)o.N * o.H * o.W * o.Cout * o.c0 * 9;
       fa += f; fe += f; f32p[0] += f;
@@ -1421,7 +1401,7 @@ static int plan_work(const dvsr_edvr_plan* p, double* out9, bool nograd) {
       if (bf == 2) bfp[1] += 6.0 * f; else if (bf == 1) bfp[1] += f; else f32p[1] += f;
     } else if (b.type == B_DGRAD) {
       const double f = conv_part(o, b.which ? o.c1 : o.c0);
-      ba += f; issue(o.dgeo[b.which], f, &be, 1);
+      ba += f; issue(o.dgrad[b.which].geo, f, &be, 1);
     } else if (b.type == B_DCN) {
       const double f = 2.0 * 2.0 * (double)o.N * o.H * o.W * o.Cout * o.c0 * 9;   // dcol + dW
       ba += f; be += f; f32p[1] += f;
@@ -1433,7 +1413,7 @@ static int plan_work(const dvsr_edvr_plan* p, double* out9, bool nograd) {
   return DVSR_OK;
 }
 extern "C" int dvsr_edvr_plan_work(const dvsr_edvr_plan* p, double* out9) { return plan_work(p, out9, false); }
-// ... with the forward tape priced as a NO-GRAD forward runs it (Op::geo_ng: the F(4x4, 3x3) kernel where the plan takes it)
+// ... with the forward tape priced as a NO-GRAD forward runs it (Op::fwd[1]: the F(4x4, 3x3) kernel where the plan takes it)
 extern "C" int dvsr_edvr_plan_work_nograd(const dvsr_edvr_plan* p, double* out9) { return plan_work(p, out9, true); }
 
 // Same launches as dvsr_edvr_forward with a hipEvent recorded on `stream` around every launch;

@@ -25,31 +25,80 @@ int mdcn_forward_run(const float* x, const float* off, long long off_bs, const f
                      int dil, int groups, int dg, int act, hipStream_t st);
 
 // conv2d_v2.hip: pipelined kernel over pre-packed weights
+// The kernel family a packed convolution launches on.  The values are ABI: dvsr_conv2d_packed_geometry writes them to geo[3].
+enum class ConvKernel : int {
+  REG = 0,        // register-staged halo (conv2d_pipe_kernel; with 32-channel chunks of a 3x3: the K-split small-grid kernel)
+  DMA_HALO = 1,   // halo by LDS-DMA (conv2d_dma_kernel): plain pad-1 3x3 inputs on a 16-byte column grid, whole 8-channel chunks
+  ROW_SPLIT = 2,  // row-split 7x7 / 9x9 (conv2d_dmarow_kernel)
+  WINO_F2 = 3,    // Winograd F(2x2, 3x3) on the fp32 pipe (conv2d_wino.hip; th = 4: 4x64-pixel tiles, th = 8: 8x32)
+  WINO_F2_BF16 = 4,  // the same on the bf16 pipe, exact 3-way operand split (conv2d_wino3.hip / conv2d_wino4.hip; also th = 16: 16x16)
+  WINO_F4 = 5,    // Winograd F(4x4, 3x3) on the bf16 pipe (conv2d_wino5.hip; th = 8: 8x64-pixel workgroup tiles, th = 16: 16x32)
+};
+// The layout of a weight pack: the ConvKernel values (a pack is made for the kernel that reads it) plus the DCN split's own.
+enum class PackLayout : int {
+  INTERLEAVED = 0,   // channel c = 2kk + hi of the chunk (register-staged halo image)
+  DMA_ORDER = 1,     // 4 consecutive channels per lane half (the planar DMA-staged halo image)
+  ROW_SPLIT = 2,     // DMA_ORDER; the taps of a kernel row are contiguous anyway
+  WINO_F2 = 3,       // Winograd-transformed image (conv2d_wino.hip)
+  WINO_F2_BF16 = 4,  // the same as three bf16 pieces (conv2d_wino3.hip)
+  WINO_F4 = 5,       // the F(4x4, 3x3) image of conv2d_wino5.hip
+  DCN_SPLIT = 6,     // three bf16 pieces of the deformable conv's weights (mdcn_split.hip)
+};
+constexpr PackLayout pack_layout(ConvKernel k) { return static_cast<PackLayout>(static_cast<int>(k)); }
+// What the kernels have in common, stated once:
+constexpr bool is_winograd(ConvKernel k) { return k == ConvKernel::WINO_F2 || k == ConvKernel::WINO_F2_BF16 || k == ConvKernel::WINO_F4; }
+constexpr bool on_bf16_split(ConvKernel k) { return k == ConvKernel::WINO_F2_BF16 || k == ConvKernel::WINO_F4; }   // six bf16 products per fp32 one
+// (3x3 / s1 / pad 1 over plain 16-byte aligned inputs, W % 4 == 0, whole 8-channel chunks: conv2d_packed_prepare)
+constexpr bool needs_dma_halo_inputs(ConvKernel k) { return k == ConvKernel::DMA_HALO || is_winograd(k); }
+// fp32 products per product of the direct sum: F(2x2, 3x3) does 16 multiplies per 2x2 outputs instead of 36, F(4x4, 3x3) 36 per
+// 4x4 outputs instead of 144
+constexpr double multiplies_per_output_ratio(ConvKernel k) { return k == ConvKernel::WINO_F4 ? 0.25 : (is_winograd(k) ? 16.0 / 36.0 : 1.0); }
+constexpr const char* kernel_tag(ConvKernel k) {   // dvsr_edvr_op_info
+  return k == ConvKernel::WINO_F4 ? "w5" : (k == ConvKernel::WINO_F2_BF16 ? "w3" : (k == ConvKernel::WINO_F2 ? "w" : (k == ConvKernel::REG ? "" : "d")));
+}
+// layouts written by a pack kernel of their own (pack_weights_wino*_kernel, pack_weights_dcn3_kernel), not by pack_weights_kernel
+// (the enum lists those last; one signed compare in pack_weights_kernel, as before the layouts had names)
+constexpr bool has_own_pack_kernel(PackLayout l) { return static_cast<int>(l) >= static_cast<int>(PackLayout::WINO_F2); }
+
 struct PackEntry {
   const float* w; float* P;
   int Cout, Ctot, KK, CC, wt, w_ctot, w_coff, ncb, nchunks, pch;
   int bf = 0;  // 1: bf16 image for the bf16 MFMA kernel (pch still counts fp32-sized slots)
-  int perm = 0;  // 1: channel order of the DMA-halo kernel (ConvGeo::dma); 3: Winograd-transformed image (conv2d_wino.hip);
-                 // 4: the same as three bf16 pieces (conv2d_wino3.hip); 5: the F(4x4, 3x3) image of conv2d_wino5.hip
+  PackLayout layout = PackLayout::INTERLEAVED;
 };
 struct PackTable {
   int n;
   PackEntry e[48];
 };
-int conv2_pch(int ks, int stride);  // floats per packed (cout block, chunk)
-int conv2_cc(int ks, int stride);   // input channels per chunk
 int pack_weights_run(const PackTable& t, hipStream_t st);
-// channels per chunk, tile rows (x32 px), 32-cout halves per workgroup; dma: 1 DMA-halo kernel, 2 row-split 7x7 / 9x9,
-// 3 Winograd F(2x2, 3x3) kernel (th = 4: 4x64-pixel tiles, th = 8: 8x32), 4 the same on the bf16 pipe (exact 3-way split),
-// 5 Winograd F(4x4, 3x3) on the bf16 pipe (conv2d_wino5.hip; th = 8: 8x64-pixel workgroup tiles, th = 16: 16x32)
-struct ConvGeo { int cc, th, mt; int bf = 0; int dma = 0; };
-// allow: bit 0 = the K-split small-grid kernel may be chosen, bit 1 = the DMA-halo kernel (plain pad-1 inputs, see conv2d_v2.hip),
-// bit 2 = the Winograd kernel (bit 1's conditions + an epilogue it implements: plain or PixelShuffle(2) stores)
-ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ctot, int allow_ksplit = 1);
-int conv2_pch_cc(int ks, int cc, int bf = 0, int dma = 0);   // fp32-sized slots per packed (64-cout block, chunk of cc channels)
-int pack_weights_wino_run(const PackTable& t, hipStream_t st);   // conv2d_wino.hip: entries with perm == 3
-int pack_weights_wino3_run(const PackTable& t, hipStream_t st);  // conv2d_wino3.hip: entries with perm == 4
-int pack_weights_wino5_run(const PackTable& t, hipStream_t st);  // conv2d_wino5.hip: entries with perm == 5 (F(4x4, 3x3))
+// channels per chunk, tile rows (x32 px), 32-cout halves per workgroup, bf16 mode (1 plain, 2 exact 3-way split), kernel family
+struct ConvGeo { int cc, th, mt; int bf = 0; ConvKernel kernel = ConvKernel::REG; };
+// What a launch's tensors let conv2_choose pick, beyond the register-staged kernel that takes everything:
+enum ConvAllow : int {
+  ALLOW_NONE = 0,
+  ALLOW_KSPLIT = 1,    // the K-split small-grid kernel (plain inputs, explicit pad of 1, 32-channel chunks)
+  ALLOW_DMA_HALO = 2,  // the DMA-halo / row-split kernels (needs_dma_halo_inputs)
+  ALLOW_WINO = 4,      // the Winograd F(2x2) kernels: ALLOW_DMA_HALO's conditions + an epilogue they implement (plain or PixelShuffle(2) stores)
+  ALLOW_WINO_F4 = 8,   // the F(4x4) kernel: ALLOW_WINO's + a forward epilogue (no accumulate / gradient mask)
+};
+constexpr ConvAllow operator|(ConvAllow a, ConvAllow b) { return static_cast<ConvAllow>(static_cast<int>(a) | static_cast<int>(b)); }
+constexpr ConvAllow without(ConvAllow a, ConvAllow b) { return static_cast<ConvAllow>(static_cast<int>(a) & ~static_cast<int>(b)); }
+ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ctot, ConvAllow allow = ALLOW_KSPLIT);
+// THE rule for a weight pack: its floats, and the table entry that makes pack_weights_run write it at P.  (cc, bf, layout) is
+// what of a geometry shapes its pack; the DCN packs have no ConvGeo and say it directly.
+size_t conv2_pack_floats(int ks, int Cout, int Ctot, int cc, int bf, PackLayout layout);
+PackEntry conv2_pack_entry(const float* w, float* P, int ks, int Cout, int Ctot, int cc, int bf, PackLayout layout, int wt = 0,
+                           int w_ctot = 0, int w_coff = 0);
+inline size_t conv2_pack_floats(int ks, int Cout, int Ctot, const ConvGeo& g) {
+  return conv2_pack_floats(ks, Cout, Ctot, g.cc, g.bf, pack_layout(g.kernel));
+}
+inline PackEntry conv2_pack_entry(const float* w, float* P, int ks, int Cout, int Ctot, const ConvGeo& g, int wt = 0, int w_ctot = 0,
+                                  int w_coff = 0) {
+  return conv2_pack_entry(w, P, ks, Cout, Ctot, g.cc, g.bf, pack_layout(g.kernel), wt, w_ctot, w_coff);
+}
+int pack_weights_wino_run(const PackTable& t, hipStream_t st);   // conv2d_wino.hip: PackLayout::WINO_F2 entries
+int pack_weights_wino3_run(const PackTable& t, hipStream_t st);  // conv2d_wino3.hip: PackLayout::WINO_F2_BF16 entries
+int pack_weights_wino5_run(const PackTable& t, hipStream_t st);  // conv2d_wino5.hip: PackLayout::WINO_F4 entries
 int conv2d_packed_run(const dvsr_conv2d_desc& d, const float* wp, const ConvExtra& ex, const ConvGeo& geo,
                       hipStream_t st);
 
@@ -90,16 +139,16 @@ int mdcn_backward_run(const float* x, const float* off, long long off_bs, const 
                       size_t ws_bytes, hipStream_t st, int groups = 1, long long gw_gs = 0, long long gb_gs = 0,
                       long long w_gs = 0);  // w_gs != 0: group g of the batch convolves with w + g * w_gs (per-sample weights)
 
-// pack_perm: the layout `wp` is in -- 0 the fp32 conv pack (pack_weights_kernel, 8-channel chunks), 6 the three bf16 pieces of
-// mdcn_split.hip; whoever makes the pack asks mdcn_pack_perm(W) and hands the answer back here.
+// layout: the one `wp` is in -- INTERLEAVED the fp32 conv pack (pack_weights_kernel, 8-channel chunks), DCN_SPLIT the three bf16
+// pieces of mdcn_split.hip; whoever makes the pack asks mdcn_pack_layout(W) and hands the answer back here.
 int mdcn_forward_packed_run(const float* x, const float* off, long long off_bs, const float* msk,
                             long long msk_bs, int mask_logit, const float* wp, const float* b, float* out,
                             int N, int C, int H, int W, int Cout, int dg, int act, hipStream_t st, int wdiv = 1,
-                            long long w_gs = 0, int b_gs = 0, int pack_perm = 0);
+                            long long w_gs = 0, int b_gs = 0, PackLayout layout = PackLayout::INTERLEAVED);
 int mdcn_fwd_variant();      // DVSR_DCN_FWD, read once: 3 split (default), 0 dma, 2 reg
-int mdcn_pack_floats();      // fp32-sized slots per (64-cout block, 8-channel chunk) of a DCN weight pack (either layout fits)
-int mdcn_pack_perm(int W);   // PackEntry::perm of a DCN weight pack for images of width W
-int pack_weights_dcn3_run(const PackTable& t, hipStream_t st);   // mdcn_split.hip: entries with perm == 6
+int mdcn_pack_floats();      // fp32-sized slots per (64-cout block, 8-channel chunk) of a PackLayout::DCN_SPLIT pack
+PackLayout mdcn_pack_layout(int W);   // PackEntry::layout of a DCN weight pack for images of width W
+int pack_weights_dcn3_run(const PackTable& t, hipStream_t st);   // mdcn_split.hip: PackLayout::DCN_SPLIT entries
 
 struct DcnK2 {
   const float* x; const float* off; const float* msk; const float* wp; const float* bias; float* out;

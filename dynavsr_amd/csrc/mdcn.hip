@@ -825,7 +825,7 @@ __global__ __launch_bounds__(256, 2) void mdcn_fwd_dma_kernel(DcnK2 a) {
 int mdcn_forward_packed_run(const float* x, const float* off, long long off_bs, const float* msk,
                             long long msk_bs, int mask_logit, const float* wp, const float* b, float* out,
                             int N, int C, int H, int W, int Cout, int dg, int act, hipStream_t st, int wdiv,
-                            long long w_gs, int b_gs, int pack_perm) {
+                            long long w_gs, int b_gs, PackLayout layout) {
   DVSR_REQUIRE(x && off && msk && wp && out, DVSR_ERR_INVALID, "mdcn_forward_packed: null pointer");
   DVSR_REQUIRE(dg > 0 && C % (dg * 8) == 0, DVSR_ERR_UNSUPPORTED,
                "mdcn_forward_packed: needs C/dg to be a multiple of 8 (got %d/%d)", C, dg);
@@ -842,13 +842,13 @@ int mdcn_forward_packed_run(const float* x, const float* off, long long off_bs, 
 #endif
   const int grid = ceil_div(k.ntiles, 8) * 8 * k.ncb;
   // DVSR_DCN_FWD: (default) the contraction on the bf16 pipe under the exact 3-way split (mdcn_split.hip; the pack is in its
-  // own layout, mdcn_pack_perm()); dma = the fp32-MFMA DMA-staged kernel below, reg = its register-staged form (A/B aids; reg
+  // own layout, mdcn_pack_layout()); dma = the fp32-MFMA DMA-staged kernel below, reg = its register-staged form (A/B aids; reg
   // is also what unaligned tensors run).  Read once per process: the packs and the kernels must agree.
   const int variant = mdcn_fwd_variant();
   // DMA-staged kernel when the 16-byte groups line up (DVSR_DCN_FWD=reg keeps the register-staged one, A/B aid)
   const bool aligned = W % 4 == 0 && (((uintptr_t)x | (uintptr_t)off | (uintptr_t)msk) & 15) == 0 && off_bs % 4 == 0 &&
                        msk_bs % 4 == 0;
-  if (pack_perm == 6) {   // the pack is in the split kernel's layout (mdcn_pack_perm: chosen where the pack was made)
+  if (layout == PackLayout::DCN_SPLIT) {   // the pack is in the split kernel's layout (mdcn_pack_layout: chosen where the pack was made)
     DVSR_REQUIRE(aligned, DVSR_ERR_UNSUPPORTED, "mdcn_forward_packed: the split kernel needs W %% 4 == 0 and 16-byte aligned tensors (W=%d)", W);
     return mdcn_fwd_split_launch(k, grid, mask_logit, st);
   }
@@ -873,7 +873,7 @@ int mdcn_forward_packed_run(const float* x, const float* off, long long off_bs, 
 // Same contract as dvsr_mdcn_forward restricted to stride = pad = dil = 1, C/dg = 8.
 extern "C" size_t dvsr_mdcn_forward_fast_workspace_bytes(int C, int Cout, int dg) {
   (void)dg;
-  return (size_t)dvsr::ceil_div(Cout, 64) * dvsr::ceil_div(C, 8) * dvsr::mdcn_pack_floats() * sizeof(float);
+  return dvsr::conv2_pack_floats(3, Cout, C, 8, 0, dvsr::PackLayout::DCN_SPLIT) * sizeof(float);   // (the larger layout: either fits)
 }
 
 extern "C" int dvsr_mdcn_forward_fast(const float* x, const float* offset, const float* mask, const float* w,
@@ -884,17 +884,15 @@ extern "C" int dvsr_mdcn_forward_fast(const float* x, const float* offset, const
   DVSR_REQUIRE(dg > 0 && C % (dg * 8) == 0, DVSR_ERR_UNSUPPORTED, "mdcn_forward_fast: needs C/dg to be a multiple of 8");
   DVSR_REQUIRE(workspace_bytes >= dvsr_mdcn_forward_fast_workspace_bytes(C, Cout, dg), DVSR_ERR_WORKSPACE,
                "mdcn_forward_fast: workspace too small");
+  const bool aligned = (((uintptr_t)x | (uintptr_t)offset | (uintptr_t)mask) & 15) == 0 && ((size_t)H * W) % 4 == 0;
+  // (unaligned tensors: the register-staged fp32 kernel and its pack)
+  const PackLayout layout = aligned ? mdcn_pack_layout(W) : PackLayout::INTERLEAVED;
   PackTable t;
   t.n = 1;
-  PackEntry& e = t.e[0];
-  e.w = w; e.P = (float*)workspace; e.Cout = Cout; e.Ctot = C; e.KK = 9; e.CC = 8; e.wt = 0; e.w_ctot = 0;
-  const bool aligned = (((uintptr_t)x | (uintptr_t)offset | (uintptr_t)mask) & 15) == 0 && ((size_t)H * W) % 4 == 0;
-  e.w_coff = 0; e.ncb = ceil_div(Cout, 64); e.nchunks = C / 8; e.bf = 0;
-  e.perm = aligned ? mdcn_pack_perm(W) : 0;   // (unaligned tensors: the register-staged fp32 kernel and its pack)
-  e.pch = e.perm == 6 ? mdcn_pack_floats() : conv2_pch(3, 1);   // the chunk pitch of the layout (the workspace fits either)
+  t.e[0] = conv2_pack_entry(w, (float*)workspace, 3, Cout, C, 8, 0, layout);
   int rc = pack_weights_run(t, (hipStream_t)stream);
   if (rc) return rc;
   const long long P = (long long)H * W;
   return mdcn_forward_packed_run(x, offset, (long long)dg * 18 * P, mask, (long long)dg * 9 * P, 0,
-                                 (const float*)workspace, b, out, N, C, H, W, Cout, dg, act, (hipStream_t)stream, 1, 0, 0, e.perm);
+                                 (const float*)workspace, b, out, N, C, H, W, Cout, dg, act, (hipStream_t)stream, 1, 0, 0, layout);
 }

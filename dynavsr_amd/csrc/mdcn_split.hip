@@ -38,7 +38,7 @@ int mdcn_fwd_variant() {
   return variant;
 }
 int mdcn_pack_floats() { return 6912; }   // 9 taps x 3 pieces x 64 couts x 8 channels bf16 (the fp32 pack needs 4608)
-int mdcn_pack_perm(int W) { return (mdcn_fwd_variant() == 3 && W % 4 == 0) ? 6 : 0; }
+PackLayout mdcn_pack_layout(int W) { return (mdcn_fwd_variant() == 3 && W % 4 == 0) ? PackLayout::DCN_SPLIT : PackLayout::INTERLEAVED; }
 
 typedef float ds2f __attribute__((ext_vector_type(2)));
 typedef __bf16 dsbf2 __attribute__((ext_vector_type(2)));
@@ -48,7 +48,7 @@ typedef unsigned dsu4 __attribute__((ext_vector_type(4)));
 // P16[cb][k][tap][piece][cout 64][slot 8] = piece of W(cout = cb*64 + col, cin = k*8 + slot, tap)
 __global__ void pack_weights_dcn3_kernel(PackTable t) {
   const PackEntry& e = t.e[blockIdx.y];
-  if (e.perm != 6) return;
+  if (e.layout != PackLayout::DCN_SPLIT) return;
   __bf16* const P16 = reinterpret_cast<__bf16*>(e.P);
   const size_t total = (size_t)e.ncb * e.nchunks * 9 * 512;   // (tap, cout, slot) triples incl. padding
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {

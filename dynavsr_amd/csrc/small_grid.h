@@ -71,10 +71,10 @@ int conv2d_wgrad_prepare(const float* x, long long x_bs, int x_bdiv, const float
                          size_t ws_bytes, hipStream_t st, int scratch_is_zero, int pad, WgradReduceEntry* defer,
                          WgradLaunch* out, int bf16 = 0, int groups = 1, long long dW_gs = 0, long long db_gs = 0);
 int conv2d_wgrad_launch(const WgradLaunch& l, hipStream_t st);
-int conv2d_wino_launch(const ConvK2& k, int th, hipStream_t st);   // conv2d_wino.hip (ConvGeo::dma == 3)
-int conv2d_wino3_launch(const ConvK2& k, int th, hipStream_t st);  // conv2d_wino3.hip (ConvGeo::dma == 4)
+int conv2d_wino_launch(const ConvK2& k, int th, hipStream_t st);   // conv2d_wino.hip (ConvKernel::WINO_F2)
+int conv2d_wino3_launch(const ConvK2& k, int th, hipStream_t st);  // conv2d_wino3.hip (ConvKernel::WINO_F2_BF16)
 int conv2d_wino4_launch(const ConvK2& k, int th, hipStream_t st);  // conv2d_wino4.hip (the same image, B operand in registers)
-int conv2d_wino5_launch(const ConvK2& k, int th, hipStream_t st);  // conv2d_wino5.hip (ConvGeo::dma == 5: F(4x4, 3x3), th = 8 | 16)
+int conv2d_wino5_launch(const ConvK2& k, int th, hipStream_t st);  // conv2d_wino5.hip (ConvKernel::WINO_F4: F(4x4, 3x3), th = 8 | 16)
 int conv2d_wgrad_bf16_launch(const WgradLaunch& l, hipStream_t st);
 int conv2d_wgrad_split3_launch(const WgradLaunch& l, hipStream_t st);   // bf = 2: exact 3-way bf16 split (fp32 accuracy)
 
