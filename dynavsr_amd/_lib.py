@@ -164,6 +164,14 @@ def _declare(lib):
         "dvsr_side_stream_overlaps": (I, [P]),
         "dvsr_edvr_op_output": (I, [P, I, I, POINTER(c_int), POINTER(LL), POINTER(LL)]),
         "dvsr_estimator_plan_work": (I, [P, POINTER(ctypes.c_double * 9)]),
+        "dvsr_edvr_stream_create": (I, [POINTER(EdvrConfig), I, I, I, POINTER(c_void_p)]),
+        "dvsr_edvr_stream_destroy": (None, [P]),
+        "dvsr_edvr_stream_num_params": (I, [P]),
+        "dvsr_edvr_stream_num_launches": (I, [P, I]),
+        "dvsr_edvr_stream_cache_bytes": (c_size_t, [P]),
+        "dvsr_edvr_stream_workspace_bytes": (c_size_t, [P]),
+        "dvsr_edvr_stream_extract": (I, [P, POINTER(c_void_p), P, I, P, c_size_t, P, c_size_t, I, P]),
+        "dvsr_edvr_stream_fuse": (I, [P, POINTER(c_void_p), POINTER(c_int), P, c_size_t, P, P, c_size_t, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

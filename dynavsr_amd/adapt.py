@@ -759,3 +759,125 @@ def _adapt_video_batched(opt, model, est_model, modelcp, est_modelcp, est_model_
         ci += 1
     if pending is not None:
         yield from hand_out(pending)
+
+
+def stream_schedule(T, nframes, padding='new_info', in_flight=2):
+    """The frame-cache schedule of super_resolve_frames, as pure Python: for every centre frame 0 .. T - 1 yields
+    (centre, frames_to_extract, [(frame, slot), ...], window_slots).
+
+    The window of a centre is data.util.index_generation(centre, T, nframes, padding).  A frame is extracted when a
+    window first needs it; frames go in increasing order, each exactly once (a window that needs frame f finds 0 .. f
+    extracted), frame f into slot f % slots of a cache of slots = nframes + in_flight - 1.  That capacity is enough for
+    the four padding modes: a frame is overwritten nframes + in_flight - 1 frames later, when neither the current window,
+    nor the in_flight - 1 before it that may still be running, nor any later one names it (tests/test_stream_schedule.py
+    simulates it).  window_slots are the cache slots of the window's frames, in window order.
+    T < nframes is accepted only where every window stays inside [0, T); otherwise ValueError, where the reference would
+    index past the end of its frame list."""
+    from .data.util import index_generation
+    T, nframes, in_flight = int(T), int(nframes), int(in_flight)
+    if T < 1 or nframes < 1 or in_flight < 1:
+        raise ValueError("stream_schedule: T=%d, nframes=%d, in_flight=%d must be positive" % (T, nframes, in_flight))
+    windows = [index_generation(c, T, nframes, padding) for c in range(T)]
+    for c, win in enumerate(windows):
+        if min(win) < 0 or max(win) >= T:
+            raise ValueError("stream_schedule: %d frames are too few for windows of %d under padding %r (centre %d would "
+                             "read frames %s)" % (T, nframes, padding, c, win))
+    slots = nframes + in_flight - 1
+    done = 0                       # frames 0 .. done - 1 are extracted
+    for c, win in enumerate(windows):
+        new = list(range(done, max(done, max(win) + 1)))
+        done += len(new)
+        yield c, new, [(f, f % slots) for f in new], [f % slots for f in win]
+
+
+def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2):
+    """Super-resolves a VIDEO: `frames` is a [T,3,H,W] tensor or a list of [3,H,W] frames (CPU or GPU); yields the SR frame
+    [1,3,sH,sW] of every frame, in order -- what `net(frames[index_generation(i, T, nframes, padding)][None])` gives, the
+    sliding-window test of the reference's video datasets (video_test_dataset_int.py:219, `padding: new_info` in the
+    shipped YAMLs), without the caller cutting clips.
+
+    EDVR: consecutive windows share all but one frame, and everything up to L3_fea depends on one frame alone, so every
+    frame's L1 / L2 / L3 features are extracted ONCE into a cache of nframes + in_flight - 1 slots (engine.StreamPlan,
+    stream_schedule) and each window runs one gather launch + the tape from PCD alignment on.  `in_flight` windows are on
+    the GPU at a time, one HIP stream each (the caller's and _clip_streams' further ones); a window's extractions run on
+    its own stream.  Two kinds of events order the cache: frame extracted -> the windows that gather it, and window done
+    -> the extraction that overwrites one of its slots (the cache is read by the gather alone, at the start of a window;
+    by stream_schedule's capacity the windows concerned finished long before).  Extraction at batch 1 may pick other kernel
+    kinds than the batch of a whole clip, so results match the per-clip forward at the parity bar, not bit for bit; they
+    do not depend on in_flight.
+    Any other network (TOFlow, DUF): the windows are built here and run by super_resolve_video -- same interface, no cache.
+    A yielded frame stays valid until the generator is advanced `in_flight` times; frames and results are ordered against
+    the caller's current stream."""
+    from .data.util import index_generation
+    from .models.archs.EDVR_arch import EDVR
+    T = len(frames)
+    in_flight = max(1, int(in_flight))
+    if not isinstance(net, EDVR):
+        n = int(opt['network_G']['nframes']) if (opt.get('network_G') or {}).get('nframes') else int(net.nframes)
+        sched = list(stream_schedule(T, n, padding, 1))            # (validates T and the mode)
+
+        def clips():
+            for c, _, _, _ in sched:
+                yield torch.stack([frames[j] for j in index_generation(c, T, n, padding)])[None]
+        yield from super_resolve_video(opt, net, clips(), in_flight)
+        return
+    leaves = net.ordered_parameters()
+    dev = leaves[0].device
+    if dev.type != 'cuda':
+        raise RuntimeError("dynavsr_amd EDVR runs on the MI355X only (the network is on %s); there is no CPU fallback" % dev)
+    sched = list(stream_schedule(T, net.nframes, padding, in_flight))
+    if tuple(frames[0].shape[-3:-2]) != (3,):
+        raise RuntimeError("super_resolve_frames expects frames [3,H,W], got %s" % (tuple(frames[0].shape),))
+    h, w = int(frames[0].shape[-2]), int(frames[0].shape[-1])
+    plan = engine.get_stream_plan(net._cfg(), h, w, net.nframes + in_flight - 1, dev)
+    main = torch.cuda.current_stream(dev)
+    streams = _clip_streams(dev, in_flight)
+    with torch.cuda.device(dev):
+        cache = plan.new_cache(dev)
+    for s in streams[1:]:
+        cache.record_stream(s)
+    extracted, readers, pending = {}, {}, []   # slot -> event of its extraction; slot -> events of the windows reading it
+    was_training = net.training
+    net.eval()
+    try:
+        for step, (centre, _, new, wslots) in enumerate(sched):
+            if len(pending) == len(streams):
+                sr, ev = pending.pop(0)
+                main.wait_event(ev)
+                sr.record_stream(main)
+                yield sr
+            s = streams[step % len(streams)]
+            if s != main:
+                s.wait_stream(main)                  # the frames (and the weights) were produced on the caller's stream
+            with torch.cuda.stream(s), torch.no_grad():
+                for f, slot in new:
+                    x = frames[f]
+                    x = engine._prep(x if x.is_cuda else x.to(dev))
+                    for ev in readers.pop(slot, ()):
+                        s.wait_event(ev)
+                    plan.extract(leaves, x, slot, cache)
+                    extracted[slot] = torch.cuda.Event()
+                    extracted[slot].record(s)
+                    if s != main:
+                        x.record_stream(s)
+                for slot in set(wslots):
+                    s.wait_event(extracted[slot])
+                sr = torch.empty((1, 3, net.scale * h, net.scale * w), dtype=torch.float32, device=dev)
+                plan.fuse(leaves, wslots, cache, sr)
+                ev = torch.cuda.Event()
+                ev.record(s)
+            for slot in set(wslots):
+                readers.setdefault(slot, []).append(ev)
+            pending.append((sr, ev))
+        while pending:
+            sr, ev = pending.pop(0)
+            main.wait_event(ev)
+            sr.record_stream(main)
+            yield sr
+    finally:
+        # a generator closed early leaves windows running on the side streams: whatever the caller does next on its stream
+        # (an update of the weights they read, the release of the cache) must come behind them
+        for sr, ev in pending:
+            main.wait_event(ev)
+            sr.record_stream(main)
+        net.train(was_training)

@@ -270,7 +270,29 @@ struct Builder {
 
 // Walks the network in forward order; parameters are consumed in state-dict order, which is
 // NOT forward order inside PCD/TSA, hence the explicit index bookkeeping there.
-static int build_plan(dvsr_edvr_plan& p) {
+//
+// The streaming forward (dvsr_edvr_stream) takes the SAME walk in two parts, split at L3_fea -- the last launch that depends
+// on one frame alone:
+//   PART_EXTRACT: the feature extraction of ONE frame; its three results go straight into a slot of the frame cache
+//                 (SP_OUTPUT = the slot, laid out by slot_layout), the walk stops after L3_fea;
+//   PART_FUSE:    B = 1; L1_fea / L2_fea / L3_fea are plain arena slots that the window gather fills (stream_gather.hip), the
+//                 extraction's parameters are skipped, everything from L3_offset_conv1 on is the whole tape's op list, and
+//                 SP_INPUT is the centre frame alone (conv_last's bilinear base is its only reader).
+enum PlanPart { PART_WHOLE = 0, PART_EXTRACT = 1, PART_FUSE = 2 };
+
+// One slot of the frame cache, in floats: [L1_fea | L2_fea | L3_fea | the frame], every section 256-byte aligned like an arena slot.
+struct SlotLayout { size_t off[3], numel[3], raw, floats; };
+static SlotLayout slot_layout(int C, int H, int W) {
+  auto up = [](size_t n) { return (n + 63) & ~(size_t)63; };
+  SlotLayout s;
+  s.numel[0] = (size_t)C * H * W; s.numel[1] = (size_t)C * (H / 2) * (W / 2); s.numel[2] = (size_t)C * (H / 4) * (W / 4);
+  s.off[0] = 0; s.off[1] = up(s.numel[0]); s.off[2] = s.off[1] + up(s.numel[1]);
+  s.raw = s.off[2] + up(s.numel[2]);
+  s.floats = s.raw + up((size_t)3 * H * W);
+  return s;
+}
+
+static int build_plan(dvsr_edvr_plan& p, PlanPart part = PART_WHOLE) {
   const dvsr_edvr_config& c = p.cfg;
   const int B = p.B, Nf = c.nframes, C = c.nf, H = p.H, W = p.W, BN = B * Nf, dg = c.groups;
   const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
@@ -278,20 +300,40 @@ static int build_plan(dvsr_edvr_plan& p) {
   Builder b(p);
   const int L = ACT_LRELU, R = ACT_RELU, NO = ACT_NONE;
   T none;
-  T xin; xin.space = SP_INPUT; xin.off = 0; xin.numel = (size_t)BN * 3 * HW;
+  const int EN = part == PART_EXTRACT ? 1 : BN;   // images through the feature extraction
+  T xin; xin.space = SP_INPUT; xin.off = 0; xin.numel = (size_t)EN * 3 * HW;
 
   // ---- feature extraction (EDVR_arch.py:272-279)
-  T f1 = b.conv("conv_first", b.take(), xin, 3, none, 0, BN, H, W, C, 3, 1, L);
-  for (int i = 0; i < c.front_RBs; ++i) {
-    auto p1 = b.take(); auto p2 = b.take();
-    T t = b.conv("fe_rb_a", p1, f1, C, none, 0, BN, H, W, C, 3, 1, R);
-    f1 = b.conv("fe_rb_b", p2, t, C, none, 0, BN, H, W, C, 3, 1, NO, f1);
+  T f1, f2, f3;
+  if (part == PART_FUSE) {
+    f1 = b.alloc("L1_fea", (size_t)BN * C * HW);
+    f2 = b.alloc("L2_fea", (size_t)BN * C * HW2);
+    f3 = b.alloc("L3_fea", (size_t)BN * C * HW4);
+    b.pcur += 2 * (1 + 2 * c.front_RBs + 4);
+  } else {
+    const SlotLayout sl = slot_layout(C, H, W);
+    // PART_EXTRACT: the launch that produces level l's final features stores them into the cache slot
+    auto dst = [&](int l, bool final_of_level) {
+      T t;
+      if (part == PART_EXTRACT && final_of_level) { t.space = SP_OUTPUT; t.off = sl.off[l]; t.numel = sl.numel[l]; }
+      return t;
+    };
+    f1 = b.conv("conv_first", b.take(), xin, 3, none, 0, EN, H, W, C, 3, 1, L, none, 0, 1, 0, 0, dst(0, c.front_RBs == 0));
+    for (int i = 0; i < c.front_RBs; ++i) {
+      auto p1 = b.take(); auto p2 = b.take();
+      T t = b.conv("fe_rb_a", p1, f1, C, none, 0, EN, H, W, C, 3, 1, R);
+      f1 = b.conv("fe_rb_b", p2, t, C, none, 0, EN, H, W, C, 3, 1, NO, f1, 0, 1, 0, 0, dst(0, i == c.front_RBs - 1));
+    }
+    p.named.emplace_back("L1_fea", f1);
+    f2 = b.conv("fea_L2_conv1", b.take(), f1, C, none, 0, EN, H, W, C, 3, 2, L);
+    f2 = b.conv("L2_fea", b.take(), f2, C, none, 0, EN, H2, W2, C, 3, 1, L, none, 0, 1, 0, 0, dst(1, true));
+    f3 = b.conv("fea_L3_conv1", b.take(), f2, C, none, 0, EN, H2, W2, C, 3, 2, L);
+    f3 = b.conv("L3_fea", b.take(), f3, C, none, 0, EN, H4, W4, C, 3, 1, L, none, 0, 1, 0, 0, dst(2, true));
   }
-  p.named.emplace_back("L1_fea", f1);
-  T f2 = b.conv("fea_L2_conv1", b.take(), f1, C, none, 0, BN, H, W, C, 3, 2, L);
-  f2 = b.conv("L2_fea", b.take(), f2, C, none, 0, BN, H2, W2, C, 3, 1, L);
-  T f3 = b.conv("fea_L3_conv1", b.take(), f2, C, none, 0, BN, H2, W2, C, 3, 2, L);
-  f3 = b.conv("L3_fea", b.take(), f3, C, none, 0, BN, H4, W4, C, 3, 1, L);
+  if (part == PART_EXTRACT) {
+    p.n_params = b.pcur;
+    return DVSR_OK;
+  }
 
   // ---- PCD alignment, all N frames batched (EDVR_arch.py:95-128, 281-297)
   // state-dict order inside pcd_align: L3_offset_conv1, L3_offset_conv2, L3_dcnpack{w,b,com.w,com.b},
@@ -406,7 +448,7 @@ static int build_plan(dvsr_edvr_plan& p) {
   T base = b.alloc("base", (size_t)B * 3 * h * w);
   for (int bi = 0; bi < B; ++bi) {
     Op o; o.type = OP_UP; o.name = "base_up";
-    o.x0 = Builder::view(xin, ((size_t)bi * Nf + ctr) * 3 * HW, 3 * HW);
+    o.x0 = Builder::view(xin, part == PART_FUSE ? 0 : ((size_t)bi * Nf + ctr) * 3 * HW, 3 * HW);
     o.planes = 3; o.H = H; o.W = W; o.S = c.scale; o.mul = 1.f;
     o.y = Builder::view(base, (size_t)bi * 3 * h * w, (size_t)3 * h * w);
     p.ops.push_back(o);
@@ -1473,6 +1515,136 @@ extern "C" int dvsr_edvr_tensor_info(const dvsr_edvr_plan* p, const char* name, 
     }
   set_error("edvr_tensor_info: no tensor named '%s'", name);
   return DVSR_ERR_INVALID;
+}
+
+
+// =================================================================================================
+// Streaming forward: the B = 1 no-grad tape split at L3_fea (build_plan: PART_EXTRACT / PART_FUSE) around a frame cache.
+// A workspace is [fuse arena | extract arena]: the calls of one window run behind each other on one HIP stream, and each
+// tape's packed weights stay in its own region between calls.
+// =================================================================================================
+struct dvsr_edvr_stream {
+  dvsr_edvr_plan extract, fuse;
+  int slots = 0;
+  dvsr::SlotLayout sl;
+  size_t fea_off[3] = {0, 0, 0};   // L1_fea / L2_fea / L3_fea of the fuse arena (floats)
+};
+
+extern "C" int dvsr_edvr_stream_create(const dvsr_edvr_config* cfg, int H, int W, int slots, dvsr_edvr_stream** out) {
+  DVSR_REQUIRE(cfg && out, DVSR_ERR_INVALID, "edvr_stream_create: null argument");
+  DVSR_REQUIRE(H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, DVSR_ERR_INVALID,
+               "edvr_stream_create: H=%d W=%d (H, W must be positive multiples of 4)", H, W);
+  DVSR_REQUIRE(cfg->nf > 0 && cfg->groups > 0 && cfg->nf % cfg->groups == 0 && cfg->nframes > 0 && cfg->front_RBs >= 0 &&
+                   cfg->back_RBs >= 0, DVSR_ERR_INVALID, "edvr_stream_create: bad network config");
+  DVSR_REQUIRE(cfg->nframes <= DVSR_STREAM_MAX_FRAMES, DVSR_ERR_UNSUPPORTED, "edvr_stream_create: nframes=%d (at most %d)",
+               cfg->nframes, DVSR_STREAM_MAX_FRAMES);
+  DVSR_REQUIRE(slots >= cfg->nframes, DVSR_ERR_INVALID, "edvr_stream_create: slots=%d < nframes=%d", slots, cfg->nframes);
+  DVSR_REQUIRE(cfg->scale == 4 || cfg->scale == 2, DVSR_ERR_UNSUPPORTED, "edvr_stream_create: scale=%d (2 or 4)", cfg->scale);
+  DVSR_REQUIRE(cfg->center >= 0 && cfg->center < cfg->nframes, DVSR_ERR_INVALID, "edvr_stream_create: center=%d out of range",
+               cfg->center);
+  const int cpg = cfg->nf / cfg->groups;
+  DVSR_REQUIRE(cpg == 4 || cpg == 8 || cpg == 16, DVSR_ERR_UNSUPPORTED, "edvr_stream_create: nf/groups=%d (supported: 4, 8, 16)", cpg);
+  dvsr_edvr_stream* s = new dvsr_edvr_stream();
+  const char* v1 = getenv("DVSR_CONV_V1");
+  int k = 0;
+  for (dvsr_edvr_plan* p : {&s->extract, &s->fuse}) {
+    p->cfg = *cfg; p->B = 1; p->H = H; p->W = W;
+    p->use_v1 = v1 && v1[0] == '1';
+    int rc = build_plan(*p, k++ == 0 ? PART_EXTRACT : PART_FUSE);   // (no backward tape: these plans never take a gradient)
+    if (rc != DVSR_OK) { delete s; return rc; }
+  }
+  s->slots = slots;
+  s->sl = slot_layout(cfg->nf, H, W);
+  static const char* const names[3] = {"L1_fea", "L2_fea", "L3_fea"};
+  for (int l = 0; l < 3; ++l)
+    for (const auto& kv : s->fuse.named)
+      if (kv.first == names[l]) s->fea_off[l] = kv.second.off;
+  *out = s;
+  return DVSR_OK;
+}
+
+extern "C" void dvsr_edvr_stream_destroy(dvsr_edvr_stream* s) { delete s; }
+
+extern "C" int dvsr_edvr_stream_num_params(const dvsr_edvr_stream* s) { return s ? s->fuse.n_params : -1; }
+
+extern "C" int dvsr_edvr_stream_num_launches(const dvsr_edvr_stream* s, int which) {
+  if (!s) return -1;
+  return which ? (int)s->fuse.ops.size() + 1 : (int)s->extract.ops.size();
+}
+
+extern "C" size_t dvsr_edvr_stream_cache_bytes(const dvsr_edvr_stream* s) {
+  return s ? (size_t)s->slots * s->sl.floats * sizeof(float) : 0;
+}
+
+extern "C" size_t dvsr_edvr_stream_workspace_bytes(const dvsr_edvr_stream* s) {
+  return s ? (s->fuse.arena_floats + s->extract.arena_floats) * sizeof(float) : 0;
+}
+
+// what both calls require of their buffers (16-byte accesses in the gather and the packed kernels)
+static int stream_check(const dvsr_edvr_stream* s, const void* params, const void* cache, size_t cache_bytes, const void* ws,
+                        size_t ws_bytes, const char* what) {
+  DVSR_REQUIRE(s && params && cache && ws, DVSR_ERR_INVALID, "%s: null argument", what);
+  DVSR_REQUIRE(cache_bytes >= dvsr_edvr_stream_cache_bytes(s), DVSR_ERR_INVALID, "%s: cache %zu < %zu bytes", what, cache_bytes,
+               dvsr_edvr_stream_cache_bytes(s));
+  DVSR_REQUIRE(ws_bytes >= dvsr_edvr_stream_workspace_bytes(s), DVSR_ERR_INVALID, "%s: workspace %zu < %zu bytes", what, ws_bytes,
+               dvsr_edvr_stream_workspace_bytes(s));
+  DVSR_REQUIRE((uintptr_t)cache % 16 == 0 && (uintptr_t)ws % 16 == 0, DVSR_ERR_INVALID, "%s: cache / workspace not 16-byte aligned", what);
+  return DVSR_OK;
+}
+
+extern "C" int dvsr_edvr_stream_extract(const dvsr_edvr_stream* s, const float* const* params, const float* frame, int slot,
+                                        void* cache, size_t cache_bytes, void* ws, size_t ws_bytes, int packed,
+                                        dvsr_stream_t stream) {
+  int rc = stream_check(s, params, cache, cache_bytes, ws, ws_bytes, "edvr_stream_extract");
+  if (rc != DVSR_OK) return rc;
+  DVSR_REQUIRE(frame, DVSR_ERR_INVALID, "edvr_stream_extract: null argument");
+  DVSR_REQUIRE(slot >= 0 && slot < s->slots, DVSR_ERR_INVALID, "edvr_stream_extract: slot %d outside [0, %d)", slot, s->slots);
+  const dvsr_edvr_plan& p = s->extract;
+  hipStream_t st = (hipStream_t)stream;
+  float* dst = (float*)cache + (size_t)slot * s->sl.floats;
+  Bases bs{(float*)ws + s->fuse.arena_floats, frame, dst, p.use_v1};
+  bs.nograd = true;
+  if (!p.use_v1 && !packed) {
+    rc = pack_all(p, params, bs.arena, bs.arena, nullptr, st, true);
+    if (rc != DVSR_OK) return rc;
+  }
+  for (const Op& o : p.ops) {
+    rc = run_forward_op(p, o, params, bs, st);
+    if (rc != DVSR_OK) return rc;
+  }
+  // conv_last's bilinear base reads the centre frame's pixels long after the caller's frame buffer may be gone
+  hipError_t e = hipMemcpyAsync(dst + s->sl.raw, frame, (size_t)3 * p.H * p.W * sizeof(float), hipMemcpyDeviceToDevice, st);
+  DVSR_REQUIRE(e == hipSuccess, DVSR_ERR_HIP, "edvr_stream_extract: copy of the frame: %s", hipGetErrorString(e));
+  return DVSR_OK;
+}
+
+extern "C" int dvsr_edvr_stream_fuse(const dvsr_edvr_stream* s, const float* const* params, const int* slots, const void* cache,
+                                     size_t cache_bytes, float* out, void* ws, size_t ws_bytes, int packed,
+                                     dvsr_stream_t stream) {
+  int rc = stream_check(s, params, cache, cache_bytes, ws, ws_bytes, "edvr_stream_fuse");
+  if (rc != DVSR_OK) return rc;
+  DVSR_REQUIRE(slots && out, DVSR_ERR_INVALID, "edvr_stream_fuse: null argument");
+  const dvsr_edvr_plan& p = s->fuse;
+  const int Nf = p.cfg.nframes;
+  for (int f = 0; f < Nf; ++f)
+    DVSR_REQUIRE(slots[f] >= 0 && slots[f] < s->slots, DVSR_ERR_INVALID, "edvr_stream_fuse: slots[%d] = %d outside [0, %d)", f,
+                 slots[f], s->slots);
+  hipStream_t st = (hipStream_t)stream;
+  const float* cf = (const float*)cache;
+  Bases bs{(float*)ws, cf + (size_t)slots[p.cfg.center] * s->sl.floats + s->sl.raw, out, p.use_v1};
+  bs.nograd = true;
+  if (!p.use_v1 && !packed) {
+    rc = pack_all(p, params, bs.arena, bs.arena, nullptr, st, true);
+    if (rc != DVSR_OK) return rc;
+  }
+  float* const dst[3] = {bs.arena + s->fea_off[0], bs.arena + s->fea_off[1], bs.arena + s->fea_off[2]};
+  rc = stream_gather_run(cf, s->sl.floats, s->sl.off, dst, s->sl.numel, Nf, slots, st);
+  if (rc != DVSR_OK) return rc;
+  for (const Op& o : p.ops) {
+    rc = run_forward_op(p, o, params, bs, st);
+    if (rc != DVSR_OK) return rc;
+  }
+  return DVSR_OK;
 }
 
 

@@ -186,6 +186,11 @@ int add_inplace(float* dst, const float* src, size_t n, hipStream_t st);
 int add_out(float* y, const float* a, const float* b, size_t n, hipStream_t st);
 int act_bwd_inplace(float* g, const float* y, size_t n, int act, hipStream_t st);
 
+// stream_gather.hip: the L1 / L2 / L3 features of the `nframes` cache slots `slots` (host array, passed to the kernel by
+// value) -> dst[l][f][level_floats[l]]; slot s starts at cache + s * slot_floats, its level l at + src_off[l]
+int stream_gather_run(const float* cache, size_t slot_floats, const size_t src_off[3], float* const dst[3],
+                      const size_t level_floats[3], int nframes, const int* slots, hipStream_t st);
+
 // pad.hip: explicit padding / layout changes of the MFDN estimator and their adjoints
 enum : int { PAD_REFLECT = 0, PAD_REFLECT_S2D = 1, PAD_REPL_T3 = 2 };
 size_t pad_out_numel(int mode, size_t N, int C, int H, int W);

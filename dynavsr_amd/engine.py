@@ -475,3 +475,115 @@ class EstimatorStackedFunction(_TapeFunction):
         ctx.plan.backward(ctx.params if ctx.per_slice else [p[0] for p in ctx.params], ctx.x, gout, gparams, ctx.ws)
         ctx.ws = None
         return (None, None, None) + tuple(gparams)
+
+
+# ---- streaming EDVR forward (csrc/engine.hip: dvsr_edvr_stream_*) --------------------------------
+_splans = {}
+
+
+class StreamPlan:
+    """Owns one dvsr_edvr_stream: the B = 1 no-grad EDVR tape split at L3_fea around a frame cache of `slots` slots
+    (include/dynavsr_hip.h).  `extract` writes one frame's features into a slot, `fuse` turns a window of slots into the
+    SR frame; adapt.super_resolve_frames drives the two over a video.
+
+    The plan keeps one workspace per (device, HIP stream) -- and with it the packed weights of both tapes -- for as long
+    as it lives, so a second video through the same frozen network packs nothing (`release()` frees them).  Packs are
+    keyed per tape on the parameters' storage and autograd version counters, as FrozenWeights does, with that class's
+    three gaps closed: the plan itself is cached under the geometry environment (`_env_key()`), so a workspace is never
+    reused under another kernel selection; a signature is recorded only AFTER the packing call returned; and a workspace
+    whose size is not the plan's is replaced, not trusted.
+    `stats` counts calls: 'extracted', 'fused', 'gathers' (one launch per fuse) and 'packs' (calls that packed weights)."""
+
+    def __init__(self, cfg, h, w, slots):
+        cfg = tuple(cfg) + (0,) * (8 - len(cfg))
+        self.cfg = dict(zip(("nf", "nframes", "groups", "front_RBs", "back_RBs", "scale", "center", "bf16_mfma"), cfg))
+        self.h, self.w, self.slots = h, w, slots
+        self._h = ctypes.c_void_p()
+        L.check(L.lib().dvsr_edvr_stream_create(L.EdvrConfig(*cfg), h, w, slots, ctypes.byref(self._h)),
+                "dvsr_edvr_stream_create")
+        self.n_params = L.lib().dvsr_edvr_stream_num_params(self._h)
+        self.n_launches = (L.lib().dvsr_edvr_stream_num_launches(self._h, 0), L.lib().dvsr_edvr_stream_num_launches(self._h, 1))
+        self.cache_bytes = int(L.lib().dvsr_edvr_stream_cache_bytes(self._h))
+        self.workspace_bytes = int(L.lib().dvsr_edvr_stream_workspace_bytes(self._h))
+        self.stats = {'extracted': 0, 'fused': 0, 'gathers': 0, 'packs': 0}
+        self._ws = {}      # (device index, stream handle) -> [workspace, {'extract': sig, 'fuse': sig}]
+
+    def new_cache(self, device):
+        return torch.empty(self.cache_bytes, dtype=torch.uint8, device=device)
+
+    def release(self):
+        """Drops the workspaces (and the packs in them); the next call on a stream allocates and packs again."""
+        self._ws.clear()
+
+    def _slot(self, device):
+        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+        have = self._ws.get(key)
+        if have is None or have[0].numel() != self.workspace_bytes:
+            have = self._ws[key] = [torch.empty(self.workspace_bytes, dtype=torch.uint8, device=device), {}]
+        return have
+
+    def _run(self, tape, leaves, call):
+        """One call of `tape` ('extract' | 'fuse') on the current stream's workspace; call(ws, packed) -> rc."""
+        dev = leaves[0].device
+        ws, sigs = self._slot(dev)
+        sig = tuple((p.data_ptr(), p._version) for p in leaves)
+        packed = sigs.get(tape) == sig
+        if not packed:
+            sigs.pop(tape, None)
+        L.check(call(ws, int(packed)), "dvsr_edvr_stream_" + tape)
+        if not packed:              # (only now: after a failed packing call the next one packs again)
+            sigs[tape] = sig
+            self.stats['packs'] += 1
+
+    def _params(self, leaves):
+        if len(leaves) != self.n_params:
+            raise RuntimeError("EDVR stream expects %d parameter tensors, got %d" % (self.n_params, len(leaves)))
+        params = [_prep(p.detach()) for p in leaves]
+        return params, (ctypes.c_void_p * len(params))(*[L.ptr(p) for p in params])
+
+    def extract(self, leaves, frame, slot, cache):
+        """frame [3,H,W] (fp32, contiguous, on the GPU) -> slot `slot` of `cache`, on the current stream."""
+        if tuple(frame.shape) != (3, self.h, self.w):
+            raise RuntimeError("EDVR stream expects frames [3,%d,%d], got %s" % (self.h, self.w, tuple(frame.shape)))
+        params, arr = self._params(leaves)
+        self._run('extract', leaves, lambda ws, packed: L.lib().dvsr_edvr_stream_extract(
+            self._h, arr, L.ptr(frame), int(slot), cache.data_ptr(), cache.numel() * cache.element_size(), ws.data_ptr(),
+            ws.numel(), packed, L.stream()))
+        self.stats['extracted'] += 1
+
+    def fuse(self, leaves, slots, cache, out):
+        """The window whose frames sit in `slots` (window order) -> out [1,3,sH,sW], on the current stream."""
+        if len(slots) != self.cfg['nframes']:
+            raise RuntimeError("EDVR stream: a window is %d slots, got %d" % (self.cfg['nframes'], len(slots)))
+        params, arr = self._params(leaves)
+        sl = (ctypes.c_int * len(slots))(*[int(s) for s in slots])
+        self._run('fuse', leaves, lambda ws, packed: L.lib().dvsr_edvr_stream_fuse(
+            self._h, arr, sl, cache.data_ptr(), cache.numel() * cache.element_size(), L.ptr(out), ws.data_ptr(), ws.numel(),
+            packed, L.stream()))
+        self.stats['fused'] += 1
+        self.stats['gathers'] += 1
+
+    def __del__(self):
+        try:
+            if self._h:
+                L.lib().dvsr_edvr_stream_destroy(self._h)
+        except Exception:
+            pass
+
+
+def get_stream_plan(cfg, h, w, slots, device=None):
+    """One StreamPlan per (config, frame size, cache slots, device, geometry environment).  Unlike a Plan it owns no
+    stream or event, so the HIP stream is not part of the key: its workspaces are per stream inside it."""
+    dev = torch.cuda.current_device() if device is None else torch.device(device).index
+    key = (tuple(cfg), h, w, slots, dev, _env_key())
+    p = _splans.get(key)
+    if p is None:
+        _check_process_env()
+        p = _splans[key] = StreamPlan(tuple(cfg), h, w, slots)
+    return p
+
+
+def release_stream_plans():
+    """Frees every StreamPlan's workspaces (a 180x320 EDVR-M workspace is ~1.5 GB per stream in use)."""
+    for p in _splans.values():
+        p.release()

@@ -259,6 +259,42 @@ int dvsr_debug_mfma_shadow(long long* cycles, float* out, int blocks, int iters,
 int dvsr_edvr_tensor_info(const dvsr_edvr_plan* plan, const char* name, long long* offset_floats,
                           long long* numel);
 
+/* ---- Streaming EDVR forward: every frame's features extracted ONCE ----------------------------
+ * A video is super-resolved over a sliding window of `nframes` frames (test_dynavsr.py:200-204 per window of
+ * data/util.py:index_generation), and the launches of EDVR.forward up to L3_fea (EDVR_arch.py:272-279: conv_first, the
+ * front residual blocks, fea_L2_conv*, fea_L3_conv*) depend on one frame each: consecutive windows recompute them for the
+ * frames they share.  A stream object splits the B = 1 no-grad tape at L3_fea:
+ *   extract: one LR frame [3][H][W] -> its L1 / L2 / L3 features + the frame itself, written into slot `slot` of a
+ *            caller-owned cache of `slots` slots (dvsr_edvr_stream_cache_bytes);
+ *   fuse:    `slots[nframes]` (HOST array, window order) -> out [3][scale*H][scale*W]: one gather launch copies the
+ *            window's features out of the cache, then the tape runs from L3_offset_conv1 to conv_last unchanged.
+ * Both tapes come from the walk that builds dvsr_edvr_plan (same parameter order: `params` is the same host array of
+ * dvsr_edvr_stream_num_params() device pointers) and ALWAYS run the no-grad launch geometries -- the mode is this entry
+ * point, not a workspace size.  cfg.bf16_mfma is respected.  At most DVSR_STREAM_MAX_FRAMES frames per window.
+ * Workspace: dvsr_edvr_stream_workspace_bytes() per window in flight, shared by the extract and fuse calls made on that
+ * window's HIP stream (it holds both tapes' activations and packed weights, in disjoint regions).
+ * packed != 0: the contract of dvsr_edvr_forward_packed, per tape -- this workspace still holds the packs an earlier
+ * extract (resp. fuse) call with packed = 0 left there for the same parameter values.
+ * Ordering is the caller's: a fuse must be ordered behind the extractions of its slots, an extract behind every fuse
+ * that still reads the slot it overwrites (the cache is read by the gather launch only, i.e. at the START of a fuse).
+ * Bad arguments (null pointer, slot outside [0, slots), short or misaligned workspace / cache) return DVSR_ERR_INVALID
+ * before any launch. */
+#define DVSR_STREAM_MAX_FRAMES 16
+typedef struct dvsr_edvr_stream dvsr_edvr_stream;
+int dvsr_edvr_stream_create(const dvsr_edvr_config* cfg, int H, int W, int slots, dvsr_edvr_stream** out);
+void dvsr_edvr_stream_destroy(dvsr_edvr_stream* stream_plan);
+int dvsr_edvr_stream_num_params(const dvsr_edvr_stream* stream_plan);
+/* launches of the extract (which = 0; + one device copy of the frame) / fuse (which = 1; gather included) tape */
+int dvsr_edvr_stream_num_launches(const dvsr_edvr_stream* stream_plan, int which);
+size_t dvsr_edvr_stream_cache_bytes(const dvsr_edvr_stream* stream_plan);
+size_t dvsr_edvr_stream_workspace_bytes(const dvsr_edvr_stream* stream_plan);
+int dvsr_edvr_stream_extract(const dvsr_edvr_stream* stream_plan, const float* const* params, const float* frame, int slot,
+                             void* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, int packed,
+                             dvsr_stream_t stream);
+int dvsr_edvr_stream_fuse(const dvsr_edvr_stream* stream_plan, const float* const* params, const int* slots,
+                          const void* cache, size_t cache_bytes, float* out, void* workspace, size_t workspace_bytes,
+                          int packed, dvsr_stream_t stream);
+
 /* ---- Down-scaling estimators MFDN / SFDN as one launch tape ------------------------------------
  * Replaces DirectKernelEstimatorVideo.forward (models/archs/LRimg_estimator.py:92-117, "MFDN":
  * Conv3d(k3)+ReplicationPad3d, ReflectionPad2d + 3x3 / 4x4-stride-2 Conv2d, Conv3d, 1x1, per-frame
