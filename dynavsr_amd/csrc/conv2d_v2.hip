@@ -959,9 +959,9 @@ ConvGeo choose_direct_tile(const ConvShape& s) {
 // rounds over the device's CUs x (cycles of a workgroup's chunks + transform / epilogue overhead); cycle figures measured on
 // MI355X (tools/wino_trace.py), 2.07 GHz under these kernels.
 struct WinoPick { int th; double cost; };
+double wino_workgroups(const ConvShape& s, int oh, int ow) { return (double)ceil_div(s.Wo, ow) * ceil_div(s.Ho, oh) * s.N * ceil_div(s.Cout, 64); }
 double wino_rounds_cost(const ConvShape& s, double cus, int oh, int ow, double chunk_cyc, double fixed_cyc) {
-  const double wgs = (double)ceil_div(s.Wo, ow) * ceil_div(s.Ho, oh) * s.N * ceil_div(s.Cout, 64);
-  return ceil(wgs / cus) * ((s.Ctot / 8) * chunk_cyc + fixed_cyc) / 2.07;
+  return ceil(wino_workgroups(s, oh, ow) / cus) * ((s.Ctot / 8) * chunk_cyc + fixed_cyc) / 2.07;
 }
 // ... the direct kernel: rounds x MFMA cycles at its measured 0.78 efficiency
 // (the direct kernels reach 0.78 of their MFMA time only over many rounds of workgroups; on grids of a few rounds their
@@ -988,6 +988,30 @@ WinoPick wino_f4_cost(const ConvShape& s, double cus) {
   const double f8 = wino_rounds_cost(s, cus, 8, 64, W5_CHUNK_CYC, W5_FIXED_CYC), f16 = wino_rounds_cost(s, cus, 16, 32, W5_CHUNK_CYC, W5_FIXED_CYC);
   return {f16 < f8 ? 16 : 8, std::min(f8, f16)};
 }
+// Grids of at most one round on a device that other streams' kernels share (ALLOW_SHARED_DEVICE: clips in flight side by side,
+// one stream each).  There latency and occupied CU-time -- workgroups x a workgroup's modelled time -- disagree: the N = 1 trunk
+// at 180x320 runs 225 F(2x2) workgroups or 115 F(4x4) ones, one per CU either way; two clips' F(4x4) launches fit on 256 CUs
+// side by side, two F(2x2) launches do not, and the CUs a launch leaves free go to the other clip's kernels
+// (profiles/r07_one_round_choice.txt: two clips in flight +1.6 %, one clip alone -2.6 %).  F(4x4) when
+//   - both grids are at most one round of workgroups,
+//   - of ONE image's grids two F(4x4) ones fit on the device together and two F(2x2) ones do not (smaller launches leave the
+//     other stream room either way; and read off one image the guard keeps a batch of small images on the kernel a single
+//     one takes: batched and single forwards stay bit-equal there),
+//   - F(4x4) occupies less CU-time, and
+//   - its modelled latency is within SHARED_LATENCY_BOUND of F(2x2)'s.
+// The bound, on MODELLED times: the one shape timed (64 channels; r07_one_round_choice.txt: 5.5 us more per launch with one clip
+// alone, 1.2x F(2x2)'s time, where the model says 0.98x) pays at that price.  With fewer channels F(4x4)'s larger fixed cost
+// weighs more (modelled 1.06x at 32 channels, 1.15x at 16) and nothing is measured: those stay on F(2x2).
+constexpr double SHARED_LATENCY_BOUND = 1.05;
+bool f4_occupies_less(const ConvShape& s, double cus, const WinoPick& f2, const WinoPick& f4) {
+  const int ow2 = f2.th == 16 ? 16 : (f2.th == 8 ? 32 : 64), ow4 = f4.th == 16 ? 32 : 64;
+  const double g2 = wino_workgroups(s, f2.th, ow2), g4 = wino_workgroups(s, f4.th, ow4);
+  if (g2 > cus || g4 > cus) return false;
+  ConvShape one = s;
+  one.N = 1;
+  if (2.0 * wino_workgroups(one, f2.th, ow2) <= cus || 2.0 * wino_workgroups(one, f4.th, ow4) > cus) return false;
+  return g4 * f4.cost < g2 * f2.cost && f4.cost <= SHARED_LATENCY_BOUND * f2.cost;   // (one round: cost = a workgroup's time)
+}
 }  // namespace
 
 ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ctot, ConvAllow allow) {
@@ -1013,9 +1037,12 @@ ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ct
   // entries, which pass the flag for every aligned 3x3 whether or not autograd records the call.
   if (wino5_on && wino3_on && (allow & ALLOW_WINO_F4) && Wo % 4 == 0 && device_lds_optin() >= (size_t)156 * 1024) {
     const WinoPick f4 = wino_f4_cost(s, cus);
-    // (the model flatters this kernel on grids of one round -- the N = 1 trunk at 180x320 measures 31 us against 26 --: it has
-    // to win by 15 %)
-    if (wino5_on >= 2 || (1.15 * f4.cost < f2.cost && f4.cost < direct)) return ConvGeo{8, wino5_on == 3 ? 16 : f4.th, 2, 0, ConvKernel::WINO_F4};
+    // (the model flatters this kernel on grids of one round -- the N = 1 trunk at 180x320 measures 31 us against 26 --: by
+    // latency it has to win by 15 %.  That is the rule of the op-level entries and of every launch that has the device to
+    // itself; the engine's no-grad forward slot shares the device and also takes it where it occupies less: f4_occupies_less)
+    const bool shared_pick = (allow & ALLOW_SHARED_DEVICE) && f2.cost < direct && f4_occupies_less(s, cus, f2, f4);
+    if (wino5_on >= 2 || ((1.15 * f4.cost < f2.cost || shared_pick) && f4.cost < direct))
+      return ConvGeo{8, wino5_on == 3 ? 16 : f4.th, 2, 0, ConvKernel::WINO_F4};
   }
   if ((wino_on == 2 || f2.cost < direct) && device_lds_optin() >= (size_t)155 * 1024)
     return ConvGeo{8, f2.th, 2, 0, wino3_on ? ConvKernel::WINO_F2_BF16 : ConvKernel::WINO_F2};

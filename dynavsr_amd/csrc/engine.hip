@@ -209,7 +209,8 @@ struct Builder {
       // the NO-GRAD forward may take the F(4x4, 3x3) kernel (never the data gradients: accumulate / mask epilogues)
       o.fwd[1] = o.fwd[0];
       if ((fwd_ok & ALLOW_WINO) && !o.fwd[0].geo.bf) {
-        const ConvGeo g5 = conv2_choose(ks, stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok | ALLOW_WINO_F4);
+        // (... and, as the slot of the forwards that run several clips in flight, one stream each, it is chosen for a shared device)
+        const ConvGeo g5 = conv2_choose(ks, stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok | ALLOW_WINO_F4 | ALLOW_SHARED_DEVICE);
         if (g5.kernel == ConvKernel::WINO_F4) {
           o.fwd[1].geo = g5;
           o.fwd[1].floats = conv2_pack_floats(ks, Cout, c0 + c1, g5);

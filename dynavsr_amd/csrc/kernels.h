@@ -80,6 +80,8 @@ enum ConvAllow : int {
   ALLOW_DMA_HALO = 2,  // the DMA-halo / row-split kernels (needs_dma_halo_inputs)
   ALLOW_WINO = 4,      // the Winograd F(2x2) kernels: ALLOW_DMA_HALO's conditions + an epilogue they implement (plain or PixelShuffle(2) stores)
   ALLOW_WINO_F4 = 8,   // the F(4x4) kernel: ALLOW_WINO's + a forward epilogue (no accumulate / gradient mask)
+  ALLOW_SHARED_DEVICE = 16,  // the launch shares the device with other streams' kernels (clips in flight side by side): between
+                             // one-round Winograd grids the smaller occupied CU-time wins, not the shorter launch
 };
 constexpr ConvAllow operator|(ConvAllow a, ConvAllow b) { return static_cast<ConvAllow>(static_cast<int>(a) | static_cast<int>(b)); }
 constexpr ConvAllow without(ConvAllow a, ConvAllow b) { return static_cast<ConvAllow>(static_cast<int>(a) & ~static_cast<int>(b)); }
