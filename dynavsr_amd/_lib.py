@@ -66,6 +66,16 @@ class EdvrConfig(Structure):
                                      "center", "bf16_mfma")]
 
 
+class FrameDesc(Structure):
+    """dvsr_frame_desc: a frame at any address and pitch (include/dynavsr_hip.h)."""
+    _fields_ = [("format", c_int), ("h", c_int), ("w", c_int), ("row_stride", c_longlong), ("plane_stride", c_longlong),
+                ("pixel_stride", c_int)]
+
+
+FRAME_F32_CHW, FRAME_U8_HWC_RGB, FRAME_U8_HWC_BGR = 0, 1, 2
+FRAME_PAD_REFLECT, FRAME_PAD_REPLICATE = 0, 1
+
+
 class EstimatorConfig(Structure):
     _fields_ = [(k, c_int) for k in ("kind", "nf", "in_nc", "scale", "nframes")]
 
@@ -172,6 +182,10 @@ def _declare(lib):
         "dvsr_edvr_stream_workspace_bytes": (c_size_t, [P]),
         "dvsr_edvr_stream_extract": (I, [P, POINTER(c_void_p), P, I, P, c_size_t, P, c_size_t, I, P]),
         "dvsr_edvr_stream_fuse": (I, [P, POINTER(c_void_p), POINTER(c_int), P, c_size_t, P, P, c_size_t, I, P]),
+        "dvsr_frame_ingest": (I, [P, POINTER(FrameDesc), P, I, I, I, P]),
+        "dvsr_frame_emit": (I, [P, I, I, P, POINTER(FrameDesc), F, F, P]),
+        "dvsr_edvr_stream_extract_frame": (I, [P, POINTER(c_void_p), P, POINTER(FrameDesc), I, I, P, c_size_t, P, c_size_t, I,
+                                               P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -14,6 +14,7 @@ estimator's output does not change inside the step loop, so it is computed once 
 """
 from copy import deepcopy
 
+import math
 import os
 
 import torch
@@ -790,7 +791,23 @@ def stream_schedule(T, nframes, padding='new_info', in_flight=2):
         yield c, new, [(f, f % slots) for f in new], [f % slots for f in win]
 
 
-def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2):
+def _video_format(frames, layout):
+    """(layout, h, w) of a video -- a [T,...] tensor or a list of frames of one kind and size.  No GPU call."""
+    from . import frames as fio
+    if len(frames) < 1:
+        raise ValueError("super_resolve_frames: no frames")
+    first = fio.resolve_layout(frames[0], layout)
+    if not torch.is_tensor(frames):
+        for i, f in enumerate(frames):
+            if torch.is_tensor(f) and (f.dtype != frames[0].dtype or tuple(f.shape) != tuple(frames[0].shape)):
+                raise ValueError("super_resolve_frames: frame %d is %s %s, frame 0 is %s %s" % (
+                    i, f.dtype, tuple(f.shape), frames[0].dtype, tuple(frames[0].shape)))
+            fio.resolve_layout(f, layout)
+    return first
+
+
+def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, layout=None, out=None, pad_mode='reflect',
+                         multiple=None):
     """Super-resolves a VIDEO: `frames` is a [T,3,H,W] tensor or a list of [3,H,W] frames (CPU or GPU); yields the SR frame
     [1,3,sH,sW] of every frame, in order -- what `net(frames[index_generation(i, T, nframes, padding)][None])` gives, the
     sliding-window test of the reference's video datasets (video_test_dataset_int.py:219, `padding: new_info` in the
@@ -807,29 +824,91 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2):
     do not depend on in_flight.
     Any other network (TOFlow, DUF): the windows are built here and run by super_resolve_video -- same interface, no cache.
     A yielded frame stays valid until the generator is advanced `in_flight` times; frames and results are ordered against
-    the caller's current stream."""
+    the caller's current stream.
+
+    What a decoder delivers is accepted as it is (frames.py, csrc/frame_io.hip): `frames` may also be uint8 [T,H,W,3|4] or
+    a list of [H,W,3|4] in RGB or BGR order (`layout`: 'chw' | 'hwc_rgb' | 'hwc_bgr'; None = 'chw' for float frames,
+    'hwc_rgb' for uint8), pitched and offset views passed by stride, CPU frames copied to the device as bytes; and any
+    H, W >= 4: a frame is padded at the bottom and right from itself (`pad_mode` 'reflect' | 'replicate', the modes of
+    torch.nn.functional.pad) to a multiple of `multiple` (None: 4 for EDVR, 1 for other networks; 16 for TOFlow), and the
+    SR frame is cropped back to s*H x s*W.  `out`: None keeps [1,3,sH,sW] fp32 for float frames and gives uint8
+    [sH,sW,3] on the device in the input's channel order for uint8 frames (util.tensor2img's image); 'float', 'hwc_rgb',
+    'hwc_bgr' force one.  Float planar frames that need no padding, with `out` unset, take exactly the calls described
+    above (the crop / conversion otherwise runs as one more launch on the window's stream, out of a per-stream staging
+    buffer).  Arguments are checked before the first GPU call (ValueError)."""
+    from . import frames as fio
     from .data.util import index_generation
     from .models.archs.EDVR_arch import EDVR
     T = len(frames)
+    if T < 1:
+        raise ValueError("super_resolve_frames: no frames")
     in_flight = max(1, int(in_flight))
-    if not isinstance(net, EDVR):
+    is_edvr = isinstance(net, EDVR)
+    if pad_mode not in ('reflect', 'replicate'):
+        raise ValueError("super_resolve_frames: pad_mode=%r ('reflect' or 'replicate')" % (pad_mode,))
+    # float frames with none of the frame arguments given, at a size the network takes as it is: the calls of before
+    plain = layout is None and out is None and multiple is None and \
+        not (torch.is_tensor(frames[0]) and frames[0].dtype == torch.uint8)
+    if is_edvr:
+        plain = plain and torch.is_tensor(frames[0]) and frames[0].dim() == 3 and frames[0].is_floating_point() and \
+            frames[0].shape[-2] % 4 == 0 and frames[0].shape[-1] % 4 == 0
+    if plain:
+        h, w, lay, out_fmt, Hp, Wp = int(frames[0].shape[-2]), int(frames[0].shape[-1]), 'chw', 'float', None, None
+    else:
+        lay, h, w = _video_format(frames, layout)
+        if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr'):
+            raise ValueError("super_resolve_frames: out=%r (None, 'float', 'hwc_rgb' or 'hwc_bgr')" % (out,))
+        out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
+        if h < 4 or w < 4:
+            raise ValueError("super_resolve_frames: frames of %d x %d (at least 4 x 4)" % (h, w))
+        mult = int(multiple) if multiple is not None else (4 if is_edvr else 1)
+        if mult < 1:
+            raise ValueError("super_resolve_frames: multiple=%r must be positive" % (multiple,))
+        if is_edvr and mult % 4:
+            mult *= 4 // math.gcd(mult, 4)            # the EDVR plans take multiples of 4 only
+        Hp, Wp = fio.padded_size(h, w, mult)
+        fio.check_pad(h, w, Hp, -(-Wp // 4) * 4, pad_mode)
+        if lay == 'chw' and out_fmt == 'float' and (Hp, Wp) == (h, w):
+            Hp = Wp = None                            # nothing to convert, pad or crop: today's calls
+    if not is_edvr:
         n = int(opt['network_G']['nframes']) if (opt.get('network_G') or {}).get('nframes') else int(net.nframes)
         sched = list(stream_schedule(T, n, padding, 1))            # (validates T and the mode)
+        if Hp is None:
+            def clips():
+                for c, _, _, _ in sched:
+                    yield torch.stack([frames[j] for j in index_generation(c, T, n, padding)])[None]
+            yield from super_resolve_video(opt, net, clips(), in_flight)
+            return
+        kept = {}                                      # frame -> its ingested tensor; the last 2n are kept
 
-        def clips():
+        def ingested(j):
+            x = kept.get(j)
+            if x is None:
+                x = kept[j] = fio.ingest(frames[j], lay, mult, pad_mode)
+                while len(kept) > 2 * n:
+                    kept.pop(next(iter(kept)))
+            return x
+
+        def padded_clips():
             for c, _, _, _ in sched:
-                yield torch.stack([frames[j] for j in index_generation(c, T, n, padding)])[None]
-        yield from super_resolve_video(opt, net, clips(), in_flight)
+                yield torch.stack([ingested(j) for j in index_generation(c, T, n, padding)])[None]
+        for sr in super_resolve_video(opt, net, padded_clips(), in_flight):
+            s = sr.shape[-2] // Hp
+            if out_fmt == 'float':
+                yield sr if (Hp, Wp) == (h, w) else fio.emit(sr, s * h, s * w, 'chw')[None]
+            else:
+                yield fio.emit(sr, s * h, s * w, out_fmt)
         return
     leaves = net.ordered_parameters()
     dev = leaves[0].device
     if dev.type != 'cuda':
         raise RuntimeError("dynavsr_amd EDVR runs on the MI355X only (the network is on %s); there is no CPU fallback" % dev)
     sched = list(stream_schedule(T, net.nframes, padding, in_flight))
-    if tuple(frames[0].shape[-3:-2]) != (3,):
+    if Hp is None and tuple(frames[0].shape[-3:-2]) != (3,):
         raise RuntimeError("super_resolve_frames expects frames [3,H,W], got %s" % (tuple(frames[0].shape),))
-    h, w = int(frames[0].shape[-2]), int(frames[0].shape[-1])
-    plan = engine.get_stream_plan(net._cfg(), h, w, net.nframes + in_flight - 1, dev)
+    direct = Hp is None                               # fp32 planar frames of the plan's size in, the fuse tape's tensor out
+    ph, pw = (h, w) if direct else (Hp, Wp)
+    plan = engine.get_stream_plan(net._cfg(), ph, pw, net.nframes + in_flight - 1, dev)
     main = torch.cuda.current_stream(dev)
     streams = _clip_streams(dev, in_flight)
     with torch.cuda.device(dev):
@@ -837,6 +916,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2):
     for s in streams[1:]:
         cache.record_stream(s)
     extracted, readers, pending = {}, {}, []   # slot -> event of its extraction; slot -> events of the windows reading it
+    staging = {}                               # stream index -> the fuse tape's output when a crop / conversion follows it
     was_training = net.training
     net.eval()
     try:
@@ -852,18 +932,34 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2):
             with torch.cuda.stream(s), torch.no_grad():
                 for f, slot in new:
                     x = frames[f]
-                    x = engine._prep(x if x.is_cuda else x.to(dev))
+                    if direct:
+                        x = engine._prep(x if x.is_cuda else x.to(dev))
+                    elif not x.is_cuda:
+                        x = x.to(dev, non_blocking=True)             # (8-bit frames travel as bytes)
                     for ev in readers.pop(slot, ()):
                         s.wait_event(ev)
-                    plan.extract(leaves, x, slot, cache)
+                    if direct:
+                        plan.extract(leaves, x, slot, cache)
+                    else:
+                        x = plan.extract_frame(leaves, x, slot, cache, lay, pad_mode)
                     extracted[slot] = torch.cuda.Event()
                     extracted[slot].record(s)
                     if s != main:
                         x.record_stream(s)
                 for slot in set(wslots):
                     s.wait_event(extracted[slot])
-                sr = torch.empty((1, 3, net.scale * h, net.scale * w), dtype=torch.float32, device=dev)
-                plan.fuse(leaves, wslots, cache, sr)
+                if direct or (out_fmt == 'float' and (ph, pw) == (h, w)):
+                    sr = torch.empty((1, 3, net.scale * ph, net.scale * pw), dtype=torch.float32, device=dev)
+                    plan.fuse(leaves, wslots, cache, sr)
+                else:
+                    k = step % len(streams)
+                    if k not in staging:
+                        staging[k] = torch.empty((1, 3, net.scale * ph, net.scale * pw), dtype=torch.float32, device=dev)
+                    plan.fuse(leaves, wslots, cache, staging[k])
+                    if out_fmt == 'float':
+                        sr = fio.emit(staging[k], net.scale * h, net.scale * w, 'chw')[None]
+                    else:
+                        sr = fio.emit(staging[k], net.scale * h, net.scale * w, out_fmt)
                 ev = torch.cuda.Event()
                 ev.record(s)
             for slot in set(wslots):

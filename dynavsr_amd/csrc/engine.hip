@@ -1593,6 +1593,23 @@ static int stream_check(const dvsr_edvr_stream* s, const void* params, const voi
   return DVSR_OK;
 }
 
+// the extract tape: frame [3][H][W] -> the feature sections of the slot at `dst` (arguments checked by the callers)
+static int stream_extract_tape(const dvsr_edvr_stream* s, const float* const* params, const float* frame, float* dst, void* ws,
+                               int packed, hipStream_t st) {
+  const dvsr_edvr_plan& p = s->extract;
+  Bases bs{(float*)ws + s->fuse.arena_floats, frame, dst, p.use_v1};
+  bs.nograd = true;
+  if (!p.use_v1 && !packed) {
+    int rc = pack_all(p, params, bs.arena, bs.arena, nullptr, st, true);
+    if (rc != DVSR_OK) return rc;
+  }
+  for (const Op& o : p.ops) {
+    int rc = run_forward_op(p, o, params, bs, st);
+    if (rc != DVSR_OK) return rc;
+  }
+  return DVSR_OK;
+}
+
 extern "C" int dvsr_edvr_stream_extract(const dvsr_edvr_stream* s, const float* const* params, const float* frame, int slot,
                                         void* cache, size_t cache_bytes, void* ws, size_t ws_bytes, int packed,
                                         dvsr_stream_t stream) {
@@ -1603,20 +1620,32 @@ extern "C" int dvsr_edvr_stream_extract(const dvsr_edvr_stream* s, const float* 
   const dvsr_edvr_plan& p = s->extract;
   hipStream_t st = (hipStream_t)stream;
   float* dst = (float*)cache + (size_t)slot * s->sl.floats;
-  Bases bs{(float*)ws + s->fuse.arena_floats, frame, dst, p.use_v1};
-  bs.nograd = true;
-  if (!p.use_v1 && !packed) {
-    rc = pack_all(p, params, bs.arena, bs.arena, nullptr, st, true);
-    if (rc != DVSR_OK) return rc;
-  }
-  for (const Op& o : p.ops) {
-    rc = run_forward_op(p, o, params, bs, st);
-    if (rc != DVSR_OK) return rc;
-  }
+  rc = stream_extract_tape(s, params, frame, dst, ws, packed, st);
+  if (rc != DVSR_OK) return rc;
   // conv_last's bilinear base reads the centre frame's pixels long after the caller's frame buffer may be gone
   hipError_t e = hipMemcpyAsync(dst + s->sl.raw, frame, (size_t)3 * p.H * p.W * sizeof(float), hipMemcpyDeviceToDevice, st);
   DVSR_REQUIRE(e == hipSuccess, DVSR_ERR_HIP, "edvr_stream_extract: copy of the frame: %s", hipGetErrorString(e));
   return DVSR_OK;
+}
+
+// A decoder's frame (frame_io.hip) goes straight into the slot's raw-frame section, padded to the plan's H x W, and the tape
+// reads it there: no temporary, no device copy behind the tape.
+extern "C" int dvsr_edvr_stream_extract_frame(const dvsr_edvr_stream* s, const float* const* params, const void* frame,
+                                              const dvsr_frame_desc* fd, int pad_mode, int slot, void* cache,
+                                              size_t cache_bytes, void* ws, size_t ws_bytes, int packed, dvsr_stream_t stream) {
+  int rc = stream_check(s, params, cache, cache_bytes, ws, ws_bytes, "edvr_stream_extract_frame");
+  if (rc != DVSR_OK) return rc;
+  DVSR_REQUIRE(slot >= 0 && slot < s->slots, DVSR_ERR_INVALID, "edvr_stream_extract_frame: slot %d outside [0, %d)", slot,
+               s->slots);
+  const dvsr_edvr_plan& p = s->extract;
+  hipStream_t st = (hipStream_t)stream;
+  float* dst = (float*)cache + (size_t)slot * s->sl.floats;
+  float* raw = dst + s->sl.raw;
+  rc = frame_ingest_check("edvr_stream_extract_frame", frame, fd, raw, p.H, p.W, pad_mode);
+  if (rc != DVSR_OK) return rc;
+  rc = frame_ingest_launch(frame, *fd, raw, p.H, p.W, pad_mode, st);
+  if (rc != DVSR_OK) return rc;
+  return stream_extract_tape(s, params, raw, dst, ws, packed, st);
 }
 
 extern "C" int dvsr_edvr_stream_fuse(const dvsr_edvr_stream* s, const float* const* params, const int* slots, const void* cache,

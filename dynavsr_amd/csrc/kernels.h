@@ -193,6 +193,12 @@ int act_bwd_inplace(float* g, const float* y, size_t n, int act, hipStream_t st)
 int stream_gather_run(const float* cache, size_t slot_floats, const size_t src_off[3], float* const dst[3],
                       const size_t level_floats[3], int nframes, const int* slots, hipStream_t st);
 
+// frame_io.hip: a source frame (any address / pitch, h x w) -> fp32 planar [3][Hp][Wp].  _check validates everything and
+// launches nothing (a caller with more launches ahead checks first); _launch expects checked arguments.
+int frame_ingest_check(const char* what, const void* src, const dvsr_frame_desc* sd, const float* dst, int Hp, int Wp,
+                       int pad_mode);
+int frame_ingest_launch(const void* src, const dvsr_frame_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
+
 // pad.hip: explicit padding / layout changes of the MFDN estimator and their adjoints
 enum : int { PAD_REFLECT = 0, PAD_REFLECT_S2D = 1, PAD_REPL_T3 = 2 };
 size_t pad_out_numel(int mode, size_t N, int C, int H, int W);

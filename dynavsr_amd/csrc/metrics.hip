@@ -17,14 +17,9 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "quant.h"
 
 namespace dvsr {
-
-// tensor2img: clamp, rescale to [0,1], x 255, round half to even -- all in fp32 like torch / numpy do it
-__device__ __forceinline__ int quant_u8(float v, float lo, float hi) {
-  const float t = (fminf(fmaxf(v, lo), hi) - lo) / (hi - lo);
-  return (int)rintf(t * 255.0f);
-}
 
 // One thread = 4 consecutive samples of every channel plane (VEC) or one sample (ragged sizes / unaligned
 // views): 16-byte loads, one dword store per uint8 plane, 4*C contiguous bytes of the HWC image.  The squared

@@ -551,6 +551,25 @@ class StreamPlan:
             ws.numel(), packed, L.stream()))
         self.stats['extracted'] += 1
 
+    def extract_frame(self, leaves, frame, slot, cache, layout=None, pad_mode='reflect'):
+        """A decoder's frame on the GPU -- uint8 [h,w,3|4] ('hwc_rgb' / 'hwc_bgr') or fp32 [3,h,w] ('chw'), h <= H, w <= W,
+        any offset and row pitch -- -> slot `slot` of `cache`, on the current stream: converted and padded to the plan's
+        H x W straight into the slot (frames.ingest's result, without the temporary), then `extract`'s tape."""
+        from . import frames as F
+        layout, h, w = F.resolve_layout(frame, layout)
+        if h > self.h or w > self.w:
+            raise ValueError("EDVR stream of %d x %d frames got a frame of %d x %d" % (self.h, self.w, h, w))
+        F.check_pad(h, w, self.h, self.w, pad_mode)
+        if not frame.is_cuda:
+            raise RuntimeError("libdynavsr_hip needs a tensor on the GPU, got device %s" % frame.device)
+        frame, desc = F.describe(frame, layout)
+        params, arr = self._params(leaves)
+        self._run('extract', leaves, lambda ws, packed: L.lib().dvsr_edvr_stream_extract_frame(
+            self._h, arr, frame.data_ptr(), ctypes.byref(desc), F._PAD[pad_mode], int(slot), cache.data_ptr(),
+            cache.numel() * cache.element_size(), ws.data_ptr(), ws.numel(), packed, L.stream()))
+        self.stats['extracted'] += 1
+        return frame
+
     def fuse(self, leaves, slots, cache, out):
         """The window whose frames sit in `slots` (window order) -> out [1,3,sH,sW], on the current stream."""
         if len(slots) != self.cfg['nframes']:

@@ -295,6 +295,49 @@ int dvsr_edvr_stream_fuse(const dvsr_edvr_stream* stream_plan, const float* cons
                           const void* cache, size_t cache_bytes, float* out, void* workspace, size_t workspace_bytes,
                           int packed, dvsr_stream_t stream);
 
+/* ---- Frames in and out of the video path ---------------------------------------------------------
+ * What a decoder delivers and an encoder takes (8-bit interleaved RGB / BGR at any size, address and row pitch), to and
+ * from what the network computes on (fp32 planar [3][H][W] in [0,1], H and W multiples of 4).  Replaces, per frame,
+ * `img.astype(np.float32) / 255.` + BGR -> RGB + HWC -> CHW (data/util.py:82, :109) on the way in and the fp32
+ * device -> host copy + util.tensor2img (utils/util.py:112-142) on the way out.
+ * dvsr_frame_desc describes the frame on the "any address, any pitch" side:
+ *   DVSR_FRAME_F32_CHW      fp32 planar; row_stride and plane_stride in FLOATS, columns contiguous, 4-byte aligned;
+ *                           pixel_stride is ignored
+ *   DVSR_FRAME_U8_HWC_RGB / _BGR   8-bit interleaved; row_stride in BYTES, pixel_stride 3 or 4 bytes (a fourth byte is
+ *                           ignored; an emitted frame has pixel_stride 3); plane_stride is ignored
+ * dvsr_frame_ingest: src (h x w) -> dst fp32 planar [3][Hp][Wp] RGB, Hp >= h, Wp >= w, Wp % 4 == 0, dst 16-byte aligned.
+ *   8-bit values become v / 255.0f (correctly rounded, numpy's result).  Rows h .. Hp-1 and columns w .. Wp-1 are filled from
+ *   the frame: DVSR_FRAME_PAD_REFLECT = torch.nn.functional.pad(x, (0, Wp-w, 0, Hp-h), 'reflect') (no edge repeat; needs
+ *   Hp - h < h and Wp - w < w), DVSR_FRAME_PAD_REPLICATE = mode 'replicate'.
+ * dvsr_frame_emit: src fp32 planar [3][Hs][Ws] (16-byte aligned, Ws % 4 == 0) -> its top-left dd->h x dd->w crop in
+ *   dd->format at dst.  8-bit: clamp to [lo,hi], rescale, x 255, round half to even -- the quantiser of
+ *   dvsr_frame_metrics, i.e. util.tensor2img(.., min_max=(lo,hi)) bit for bit on finite inputs (BGR = its mode 'bgr').
+ *   F32_CHW: the plain crop (lo, hi unused).  Bytes between rows and behind the last row are not written.
+ * dvsr_edvr_stream_extract_frame: dvsr_frame_ingest straight into the raw-frame section of cache slot `slot` (the stream
+ *   plan's H x W are the padded size, the descriptor carries the true one), then the extract tape reading it there: the
+ *   bits of dvsr_frame_ingest into a temporary + dvsr_edvr_stream_extract, without the temporary and the device copy.
+ * Bad arguments (null pointer, unknown format / pad mode, h or w < 1 or beyond the target, a reflect pad not smaller than
+ * the dimension, pixel stride outside {3,4}, a row stride shorter than a row, a misaligned fp32 side) return
+ * DVSR_ERR_INVALID before any launch. */
+#define DVSR_FRAME_F32_CHW 0
+#define DVSR_FRAME_U8_HWC_RGB 1
+#define DVSR_FRAME_U8_HWC_BGR 2
+#define DVSR_FRAME_PAD_REFLECT 0
+#define DVSR_FRAME_PAD_REPLICATE 1
+typedef struct dvsr_frame_desc {
+  int format;   /* DVSR_FRAME_* */
+  int h, w;     /* the frame's own size */
+  long long row_stride, plane_stride;
+  int pixel_stride;
+} dvsr_frame_desc;
+int dvsr_frame_ingest(const void* src, const dvsr_frame_desc* sd, float* dst, int Hp, int Wp, int pad_mode,
+                      dvsr_stream_t stream);
+int dvsr_frame_emit(const float* src, int Hs, int Ws, void* dst, const dvsr_frame_desc* dd, float lo, float hi,
+                    dvsr_stream_t stream);
+int dvsr_edvr_stream_extract_frame(const dvsr_edvr_stream* stream_plan, const float* const* params, const void* frame,
+                                   const dvsr_frame_desc* fd, int pad_mode, int slot, void* cache, size_t cache_bytes,
+                                   void* workspace, size_t workspace_bytes, int packed, dvsr_stream_t stream);
+
 /* ---- Down-scaling estimators MFDN / SFDN as one launch tape ------------------------------------
  * Replaces DirectKernelEstimatorVideo.forward (models/archs/LRimg_estimator.py:92-117, "MFDN":
  * Conv3d(k3)+ReplicationPad3d, ReflectionPad2d + 3x3 / 4x4-stride-2 Conv2d, Conv3d, 1x1, per-frame
