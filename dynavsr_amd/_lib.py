@@ -58,7 +58,8 @@ class Conv2dDesc(Structure):
                 ("N", c_int), ("c0", c_int), ("c1", c_int), ("H", c_int), ("W", c_int),
                 ("Cout", c_int), ("ks", c_int), ("stride", c_int), ("pad", c_int), ("act", c_int),
                 ("pixel_shuffle", c_int), ("x1_bdiv", c_int),
-                ("x0_bstride", c_longlong), ("x1_bstride", c_longlong)]
+                ("x0_bstride", c_longlong), ("x1_bstride", c_longlong),
+                ("pre", c_void_p), ("pre_bdiv", c_int)]
 
 
 class EdvrConfig(Structure):
@@ -171,6 +172,7 @@ def _declare(lib):
         "dvsr_edvr_tensor_info": (I, [P, c_char_p, POINTER(LL), POINTER(LL)]),
         "dvsr_edvr_plan_work": (I, [P, POINTER(ctypes.c_double * 9)]),
         "dvsr_edvr_plan_work_nograd": (I, [P, POINTER(ctypes.c_double * 9)]),
+        "dvsr_edvr_op_launch_count": (I, [P, I, I]),
         "dvsr_side_stream_overlaps": (I, [P]),
         "dvsr_edvr_op_output": (I, [P, I, I, POINTER(c_int), POINTER(LL), POINTER(LL)]),
         "dvsr_estimator_plan_work": (I, [P, POINTER(ctypes.c_double * 9)]),

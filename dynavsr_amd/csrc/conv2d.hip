@@ -178,6 +178,8 @@ int conv2d_run(const dvsr_conv2d_desc& d, const ConvExtra& ex, hipStream_t st) {
                "conv2d: stride=%d with ks=%d unsupported", d.stride, d.ks);
   DVSR_REQUIRE(d.pad == d.ks / 2, DVSR_ERR_UNSUPPORTED, "conv2d: pad=%d must be ks/2", d.pad);
   DVSR_REQUIRE(d.act >= 0 && d.act <= 2, DVSR_ERR_INVALID, "conv2d: act=%d", d.act);
+  DVSR_REQUIRE(!d.pre, DVSR_ERR_UNSUPPORTED, "conv2d: a pre-activation addend (pre) needs the packed F(4x4, 3x3) kernel "
+               "(dvsr_conv2d_forward_packed); this kernel has no pack");
   DVSR_REQUIRE(d.pixel_shuffle == 0 || (d.pixel_shuffle == 2 && d.Cout % 4 == 0 && !d.res),
                DVSR_ERR_INVALID, "conv2d: pixel_shuffle needs Cout%%4==0 and no residual");
   ConvK k;

@@ -144,6 +144,9 @@ int pack_weights_run(const PackTable& t, hipStream_t st) {
     for (int i = 0; i < t.n; ++i) if (pred(t.e[i])) return true;
     return false;
   };
+  for (int i = 0; i < t.n; ++i)
+    DVSR_REQUIRE(t.e[i].wt || !t.e[i].w_ctot || (t.e[i].layout == PackLayout::WINO_F4 && !t.e[i].bf), DVSR_ERR_UNSUPPORTED,
+                 "pack_weights: only the F(4x4) pack takes a slice of the input channels");
   const struct { PackLayout layout; int (*run)(const PackTable&, hipStream_t); } own[] = {
       {PackLayout::DCN_SPLIT, pack_weights_dcn3_run}, {PackLayout::WINO_F2, pack_weights_wino_run},
       {PackLayout::WINO_F2_BF16, pack_weights_wino3_run}, {PackLayout::WINO_F4, pack_weights_wino5_run}};
@@ -1014,6 +1017,11 @@ bool f4_occupies_less(const ConvShape& s, double cus, const WinoPick& f2, const 
 }
 }  // namespace
 
+double conv2_f4_occupied_cycles(int N, int Ho, int Wo, int Cout, int Ctot, int th) {
+  const ConvShape s{3, 1, N, Ho, Wo, Cout, Ctot};
+  return wino_workgroups(s, th, th == 16 ? 32 : 64) * ((Ctot / 8) * W5_CHUNK_CYC + W5_FIXED_CYC);
+}
+
 ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ctot, ConvAllow allow) {
   const ConvShape s{ks, stride, N, Ho, Wo, Cout, Ctot};
   if (ks == 7 || ks == 9) return choose_row_split(s, allow);
@@ -1026,6 +1034,7 @@ ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ct
   // them at run time.  DVSR_CONV_WINO=0 disables, =2 takes F(2x2) wherever it is eligible (A/B aid); DVSR_CONV_WINO3 (default 1):
   // F(2x2) on the bf16 pipe with the exact 3-way operand split, 0: on the fp32 pipe and no F(4x4); DVSR_CONV_WINO5: 0 no F(4x4),
   // 1 where the model says it is faster (default), 2 wherever it is eligible, 3 eligible and 16x32-pixel workgroup tiles (A/B aids).
+  // ALLOW_ONLY_F4 is the 2 of one launch: it does not override a switch that turns the kernel off.
   const int wino_on = int_or(getenv("DVSR_CONV_WINO"), 1);
   if (!(wino_on && g.kernel == ConvKernel::DMA_HALO && (allow & ALLOW_WINO) && Cout >= 32 && Ctot >= 16)) return g;
   const int wino3_on = int_or(getenv("DVSR_CONV_WINO3"), 1), wino5_on = int_or(getenv("DVSR_CONV_WINO5"), 1);
@@ -1041,7 +1050,7 @@ ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ct
     // latency it has to win by 15 %.  That is the rule of the op-level entries and of every launch that has the device to
     // itself; the engine's no-grad forward slot shares the device and also takes it where it occupies less: f4_occupies_less)
     const bool shared_pick = (allow & ALLOW_SHARED_DEVICE) && f2.cost < direct && f4_occupies_less(s, cus, f2, f4);
-    if (wino5_on >= 2 || ((1.15 * f4.cost < f2.cost || shared_pick) && f4.cost < direct))
+    if (wino5_on >= 2 || (allow & ALLOW_ONLY_F4) || ((1.15 * f4.cost < f2.cost || shared_pick) && f4.cost < direct))
       return ConvGeo{8, wino5_on == 3 ? 16 : f4.th, 2, 0, ConvKernel::WINO_F4};
   }
   if ((wino_on == 2 || f2.cost < direct) && device_lds_optin() >= (size_t)155 * 1024)
@@ -1103,6 +1112,12 @@ int conv2d_packed_prepare(const dvsr_conv2d_desc& d, const float* wp, const Conv
   k.in_ps = ex.in_ps; k.in_dil = ex.in_dil; k.Hs = ex.Hs; k.Ws = ex.Ws; k.accum = ex.accum;
   k.gmask = ex.gmask; k.gmask_act = ex.gmask_act;
   k.wdiv = ex.wdiv > 0 ? ex.wdiv : 1; k.w_gs = ex.w_gs; k.b_gs = ex.b_gs;
+  // a launch with an addend goes to the kernel that implements it or nowhere (conv2d_wino5_kernel's PRE instantiation: 16-byte
+  // rows of a dense [ceil(N / pre_bdiv)][Cout][Ho][Wo] tensor, no residual, plain stores)
+  DVSR_REQUIRE(!d.pre || (geo.kernel == ConvKernel::WINO_F4 && !d.res && d.pixel_shuffle == 0 && ((uintptr_t)d.pre & 15) == 0),
+               DVSR_ERR_UNSUPPORTED, "conv2d_packed: a pre-activation addend needs the F(4x4, 3x3) kernel, a 16-byte aligned tensor, "
+               "no residual and no PixelShuffle");
+  k.pre = d.pre; k.pre_bdiv = d.pre_bdiv > 0 ? d.pre_bdiv : 1; k.pre_bs = (long long)d.Cout * k.Ho * k.Wo;
 #ifdef DVSR_CONV_TRACE
   {
     // measurement aid of the debug build, results are WRONG when set (profiles/r02_z_conv_dma_ablation.txt): bit 0 no
@@ -1212,14 +1227,17 @@ struct OpPack {
   dvsr::ConvGeo geo;
   size_t floats;
 };
-OpPack op_pack(int ks, int stride, int pad, int N, int Ho, int Wo, int Cout, int Ctot, bool plain, bool aligned = false) {
+OpPack op_pack(int ks, int stride, int pad, int N, int Ho, int Wo, int Cout, int Ctot, bool plain, bool aligned = false,
+               bool only_f4 = false) {
   using namespace dvsr;
   OpPack o;
   const bool k3 = ks == 3 && stride == 1 && pad == 1, kbig = (ks == 7 || ks == 9) && stride == 1 && pad == ks / 2;
   // (every aligned 3x3 may take the Winograd kernels, F(4x4) included, whether or not autograd records the caller: these entries
   // run plain forward-style epilogues only -- no accumulate, no gradient mask)
-  o.geo = conv2_choose(ks, stride, N, Ho, Wo, Cout, Ctot, (k3 && plain ? ALLOW_KSPLIT : ALLOW_NONE) | ((k3 || kbig) && aligned ? ALLOW_DMA_HALO : ALLOW_NONE) |
-                                                              (k3 && aligned ? ALLOW_WINO | ALLOW_WINO_F4 : ALLOW_NONE));
+  // (only_f4: a descriptor with an addend -- no K-split kernel ahead of the choice, F(4x4) wherever it is eligible; op_run refuses
+  // the launch if that is nowhere)
+  o.geo = conv2_choose(ks, stride, N, Ho, Wo, Cout, Ctot, (k3 && plain && !only_f4 ? ALLOW_KSPLIT : ALLOW_NONE) | ((k3 || kbig) && aligned ? ALLOW_DMA_HALO : ALLOW_NONE) |
+                                                              (k3 && aligned ? ALLOW_WINO | ALLOW_WINO_F4 : ALLOW_NONE) | (only_f4 ? ALLOW_ONLY_F4 : ALLOW_NONE));
   o.floats = conv2_pack_floats(ks, Cout, Ctot, o.geo);
   return o;
 }
@@ -1228,7 +1246,7 @@ OpPack op_pack_for(const dvsr_conv2d_desc& d, int Cout, int Ctot) {
   const bool big = d.ks == 7 || d.ks == 9;
   const bool aligned = (((uintptr_t)d.x0 | (uintptr_t)d.x1) & 15) == 0 && (big ? (d.c1 == 0 || d.c0 % 8 == 0) : (d.c0 % 8 == 0 && d.c1 % 8 == 0)) &&
                        d.x0_bstride % 4 == 0 && d.x1_bstride % 4 == 0 && (d.H * d.W) % 4 == 0;
-  return op_pack(d.ks, 1, d.pad, d.N, d.H, d.W, Cout, Ctot, d.c1 == 0 || d.c0 % 32 == 0, aligned);
+  return op_pack(d.ks, 1, d.pad, d.N, d.H, d.W, Cout, Ctot, d.c1 == 0 || d.c0 % 32 == 0, aligned, d.pre != nullptr);
 }
 int op_run(const dvsr_conv2d_desc& d, const dvsr::ConvExtra& ex, int Cout, int Ctot, void* ws, size_t bytes, hipStream_t st) {
   using namespace dvsr;
@@ -1237,6 +1255,10 @@ int op_run(const dvsr_conv2d_desc& d, const dvsr::ConvExtra& ex, int Cout, int C
   const OpPack o = op_pack_for(d, Cout, Ctot);
   DVSR_REQUIRE(d.ks <= 3 || o.geo.kernel == ConvKernel::ROW_SPLIT, DVSR_ERR_UNSUPPORTED, "conv2d (packed): this %dx%d convolution is not eligible for the "
                "row-split kernel (dvsr_conv2d_packed_geometry): use dvsr_conv2d_forward / _backward", d.ks, d.ks);
+  DVSR_REQUIRE(!d.pre || (o.geo.kernel == ConvKernel::WINO_F4 && !d.res && !d.pixel_shuffle), DVSR_ERR_UNSUPPORTED,
+               "conv2d (packed): a pre-activation addend (pre) needs a launch the F(4x4, 3x3) kernel takes -- an aligned 3x3 / "
+               "stride 1 / pad 1 convolution, W %% 4 == 0, whole 8-channel chunks, at least 32 outputs and 16 inputs -- without a "
+               "residual or a PixelShuffle");
   DVSR_REQUIRE(ws && bytes >= o.floats * sizeof(float), DVSR_ERR_WORKSPACE, "conv2d (packed): workspace %zu < %zu bytes", bytes,
                o.floats * sizeof(float));
   PackTable t;

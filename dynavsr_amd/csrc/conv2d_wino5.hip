@@ -116,7 +116,9 @@ __global__ void pack_weights_wino5_kernel(PackTable t) {
     const int co = cb * 64 + col, ci = k * 8 + c8;
     double g[3][3];
     const bool ok = co < e.Cout && ci < e.Ctot;
-    const float* src = !e.wt ? e.w + ((size_t)co * e.Ctot + ci) * 9 : e.w + ((size_t)ci * e.w_ctot + e.w_coff + co) * 9;
+    // (not transposed: w_ctot > 0 packs the input channels [w_coff, w_coff + Ctot) of a [Cout][w_ctot][3][3] tensor)
+    const float* src = !e.wt ? e.w + ((size_t)co * (e.w_ctot ? e.w_ctot : e.Ctot) + (e.w_ctot ? e.w_coff : 0) + ci) * 9
+                             : e.w + ((size_t)ci * e.w_ctot + e.w_coff + co) * 9;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) g[tap / 3][tap % 3] = ok ? (double)src[e.wt ? 8 - tap : tap] : 0.0;
     double c[6][3];
@@ -151,8 +153,13 @@ int pack_weights_wino5_run(const PackTable& t, hipStream_t st) {
 // waves read the exchange image, one cout each; otherwise eight consumer waves read a cout PAIR each -- what PixelShuffle(2)
 // needs for 16-byte rows of the shuffled image, and what measures faster without a residual -- and the producers leave after
 // the loop.
-template <int TC, bool RES, bool R16>
+// PRE (with R16, without RES): the epilogue adds a.pre[n / a.pre_bdiv][cout][oy][ox] BEFORE the activation -- the half of a
+// two-input convolution whose input pre_bdiv batch items share, convolved once by a launch of its own (engine.hip: Op::hoist).
+// Its 16-byte rows are fetched like the residual's -- the four rows of a cout together, ahead of the stores, none past a cut last
+// tile row -- and earlier: at the top of the reader, under the exchange reads.  A separate instantiation for the residual's reason: the other two compile to what they did without it.
+template <int TC, bool RES, bool R16, bool PRE>
 __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
+  static_assert(!PRE || (R16 && !RES), "the addend is read by the sixteen-reader epilogue, never beside a residual");
   using Sh = Wino5Shape<TC>;
   constexpr int IH = Sh::IH, RP = Sh::RP, GR = Sh::GR;
   constexpr int CHF = IH * RP;              // floats between two channels of one quad of the raw image
@@ -204,6 +211,16 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
     const float slope = a.act == ACT_LRELU ? 0.1f : (a.act == ACT_RELU ? 0.f : 1.f);
     const float* bias = wset_ptr(a.bias, a.b_gs, n, a.wdiv);
     const int co0 = cbi * 64 + m * 32 + 8 * rq_r + 4 * hi_e + cp_r;   // this thread's cout
+    f32x4 pr[4];
+    if constexpr (PRE) {
+      // the addend's four rows go out FIRST: the exchange reads and the row transform below cover their latency.  Nothing is
+      // read for a tile outside the image, a cout past Cout or a row past a cut last tile row.
+      const bool live = oy < a.Ho && ox < a.Wo && co0 < a.Cout;
+      const float* pre = a.pre + (size_t)(n / a.pre_bdiv) * a.pre_bs + (size_t)co0 * HWo + (size_t)oy * a.Wo + ox;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        pr[i] = (live && oy + i < a.Ho) ? *reinterpret_cast<const f32x4*>(pre + (size_t)i * a.Wo) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     float y[4][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -234,7 +251,8 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
         f32x4 v;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float v0 = y[i][j] + b0;
+          float v0 = y[i][j] + b0;
+          if constexpr (PRE) v0 += pr[i][j];
           v[j] = fmaxf(v0, v0 * slope);
         }
         if constexpr (RES) v += rr[i];
@@ -640,10 +658,14 @@ static int launch_wino5(ConvK2 k, hipStream_t st) {
   // Sixteen readers only where the epilogue also fetches a residual (fe_rb_b 96-99 -> 91-92 us on one box); without one the
   // eight pair readers measure 2-3 % FASTER per launch (L1_om 238 against 243 us, HRconv 222-226 against 229-233), and a
   // PixelShuffle(2) launch (never with a residual: conv2_prepare) needs the pairs for its 16-byte rows.
-  auto kern = k.res ? conv2d_wino5_kernel<TC, true, true> : conv2d_wino5_kernel<TC, false, false>;
-  static PerDeviceOnce attr_once, attr_once_r;
-  set_dyn_lds_once(attr_once, (const void*)conv2d_wino5_kernel<TC, false, false>, Sh::LDS_BYTES);
-  set_dyn_lds_once(attr_once_r, (const void*)conv2d_wino5_kernel<TC, true, true>, Sh::LDS_BYTES);
+  // The addend (k.pre; never with a residual or a PixelShuffle: conv2d_packed_prepare) is one more fetch in the epilogue, as the
+  // residual is: sixteen readers.
+  auto kern = k.pre ? conv2d_wino5_kernel<TC, false, true, true>
+                    : (k.res ? conv2d_wino5_kernel<TC, true, true, false> : conv2d_wino5_kernel<TC, false, false, false>);
+  static PerDeviceOnce attr_once, attr_once_r, attr_once_p;
+  set_dyn_lds_once(attr_once, (const void*)conv2d_wino5_kernel<TC, false, false, false>, Sh::LDS_BYTES);
+  set_dyn_lds_once(attr_once_r, (const void*)conv2d_wino5_kernel<TC, true, true, false>, Sh::LDS_BYTES);
+  set_dyn_lds_once(attr_once_p, (const void*)conv2d_wino5_kernel<TC, false, true, true>, Sh::LDS_BYTES);
   k.tiles_x = ceil_div(k.Wo, Sh::OW); k.tiles_y = ceil_div(k.Ho, Sh::OH); k.ntiles = k.tiles_x * k.tiles_y * k.N;
   k.ncb = ceil_div(k.Cout, 64);
   k.tiles_per_xcd = ceil_div(k.ntiles, 8);

@@ -75,6 +75,15 @@ struct Op {
   // identities and the goldens of the inner step are what they were.  fwd[1] == fwd[0] elsewhere: same geometry, same pack.
   // (OP_DCN: fwd[0] alone, floats == 0 without a pack)
   PackSlot fwd[2], dgrad[2];
+  // NO-GRAD forward only.  A 3x3 stride-1 conv over cat(x0, x1) whose x1 is batch-broadcast (x1_bdiv > 1: the centre frame's
+  // features under the PCD offset convs) is linear in its input channels,
+  //     act(conv_W(cat(f_i, ref)) + b)  =  act(conv_W[:, :c0](f_i) + [conv_W[:, c0:](ref) + b]),
+  // and the bracket is the same for the x1_bdiv frames of a clip.  With hoist.on the op runs as TWO launches: the reference part
+  // -- N / x1_bdiv images, the op's bias, no activation -- into `pre`, then the main part over x0 alone with `pre` as the
+  // pre-activation addend of its epilogue (conv2d_wino5_kernel's PRE instantiation).  fwd[1] is then the MAIN part's geometry and
+  // pack (input channels [0, c0) of the parameter), hoist.ref the reference part's ([c0, c0 + c1)); the two packs share the slot
+  // the unsplit pack had.  Builder::conv decides; the op list, fwd[0] and the backward tape know nothing of it.
+  struct Hoist { bool on = false; struct T pre; PackSlot ref; } hoist;
 };
 
 // ---- backward tape -------------------------------------------------------------------------
@@ -215,6 +224,33 @@ struct Builder {
           o.fwd[1].geo = g5;
           o.fwd[1].floats = conv2_pack_floats(ks, Cout, c0 + c1, g5);
           o.fwd[1].off = alloc("", o.fwd[1].floats * p.wsets).off;
+        }
+      }
+      // ... and runs the shared half of a batch-broadcast second input once per clip where that is modelled to pay (Op::hoist):
+      // the unsplit launch and the main part both on F(4x4) (the one kernel with the addend), one weight set, and main +
+      // reference below the unsplit launch in occupied CU-time.  Geometries and times are read off ONE clip's grids -- x1_bdiv
+      // images and the one they share --, as f4_occupies_less reads one image's: a batch of clips runs what a single clip runs.
+      // DVSR_PCD_HOIST=0 (read per plan build) keeps the one launch.  At 180x320: L1_offset_conv1, cas_offset_conv1,
+      // L2_offset_conv1; L3_offset_conv1 (45x80) is on the K-split kernel and stays whole.
+      const char* hv = getenv("DVSR_PCD_HOIST");
+      if (!(hv && hv[0] == '0') && !p.use_v1 && p.wsets == 1 && o.fwd[1].geo.kernel == ConvKernel::WINO_F4 && x1_bdiv > 1 && c1 > 0 &&
+          N % x1_bdiv == 0 && !res.valid() && !ps) {
+        const ConvAllow shared = fwd_ok | ALLOW_WINO_F4 | ALLOW_SHARED_DEVICE;
+        const ConvAllow only_f4 = without(fwd_ok, ALLOW_KSPLIT) | ALLOW_WINO_F4 | ALLOW_ONLY_F4;   // the reference part: no other pack is sliced
+        auto f4 = [](const ConvGeo& g) { return g.kernel == ConvKernel::WINO_F4; };
+        const ConvGeo gm = conv2_choose(ks, stride, N, Ho, Wo, Cout, c0, shared), gr = conv2_choose(ks, stride, N / x1_bdiv, Ho, Wo, Cout, c1, only_f4);
+        const ConvGeo u1 = conv2_choose(ks, stride, x1_bdiv, Ho, Wo, Cout, c0 + c1, shared), m1 = conv2_choose(ks, stride, x1_bdiv, Ho, Wo, Cout, c0, shared),
+                      r1 = conv2_choose(ks, stride, 1, Ho, Wo, Cout, c1, only_f4);
+        if (f4(gm) && f4(gr) && f4(u1) && f4(m1) && f4(r1) &&
+            conv2_f4_occupied_cycles(x1_bdiv, Ho, Wo, Cout, c0, m1.th) + conv2_f4_occupied_cycles(1, Ho, Wo, Cout, c1, r1.th) <
+                conv2_f4_occupied_cycles(x1_bdiv, Ho, Wo, Cout, c0 + c1, u1.th)) {
+          const Op::PackSlot whole = o.fwd[1];
+          o.hoist.on = true;
+          o.hoist.pre = alloc("", (size_t)(N / x1_bdiv) * Cout * Ho * Wo);
+          o.fwd[1].geo = gm; o.fwd[1].floats = conv2_pack_floats(ks, Cout, c0, gm);
+          o.hoist.ref.geo = gr; o.hoist.ref.floats = conv2_pack_floats(ks, Cout, c1, gr);
+          o.hoist.ref.off = whole.off + o.fwd[1].floats;   // (c0 / 8 + c1 / 8 chunks: the (c0 + c1) / 8 of the unsplit pack)
+          if (o.fwd[1].floats + o.hoist.ref.floats > whole.floats) { o.hoist = Op::Hoist(); o.fwd[1] = whole; }   // (never: whole chunks)
         }
       }
       for (int which = 0; which < 2; ++which) {
@@ -1019,7 +1055,14 @@ static int pack_all(const dvsr_edvr_plan& p, const float* const* P, float* arena
       }
     }
     for (int ws = 0; ws < S; ++ws) {
-      if (fwd_base) {
+      if (fwd_base && nograd && o.hoist.on) {   // (one weight set) two packs sliced from the one parameter: main [0, c0), reference [c0, ctot)
+        const Op::PackSlot& f = o.fwd[1];
+        const Op::PackSlot& r = o.hoist.ref;
+        t.e[t.n++] = conv2_pack_entry(wsrc, fwd_base + f.off, o.ks, o.Cout, o.c0, f.geo, 0, ctot, 0);
+        if (t.n == 48) { int rc = flush(); if (rc) return rc; }
+        t.e[t.n++] = conv2_pack_entry(wsrc, fwd_base + r.off, o.ks, o.Cout, o.c1, r.geo, 0, ctot, o.c0);
+        if (t.n == 48) { int rc = flush(); if (rc) return rc; }
+      } else if (fwd_base) {
         const Op::PackSlot& f = o.fwd[nograd];
         t.e[t.n++] = conv2_pack_entry(wsrc + ws * wnum, fwd_base + f.off + (size_t)ws * f.floats, o.ks, o.Cout, ctot, f.geo);
         if (t.n == 48) { int rc = flush(); if (rc) return rc; }
@@ -1042,7 +1085,7 @@ static int pack_all(const dvsr_edvr_plan& p, const float* const* P, float* arena
 static int run_forward_op(const dvsr_edvr_plan& p, const Op& o, const float* const* P, const Bases& bs, hipStream_t st) {
   switch (o.type) {
     case OP_CONV: {
-      dvsr_conv2d_desc d;
+      dvsr_conv2d_desc d = {};
       d.x0 = bs.at(o.x0); d.x1 = bs.at(o.x1); d.w = P[o.pw]; d.bias = P[o.pb]; d.res = bs.at(o.res);
       d.y = bs.at(o.y);
       d.N = o.N; d.c0 = o.c0; d.c1 = o.c1; d.H = o.H; d.W = o.W; d.Cout = o.Cout; d.ks = o.ks;
@@ -1075,6 +1118,16 @@ static int run_forward_op(const dvsr_edvr_plan& p, const Op& o, const float* con
                                       p.wsets > 1 ? o.Cout : 0);
       ConvExtra ex;
       const Op::PackSlot& f = o.fwd[bs.nograd];
+      if (bs.nograd && o.hoist.on) {   // reference part, then main part (Op::hoist)
+        dvsr_conv2d_desc r = d;
+        r.x0 = d.x1; r.x1 = nullptr; r.c0 = o.c1; r.c1 = 0; r.N = o.N / o.x1_bdiv; r.x0_bstride = o.x1_bs; r.x1_bstride = 0; r.x1_bdiv = 1;
+        r.act = ACT_NONE; r.y = bs.at(o.hoist.pre);
+        int rc = conv2d_packed_run(r, bs.arena + o.hoist.ref.off, ex, o.hoist.ref.geo, st);
+        if (rc != DVSR_OK) return rc;
+        d.x1 = nullptr; d.c1 = 0; d.x1_bdiv = 1; d.x1_bstride = 0; d.bias = nullptr;
+        d.pre = r.y; d.pre_bdiv = o.x1_bdiv;
+        return conv2d_packed_run(d, bs.arena + f.off, ex, f.geo, st);
+      }
       set_wsets(p, o.N, f.floats, o.Cout, &ex);
       return conv2d_packed_run(d, bs.arena + f.off, ex, f.geo, st);
     }
@@ -1396,6 +1449,12 @@ extern "C" int dvsr_edvr_op_info(const dvsr_edvr_plan* p, int index, char* kind,
   return DVSR_OK;
 }
 
+extern "C" int dvsr_edvr_op_launch_count(const dvsr_edvr_plan* p, int index, int nograd) {
+  if (!p || index < 0 || index >= (int)p->ops.size()) return -1;
+  const Op& o = p->ops[index];
+  return (nograd && o.type == OP_CONV && o.hoist.on) ? 2 : 1;
+}
+
 // Contraction work of a whole plan, forward and backward tapes (out: NINE doubles): out[0] / out[2] = algorithmic FLOPs (2 x MACs of the direct
 // sums: convolutions and the DCN contraction; weight + data gradients for the backward), out[1] / out[3] = the same work as
 // the kernels shape it, in fp32 products -- launches on the Winograd kernels do multiplies_per_output_ratio() of theirs;
@@ -1426,7 +1485,13 @@ static int plan_work(const dvsr_edvr_plan* p, double* out9, bool nograd) {
     }
     if (o.type == OP_CONV) {
       const double f = conv_part(o, o.c0 + o.c1);
-      fa += f; issue(o.fwd[nograd].geo, f, &fe, 0);
+      fa += f;
+      if (nograd && o.hoist.on) {   // what is issued: the main part over x0, the reference part once per x1_bdiv images
+        issue(o.fwd[1].geo, conv_part(o, o.c0), &fe, 0);
+        issue(o.hoist.ref.geo, conv_part(o, o.c1) / o.x1_bdiv, &fe, 0);
+      } else {
+        issue(o.fwd[nograd].geo, f, &fe, 0);
+      }
     } else if (o.type == OP_DCN) {
       const double f = 2.0 * (double)o.N * o.H * o.W * o.Cout * o.c0 * 9;
       fa += f; fe += f; f32p[0] += f;

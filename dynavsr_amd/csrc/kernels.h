@@ -62,6 +62,8 @@ constexpr bool has_own_pack_kernel(PackLayout l) { return static_cast<int>(l) >=
 
 struct PackEntry {
   const float* w; float* P;
+  // wt = 1: w is read as the transposed, tap-mirrored view of a [w_ctot][..] tensor at output-channel offset w_coff (dgrad);
+  // wt = 0 with w_ctot > 0 (PackLayout::WINO_F4 only): the input channels [w_coff, w_coff + Ctot) of a [Cout][w_ctot][ks][ks] one
   int Cout, Ctot, KK, CC, wt, w_ctot, w_coff, ncb, nchunks, pch;
   int bf = 0;  // 1: bf16 image for the bf16 MFMA kernel (pch still counts fp32-sized slots)
   PackLayout layout = PackLayout::INTERLEAVED;
@@ -82,6 +84,8 @@ enum ConvAllow : int {
   ALLOW_WINO_F4 = 8,   // the F(4x4) kernel: ALLOW_WINO's + a forward epilogue (no accumulate / gradient mask)
   ALLOW_SHARED_DEVICE = 16,  // the launch shares the device with other streams' kernels (clips in flight side by side): between
                              // one-round Winograd grids the smaller occupied CU-time wins, not the shorter launch
+  ALLOW_ONLY_F4 = 32,  // the launch needs what the F(4x4) kernel alone implements (the pre-activation addend, a pack of a slice of
+                       // the input channels): F(4x4) wherever it is eligible, whatever the cost model says; the caller checks
 };
 constexpr ConvAllow operator|(ConvAllow a, ConvAllow b) { return static_cast<ConvAllow>(static_cast<int>(a) | static_cast<int>(b)); }
 constexpr ConvAllow without(ConvAllow a, ConvAllow b) { return static_cast<ConvAllow>(static_cast<int>(a) & ~static_cast<int>(b)); }
@@ -98,6 +102,8 @@ inline PackEntry conv2_pack_entry(const float* w, float* P, int ks, int Cout, in
                                   int w_coff = 0) {
   return conv2_pack_entry(w, P, ks, Cout, Ctot, g.cc, g.bf, pack_layout(g.kernel), wt, w_ctot, w_coff);
 }
+// Occupied CU-time of a launch on the F(4x4) kernel as conv2_choose models it: workgroups x (chunks x cycles + fixed cycles)
+double conv2_f4_occupied_cycles(int N, int Ho, int Wo, int Cout, int Ctot, int th);
 int pack_weights_wino_run(const PackTable& t, hipStream_t st);   // conv2d_wino.hip: PackLayout::WINO_F2 entries
 int pack_weights_wino3_run(const PackTable& t, hipStream_t st);  // conv2d_wino3.hip: PackLayout::WINO_F2_BF16 entries
 int pack_weights_wino5_run(const PackTable& t, hipStream_t st);  // conv2d_wino5.hip: PackLayout::WINO_F4 entries

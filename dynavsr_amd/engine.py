@@ -17,7 +17,7 @@ _plans = {}
 # Environment switches the native plan builder reads EVERY TIME it builds a plan (conv2_choose, Builder::conv, build_backward,
 # dvsr_*_plan_create): they are part of the plan-cache key, so a plan built under one setting is never handed out under another.
 _GEOMETRY_ENV = ("DVSR_CONV_WINO", "DVSR_CONV_WINO3", "DVSR_CONV_WINO5", "DVSR_CONV_V1", "DVSR_EST_SPLIT", "DVSR_EST_SPLIT2", "DVSR_FUSE_ACT_BWD",
-                 "DVSR_BWD_STREAMS")
+                 "DVSR_BWD_STREAMS", "DVSR_PCD_HOIST")
 # ... and the ones the native side reads ONCE PER PROCESS (function-local statics): changing them after the first plan has no
 # effect, so they are deliberately NOT in the key -- set them before the first call (the A/B tools run one process per value).
 _PROCESS_ENV = ("DVSR_CONV_LDS", "DVSR_CONV_LAST_MFMA", "DVSR_SPLIT_TH8_FROM", "DVSR_WGRAD_SPLIT3",

@@ -113,6 +113,15 @@ typedef struct dvsr_conv2d_desc {
   int x1_bdiv;       /* x1 batch index = n / x1_bdiv (>=1): one reference frame shared by N frames */
   long long x0_bstride; /* elements between batch items of x0; 0 = dense (c0*H*W) */
   long long x1_bstride; /* same for x1; 0 = dense (c1*H*W) */
+  /* Optional addend BEFORE the activation: y = act(conv + bias + pre[n / pre_bdiv]), pre a dense fp32
+   * [ceil(N/pre_bdiv)][Cout][Ho][Wo], 16-byte aligned; NULL = none (pre_bdiv <= 0 counts as 1).  By linearity it carries the
+   * part of a two-input convolution whose input several batch items share -- conv_W(cat(f_i, ref)) = conv_W[:, :c0](f_i) +
+   * conv_W[:, c0:](ref) -- computed once.  Only the packed Winograd F(4x4,3x3) kernel implements it: dvsr_conv2d_forward_packed
+   * runs that kernel whenever the launch is eligible for it (aligned 3x3 / stride 1 / pad 1, W % 4 == 0, c0 and c1 multiples of
+   * 8, at least 16 inputs and 32 outputs, no res, no pixel_shuffle) and returns DVSR_ERR_UNSUPPORTED otherwise, as
+   * dvsr_conv2d_forward (no pack) and every other entry always do: the addend is never dropped. */
+  const float* pre;
+  int pre_bdiv;
 } dvsr_conv2d_desc;
 
 int dvsr_conv2d_forward(const dvsr_conv2d_desc* d, dvsr_stream_t stream);
@@ -232,6 +241,13 @@ int dvsr_edvr_plan_work(const dvsr_edvr_plan* plan, double* out9);
  * Winograd F(4x4,3x3) kernel (36/144 of the direct sum's multiplies, six bf16 products each) on layers whose training tape
  * keeps F(2x2,3x3); dvsr_edvr_op_info's tags ("w5") and dvsr_edvr_forward_timed describe that forward. */
 int dvsr_edvr_plan_work_nograd(const dvsr_edvr_plan* plan, double* out9);
+/* Kernels that forward launch `index` issues for its own work: 2 for a two-input 3x3 convolution that a no-grad forward
+ * (nograd != 0) runs as reference part + main part -- the half whose input the frames of a clip share is convolved once per
+ * clip and enters the other half's epilogue as an addend; DVSR_PCD_HOIST=0 at plan creation keeps it one launch -- and 1 for
+ * everything else (also for the two 1x1 convolutions that may share one launch: that is settled when they run).  The op list,
+ * its names and tags and the algorithmic figures of dvsr_edvr_op_info do not change with it; dvsr_edvr_forward_timed times
+ * both kernels under the launch.  -1: bad argument. */
+int dvsr_edvr_op_launch_count(const dvsr_edvr_plan* plan, int index, int nograd);
 /* Does the plans' weight-gradient side stream run BESIDE `stream` on the current device?  ROCm maps HIP streams onto
  * GPU_MAX_HW_QUEUES hardware queues and two streams on one queue serialise -- which queue a stream gets depends on every
  * stream the process created before (an initialised RCCL communicator holds some; train_dynavsr.py:23-30 creates it first).
