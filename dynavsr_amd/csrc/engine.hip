@@ -16,7 +16,6 @@
 //    (dynavsr_amd/spec.py mirrors the walk below).
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -69,22 +68,27 @@ struct Op {
   // packed-weight slots (conv2d_v2.hip): a launch geometry chosen at plan time and where its pack lives (floats: of ONE weight
   // set).  Forward packs in the activation arena, the two data-gradient packs (per input) in the backward-only region.
   struct PackSlot { ConvGeo geo = {8, 8, 2}; size_t off = 0, floats = 0; };
-  // fwd[nograd].  NO-GRAD forwards (a workspace without the gradient region: test(), the baseline / adapted forwards of the
-  // per-frame pipeline -- Video_base_model.py:197-201) may take another kernel for the same layer: the F(4x4, 3x3) Winograd
-  // kernel (conv2d_wino5.hip).  Training tapes keep fwd[0], so that everything the backward re-reads, the batched == per-frame
-  // identities and the goldens of the inner step are what they were.  fwd[1] == fwd[0] elsewhere: same geometry, same pack.
-  // (OP_DCN: fwd[0] alone, floats == 0 without a pack)
-  PackSlot fwd[2], dgrad[2];
-  // NO-GRAD forward only.  A 3x3 stride-1 conv over cat(x0, x1) whose x1 is batch-broadcast (x1_bdiv > 1: the centre frame's
-  // features under the PCD offset convs) is linear in its input channels,
-  //     act(conv_W(cat(f_i, ref)) + b)  =  act(conv_W[:, :c0](f_i) + [conv_W[:, c0:](ref) + b]),
-  // and the bracket is the same for the x1_bdiv frames of a clip.  With hoist.on the op runs as TWO launches: the reference part
-  // -- N / x1_bdiv images, the op's bias, no activation -- into `pre`, then the main part over x0 alone with `pre` as the
-  // pre-activation addend of its epilogue (conv2d_wino5_kernel's PRE instantiation).  fwd[1] is then the MAIN part's geometry and
-  // pack (input channels [0, c0) of the parameter), hoist.ref the reference part's ([c0, c0 + c1)); the two packs share the slot
-  // the unsplit pack had.  Builder::conv decides; the op list, fwd[0] and the backward tape know nothing of it.
-  struct Hoist { bool on = false; struct T pre; PackSlot ref; } hoist;
+  PackSlot dgrad[2], dcn_pack;   // dcn_pack: OP_DCN's LDS-sampler pack (geo unused; floats == 0: no pack, the plain kernel runs)
+  // OP_CONV: what a forward in each mode launches, resolved at plan time (plan_conv_launches); every reader walks the list.
+  // One entry is one packed-kernel launch: its geometry and pack, the input-channel slice [c_off, c_off + c) of the parameter it
+  // convolves, and its role.  FWD_GRAD lists ONE whole-op launch: everything the backward re-reads, the batched == per-frame
+  // identities and the goldens of the inner step rest on it.  FWD_NOGRAD (test(), the baseline / adapted forwards of the
+  // per-frame pipeline -- Video_base_model.py:197-201) lists the same launch, or a whole-op launch on the F(4x4, 3x3) Winograd
+  // kernel (conv2d_wino5.hip) with a pack of its own, or a hoisted pair (plan_hoist; launch_desc states the algebra): the
+  // REFERENCE part of a batch-broadcast x1 into `pre`, once per clip, then the MAIN part over x0 alone with `pre` as the
+  // pre-activation addend of its epilogue (conv2d_wino5_kernel's PRE instantiation).  The backward tape knows nothing of it.
+  enum LaunchRole { WHOLE, MAIN_PART, REF_PART };
+  struct Launch { PackSlot pack; int c_off = 0, c = 0; LaunchRole role = WHOLE; };
+  struct LaunchList {
+    int n = 0; Launch l[2];
+    const Launch* begin() const { return l; }
+    const Launch* end() const { return l + n; }
+    const Launch& primary() const { return l[n - 1]; }   // the whole-op launch, or the main part (a reference part comes first)
+  } launches[2];   // [FwdMode]
+  struct T pre;
 };
+// Which launch list a forward walks: FWD_NOGRAD on a workspace without the gradient region (forward_mode)
+enum FwdMode { FWD_GRAD = 0, FWD_NOGRAD = 1 };
 
 // ---- backward tape -------------------------------------------------------------------------
 // Pointer spaces of the backward pass.
@@ -150,21 +154,113 @@ struct dvsr_edvr_plan {
 
 namespace dvsr {
 
+// Bump allocation of one arena slot.
+static T arena_alloc(dvsr_edvr_plan& p, const char* name, size_t numel) {
+  T t;
+  t.space = SP_ARENA;
+  t.off = p.arena_floats;
+  t.numel = numel;
+  p.allocs.emplace_back(t.off, numel);
+  p.arena_floats += (numel + 63) & ~(size_t)63;  // 256-byte aligned slots
+  if (name && *name) p.named.emplace_back(name, t);
+  return t;
+}
+
+// ---- launch planning of a conv op: which packed kernel, on which geometry, runs its forward in each mode and its data gradients
+// The hoisted pair of a no-grad forward whose unsplit launch is `whole` (n == 0: the op stays whole): runs the shared half of a
+// batch-broadcast second input once per clip where that is modelled to pay -- the unsplit launch and the main part both on
+// F(4x4) (the one kernel with the addend), one weight set, and main + reference below the unsplit launch in occupied CU-time.
+// Geometries and times are read off ONE clip's grids -- x1_bdiv images and the one they share --, as f4_occupies_less reads
+// one image's: a batch of clips runs what a single clip runs.  DVSR_PCD_HOIST=0 (read per plan build) keeps the one launch.
+// At 180x320: L1_offset_conv1, cas_offset_conv1, L2_offset_conv1; L3_offset_conv1 (45x80) is on the K-split kernel and stays
+// whole.  The two packs share whole's slot: main [0, c0), then reference [c0, c0 + c1) of the parameter.
+static Op::LaunchList plan_hoist(const Op& o, const dvsr_edvr_plan& p, ConvAllow fwd_ok, const Op::Launch& whole) {
+  Op::LaunchList pair;
+  const char* hv = getenv("DVSR_PCD_HOIST");
+  if ((hv && hv[0] == '0') || p.use_v1 || p.wsets != 1 || whole.pack.geo.kernel != ConvKernel::WINO_F4 || o.x1_bdiv <= 1 || o.c1 <= 0 ||
+      o.N % o.x1_bdiv != 0 || o.res.valid() || o.ps)
+    return pair;
+  const int Ho = conv_out(o, o.H), Wo = conv_out(o, o.W), bd = o.x1_bdiv;
+  const ConvAllow shared = fwd_ok | ALLOW_WINO_F4 | ALLOW_SHARED_DEVICE;
+  const ConvAllow only_f4 = without(fwd_ok, ALLOW_KSPLIT) | ALLOW_WINO_F4 | ALLOW_ONLY_F4;   // the reference part: no other pack is sliced
+  auto choose = [&](int n, int c, ConvAllow allow) { return conv2_choose(o.ks, o.stride, n, Ho, Wo, o.Cout, c, allow); };
+  auto f4 = [](const ConvGeo& g) { return g.kernel == ConvKernel::WINO_F4; };
+  const ConvGeo gm = choose(o.N, o.c0, shared), gr = choose(o.N / bd, o.c1, only_f4);
+  const ConvGeo u1 = choose(bd, o.c0 + o.c1, shared), m1 = choose(bd, o.c0, shared), r1 = choose(1, o.c1, only_f4);
+  if (f4(gm) && f4(gr) && f4(u1) && f4(m1) && f4(r1) &&
+      conv2_f4_occupied_cycles(bd, Ho, Wo, o.Cout, o.c0, m1.th) + conv2_f4_occupied_cycles(1, Ho, Wo, o.Cout, o.c1, r1.th) <
+          conv2_f4_occupied_cycles(bd, Ho, Wo, o.Cout, o.c0 + o.c1, u1.th)) {
+    // (c0 / 8 + c1 / 8 chunks: the (c0 + c1) / 8 of the unsplit pack)
+    const size_t mf = conv2_pack_floats(o.ks, o.Cout, o.c0, gm), rf = conv2_pack_floats(o.ks, o.Cout, o.c1, gr);
+    if (mf + rf <= whole.pack.floats)   // (always: whole chunks.  Launch order: the main part adds what the reference part wrote)
+      pair = {2, {{{gr, whole.pack.off + mf, rf}, o.c0, o.c1, Op::REF_PART}, {{gm, whole.pack.off, mf}, 0, o.c0, Op::MAIN_PART}}};
+  }
+  return pair;
+}
+
+// Fills o.launches, o.pre and o.dgrad.  Arena order: the grad-mode pack, the F(4x4) pack if any, `pre` if hoisted.
+static void plan_conv_launches(Op& o, dvsr_edvr_plan& p) {
+  const int ks = o.ks, N = o.N, c0 = o.c0, c1 = o.c1, Cout = o.Cout, Ho = conv_out(o, o.H), Wo = conv_out(o, o.W);
+  // (estimator plans: also the 2x2 space-to-depth form of the 4x4 stride-2 convolutions, DVSR_EST_SPLIT2=0 keeps those
+  // on the fp32 MFMA)
+  const char* s2 = getenv("DVSR_EST_SPLIT2");
+  const int split2 = s2 ? atoi(s2) : 1;   // (read per plan build, as DVSR_EST_SPLIT is; 2: forward launches only)
+  const bool bf = p.cfg.bf16_mfma && (ks == 3 || (ks == 2 && p.split_any_pad && p.cfg.bf16_mfma == 2 && split2 && c0 % 16 == 0)) &&
+                  o.stride == 1 && (o.pad < 0 || p.split_any_pad) && (c1 == 0 || c0 % 16 == 0);
+  // bf16_mfma = 2: 8-row tiles (two 32-pixel rows per wave) once they still give ~a workgroup per CU
+  static const int split_th8_from = getenv("DVSR_SPLIT_TH8_FROM") ? atoi(getenv("DVSR_SPLIT_TH8_FROM")) : 200;
+  auto as_bf = [&](ConvGeo g, int ho, int wo, int cout, bool dgrad = false) {
+    if (!bf || (ks == 2 && split2 == 2 && dgrad)) return g;
+    // the 2x2 form only where it pays (launches of at least a workgroup per CU): small launches stay on the fp32 kernel
+    if (ks == 2 && (long long)ceil_div(wo, 32) * ceil_div(ho, 4) * N * ceil_div(cout, 64) < 256) return g;
+    g.cc = 16; g.th = 4; g.bf = p.cfg.bf16_mfma == 2 ? 2 : 1;
+    if (g.bf == 2 && (long long)ceil_div(wo, 32) * ceil_div(ho, 8) * N * ceil_div(cout, 32 * g.mt) >= split_th8_from)
+      g.th = 8;
+    return g;
+  };
+  // the K-split small-grid kernel takes plain inputs with an explicit pad of 1 and 32-channel chunks, the DMA-halo kernel
+  // plain inputs in whole 8-channel chunks
+  const bool plain = o.pad < 0 && !o.wmap && !p.cfg.bf16_mfma;
+  // ... and the Winograd kernel where the DMA-halo kernel could run (its epilogue stores plain or PixelShuffle(2) tiles)
+  const ConvAllow ks_ok = (plain && (c1 == 0 || c0 % 32 == 0) ? ALLOW_KSPLIT : ALLOW_NONE) |
+                          (plain && c0 % 8 == 0 && c1 % 8 == 0 ? ALLOW_DMA_HALO | ALLOW_WINO : ALLOW_NONE);
+  const ConvAllow fwd_ok = (o.ps == 0 || (o.ps == 2 && !o.res.valid())) ? ks_ok : without(ks_ok, ALLOW_WINO);
+  auto whole = [&](const ConvGeo& g) {   // one pack per weight set, consecutive
+    const size_t floats = conv2_pack_floats(ks, Cout, c0 + c1, g);
+    return Op::Launch{{g, arena_alloc(p, "", floats * p.wsets).off, floats}, 0, c0 + c1, Op::WHOLE};
+  };
+  o.launches[FWD_GRAD] = {1, {whole(as_bf(conv2_choose(ks, o.stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok), Ho, Wo, Cout))}};
+  // the NO-GRAD forward may take the F(4x4, 3x3) kernel (never the data gradients: accumulate / mask epilogues)
+  Op::LaunchList& nograd = o.launches[FWD_NOGRAD] = o.launches[FWD_GRAD];
+  if ((fwd_ok & ALLOW_WINO) && !nograd.l[0].pack.geo.bf) {
+    // (... and, as the slot of the forwards that run several clips in flight, one stream each, it is chosen for a shared device)
+    const ConvGeo g5 = conv2_choose(ks, o.stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok | ALLOW_WINO_F4 | ALLOW_SHARED_DEVICE);
+    if (g5.kernel == ConvKernel::WINO_F4) nograd.l[0] = whole(g5);
+  }
+  const Op::LaunchList pair = plan_hoist(o, p, fwd_ok, nograd.l[0]);
+  if (pair.n) {
+    o.pre = arena_alloc(p, "", (size_t)(N / o.x1_bdiv) * Cout * Ho * Wo);
+    nograd = pair;
+  }
+  for (int which = 0; which < 2; ++which) {
+    const int ci = which ? c1 : c0;
+    if (!ci) continue;
+    // dgrad = stride-1 conv over the input grid with Cout' = ci, Ctot' = Cout
+    // (data gradient: the gradient tensor is the plain input unless it is pixel-shuffled or zero-dilated)
+    Op::PackSlot& dg = o.dgrad[which];
+    dg.geo = as_bf(conv2_choose(ks, 1, N, o.H, o.W, ci, Cout, (!o.ps && o.stride == 1) ? ks_ok : ALLOW_NONE), o.H, o.W, ci, true);
+    dg.floats = conv2_pack_floats(ks, ci, Cout, dg.geo);
+    dg.off = p.dpack_floats;
+    p.dpack_floats += dg.floats * p.wsets;
+  }
+}
+
 struct Builder {
   dvsr_edvr_plan& p;
   int pcur = 0;  // parameter cursor (state-dict order)
   explicit Builder(dvsr_edvr_plan& plan) : p(plan) {}
 
-  T alloc(const char* name, size_t numel) {
-    T t;
-    t.space = SP_ARENA;
-    t.off = p.arena_floats;
-    t.numel = numel;
-    p.allocs.emplace_back(t.off, numel);
-    p.arena_floats += (numel + 63) & ~(size_t)63;  // 256-byte aligned slots
-    if (name && *name) p.named.emplace_back(name, t);
-    return t;
-  }
+  T alloc(const char* name, size_t numel) { return arena_alloc(p, name, numel); }
   static T view(const T& base, size_t off, size_t numel) {
     T t = base;
     t.off += off;
@@ -183,88 +279,10 @@ struct Builder {
     o.x0 = x0; o.x1 = x1; o.res = res;
     o.N = N; o.c0 = c0; o.c1 = c1; o.H = H; o.W = W; o.Cout = Cout; o.ks = ks; o.stride = stride;
     o.act = act; o.ps = ps; o.x1_bdiv = x1_bdiv; o.x0_bs = x0_bs; o.x1_bs = x1_bs;
-    const int Ho = conv_out(o, H), Wo = conv_out(o, W);
-    o.y = y_override.valid() ? y_override : alloc(name, (size_t)N * Cout * Ho * Wo);
+    o.y = y_override.valid() ? y_override : alloc(name, (size_t)N * Cout * conv_out(o, H) * conv_out(o, W));
     // (the gradient arena mirrors this slot: one re-laid-out gradient per group)
     if (wmap) o.w2_off = alloc("", (size_t)std::max(p.wgroups, p.wsets) * Cout * (c0 + c1) * ks * ks).off;
-    {
-      // (estimator plans: also the 2x2 space-to-depth form of the 4x4 stride-2 convolutions, DVSR_EST_SPLIT2=0 keeps those
-      // on the fp32 MFMA)
-      const char* s2 = getenv("DVSR_EST_SPLIT2");
-      const int split2 = s2 ? atoi(s2) : 1;   // (read per plan build, as DVSR_EST_SPLIT is; 2: forward launches only)
-      const bool bf = p.cfg.bf16_mfma && (ks == 3 || (ks == 2 && p.split_any_pad && p.cfg.bf16_mfma == 2 && split2 && c0 % 16 == 0)) &&
-                      stride == 1 && (pad < 0 || p.split_any_pad) && (c1 == 0 || c0 % 16 == 0);
-      // bf16_mfma = 2: 8-row tiles (two 32-pixel rows per wave) once they still give ~a workgroup per CU
-      static const int split_th8_from = getenv("DVSR_SPLIT_TH8_FROM") ? atoi(getenv("DVSR_SPLIT_TH8_FROM")) : 200;
-      auto as_bf = [&](ConvGeo g, int ho, int wo, int cout, bool dgrad = false) {
-        if (!bf || (ks == 2 && split2 == 2 && dgrad)) return g;
-        // the 2x2 form only where it pays (launches of at least a workgroup per CU): small launches stay on the fp32 kernel
-        if (ks == 2 && (long long)ceil_div(wo, 32) * ceil_div(ho, 4) * N * ceil_div(cout, 64) < 256) return g;
-        g.cc = 16; g.th = 4; g.bf = p.cfg.bf16_mfma == 2 ? 2 : 1;
-        if (g.bf == 2 && (long long)ceil_div(wo, 32) * ceil_div(ho, 8) * N * ceil_div(cout, 32 * g.mt) >= split_th8_from)
-          g.th = 8;
-        return g;
-      };
-      // the K-split small-grid kernel takes plain inputs with an explicit pad of 1 and 32-channel chunks, the DMA-halo kernel
-      // plain inputs in whole 8-channel chunks
-      const bool plain = pad < 0 && !wmap && !p.cfg.bf16_mfma;
-      // ... and the Winograd kernel where the DMA-halo kernel could run (its epilogue stores plain or PixelShuffle(2) tiles)
-      const ConvAllow ks_ok = (plain && (c1 == 0 || c0 % 32 == 0) ? ALLOW_KSPLIT : ALLOW_NONE) |
-                              (plain && c0 % 8 == 0 && c1 % 8 == 0 ? ALLOW_DMA_HALO | ALLOW_WINO : ALLOW_NONE);
-      const ConvAllow fwd_ok = (ps == 0 || (ps == 2 && !res.valid())) ? ks_ok : without(ks_ok, ALLOW_WINO);
-      o.fwd[0].geo = as_bf(conv2_choose(ks, stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok), Ho, Wo, Cout);
-      o.fwd[0].floats = conv2_pack_floats(ks, Cout, c0 + c1, o.fwd[0].geo);
-      o.fwd[0].off = alloc("", o.fwd[0].floats * p.wsets).off;   // one pack per weight set, consecutive
-      // the NO-GRAD forward may take the F(4x4, 3x3) kernel (never the data gradients: accumulate / mask epilogues)
-      o.fwd[1] = o.fwd[0];
-      if ((fwd_ok & ALLOW_WINO) && !o.fwd[0].geo.bf) {
-        // (... and, as the slot of the forwards that run several clips in flight, one stream each, it is chosen for a shared device)
-        const ConvGeo g5 = conv2_choose(ks, stride, N, Ho, Wo, Cout, c0 + c1, fwd_ok | ALLOW_WINO_F4 | ALLOW_SHARED_DEVICE);
-        if (g5.kernel == ConvKernel::WINO_F4) {
-          o.fwd[1].geo = g5;
-          o.fwd[1].floats = conv2_pack_floats(ks, Cout, c0 + c1, g5);
-          o.fwd[1].off = alloc("", o.fwd[1].floats * p.wsets).off;
-        }
-      }
-      // ... and runs the shared half of a batch-broadcast second input once per clip where that is modelled to pay (Op::hoist):
-      // the unsplit launch and the main part both on F(4x4) (the one kernel with the addend), one weight set, and main +
-      // reference below the unsplit launch in occupied CU-time.  Geometries and times are read off ONE clip's grids -- x1_bdiv
-      // images and the one they share --, as f4_occupies_less reads one image's: a batch of clips runs what a single clip runs.
-      // DVSR_PCD_HOIST=0 (read per plan build) keeps the one launch.  At 180x320: L1_offset_conv1, cas_offset_conv1,
-      // L2_offset_conv1; L3_offset_conv1 (45x80) is on the K-split kernel and stays whole.
-      const char* hv = getenv("DVSR_PCD_HOIST");
-      if (!(hv && hv[0] == '0') && !p.use_v1 && p.wsets == 1 && o.fwd[1].geo.kernel == ConvKernel::WINO_F4 && x1_bdiv > 1 && c1 > 0 &&
-          N % x1_bdiv == 0 && !res.valid() && !ps) {
-        const ConvAllow shared = fwd_ok | ALLOW_WINO_F4 | ALLOW_SHARED_DEVICE;
-        const ConvAllow only_f4 = without(fwd_ok, ALLOW_KSPLIT) | ALLOW_WINO_F4 | ALLOW_ONLY_F4;   // the reference part: no other pack is sliced
-        auto f4 = [](const ConvGeo& g) { return g.kernel == ConvKernel::WINO_F4; };
-        const ConvGeo gm = conv2_choose(ks, stride, N, Ho, Wo, Cout, c0, shared), gr = conv2_choose(ks, stride, N / x1_bdiv, Ho, Wo, Cout, c1, only_f4);
-        const ConvGeo u1 = conv2_choose(ks, stride, x1_bdiv, Ho, Wo, Cout, c0 + c1, shared), m1 = conv2_choose(ks, stride, x1_bdiv, Ho, Wo, Cout, c0, shared),
-                      r1 = conv2_choose(ks, stride, 1, Ho, Wo, Cout, c1, only_f4);
-        if (f4(gm) && f4(gr) && f4(u1) && f4(m1) && f4(r1) &&
-            conv2_f4_occupied_cycles(x1_bdiv, Ho, Wo, Cout, c0, m1.th) + conv2_f4_occupied_cycles(1, Ho, Wo, Cout, c1, r1.th) <
-                conv2_f4_occupied_cycles(x1_bdiv, Ho, Wo, Cout, c0 + c1, u1.th)) {
-          const Op::PackSlot whole = o.fwd[1];
-          o.hoist.on = true;
-          o.hoist.pre = alloc("", (size_t)(N / x1_bdiv) * Cout * Ho * Wo);
-          o.fwd[1].geo = gm; o.fwd[1].floats = conv2_pack_floats(ks, Cout, c0, gm);
-          o.hoist.ref.geo = gr; o.hoist.ref.floats = conv2_pack_floats(ks, Cout, c1, gr);
-          o.hoist.ref.off = whole.off + o.fwd[1].floats;   // (c0 / 8 + c1 / 8 chunks: the (c0 + c1) / 8 of the unsplit pack)
-          if (o.fwd[1].floats + o.hoist.ref.floats > whole.floats) { o.hoist = Op::Hoist(); o.fwd[1] = whole; }   // (never: whole chunks)
-        }
-      }
-      for (int which = 0; which < 2; ++which) {
-        const int ci = which ? c1 : c0;
-        if (!ci) continue;
-        // dgrad = stride-1 conv over the input grid with Cout' = ci, Ctot' = Cout
-        // (data gradient: the gradient tensor is the plain input unless it is pixel-shuffled or zero-dilated)
-        Op::PackSlot& dg = o.dgrad[which];
-        dg.geo = as_bf(conv2_choose(ks, 1, N, H, W, ci, Cout, (!ps && stride == 1) ? ks_ok : ALLOW_NONE), H, W, ci, true);
-        dg.floats = conv2_pack_floats(ks, ci, Cout, dg.geo);
-        dg.off = p.dpack_floats;
-        p.dpack_floats += dg.floats * p.wsets;
-      }
-    }
+    plan_conv_launches(o, p);
     p.ops.push_back(o);
     return o.y;
   }
@@ -274,8 +292,8 @@ struct Builder {
     o.N = N; o.c0 = C; o.H = H; o.W = W; o.Cout = C; o.dg = dg; o.act = act;
     o.y = alloc(name, (size_t)N * C * H * W);
     if (C % (dg * 8) == 0) {  // LDS-sampler kernel: weights packed like a conv with 8-channel chunks
-      o.fwd[0].floats = conv2_pack_floats(3, C, C, 8, 0, PackLayout::DCN_SPLIT);   // (the larger layout: the slot fits either)
-      o.fwd[0].off = alloc("", o.fwd[0].floats * p.wsets).off;
+      o.dcn_pack.floats = conv2_pack_floats(3, C, C, 8, 0, PackLayout::DCN_SPLIT);   // (the larger layout: the slot fits either)
+      o.dcn_pack.off = alloc("", o.dcn_pack.floats * p.wsets).off;
     }
     p.ops.push_back(o);
     return o.y;
@@ -619,7 +637,6 @@ static void build_backward(dvsr_edvr_plan& p) {
     if (o.type == OP_GATE) bb.materialize(o.res);
     switch (o.type) {
       case OP_CONV: {
-        const int Ho = conv_out(o, o.H), Wo = conv_out(o, o.W);
         // y = act(conv + b) + res: the residual gradient is the RAW gy, and act' would need the sign of the pre-residual
         // value, which the tape does not keep (B_ACT masks gy in place by the sign of y; a deferred residual copy would
         // then read the masked gy).  No tape combines the two (fe_rb_b, rc_rb_b, conv_last are ACT_NONE): refuse it.
@@ -677,7 +694,6 @@ static void build_backward(dvsr_edvr_plan& p) {
             p.bops.push_back(r);
           }
         }
-        (void)Ho; (void)Wo;
         break;
       }
       case OP_DCN: {
@@ -761,7 +777,6 @@ static void build_backward(dvsr_edvr_plan& p) {
 struct BBases {
   float* arena = nullptr; float* garena = nullptr; const float* x = nullptr; float* gx = nullptr;
   const float* gout = nullptr; float* tmp = nullptr; float* dpack = nullptr;
-  bool use_v1 = false;
   float* at(const Ref& r) const {
     switch (r.space) {
       case R_ACT: return arena + r.off;
@@ -812,7 +827,7 @@ static void dgrad_desc(const dvsr_edvr_plan& p, const BOp& b, const float* const
   g.res = bs.at(b.e);   // skip-connection gradient folded into this launch (BackBuilder::take_pending_as_residual)
   ConvExtra ex;
   ex.wt = 1; ex.w_ctot = o->c0 + o->c1; ex.w_coff = b.which ? o->c0 : 0; ex.accum = b.accum; ex.in_ps = o->ps ? 1 : 0;
-  if (b.mask_op >= 0 && !bs.use_v1) { ex.gmask = bs.arena + p.ops[b.mask_op].y.off; ex.gmask_act = p.ops[b.mask_op].act; }
+  if (b.mask_op >= 0 && !p.use_v1) { ex.gmask = bs.arena + p.ops[b.mask_op].y.off; ex.gmask_act = p.ops[b.mask_op].act; }
   if (o->stride == 2) { ex.in_dil = 2; ex.Hs = Ho; ex.Ws = Wo; g.H = o->H; g.W = o->W; }
   else { g.H = Ho; g.W = Wo; }
   set_wsets(p, o->N, o->dgrad[b.which].floats, 0, &ex);
@@ -866,7 +881,7 @@ static int run_backward_op(const dvsr_edvr_plan& p, const BOp& b, const float* c
       dvsr_conv2d_desc g;
       ConvExtra ex;
       dgrad_desc(p, b, P, bs, &g, &ex);
-      if (bs.use_v1) return conv2d_run(g, ex, st);
+      if (p.use_v1) return conv2d_run(g, ex, st);
       return conv2d_packed_run(g, bs.dpack + o->dgrad[b.which].off, ex, o->dgrad[b.which].geo, st);
     }
     case B_REDUCE: {
@@ -904,8 +919,8 @@ static int run_backward_op(const dvsr_edvr_plan& p, const BOp& b, const float* c
 }
 
 struct Bases {
-  float* arena; const float* x; float* out; bool use_v1;
-  bool nograd = false;   // the workspace has no gradient region: the forward may run the no-grad geometries (Op::fwd[1])
+  float* arena; const float* x; float* out;
+  FwdMode mode;   // which launch list of every conv this forward walks
   float* at(const T& t) const {
     if (t.space == SP_ARENA) return arena + t.off;
     if (t.space == SP_INPUT) return const_cast<float*>(x) + t.off;
@@ -914,131 +929,18 @@ struct Bases {
   }
 };
 
-// The weight-gradient side streams: a small pool per device for the whole process (never destroyed).  Plans on different
-// launch streams share it: their weight gradients then queue behind each other, ordered by the plans' own fork / join events.
-// Candidate 0 is THE side stream whenever it runs beside the launch stream; the others exist only for launch streams it
-// shares a hardware queue with (side_stream_for).
-constexpr int SIDE_POOL = 4;
-static hipStream_t pool_side_stream(int i) {
-  static std::mutex mu;
-  static hipStream_t streams[64][SIDE_POOL] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || i < 0 || i >= SIDE_POOL) { (void)hipGetLastError(); return nullptr; }
-  std::lock_guard<std::mutex> lock(mu);
-  if (!streams[dev][i] && hipStreamCreateWithFlags(&streams[dev][i], hipStreamNonBlocking) != hipSuccess) {
-    (void)hipGetLastError();
-    streams[dev][i] = nullptr;
-  }
-  return streams[dev][i];
-}
-static hipStream_t shared_side_stream() { return pool_side_stream(0); }
-
-// ---- does work on the side stream run BESIDE work on a launch stream?
-// ROCm maps HIP streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default) and two streams that land on one queue run
-// behind each other: a plan whose weight gradients sit on such a side stream pays the fork / join events and gets no
-// overlap (the inner step measured 10.0 instead of 8.2 ms with an RCCL communicator's streams in the process, r02-r04).
-// Which queue a stream gets depends on every stream the process created before -- nothing a plan can know -- so it is
-// MEASURED, once per (device, launch stream): a kernel that spins for 150 us on the launch stream, a marker kernel on the
-// side stream behind it; the marker's start time tells whether it waited for the spinner.  dvsr_edvr_backward falls back to
-// single-stream weight gradients for a launch stream that fails the probe.  DVSR_BWD_PROBE=0 skips it (assume overlap).
-__global__ void probe_spin_kernel(long long* out, long long ticks) {
-  const long long t0 = __builtin_amdgcn_s_memrealtime();
-  long long t = t0;
-  while (t - t0 < ticks) { __builtin_amdgcn_s_sleep(8); t = __builtin_amdgcn_s_memrealtime(); }
-  out[0] = t0;
-  out[1] = t;
-}
-__global__ void probe_mark_kernel(long long* out) { out[2] = __builtin_amdgcn_s_memrealtime(); }
-
-// 1: overlaps, 0: serialised, -1: could not tell (capturing, allocation failure, probe disabled by the caller)
-static int probe_side_overlap(hipStream_t st, hipStream_t side) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return -1; }
-  long long* d = nullptr;
-  if (hipMalloc(&d, 4 * sizeof(long long)) != hipSuccess) { (void)hipGetLastError(); return -1; }
-  int res = -1;
-  long long h[4] = {0, 0, 0, 0};
-  // (the streams are drained first: what is still queued on either would be measured instead)
-  if (hipStreamSynchronize(st) == hipSuccess && hipStreamSynchronize(side) == hipSuccess &&
-      hipMemsetAsync(d, 0, sizeof(h), st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-    // (one untimed marker first: the first launch on a fresh stream costs its queue set-up, > 100 us at times -- timed, that is a
-    // false "serialised")
-    hipLaunchKernelGGL(probe_mark_kernel, dim3(1), dim3(64), 0, side, d);
-    (void)hipStreamSynchronize(side);
-    (void)hipMemsetAsync(d, 0, sizeof(h), st);
-    (void)hipStreamSynchronize(st);
-    hipLaunchKernelGGL(probe_spin_kernel, dim3(1), dim3(64), 0, st, d, 15000LL);   // 150 us of the 100 MHz counter
-    hipLaunchKernelGGL(probe_mark_kernel, dim3(1), dim3(64), 0, side, d);
-    if (hipStreamSynchronize(side) == hipSuccess && hipStreamSynchronize(st) == hipSuccess &&
-        hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[1] > h[0] && h[2] > 0)
-      res = h[2] < h[1] - 5000 ? 1 : 0;   // the marker started at least 50 us before the spinner ended
-  }
-  (void)hipGetLastError();
-  (void)hipFree(d);
-  return res;
-}
-
-// The side stream to use beside launch stream `st`: the first of the pool that the probe finds running concurrently with
-// it (a new stream lands on another hardware queue than its predecessor, so one of four consecutive candidates is off the
-// launch stream's queue unless everything is on one), cached per (device, launch stream).  nullptr: none overlaps -- the
-// caller keeps its weight gradients on `st`.  *known = false: the probe could not run (stream capture): candidate 0, unprobed.
-static hipStream_t side_stream_for(hipStream_t st, bool* known = nullptr) {
-  static const bool probe_on = [] { const char* v = getenv("DVSR_BWD_PROBE"); return !(v && v[0] == '0'); }();
-  if (known) *known = probe_on;
-  if (!probe_on) return shared_side_stream();
-  // (a NEGATIVE answer is not kept for ever: the stream -> hardware-queue mapping moves as the process creates streams, and a
-  // destroyed stream's handle can come back as another stream -- it is asked again every 64th use)
-  struct Entry { int dev; hipStream_t st, side; int uses; };
-  static std::mutex mu;
-  static std::vector<Entry> cache;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lock(mu);
-  for (size_t i = 0; i < cache.size(); ++i) {
-    Entry& e = cache[i];
-    if (e.dev != dev || e.st != st) continue;
-    if (e.side || ++e.uses < 64) return e.side;
-    cache.erase(cache.begin() + i);   // re-probe below
-    break;
-  }
-  for (int i = 0; i < SIDE_POOL; ++i) {
-    hipStream_t cand = pool_side_stream(i);
-    if (!cand) break;
-    const int r = probe_side_overlap(st, cand);
-    if (r < 0) {   // (capturing: no measurement possible, nothing cached)
-      if (known) *known = false;
-      return shared_side_stream();
-    }
-    if (r == 1) {
-      cache.push_back({dev, st, cand, 0});
-      return cand;
-    }
-  }
-  cache.push_back({dev, st, nullptr, 0});
-  return nullptr;
-}
-
-// 1: a side stream of the pool runs beside `stream` on this device (the plans fork their weight gradients onto it), 0: none
-// does (they stay on `stream`), -1: unknown (see probe_side_overlap)
-extern "C" int dvsr_side_stream_overlaps(dvsr_stream_t stream) {
-  bool known = true;
-  hipStream_t side = side_stream_for((hipStream_t)stream, &known);
-  if (!known) return -1;
-  return side ? 1 : 0;
-}
-
 // Packs the weights of every conv of the tape (forward: wt=0; backward: the two transposed views).
 static int pack_all(const dvsr_edvr_plan& p, const float* const* P, float* arena_base, float* fwd_base,
-                    float* bwd_base, hipStream_t st, bool nograd = false) {
+                    float* bwd_base, hipStream_t st, FwdMode mode = FWD_GRAD) {
   PackTable t;
   t.n = 0;
   auto flush = [&]() { int rc = pack_weights_run(t, st); t.n = 0; return rc; };
   const int S = p.wsets;   // weight sets: params are [S][numel], every pack slot holds S consecutive packs
   for (const Op& o : p.ops) {
     // (table entries are reused after a flush: conv2_pack_entry writes every field)
-    if (o.type == OP_DCN && fwd_base && o.fwd[0].floats) {
+    if (o.type == OP_DCN && fwd_base && o.dcn_pack.floats) {
       for (int ws = 0; ws < S; ++ws) {
-        t.e[t.n++] = conv2_pack_entry(P[o.pw] + (size_t)ws * o.Cout * o.c0 * 9, fwd_base + o.fwd[0].off + (size_t)ws * o.fwd[0].floats,
+        t.e[t.n++] = conv2_pack_entry(P[o.pw] + (size_t)ws * o.Cout * o.c0 * 9, fwd_base + o.dcn_pack.off + (size_t)ws * o.dcn_pack.floats,
                                       3, o.Cout, o.c0, 8, 0, mdcn_pack_layout(o.W));
         if (t.n == 48) { int rc = flush(); if (rc) return rc; }
       }
@@ -1055,17 +957,13 @@ static int pack_all(const dvsr_edvr_plan& p, const float* const* P, float* arena
       }
     }
     for (int ws = 0; ws < S; ++ws) {
-      if (fwd_base && nograd && o.hoist.on) {   // (one weight set) two packs sliced from the one parameter: main [0, c0), reference [c0, ctot)
-        const Op::PackSlot& f = o.fwd[1];
-        const Op::PackSlot& r = o.hoist.ref;
-        t.e[t.n++] = conv2_pack_entry(wsrc, fwd_base + f.off, o.ks, o.Cout, o.c0, f.geo, 0, ctot, 0);
-        if (t.n == 48) { int rc = flush(); if (rc) return rc; }
-        t.e[t.n++] = conv2_pack_entry(wsrc, fwd_base + r.off, o.ks, o.Cout, o.c1, r.geo, 0, ctot, o.c0);
-        if (t.n == 48) { int rc = flush(); if (rc) return rc; }
-      } else if (fwd_base) {
-        const Op::PackSlot& f = o.fwd[nograd];
-        t.e[t.n++] = conv2_pack_entry(wsrc + ws * wnum, fwd_base + f.off + (size_t)ws * f.floats, o.ks, o.Cout, ctot, f.geo);
-        if (t.n == 48) { int rc = flush(); if (rc) return rc; }
+      if (fwd_base) {
+        for (const Op::Launch& l : o.launches[mode]) {   // (a launch over a slice of the parameter packs that slice)
+          const bool sliced = l.c != ctot;
+          t.e[t.n++] = conv2_pack_entry(wsrc + ws * wnum, fwd_base + l.pack.off + (size_t)ws * l.pack.floats, o.ks, o.Cout, l.c, l.pack.geo,
+                                        0, sliced ? ctot : 0, sliced ? l.c_off : 0);
+          if (t.n == 48) { int rc = flush(); if (rc) return rc; }
+        }
       }
       if (bwd_base) {
         for (int which = 0; which < 2; ++which) {
@@ -1082,6 +980,18 @@ static int pack_all(const dvsr_edvr_plan& p, const float* const* P, float* arena
   return flush();
 }
 
+// The descriptor of one listed launch, from the whole op's.  A conv is linear in its input channels:
+//     act(conv_W(cat(f_i, ref)) + b)  =  act(conv_W[:, :c0](f_i) + [conv_W[:, c0:](ref) + b]);
+// the reference part computes the bracket -- x1 alone, one image per x1_bdiv, the bias, no activation -- into `pre`, the main
+// part the left-hand sum: x0 alone, no bias, `pre` as the pre-activation addend shared by x1_bdiv images.
+static dvsr_conv2d_desc launch_desc(dvsr_conv2d_desc d, const Op& o, Op::LaunchRole role, float* pre) {
+  if (role == Op::WHOLE) return d;
+  if (role == Op::REF_PART) { d.x0 = d.x1; d.c0 = o.c1; d.x0_bstride = o.x1_bs; d.N = o.N / o.x1_bdiv; d.act = ACT_NONE; d.y = pre; }
+  else { d.bias = nullptr; d.pre = pre; d.pre_bdiv = o.x1_bdiv; }
+  d.x1 = nullptr; d.c1 = 0; d.x1_bdiv = 1; d.x1_bstride = 0;
+  return d;
+}
+
 static int run_forward_op(const dvsr_edvr_plan& p, const Op& o, const float* const* P, const Bases& bs, hipStream_t st) {
   switch (o.type) {
     case OP_CONV: {
@@ -1091,7 +1001,7 @@ static int run_forward_op(const dvsr_edvr_plan& p, const Op& o, const float* con
       d.N = o.N; d.c0 = o.c0; d.c1 = o.c1; d.H = o.H; d.W = o.W; d.Cout = o.Cout; d.ks = o.ks;
       d.stride = o.stride; d.pad = conv_pad(o); d.act = o.act; d.pixel_shuffle = o.ps;
       if (o.pad_out) { d.y = bs.at(o.ypad); d.pixel_shuffle = o.pad_out; }
-      if (!bs.use_v1 && (o.dual >= 0 || o.fused_into >= 0)) {   // the pair of 1x1 convs over one input (see Op::dual)
+      if (!p.use_v1 && (o.dual >= 0 || o.fused_into >= 0)) {   // the pair of 1x1 convs over one input (see Op::dual)
         const Op& oa = o.dual >= 0 ? o : p.ops[o.fused_into];
         const Op& ob = p.ops[oa.dual];
         const long long HW = (long long)oa.H * oa.W;
@@ -1111,34 +1021,27 @@ static int run_forward_op(const dvsr_edvr_plan& p, const Op& o, const float* con
       }
       if (o.wmap) d.w = bs.arena + o.w2_off;
       d.x1_bdiv = o.x1_bdiv; d.x0_bstride = o.x0_bs; d.x1_bstride = o.x1_bs;
-      if (bs.use_v1) return conv2d_run(d, ConvExtra(), st);
+      if (p.use_v1) return conv2d_run(d, ConvExtra(), st);
       if (o.Cout <= 4 && o.ks == 3 && o.stride == 1 && !o.c1 && !o.ps && !o.x0_bs && o.pad < 0)  // conv_last
         return conv3x3_small_cout_run(d.x0, d.w, d.bias, d.res, d.y, o.N, o.c0, o.H, o.W, o.Cout, o.act, st,
                                       p.wsets > 1 ? o.N / p.wsets : 1, p.wsets > 1 ? (long long)o.Cout * o.c0 * 9 : 0,
                                       p.wsets > 1 ? o.Cout : 0);
-      ConvExtra ex;
-      const Op::PackSlot& f = o.fwd[bs.nograd];
-      if (bs.nograd && o.hoist.on) {   // reference part, then main part (Op::hoist)
-        dvsr_conv2d_desc r = d;
-        r.x0 = d.x1; r.x1 = nullptr; r.c0 = o.c1; r.c1 = 0; r.N = o.N / o.x1_bdiv; r.x0_bstride = o.x1_bs; r.x1_bstride = 0; r.x1_bdiv = 1;
-        r.act = ACT_NONE; r.y = bs.at(o.hoist.pre);
-        int rc = conv2d_packed_run(r, bs.arena + o.hoist.ref.off, ex, o.hoist.ref.geo, st);
+      for (const Op::Launch& l : o.launches[bs.mode]) {
+        ConvExtra ex;
+        set_wsets(p, o.N, l.pack.floats, o.Cout, &ex);   // (parts: one weight set, nothing to set)
+        int rc = conv2d_packed_run(launch_desc(d, o, l.role, bs.at(o.pre)), bs.arena + l.pack.off, ex, l.pack.geo, st);
         if (rc != DVSR_OK) return rc;
-        d.x1 = nullptr; d.c1 = 0; d.x1_bdiv = 1; d.x1_bstride = 0; d.bias = nullptr;
-        d.pre = r.y; d.pre_bdiv = o.x1_bdiv;
-        return conv2d_packed_run(d, bs.arena + f.off, ex, f.geo, st);
       }
-      set_wsets(p, o.N, f.floats, o.Cout, &ex);
-      return conv2d_packed_run(d, bs.arena + f.off, ex, f.geo, st);
+      return DVSR_OK;
     }
     case OP_DCN: {
       const float* om = bs.at(o.x1);
       const long long bstride = (long long)o.dg * 27 * o.H * o.W;
-      if (!bs.use_v1 && o.fwd[0].floats)
+      if (!p.use_v1 && o.dcn_pack.floats)
         return mdcn_forward_packed_run(bs.at(o.x0), om, bstride, om + (size_t)o.dg * 18 * o.H * o.W, bstride, 1,
-                                       bs.arena + o.fwd[0].off, P[o.pb], bs.at(o.y), o.N, o.c0, o.H, o.W, o.Cout,
+                                       bs.arena + o.dcn_pack.off, P[o.pb], bs.at(o.y), o.N, o.c0, o.H, o.W, o.Cout,
                                        o.dg, o.act, st, p.wsets > 1 ? o.N / p.wsets : 1,
-                                       p.wsets > 1 ? (long long)o.fwd[0].floats : 0, p.wsets > 1 ? o.Cout : 0, mdcn_pack_layout(o.W));
+                                       p.wsets > 1 ? (long long)o.dcn_pack.floats : 0, p.wsets > 1 ? o.Cout : 0, mdcn_pack_layout(o.W));
       return mdcn_forward_run(bs.at(o.x0), om, bstride, om + (size_t)o.dg * 18 * o.H * o.W, bstride, 1,
                               P[o.pw], P[o.pb], bs.at(o.y), o.N, o.c0, o.H, o.W, o.Cout, 3, 3, 1, 1,
                               1, 1, o.dg, o.act, st);
@@ -1250,7 +1153,6 @@ extern "C" int dvsr_edvr_backward(const dvsr_edvr_plan* p, const float* const* p
   bs.arena = (float*)ws; bs.garena = bs.arena + p->arena_floats; bs.x = x; bs.gx = grad_x; bs.gout = grad_out;
   bs.tmp = bs.garena + p->arena_floats;
   bs.dpack = bs.tmp + p->tmp_floats;
-  bs.use_v1 = p->use_v1;
   void* scratch = bs.dpack + p->dpack_floats;
   if (!p->use_v1) {
     int rc = pack_all(*p, params, bs.arena, nullptr, bs.dpack, st);
@@ -1264,7 +1166,7 @@ extern "C" int dvsr_edvr_backward(const dvsr_edvr_plan* p, const float* const* p
   // fork/join state of the side stream (events created on first use, owned by the plan)
   bool use_side = p->side_streams != 0;
   if (use_side && !p->ev_fork) {
-    // Side streams are per DEVICE, shared by all plans (pool_side_stream): ROCm maps streams onto a few hardware queues
+    // Side streams are per DEVICE, shared by all plans (side_stream.hip): ROCm maps streams onto a few hardware queues
     // (GPU_MAX_HW_QUEUES, 4 by default; more than ~6 in use and the command processor time-slices them: EDVR-L
     // forward+backward 20 -> 31 ms), and streams that share a queue run behind each other.  With a stream per plan the
     // mapping, and with it the overlap, depended on how many plans and other streams (an RCCL communicator holds some)
@@ -1361,6 +1263,26 @@ extern "C" int dvsr_edvr_backward(const dvsr_edvr_plan* p, const float* const* p
 
 extern "C" int dvsr_edvr_num_backward_launches(const dvsr_edvr_plan* p) { return p ? (int)p->bops.size() : -1; }
 
+// The forward mode of a plan on a workspace of ws_bytes.  One too small for dvsr_edvr_backward is a no-grad forward (the header's
+// contract: "allocate with need_grad = 1 BEFORE the forward"): only then may a layer run on kernels the backward's tape was
+// not built around.
+static FwdMode forward_mode(const dvsr_edvr_plan* p, size_t ws_bytes) {
+  return ws_bytes < dvsr_edvr_workspace_bytes(p, 1) ? FWD_NOGRAD : FWD_GRAD;
+}
+
+// The forward tape of `p` in bs.mode, behind its weight packs unless the workspace still holds them
+static int run_forward_tape(const dvsr_edvr_plan& p, const float* const* params, const Bases& bs, bool packs_valid, hipStream_t st) {
+  if (!p.use_v1 && !packs_valid) {
+    int rc = pack_all(p, params, bs.arena, bs.arena, nullptr, st, bs.mode);
+    if (rc != DVSR_OK) return rc;
+  }
+  for (const Op& o : p.ops) {
+    int rc = run_forward_op(p, o, params, bs, st);
+    if (rc != DVSR_OK) return rc;
+  }
+  return DVSR_OK;
+}
+
 static int edvr_forward_impl(const dvsr_edvr_plan* p, const float* const* params, const float* x, float* out, void* ws,
                              size_t ws_bytes, dvsr_stream_t stream, bool packs_valid);
 
@@ -1382,19 +1304,7 @@ static int edvr_forward_impl(const dvsr_edvr_plan* p, const float* const* params
   DVSR_REQUIRE(p && params && x && out && ws, DVSR_ERR_INVALID, "edvr_forward: null argument");
   DVSR_REQUIRE(ws_bytes >= p->arena_floats * sizeof(float), DVSR_ERR_WORKSPACE,
                "edvr_forward: workspace %zu < %zu bytes", ws_bytes, p->arena_floats * sizeof(float));
-  Bases bs{(float*)ws, x, out, p->use_v1};
-  // a workspace too small for dvsr_edvr_backward is a no-grad forward (the header's contract: "allocate with need_grad = 1
-  // BEFORE the forward"): only then may a layer run on a kernel the backward's tape was not built around
-  bs.nograd = ws_bytes < dvsr_edvr_workspace_bytes(p, 1);
-  if (!p->use_v1 && !packs_valid) {
-    int rc = pack_all(*p, params, bs.arena, bs.arena, nullptr, (hipStream_t)stream, bs.nograd);
-    if (rc != DVSR_OK) return rc;
-  }
-  for (const Op& o : p->ops) {
-    int rc = run_forward_op(*p, o, params, bs, (hipStream_t)stream);
-    if (rc != DVSR_OK) return rc;
-  }
-  return DVSR_OK;
+  return run_forward_tape(*p, params, Bases{(float*)ws, x, out, forward_mode(p, ws_bytes)}, packs_valid, (hipStream_t)stream);
 }
 
 // Algorithmic work of one launch: FLOPs = 2*MAC of the contraction (+ the bilinear blends for the
@@ -1439,9 +1349,10 @@ extern "C" int dvsr_edvr_op_info(const dvsr_edvr_plan* p, int index, char* kind,
   snprintf(kind, kind_cap, "%s", k);
   if (p->ops[index].type == OP_CONV)
   {
-    // (the geometry of the NO-GRAD forward -- what dvsr_edvr_forward_timed's workspace runs; a training tape's forward runs
-    // Op::fwd[0], which differs only where the tag ends in "w5": those layers are "w3" there)
-    const ConvGeo& g = p->ops[index].fwd[1].geo;
+    // (the geometry of the NO-GRAD forward's whole-op launch, or of its main part where the op runs in two parts -- what
+    // dvsr_edvr_forward_timed runs on a no-grad workspace; a need-grad workspace runs the FWD_GRAD list, whose tag differs
+    // only where this one ends in "w5": those layers are "w3" there)
+    const ConvGeo& g = p->ops[index].launches[FWD_NOGRAD].primary().pack.geo;
     snprintf(name, name_cap, "%s[%d/%d/%d%s]", p->ops[index].name, g.cc, g.th, g.mt, kernel_tag(g.kernel));
   }
   else
@@ -1452,7 +1363,7 @@ extern "C" int dvsr_edvr_op_info(const dvsr_edvr_plan* p, int index, char* kind,
 extern "C" int dvsr_edvr_op_launch_count(const dvsr_edvr_plan* p, int index, int nograd) {
   if (!p || index < 0 || index >= (int)p->ops.size()) return -1;
   const Op& o = p->ops[index];
-  return (nograd && o.type == OP_CONV && o.hoist.on) ? 2 : 1;
+  return o.type == OP_CONV ? o.launches[nograd ? FWD_NOGRAD : FWD_GRAD].n : 1;
 }
 
 // Contraction work of a whole plan, forward and backward tapes (out: NINE doubles): out[0] / out[2] = algorithmic FLOPs (2 x MACs of the direct
@@ -1463,7 +1374,7 @@ extern "C" int dvsr_edvr_op_launch_count(const dvsr_edvr_plan* p, int index, int
 // backward tape: a launch on the exact 3-way operand split issues SIX bf16 products per fp32 product (geo.bf == 2, the
 // Winograd bf16x3 kernels -- on_bf16_split() --, the split3 weight gradient), a plain bf16 launch (geo.bf == 1) one.  bench.py prices
 // every roofline fraction with the issued figures against the peak of the pipe they were issued to.
-static int plan_work(const dvsr_edvr_plan* p, double* out9, bool nograd) {
+static int plan_work(const dvsr_edvr_plan* p, double* out9, FwdMode mode) {
   DVSR_REQUIRE(p && out9, DVSR_ERR_INVALID, "edvr_plan_work: null argument");
   double fa = 0, fe = 0, ba = 0, be = 0, fby = 0, f32p[2] = {0, 0}, bfp[2] = {0, 0};
   auto conv_part = [](const Op& o, int ci) {
@@ -1486,12 +1397,8 @@ static int plan_work(const dvsr_edvr_plan* p, double* out9, bool nograd) {
     if (o.type == OP_CONV) {
       const double f = conv_part(o, o.c0 + o.c1);
       fa += f;
-      if (nograd && o.hoist.on) {   // what is issued: the main part over x0, the reference part once per x1_bdiv images
-        issue(o.fwd[1].geo, conv_part(o, o.c0), &fe, 0);
-        issue(o.hoist.ref.geo, conv_part(o, o.c1) / o.x1_bdiv, &fe, 0);
-      } else {
-        issue(o.fwd[nograd].geo, f, &fe, 0);
-      }
+      for (const Op::Launch& l : o.launches[mode])   // what is issued: each launch on its slice, a reference part once per x1_bdiv images
+        issue(l.pack.geo, conv_part(o, l.c) / (l.role == Op::REF_PART ? o.x1_bdiv : 1), &fe, 0);
     } else if (o.type == OP_DCN) {
       const double f = 2.0 * (double)o.N * o.H * o.W * o.Cout * o.c0 * 9;
       fa += f; fe += f; f32p[0] += f;
@@ -1520,9 +1427,9 @@ static int plan_work(const dvsr_edvr_plan* p, double* out9, bool nograd) {
   out9[5] = f32p[0]; out9[6] = bfp[0]; out9[7] = f32p[1]; out9[8] = bfp[1];
   return DVSR_OK;
 }
-extern "C" int dvsr_edvr_plan_work(const dvsr_edvr_plan* p, double* out9) { return plan_work(p, out9, false); }
-// ... with the forward tape priced as a NO-GRAD forward runs it (Op::fwd[1]: the F(4x4, 3x3) kernel where the plan takes it)
-extern "C" int dvsr_edvr_plan_work_nograd(const dvsr_edvr_plan* p, double* out9) { return plan_work(p, out9, true); }
+extern "C" int dvsr_edvr_plan_work(const dvsr_edvr_plan* p, double* out9) { return plan_work(p, out9, FWD_GRAD); }
+// ... with the forward tape priced as a NO-GRAD forward runs it (the F(4x4, 3x3) kernel and the split where the plan takes them)
+extern "C" int dvsr_edvr_plan_work_nograd(const dvsr_edvr_plan* p, double* out9) { return plan_work(p, out9, FWD_NOGRAD); }
 
 // Same launches as dvsr_edvr_forward with a hipEvent recorded on `stream` around every launch;
 // synchronises the stream and returns per-launch milliseconds (measurement aid for bench.py).
@@ -1536,9 +1443,8 @@ extern "C" int dvsr_edvr_forward_timed(const dvsr_edvr_plan* p, const float* con
   const size_t n = p->ops.size();
   std::vector<hipEvent_t> ev(n + 1);
   for (auto& e : ev) DVSR_REQUIRE(hipEventCreate(&e) == hipSuccess, DVSR_ERR_HIP, "hipEventCreate failed");
-  Bases bs{(float*)ws, x, out, p->use_v1};
-  bs.nograd = ws_bytes < dvsr_edvr_workspace_bytes(p, 1);
-  int rc = p->use_v1 ? DVSR_OK : pack_all(*p, params, bs.arena, bs.arena, nullptr, st, bs.nograd);
+  const Bases bs{(float*)ws, x, out, forward_mode(p, ws_bytes)};
+  int rc = p->use_v1 ? DVSR_OK : pack_all(*p, params, bs.arena, bs.arena, nullptr, st, bs.mode);
   hipEventRecord(ev[0], st);
   for (size_t i = 0; i < n && rc == DVSR_OK; ++i) {
     rc = run_forward_op(*p, p->ops[i], params, bs, st);
@@ -1661,18 +1567,7 @@ static int stream_check(const dvsr_edvr_stream* s, const void* params, const voi
 // the extract tape: frame [3][H][W] -> the feature sections of the slot at `dst` (arguments checked by the callers)
 static int stream_extract_tape(const dvsr_edvr_stream* s, const float* const* params, const float* frame, float* dst, void* ws,
                                int packed, hipStream_t st) {
-  const dvsr_edvr_plan& p = s->extract;
-  Bases bs{(float*)ws + s->fuse.arena_floats, frame, dst, p.use_v1};
-  bs.nograd = true;
-  if (!p.use_v1 && !packed) {
-    int rc = pack_all(p, params, bs.arena, bs.arena, nullptr, st, true);
-    if (rc != DVSR_OK) return rc;
-  }
-  for (const Op& o : p.ops) {
-    int rc = run_forward_op(p, o, params, bs, st);
-    if (rc != DVSR_OK) return rc;
-  }
-  return DVSR_OK;
+  return run_forward_tape(s->extract, params, Bases{(float*)ws + s->fuse.arena_floats, frame, dst, FWD_NOGRAD}, packed != 0, st);
 }
 
 extern "C" int dvsr_edvr_stream_extract(const dvsr_edvr_stream* s, const float* const* params, const float* frame, int slot,
@@ -1726,20 +1621,11 @@ extern "C" int dvsr_edvr_stream_fuse(const dvsr_edvr_stream* s, const float* con
                  slots[f], s->slots);
   hipStream_t st = (hipStream_t)stream;
   const float* cf = (const float*)cache;
-  Bases bs{(float*)ws, cf + (size_t)slots[p.cfg.center] * s->sl.floats + s->sl.raw, out, p.use_v1};
-  bs.nograd = true;
-  if (!p.use_v1 && !packed) {
-    rc = pack_all(p, params, bs.arena, bs.arena, nullptr, st, true);
-    if (rc != DVSR_OK) return rc;
-  }
+  const Bases bs{(float*)ws, cf + (size_t)slots[p.cfg.center] * s->sl.floats + s->sl.raw, out, FWD_NOGRAD};
   float* const dst[3] = {bs.arena + s->fea_off[0], bs.arena + s->fea_off[1], bs.arena + s->fea_off[2]};
   rc = stream_gather_run(cf, s->sl.floats, s->sl.off, dst, s->sl.numel, Nf, slots, st);
   if (rc != DVSR_OK) return rc;
-  for (const Op& o : p.ops) {
-    rc = run_forward_op(p, o, params, bs, st);
-    if (rc != DVSR_OK) return rc;
-  }
-  return DVSR_OK;
+  return run_forward_tape(p, params, bs, packed != 0, st);
 }
 
 

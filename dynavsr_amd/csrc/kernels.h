@@ -199,6 +199,10 @@ int act_bwd_inplace(float* g, const float* y, size_t n, int act, hipStream_t st)
 int stream_gather_run(const float* cache, size_t slot_floats, const size_t src_off[3], float* const dst[3],
                       const size_t level_floats[3], int nframes, const int* slots, hipStream_t st);
 
+// side_stream.hip: the weight-gradient side stream to use beside launch stream `st`, out of a small per-device pool: the first
+// that a probe finds running concurrently with it (cached).  nullptr: none overlaps.  *known = false: the probe could not run.
+hipStream_t side_stream_for(hipStream_t st, bool* known = nullptr);
+
 // frame_io.hip: a source frame (any address / pitch, h x w) -> fp32 planar [3][Hp][Wp].  _check validates everything and
 // launches nothing (a caller with more launches ahead checks first); _launch expects checked arguments.
 int frame_ingest_check(const char* what, const void* src, const dvsr_frame_desc* sd, const float* dst, int Hp, int Wp,

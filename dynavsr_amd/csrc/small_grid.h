@@ -27,7 +27,7 @@ struct ConvK2 {
   // step; the adapted forwards) still run as one batch.  w_gs == 0: one set for the whole batch.
   int wdiv = 1; long long w_gs = 0; int b_gs = 0;
   // pre-activation addend: y = act(conv + bias + pre[n / pre_bdiv][cout][oy][ox]), pre_bs floats between its batch items --
-  // the part of a two-input convolution whose input is shared by pre_bdiv batch items, convolved once (engine.hip: Op::hoist).
+  // the part of a two-input convolution whose input is shared by pre_bdiv batch items, convolved once (engine.hip: plan_hoist).
   // conv2d_wino5_kernel's PRE instantiation alone implements it: conv2d_packed_prepare refuses it for every other kernel.
   const float* pre = nullptr; int pre_bdiv = 1; long long pre_bs = 0;
 #ifdef DVSR_CONV_TRACE
