@@ -135,6 +135,8 @@ def _declare(lib):
         "dvsr_conv2d_forward_packed": (I, [POINTER(Conv2dDesc), P, c_size_t, P]),
         "dvsr_conv2d_dgrad_packed": (I, [POINTER(Conv2dDesc), P, P, P, c_size_t, P]),
         "dvsr_conv2d_packed_geometry": (I, [POINTER(Conv2dDesc), POINTER(ctypes.c_int * 4)]),
+        "dvsr_conv2d_wgrad_geometry": (I, [POINTER(Conv2dDesc), I, I, POINTER(ctypes.c_int * 8)]),
+        "dvsr_conv2d_wgrad_workspace_bytes": (c_size_t, [POINTER(Conv2dDesc), I]),
         "dvsr_conv2d_wgrad_bf16": (I, [POINTER(Conv2dDesc), P, P, P, P, c_size_t, P]),
         "dvsr_conv2d_wgrad_split3": (I, [POINTER(Conv2dDesc), P, P, P, P, c_size_t, P]),
         "dvsr_flow_warp_forward": (I, [P, P, P, I, I, I, I, LL, P]),

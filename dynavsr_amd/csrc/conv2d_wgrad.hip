@@ -14,6 +14,7 @@
 //   B (lane l): x [c = l&31][px shifted by tap]   <- s_x[c*PLANEP + (py*S+ty)*IW + px*S+tx]
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -156,44 +157,10 @@ __global__ __launch_bounds__(256, KYS ? 2 : 1) void conv2d_wgrad_pipe_kernel(Wgr
   conv2d_wgrad_pipe_item<KS, KYS, false>(a, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
 
-// dW[o][c_off + c][tap] = sum_s partial[s][tap][o][c];  db[o] = sum_s dbp[s][o]
-// The slots are zeroed again while they are read, so the next wgrad launch on the same scratch can
+// dW[o][c_off + c][tap] = sum_s partial[s][tap][o][c];  db[o] = sum_s dbp[s][o], for a table of layers in ONE launch
+// (blockIdx.y = layer): on the small inner-step clips a per-layer reduce is a 6 us kernel plus a launch gap behind every 44 us
+// weight-gradient kernel.  The slots are zeroed again while they are read, so the next wgrad launch on the same scratch can
 // accumulate into them without a memset of its own (conv2d_wgrad_run's `scratch_is_zero` contract).
-__global__ void wgrad_reduce_kernel(float* __restrict__ partial, float* __restrict__ dbp,
-                                    float* __restrict__ dW, float* __restrict__ db, int nsplit, int KK,
-                                    int OP, int CP, int Cout, int Cin, int Ctot, int c_off, long long dW_gs,
-                                    long long db_gs) {
-  // blockIdx.y = group (per-group gradients): its own nsplit slots, its own output
-  partial += (size_t)blockIdx.y * nsplit * KK * OP * CP;
-  dbp += (size_t)blockIdx.y * nsplit * OP;
-  dW += (size_t)blockIdx.y * dW_gs;
-  if (db) db += (size_t)blockIdx.y * db_gs;
-  const int total = Cout * Cin * KK;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int c = i % Cin;
-    const int t2 = i / Cin;
-    const int o = t2 % Cout;
-    const int t = t2 / Cout;
-    float s = 0.f;
-    for (int sp = 0; sp < nsplit; ++sp) {
-      float* q = partial + (((size_t)sp * KK + t) * OP + o) * CP + c;
-      s += *q;
-      *q = 0.f;
-    }
-    dW[((size_t)o * Ctot + c_off + c) * KK + t] = s;
-  }
-  for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < OP; o += gridDim.x * blockDim.x) {
-    float s = 0.f;
-    for (int sp = 0; sp < nsplit; ++sp) {
-      s += dbp[(size_t)sp * OP + o];
-      dbp[(size_t)sp * OP + o] = 0.f;
-    }
-    if (db && o < Cout) db[o] = s;
-  }
-}
-
-// Same reduction for a table of layers in ONE launch (blockIdx.y = layer): on the small inner-step clips a
-// per-layer reduce is a 6 us kernel plus a launch gap behind every 44 us weight-gradient kernel.
 __global__ void wgrad_reduce_batch_kernel(WgradReduceTable t) {
   const WgradReduceEntry& e = t.e[blockIdx.y];
   const int g = blockIdx.z;   // group of a per-group gradient (launch: z = the largest group count of the table)
@@ -226,255 +193,289 @@ __global__ void wgrad_reduce_batch_kernel(WgradReduceTable t) {
   }
 }
 
-int wgrad_reduce_batch(const WgradReduceEntry* entries, int n, hipStream_t st) {
+int wgrad_reduce_batch(const WgradReduceEntry* entries, int n, hipStream_t st, int blocks) {
   for (int base = 0; base < n; base += WGRAD_REDUCE_BATCH) {
     WgradReduceTable t;
     t.n = n - base < WGRAD_REDUCE_BATCH ? n - base : WGRAD_REDUCE_BATCH;
     int gmax = 1;
     for (int i = 0; i < t.n; ++i) { t.e[i] = entries[base + i]; gmax = t.e[i].ngroups > gmax ? t.e[i].ngroups : gmax; }
-    hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3(96, t.n, gmax), dim3(256), 0, st, t);
+    hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3(blocks, t.n, gmax), dim3(256), 0, st, t);
     int rc = check_launch("wgrad_reduce_batch_kernel");
     if (rc) return rc;
   }
   return DVSR_OK;
 }
 
-template <int KS, int S>
-static void launch_wgrad(const WgradK& k, dim3 grid, hipStream_t st) {
-  using Sh = WgShape<KS, S>;
-  auto kern = conv2d_wgrad_kernel<KS, S>;
-  static PerDeviceOnce attr_once;
-  set_dyn_lds_once(attr_once, (const void*)kern, Sh::LDS_BYTES);
-  const size_t lds = Sh::LDS_BYTES;
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, k);
-}
+// ---- launch geometry ----------------------------------------------------------------------------------------
+// One function per decision; conv2d_wgrad_choose below lists them in priority order.
 
-static int wgrad_splits(int ntiles, int nob, int ncb, int KK, bool one_per_cu = false) {
-  // one workgroup per CU when the pixel grid is small (latency-bound: every extra tile per workgroup
-  // is serial time), two per CU for big grids
-  (void)KK;
-  static int force = -2;  // DVSR_WGRAD_SPLITS=<n> pins the number of pixel splits (A/B aid)
-  if (force == -2) {
-    const char* v = getenv("DVSR_WGRAD_SPLITS");
-    force = v ? atoi(v) : -1;
-  }
-  int s = force > 0 ? force : ceil_div((ntiles >= 2048 && !one_per_cu) ? 512 : 256, nob * ncb);
-  if (s > ntiles) s = ntiles;
-  return s < 1 ? 1 : s;
-}
+// A/B switches, read once per process.  Every other figure of the rule is a named constant beside its decision.
+static bool env_off(const char* v) { return v && v[0] == '0'; }
+struct WgradSwitches {
+  bool wide = !env_off(getenv("DVSR_WGRAD_WIDE"));   // =0: scalar loads in the fp32 and the split kernels
+  bool s3v = !env_off(getenv("DVSR_WGRAD_S3V"));     // =0: the split stays on its scalar-staging (round-4) kernel
+  bool s3w = !env_off(getenv("DVSR_WGRAD_S3W"));     // =0: no eight-wave form
+  // =<tiles x cout blocks x cin blocks>: moves split_row_split's threshold (0 = never)
+  int s3_kys_below = getenv("DVSR_WGRAD_S3_KYS_BELOW") ? atoi(getenv("DVSR_WGRAD_S3_KYS_BELOW")) : 4000;
+  int s3_wgs = getenv("DVSR_WGRAD_S3_WGS") ? atoi(getenv("DVSR_WGRAD_S3_WGS")) : 0;   // =<workgroups per row-split launch of the split kernel>
+  bool split3 = !env_off(getenv("DVSR_WGRAD_SPLIT3"));   // =0: the plans' 3x3 stride-1 weight gradients stay on the fp32 MFMA kernel
+};
+static const WgradSwitches& wgrad_switches() { static const WgradSwitches s; return s; }
+bool wgrad_split3_default() { return wgrad_switches().split3; }
 
-// Pixel splits PER GROUP: the launch as a whole (groups x splits x cout blocks x cin blocks) aims at the same number of
-// workgroups as an ungrouped one over the same tensor.
-// (rounded DOWN: the un-split kernel runs one workgroup per CU, and 12 groups x ceil(256 / 12) = 264 workgroups are two
-// rounds on 256 CUs -- the batched inner step measured 6.07 ms per frame at 12 frames against 5.38 at 8 and 5.09 at 16)
-static int wgrad_group_splits(int gtiles, int nob, int ncb, int KK, int groups, bool one_per_cu = false) {
-  if (groups <= 1) return wgrad_splits(gtiles, nob, ncb, KK, one_per_cu);
-  int s = wgrad_splits(gtiles * groups, nob, ncb, KK, one_per_cu) / groups;
-  if (s > gtiles) s = gtiles;
-  return s < 1 ? 1 : s;
-}
-
-size_t conv2d_wgrad_workspace_bytes(int N, int Cin, int H, int W, int Cout, int ks, int stride, int pad, int groups) {
-  if (pad < 0) pad = ks / 2;
-  if (groups < 1) groups = 1;
-  const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
-  const int gtiles = ceil_div(Wo, 32) * ceil_div(Ho, 2) * (N / groups);
-  const int nob = ceil_div(Cout, 64), ncb = ceil_div(Cin, 64), KK = ks * ks;
-  const int sp = wgrad_group_splits(gtiles, nob, ncb, KK, groups);
-  const int ns = sp < 8 ? sp : 8;
-  return (size_t)groups * ((size_t)ns * KK * nob * 64 * ncb * 64 + (size_t)ns * nob * 64) * sizeof(float);
-}
-
-int conv2d_wgrad_prepare(const float* x, long long x_bs, int x_bdiv, const float* gy, int gy_ps, float* dW, float* db,
-                         int N, int Cin, int H, int W, int Cout, int Ctot, int c_off, int ks, int stride, void* ws,
-                         size_t ws_bytes, hipStream_t st, int scratch_is_zero, int pad, WgradReduceEntry* defer,
-                         WgradLaunch* out, int bf16, int groups, long long dW_gs, long long db_gs) {
-  DVSR_REQUIRE(x && gy && dW && ws, DVSR_ERR_INVALID, "conv2d_wgrad: null pointer");
-  DVSR_REQUIRE(((ks == 1 || ks == 2 || ks == 7 || ks == 9) && stride == 1) || (ks == 3 && (stride == 1 || stride == 2)),
-               DVSR_ERR_UNSUPPORTED, "conv2d_wgrad: ks=%d stride=%d unsupported", ks, stride);
-  if (groups < 1) groups = 1;
-  DVSR_REQUIRE(N % groups == 0, DVSR_ERR_INVALID, "conv2d_wgrad: N=%d is not a multiple of groups=%d", N, groups);
-  if (pad < 0) pad = ks / 2;
-  const size_t need = conv2d_wgrad_workspace_bytes(N, Cin, H, W, Cout, ks, stride, pad, groups);
-  DVSR_REQUIRE(ws_bytes >= need, DVSR_ERR_WORKSPACE, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
-  WgradK& k = out->k;
-  k.x = x; k.gy = gy; k.x_bs = x_bs > 0 ? x_bs : (long long)Cin * H * W; k.x_bdiv = x_bdiv > 0 ? x_bdiv : 1;
-  k.N = N; k.Cin = Cin; k.H = H; k.W = W; k.Cout = Cout; k.pad = pad; k.gy_ps = gy_ps;
-  k.Ho = (H + 2 * k.pad - ks) / stride + 1;
-  k.Wo = (W + 2 * k.pad - ks) / stride + 1;
+// The kernel argument without the rule's answers and the slot pointers: the descriptor's defaults resolved, and the tiling every
+// kernel shares (2 x 32-pixel tiles, 64 x 64 (cout, cin) blocks)
+static WgradK wgrad_shape(const WgradDesc& d) {
+  WgradK k = {};
+  k.x = d.x; k.gy = d.gy; k.x_bs = d.x_bs > 0 ? d.x_bs : (long long)d.Cin * d.H * d.W; k.x_bdiv = d.x_bdiv > 0 ? d.x_bdiv : 1;
+  k.N = d.N; k.Cin = d.Cin; k.H = d.H; k.W = d.W; k.Cout = d.Cout; k.pad = d.pad < 0 ? d.ks / 2 : d.pad; k.gy_ps = d.gy_ps;
+  k.Ho = (d.H + 2 * k.pad - d.ks) / d.stride + 1;
+  k.Wo = (d.W + 2 * k.pad - d.ks) / d.stride + 1;
   k.tiles_x = ceil_div(k.Wo, 32); k.tiles_y = ceil_div(k.Ho, 2);
-  k.ngroups = groups; k.gtiles = k.tiles_x * k.tiles_y * (N / groups); k.ntiles = k.gtiles * groups;
-  k.nob = ceil_div(Cout, 64); k.ncb = ceil_div(Cin, 64);
-  const int KK = ks * ks;
-  // (all split counts below are PER GROUP; groups == 1 is the plain batch-summed gradient)
-  k.nsplit = wgrad_group_splits(k.gtiles, k.nob, k.ncb, KK, groups, stride == 1);
-  // (the estimator's 4x4 stride-2 convs, ks == 2 here: 128 / 256 / 512 / 1024 workgroups per launch measured 2.79 / 2.51 /
-  // 2.54 / 2.56 ms per MFDN forward+backward -- the kernel is staging-bound, 16 accumulator tiles per staged tile against
-  // 36 for 3x3, not parallelism-bound)
-  k.nslot = k.nsplit < 8 ? k.nsplit : 8;
-  out->ks = ks; out->stride = stride;
+  k.ngroups = d.groups < 1 ? 1 : d.groups; k.gtiles = k.tiles_x * k.tiles_y * (d.N / k.ngroups); k.ntiles = k.gtiles * k.ngroups;
+  k.nob = ceil_div(d.Cout, 64); k.ncb = ceil_div(d.Cin, 64);
+  return k;
+}
+static long long work(const WgradK& k) { return (long long)k.ntiles * k.nob * k.ncb; }
+// a launch-wide split count -> per group (rounded DOWN: the un-split kernel runs one workgroup per CU, and 12 groups x
+// ceil(256 / 12) = 264 workgroups are two rounds on 256 CUs -- the batched inner step measured 6.07 ms per frame at 12 frames
+// against 5.38 at 8 and 5.09 at 16), never more than a group has tiles
+static int per_group(const WgradK& k, int s) {
+  s = k.ngroups > 1 ? s / k.ngroups : s;
+  return s > k.gtiles ? k.gtiles : (s < 1 ? 1 : s);
+}
+
+// Pixel splits of the fp32 kernels: one workgroup per CU for the pipelined kernel (its LDS allows no more; latency-bound on small
+// grids: every extra tile per workgroup is serial time), two per CU for the simple kernel on big grids.  The launch as a whole
+// (groups x splits x cout blocks x cin blocks) aims at the same number of workgroups as an ungrouped one over the same tensor.
+// (the estimator's 4x4 stride-2 convs, ks == 2 here: 128 / 256 / 512 / 1024 workgroups per launch measured 2.79 / 2.51 /
+// 2.54 / 2.56 ms per MFDN forward+backward -- the kernel is staging-bound, 16 accumulator tiles per staged tile against
+// 36 for 3x3, not parallelism-bound)
+static int base_splits(const WgradDesc& d, const WgradK& k) {
+  int s = ceil_div((k.ntiles >= 2048 && d.stride != 1) ? 512 : 256, k.nob * k.ncb);
+  if (s > k.ntiles) s = k.ntiles;
+  return per_group(k, s < 1 ? 1 : s);
+}
+// The flush slots, and what conv2d_wgrad_workspace_bytes sizes: the later decisions only lower the split count.
+constexpr int WGRAD_MAX_SLOTS = 8;
+static int max_slots(const WgradDesc& d, const WgradK& k) { return std::min(base_splits(d, k), WGRAD_MAX_SLOTS); }
+
+// The operands the launch gets: the bf16 kernels are 3x3 stride 1; the split kernel also has a 2x2 form.  0: fp32.
+static int operand_mode(const WgradDesc& d) {
+  return (d.mode && d.stride == 1 && (d.ks == 3 || (d.ks == 2 && d.mode == 2))) ? d.mode : 0;
+}
+
+// The bf16 kernels are staging- and flush-bound (36 MFMAs per tile): fewer workgroups, each with more tiles, keep the
+// 147 KB-per-workgroup atomic flush small.  128 at the 64x64 tiles of configs[4] -- sweep in profiles/r02_z_bf16_wgrad.txt --
+// growing with the pixel grid: about eight tiles per workgroup, at most 512 workgroups.
+constexpr int BF_MIN_WGS = 128, BF_MAX_WGS = 512, BF_TILES_PER_WG = 8;
+static int bf_splits(const WgradK& k) {
+  const int target = std::max(BF_MIN_WGS, std::min(BF_MAX_WGS, k.ntiles / BF_TILES_PER_WG));
+  return per_group(k, ceil_div(target, k.nob * k.ncb));
+}
+
+// fp32, small pixel grids: one kernel row per workgroup (conv2d_wgrad_pipe_kernel<3, true>), the pixel split sized for ~two
+// workgroups per CU over the three rows; 7x7 / 9x9 always (their 49 / 81 accumulators would not fit the register file).
+// 1024 (r03; 4096 before): the row split pays when a workgroup would otherwise get less than ~4 tiles; above that its three-fold
+// re-staging of x costs more than the parallelism gives -- the batched inner step (8 frames, 40 x 44x80 = 2640 tiles per layer)
+// measured 5.96 ms per frame with the row split on those layers and 5.45 without (profiles/r03_inner_batch_sweeps.txt).
+constexpr long long PIPE_ROW_SPLIT_BELOW = 1024;   // tiles x cout blocks x cin blocks
+constexpr int PIPE_ROW_SPLIT_WGS = 288, PIPE_ROW_SPLIT_WGS_7_9 = 512;
+static bool pipe_row_split(const WgradDesc& d, const WgradK& k) {
+  return (d.ks == 3 && d.stride == 1 && work(k) < PIPE_ROW_SPLIT_BELOW) || d.ks == 7 || d.ks == 9;
+}
+static int pipe_row_splits(const WgradDesc& d, const WgradK& k) {
+  return per_group(k, ceil_div(d.ks == 3 ? PIPE_ROW_SPLIT_WGS : PIPE_ROW_SPLIT_WGS_7_9, d.ks * k.nob * k.ncb));
+}
+
+// Wide staging: gy rows as float4 (Wo % 4 == 0, not pixel-shuffled), x as float4 / float2 when the row pitch, the batch stride
+// and the pointers allow it.  The fp32 pipelined kernel and the split kernel have the same two vector forms; plain bf16 has none.
+static int vector_width(const WgradDesc& d, const WgradK& k, int bf) {
+  const bool gy_ok = !k.gy_ps && k.Wo % 4 == 0 && ((uintptr_t)k.gy & 15) == 0;
+  if (!wgrad_switches().wide || !gy_ok || d.stride != 1 || d.ks > 3 || bf == 1) return 0;
+  if (k.W % 4 == 0 && k.x_bs % 4 == 0 && ((uintptr_t)k.x & 15) == 0) return 4;
+  if (k.W % 2 == 0 && k.x_bs % 2 == 0 && ((uintptr_t)k.x & 7) == 0) return 2;
+  return 0;
+}
+
+// The split's vector-staging kernels exist for 3x3 with pad 0 / 1 and for the 2x2 form with pad 0 (any other pad runs the
+// scalar-staging kernel), and address a sample with 32-bit byte offsets.
+static bool split_vector_staging(const WgradDesc& d, const WgradK& k, int vx) {
+  const bool vec_form = (d.ks == 3 && (k.pad == 0 || k.pad == 1)) || (d.ks == 2 && k.pad == 0);
+  const bool fits = (unsigned long long)k.Cin * k.H * k.W < (1ull << 30) && (unsigned long long)k.Cout * k.Ho * k.Wo < (1ull << 30);
+  return wgrad_switches().s3v && vx != 0 && vec_form && fits;
+}
+// The vector-staging form can run one kernel ROW per workgroup, two workgroups per CU (conv2d_wgrad_bf16.hip:
+// conv2d_wgrad_split3v_kernel<.., KYS>).  It stages gy three times and x one and a half times, so it pays where a workgroup has
+// few tiles and the fixed costs (first loads, flush, the tail of the last round) weigh most -- measured (tools/wgrad_bench.py,
+// us with / without): 40 x 44x80 93 / 102, 8 x 44x80 40 / 51, 40 x 22x40 47 / 61, 1 x 176x320 52 / 63, but 40 x 176x320
+// 1046 / 941, 64 -> 216 at 40 x 44x80 290 / 264.
+static bool split_row_split(const WgradK& k) { return work(k) < wgrad_switches().s3_kys_below; }
+// two workgroups per CU from ~1000 tiles, one below; rounded DOWN (one workgroup more than the CUs hold at once is a second
+// round with one workgroup in it)
+static int split_row_splits(const WgradDesc& d, const WgradK& k) {
+  const int wgs = wgrad_switches().s3_wgs > 0 ? wgrad_switches().s3_wgs : (work(k) >= 1000 ? 512 : 256);
+  return per_group(k, wgs / (d.ks * k.nob * k.ncb));
+}
+// The eight-wave form (two waves per SIMD, 16x16x32 MFMAs) for the float4-staged launches that are not row-split: 7 - 14 % per
+// launch over the four-wave form (profiles/r05_wgrad_s3w.txt); the float2 forms spill there and stay on four waves.
+static bool split_eight_waves(int vx) { return wgrad_switches().s3w && vx == 4; }
+
+static WgradGeo choose(const WgradDesc& d, const WgradK& k) {
+  WgradGeo g;
+  const int bf = operand_mode(d);
+  g.nsplit = base_splits(d, k);
+  g.vx = vector_width(d, k, bf);
+  if (bf == 2) {
+    g.nsplit = std::min(g.nsplit, bf_splits(k));
+    const bool vec = split_vector_staging(d, k, g.vx);
+    g.row_split = vec && split_row_split(k);
+    if (g.row_split) g.nsplit = split_row_splits(d, k);
+    g.kernel = !vec ? WgradKernel::SPLIT_SCALAR
+                    : (!g.row_split && split_eight_waves(g.vx) ? WgradKernel::SPLIT_WAVE8 : WgradKernel::SPLIT_VECTOR);
+  } else if (bf == 1) {
+    g.nsplit = std::min(g.nsplit, bf_splits(k));
+    g.kernel = WgradKernel::BF16;
+  } else {
+    g.row_split = pipe_row_split(d, k);
+    if (g.row_split) g.nsplit = pipe_row_splits(d, k);
+    g.kernel = d.stride == 1 ? WgradKernel::PIPE : WgradKernel::SIMPLE;
+  }
+  g.nslot = std::min(max_slots(d, k), g.nsplit);
+  g.grid = dim3((g.row_split ? d.ks : 1) * k.ngroups * g.nsplit, k.nob, k.ncb);
+  g.block = g.kernel == WgradKernel::SPLIT_WAVE8 ? 512 : 256;
+  return g;
+}
+WgradGeo conv2d_wgrad_choose(const WgradDesc& d) { return choose(d, wgrad_shape(d)); }
+
+// slot regions: [group][slot][tap][o][c] partial sums, then [group][slot][o] bias sums
+static size_t partial_floats(const WgradDesc& d, const WgradK& k, int nslot) {
+  return (size_t)k.ngroups * nslot * d.ks * d.ks * k.nob * 64 * k.ncb * 64;
+}
+static size_t slot_bytes(const WgradDesc& d, const WgradK& k, int nslot) {
+  return (partial_floats(d, k, nslot) + (size_t)k.ngroups * nslot * k.nob * 64) * sizeof(float);
+}
+size_t conv2d_wgrad_workspace_bytes(const WgradDesc& d) {
+  const WgradK k = wgrad_shape(d);
+  return slot_bytes(d, k, max_slots(d, k));
+}
+
+static int wgrad_check(const WgradDesc& d) {
+  DVSR_REQUIRE(((d.ks == 1 || d.ks == 2 || d.ks == 7 || d.ks == 9) && d.stride == 1) || (d.ks == 3 && (d.stride == 1 || d.stride == 2)),
+               DVSR_ERR_UNSUPPORTED, "conv2d_wgrad: ks=%d stride=%d unsupported", d.ks, d.stride);
+  DVSR_REQUIRE(d.N % (d.groups < 1 ? 1 : d.groups) == 0, DVSR_ERR_INVALID, "conv2d_wgrad: N=%d is not a multiple of groups=%d", d.N,
+               d.groups);
+  return DVSR_OK;
+}
+
+int conv2d_wgrad_prepare(const WgradDesc& d, void* ws, size_t ws_bytes, hipStream_t st, int scratch_is_zero, WgradReduceEntry* entry,
+                         WgradLaunch* out) {
+  DVSR_REQUIRE(d.x && d.gy && d.dW && ws, DVSR_ERR_INVALID, "conv2d_wgrad: null pointer");
+  int rc = wgrad_check(d);
+  if (rc) return rc;
+  WgradK& k = out->k;
+  k = wgrad_shape(d);
+  const size_t need = slot_bytes(d, k, max_slots(d, k));
+  DVSR_REQUIRE(ws_bytes >= need, DVSR_ERR_WORKSPACE, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
+  const WgradGeo g = choose(d, k);
+  k.nsplit = g.nsplit; k.nslot = g.nslot; k.vx = g.vx;
+  out->geo = g; out->ks = d.ks;
 #ifdef DVSR_CONV_TRACE
   { static const int nf = getenv("DVSR_WGRAD_NOFLUSH") ? atoi(getenv("DVSR_WGRAD_NOFLUSH")) : 0; k.noflush = nf; }
   k.trace = g_wgrad_trace;
 #endif
-  // small pixel grids: one kernel row per workgroup (conv2d_wgrad_pipe_kernel<3, true>); the pixel split is then
-  // sized for ~two workgroups per CU over the three rows.  DVSR_WGRAD_KYS_BELOW=<tiles x cout blocks x cin blocks>
-  // moves the threshold (0 disables).  1024 (r03; 4096 before): the row split pays when a workgroup would otherwise
-  // get less than ~4 tiles; above that its three-fold re-staging of x costs more than the parallelism gives -- the
-  // batched inner step (8 frames, 40 x 44x80 = 2640 tiles per layer) measured 5.96 ms per frame with the row split on
-  // those layers and 5.45 without (profiles/r03_inner_batch_sweeps.txt).
-  static int kys_below = -1;
-  if (kys_below < 0) {
-    const char* v = getenv("DVSR_WGRAD_KYS_BELOW");
-    kys_below = v ? atoi(v) : 1024;
-  }
-  auto per_group = [&](int s) {   // a launch-wide split count -> per group (rounded down), never more than a group has tiles
-    s = groups > 1 ? s / groups : s;
-    return s > k.gtiles ? k.gtiles : (s < 1 ? 1 : s);
-  };
-  out->bf = (bf16 && stride == 1 && (ks == 3 || (ks == 2 && bf16 == 2))) ? bf16 : 0;   // (the split kernel also has a 2x2 form)
-  if (out->bf) {
-    // the bf16 kernel is staging- and flush-bound (36 MFMAs per tile): fewer workgroups, each with more tiles, keep the
-    // 147 KB-per-workgroup atomic flush small.  DVSR_WGRAD_BF_WGS=<workgroups per launch to aim for>.
-    static int bf_wgs = -1;
-    if (bf_wgs < 0) {
-      const char* v = getenv("DVSR_WGRAD_BF_WGS");
-      bf_wgs = v ? atoi(v) : 128;
-    }
-    // (128 at the 64x64 tiles of configs[4] -- sweep in profiles/r02_z_bf16_wgrad.txt -- growing with the pixel grid:
-    // about eight tiles per workgroup, at most 512 workgroups)
-    int target = k.ntiles / 8;
-    target = target < bf_wgs ? bf_wgs : (target > 512 ? 512 : target);
-    const int s2 = per_group(ceil_div(target, k.nob * k.ncb));
-    if (s2 < k.nsplit) k.nsplit = s2;
-  }
-  out->kys = !out->bf && ((ks == 3 && stride == 1 && (long long)k.ntiles * k.nob * k.ncb < kys_below) || ks == 7 || ks == 9);
-  if (out->kys) {
-    static int kys_wgs = -1;   // DVSR_WGRAD_KYS_WGS=<workgroups per launch to aim for>
-    if (kys_wgs < 0) {
-      const char* v = getenv("DVSR_WGRAD_KYS_WGS");
-      kys_wgs = v ? atoi(v) : 288;
-    }
-    k.nsplit = per_group(ceil_div(ks == 3 ? kys_wgs : 512, ks * k.nob * k.ncb));
-  }
-  // wide staging: gy rows as float4 (Wo % 4 == 0, not pixel-shuffled), x as float4 / float2 when the row pitch, the batch
-  // stride and the pointers allow it (DVSR_WGRAD_WIDE=0 keeps the scalar loads: A/B aid)
-  k.vx = 0;
-  {
-    static const bool wide = [] { const char* v = getenv("DVSR_WGRAD_WIDE"); return !(v && v[0] == '0'); }();
-    const bool gy_ok = !gy_ps && k.Wo % 4 == 0 && ((uintptr_t)gy & 15) == 0;
-    if (wide && gy_ok && stride == 1 && ks <= 3 && out->bf != 1) {   // (bf == 2: the split kernel has the same two vector forms)
-      if (W % 4 == 0 && k.x_bs % 4 == 0 && ((uintptr_t)x & 15) == 0) k.vx = 4;
-      else if (W % 2 == 0 && k.x_bs % 2 == 0 && ((uintptr_t)x & 7) == 0) k.vx = 2;
-    }
-  }
-  if (out->bf == 2 && k.vx != 0) {
-    // the split kernel's vector-staging form can run one kernel ROW per workgroup, two workgroups per CU (conv2d_wgrad_bf16.hip:
-    // conv2d_wgrad_split3v_kernel<.., KYS>).  It stages gy three times and x one and a half times, so it pays where a
-    // workgroup has few tiles and the fixed costs (first loads, flush, the tail of the last round) weigh most -- measured
-    // (tools/wgrad_bench.py, us with / without): 40 x 44x80 93 / 102, 8 x 44x80 40 / 51, 40 x 22x40 47 / 61, 1 x 176x320 52 / 63,
-    // but 40 x 176x320 1046 / 941, 64 -> 216 at 40 x 44x80 290 / 264.  DVSR_WGRAD_S3_KYS_BELOW=<tiles x cout blocks x cin
-    // blocks> moves the threshold (0 = never); DVSR_WGRAD_S3V=0 keeps the round-4 kernel.  Switches are read once per process.
-    static const int s3_below = [] {
-      const char* w = getenv("DVSR_WGRAD_S3V");
-      if (w && w[0] == '0') return 0;
-      const char* v = getenv("DVSR_WGRAD_S3_KYS_BELOW");
-      return v ? atoi(v) : 4000;
-    }();
-    const bool fits = (unsigned long long)Cin * H * W < (1ull << 30) && (unsigned long long)Cout * k.Ho * k.Wo < (1ull << 30);
-    const long long work = (long long)k.ntiles * k.nob * k.ncb;
-    // (only where conv2d_wgrad_split3_launch has a vector-staging form: 3x3 with pad 0 / 1, the 2x2 form with pad 0 -- any
-    // other pad runs the scalar-staging kernel, which has no row split)
-    const bool vec_form = (ks == 3 && (k.pad == 0 || k.pad == 1)) || (ks == 2 && k.pad == 0);
-    if (work < s3_below && fits && vec_form) {
-      // two workgroups per CU from ~1000 tiles, one below; rounded DOWN (one workgroup more than the CUs hold at once is a
-      // second round with one workgroup in it)
-      static const int s3_wgs = [] { const char* v = getenv("DVSR_WGRAD_S3_WGS"); return v ? atoi(v) : 0; }();
-      const int wgs = s3_wgs > 0 ? s3_wgs : (work >= 1000 ? 512 : 256);
-      out->kys = 1;
-      k.nsplit = per_group(wgs / (ks * k.nob * k.ncb));
-    }
-  }
-  if (k.nslot > k.nsplit) k.nslot = k.nsplit;   // (the slot region was sized for the un-split launch: never larger)
-  out->grid = dim3((out->kys ? ks : 1) * groups * k.nsplit, k.nob, k.ncb);
-  // slot regions: [group][slot][tap][o][c] partial sums, then [group][slot][o] bias sums
-  const size_t pfloats = (size_t)groups * k.nslot * KK * k.nob * 64 * k.ncb * 64;
   k.partial = (float*)ws;
-  k.dbp = k.partial + pfloats;
-  if (!scratch_is_zero) {
-    const size_t zbytes = (pfloats + (size_t)groups * k.nslot * k.nob * 64) * sizeof(float);
-    DVSR_REQUIRE(hipMemsetAsync(ws, 0, zbytes, st) == hipSuccess, DVSR_ERR_HIP, "conv2d_wgrad: memset failed");
-  }
-  if (defer) {  // the caller reduces a batch of layers later (wgrad_reduce_batch); `ws` must stay untouched until then
-    *defer = WgradReduceEntry{k.partial, k.dbp, dW, db, k.nslot, KK, k.nob * 64, k.ncb * 64, Cout, Cin, Ctot, c_off};
-    defer->ngroups = groups; defer->dW_gs = dW_gs; defer->db_gs = db_gs;
-  }
+  k.dbp = k.partial + partial_floats(d, k, k.nslot);
+  if (!scratch_is_zero)
+    DVSR_REQUIRE(hipMemsetAsync(ws, 0, slot_bytes(d, k, k.nslot), st) == hipSuccess, DVSR_ERR_HIP, "conv2d_wgrad: memset failed");
+  *entry = WgradReduceEntry{k.partial, k.dbp, d.dW, d.db, k.nslot, d.ks * d.ks, k.nob * 64, k.ncb * 64, d.Cout, d.Cin, d.Ctot, d.c_off};
+  entry->ngroups = k.ngroups; entry->dW_gs = d.dW_gs; entry->db_gs = d.db_gs;
   return DVSR_OK;
 }
 
+template <int KS, bool KYS>
+static void launch_pipe(const WgradLaunch& l, hipStream_t st) {
+  constexpr size_t lds_a = WgPipeShape<KS, KYS>::LDS_BYTES;
+  constexpr size_t lds_b = KS <= 3 ? (WgWideShape<KS, KYS, 4>::LDS_BYTES > WgWideShape<KS, KYS, 2>::LDS_BYTES
+                                          ? WgWideShape<KS, KYS, 4>::LDS_BYTES : WgWideShape<KS, KYS, 2>::LDS_BYTES) : 0;
+  constexpr size_t lds = lds_a > lds_b ? lds_a : lds_b;
+  static PerDeviceOnce attr_once;
+  set_dyn_lds_once(attr_once, (const void*)conv2d_wgrad_pipe_kernel<KS, KYS>, lds);
+  hipLaunchKernelGGL((conv2d_wgrad_pipe_kernel<KS, KYS>), l.geo.grid, dim3(l.geo.block), lds, st, l.k);
+}
+
 int conv2d_wgrad_launch(const WgradLaunch& l, hipStream_t st) {
-  if (l.bf == 2) return conv2d_wgrad_split3_launch(l, st);
-  if (l.bf) return conv2d_wgrad_bf16_launch(l, st);
-  const WgradK& k = l.k;
-  const dim3 grid = l.grid;
-  const int ks = l.ks, stride = l.stride;
-  static int use_simple = -1;  // DVSR_WGRAD_SIMPLE=1: the non-pipelined kernel for every shape (A/B aid)
-  if (use_simple < 0) {
-    const char* v = getenv("DVSR_WGRAD_SIMPLE");
-    use_simple = (v && v[0] == '1') ? 1 : 0;
-  }
-  if (stride == 1 && !use_simple) {
-    auto launch_pipe = [&](auto ks_tag, auto kys_tag) {
-      constexpr int KS_ = decltype(ks_tag)::value;
-      constexpr bool KYS_ = decltype(kys_tag)::value;
-      constexpr size_t lds_a = WgPipeShape<KS_, KYS_>::LDS_BYTES;
-      constexpr size_t lds_b = KS_ <= 3 ? (WgWideShape<KS_, KYS_, 4>::LDS_BYTES > WgWideShape<KS_, KYS_, 2>::LDS_BYTES
-                                               ? WgWideShape<KS_, KYS_, 4>::LDS_BYTES : WgWideShape<KS_, KYS_, 2>::LDS_BYTES) : 0;
-      constexpr size_t lds = lds_a > lds_b ? lds_a : lds_b;
+  switch (l.geo.kernel) {
+    case WgradKernel::BF16: return conv2d_wgrad_bf16_launch(l, st);
+    case WgradKernel::SPLIT_SCALAR: case WgradKernel::SPLIT_VECTOR: case WgradKernel::SPLIT_WAVE8:
+      return conv2d_wgrad_split3_launch(l, st);
+    case WgradKernel::SIMPLE: {   // 3x3 stride 2 (wgrad_check)
+      using Sh = WgShape<3, 2>;
       static PerDeviceOnce attr_once;
-      set_dyn_lds_once(attr_once, (const void*)conv2d_wgrad_pipe_kernel<KS_, KYS_>, lds);
-      hipLaunchKernelGGL((conv2d_wgrad_pipe_kernel<KS_, KYS_>), grid, dim3(256), lds, st, k);
-    };
-    if (ks == 7) launch_pipe(std::integral_constant<int, 7>{}, std::true_type{});
-    else if (ks == 9) launch_pipe(std::integral_constant<int, 9>{}, std::true_type{});
-    else if (ks == 3 && l.kys) launch_pipe(std::integral_constant<int, 3>{}, std::true_type{});
-    else if (ks == 3) launch_pipe(std::integral_constant<int, 3>{}, std::false_type{});
-    else if (ks == 2) launch_pipe(std::integral_constant<int, 2>{}, std::false_type{});
-    else launch_pipe(std::integral_constant<int, 1>{}, std::false_type{});
-  } else if (ks == 3 && stride == 1) launch_wgrad<3, 1>(k, grid, st);
-  else if (ks == 3) launch_wgrad<3, 2>(k, grid, st);
-  else if (ks == 2) launch_wgrad<2, 1>(k, grid, st);
-  else launch_wgrad<1, 1>(k, grid, st);
+      set_dyn_lds_once(attr_once, (const void*)conv2d_wgrad_kernel<3, 2>, Sh::LDS_BYTES);
+      hipLaunchKernelGGL((conv2d_wgrad_kernel<3, 2>), l.geo.grid, dim3(l.geo.block), Sh::LDS_BYTES, st, l.k);
+      break;
+    }
+    case WgradKernel::PIPE:
+      if (l.ks == 7) launch_pipe<7, true>(l, st);
+      else if (l.ks == 9) launch_pipe<9, true>(l, st);
+      else if (l.ks == 3 && l.geo.row_split) launch_pipe<3, true>(l, st);
+      else if (l.ks == 3) launch_pipe<3, false>(l, st);
+      else if (l.ks == 2) launch_pipe<2, false>(l, st);
+      else launch_pipe<1, false>(l, st);
+      break;
+  }
   return check_launch("conv2d_wgrad_kernel");
 }
 
-// x: one input of the conv ([N/x_bdiv][Cin][H][W], batch stride x_bs or dense), gy: gradient of the
-// conv's pre-activation output.  Writes dW[:, c_off:c_off+Cin, :, :] of a [Cout][Ctot][ks][ks]
-// gradient (and db when non-null).
-int conv2d_wgrad_run(const float* x, long long x_bs, int x_bdiv, const float* gy, int gy_ps, float* dW,
-                     float* db, int N, int Cin, int H, int W, int Cout, int Ctot, int c_off, int ks,
-                     int stride, void* ws, size_t ws_bytes, hipStream_t st, int scratch_is_zero, int pad,
-                     WgradReduceEntry* defer, int groups, long long dW_gs, long long db_gs) {
+int conv2d_wgrad_run(const WgradDesc& d, void* ws, size_t ws_bytes, hipStream_t st, int scratch_is_zero, WgradReduceEntry* defer) {
   WgradLaunch l;
-  int rc = conv2d_wgrad_prepare(x, x_bs, x_bdiv, gy, gy_ps, dW, db, N, Cin, H, W, Cout, Ctot, c_off, ks, stride, ws,
-                                ws_bytes, st, scratch_is_zero, pad, defer, &l, 0, groups, dW_gs, db_gs);
+  WgradReduceEntry own;
+  int rc = conv2d_wgrad_prepare(d, ws, ws_bytes, st, scratch_is_zero, defer ? defer : &own, &l);
   if (rc) return rc;
   rc = conv2d_wgrad_launch(l, st);
   if (rc || defer) return rc;
-  const WgradK& k = l.k;
-  const int KK = ks * ks, total = Cout * Cin * KK;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(total, 256), k.ngroups), dim3(256), 0, st, k.partial, k.dbp,
-                     dW, db, k.nslot, KK, k.nob * 64, k.ncb * 64, Cout, Cin, Ctot, c_off, dW_gs, db_gs);
-  return check_launch("wgrad_reduce_kernel");
+  return wgrad_reduce_batch(&own, 1, st, ceil_div(d.Cout * d.Cin * d.ks * d.ks, 256));   // (alone on the stream: a thread per element)
+}
+
+// The weight gradient of a C-ABI descriptor's first input (plain layout, dense dW)
+static WgradDesc wgrad_desc_of(const dvsr_conv2d_desc& d, const float* gy, float* gw, float* gb) {
+  WgradDesc w;
+  w.x = d.x0; w.x_bs = d.x0_bstride; w.gy = gy; w.gy_ps = d.pixel_shuffle ? 1 : 0; w.dW = gw; w.db = gb;
+  w.N = d.N; w.Cin = d.c0; w.H = d.H; w.W = d.W; w.Cout = d.Cout; w.Ctot = d.c0 + d.c1; w.c_off = 0;
+  w.ks = d.ks; w.stride = d.stride; w.pad = d.pad;
+  return w;
 }
 
 }  // namespace dvsr
 
 extern "C" size_t dvsr_conv2d_backward_workspace_bytes(const dvsr_conv2d_desc* d) {
   if (!d) return 0;
-  size_t a = dvsr::conv2d_wgrad_workspace_bytes(d->N, d->c0 > d->c1 ? d->c0 : d->c1, d->H, d->W, d->Cout,
-                                                d->ks, d->stride);
-  return a;
+  dvsr::WgradDesc w = dvsr::wgrad_desc_of(*d, nullptr, nullptr, nullptr);
+  w.Cin = d->c0 > d->c1 ? d->c0 : d->c1; w.pad = d->ks / 2;
+  return dvsr::conv2d_wgrad_workspace_bytes(w);
+}
+
+// What dvsr_conv2d_wgrad_bf16 / _split3 (mode 1 / 2) or dvsr_conv2d_backward (mode 0; it pads by ks / 2) launch for d's first
+// input, gy at an address aligned like d->y, `groups` per-group gradients: geo = {WgradKernel, row_split, vx, nsplit, nslot,
+// grid x, y, z}.  Launches nothing and needs no device.
+extern "C" int dvsr_conv2d_wgrad_geometry(const dvsr_conv2d_desc* d, int mode, int groups, int geo[8]) {
+  DVSR_REQUIRE(d && geo && mode >= 0 && mode <= 2 && groups >= 1, DVSR_ERR_INVALID, "conv2d_wgrad_geometry: invalid argument");
+  dvsr::WgradDesc w = dvsr::wgrad_desc_of(*d, d->y, nullptr, nullptr);
+  w.mode = mode; w.groups = groups;
+  int rc = dvsr::wgrad_check(w);
+  if (rc) return rc;
+  const dvsr::WgradGeo g = dvsr::conv2d_wgrad_choose(w);
+  geo[0] = static_cast<int>(g.kernel); geo[1] = g.row_split; geo[2] = g.vx; geo[3] = g.nsplit; geo[4] = g.nslot;
+  geo[5] = (int)g.grid.x; geo[6] = (int)g.grid.y; geo[7] = (int)g.grid.z;
+  return DVSR_OK;
+}
+// The workspace of that launch (dvsr_conv2d_backward_workspace_bytes is the groups = 1, pad = ks / 2 case over the wider input)
+extern "C" size_t dvsr_conv2d_wgrad_workspace_bytes(const dvsr_conv2d_desc* d, int groups) {
+  if (!d) return 0;
+  dvsr::WgradDesc w = dvsr::wgrad_desc_of(*d, nullptr, nullptr, nullptr);
+  w.groups = groups;
+  return dvsr::conv2d_wgrad_workspace_bytes(w);
 }
 
 // Backward of dvsr_conv2d_forward for the plain layout (no pixel shuffle): `gy` is the gradient
@@ -492,12 +493,13 @@ extern "C" int dvsr_conv2d_backward(const dvsr_conv2d_desc* d, const float* gy, 
   const int Ho = (d->H + 2 * pad - d->ks) / d->stride + 1, Wo = (d->W + 2 * pad - d->ks) / d->stride + 1;
   int rc;
   if (gw) {
-    rc = conv2d_wgrad_run(d->x0, d->x0_bstride, 1, gy, 0, gw, gb, d->N, d->c0, d->H, d->W, d->Cout, ctot, 0,
-                          d->ks, d->stride, workspace, workspace_bytes, st, 0);
+    WgradDesc w = wgrad_desc_of(*d, gy, gw, gb);
+    w.pad = pad;
+    rc = conv2d_wgrad_run(w, workspace, workspace_bytes, st);
     if (rc) return rc;
     if (d->c1) {
-      rc = conv2d_wgrad_run(d->x1, d->x1_bstride, 1, gy, 0, gw, nullptr, d->N, d->c1, d->H, d->W, d->Cout,
-                            ctot, d->c0, d->ks, d->stride, workspace, workspace_bytes, st, 0);
+      w.x = d->x1; w.x_bs = d->x1_bstride; w.Cin = d->c1; w.c_off = d->c0; w.db = nullptr;
+      rc = conv2d_wgrad_run(w, workspace, workspace_bytes, st);
       if (rc) return rc;
     }
   }
@@ -527,18 +529,9 @@ static int wgrad_bf_mode(const dvsr_conv2d_desc* d, const float* gy, float* gw, 
   DVSR_REQUIRE(d && gy && gw && d->x0, DVSR_ERR_INVALID, "conv2d_wgrad_bf16: null argument");
   DVSR_REQUIRE(d->ks == 3 && d->stride == 1 && d->c1 == 0 && d->pixel_shuffle == 0, DVSR_ERR_UNSUPPORTED,
                "conv2d_wgrad_bf16: 3x3 stride-1 single-input convolutions only");
-  hipStream_t st = (hipStream_t)stream;
-  WgradLaunch l;
-  int rc = conv2d_wgrad_prepare(d->x0, d->x0_bstride, 1, gy, 0, gw, gb, d->N, d->c0, d->H, d->W, d->Cout, d->c0, 0, 3, 1,
-                                workspace, workspace_bytes, st, 0, d->pad, nullptr, &l, mode);
-  if (rc) return rc;
-  rc = conv2d_wgrad_launch(l, st);
-  if (rc) return rc;
-  const WgradK& k = l.k;
-  const int total = d->Cout * d->c0 * 9;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, k.partial, k.dbp, gw, gb, k.nslot, 9,
-                     k.nob * 64, k.ncb * 64, d->Cout, d->c0, d->c0, 0, 0LL, 0LL);
-  return check_launch("wgrad_reduce_kernel");
+  WgradDesc w = wgrad_desc_of(*d, gy, gw, gb);
+  w.mode = mode;
+  return conv2d_wgrad_run(w, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int dvsr_conv2d_wgrad_bf16(const dvsr_conv2d_desc* d, const float* gy, float* gw, float* gb, void* workspace,

@@ -1078,51 +1078,31 @@ __global__ __launch_bounds__(512, 2) void conv2d_wgrad_split3w_kernel(WgradK a) 
   }
 }
 
+template <auto KERNEL>
+static int launch_wgrad_bf(const WgradLaunch& l, size_t lds, const char* name, hipStream_t st) {
+  static PerDeviceOnce attr_once;
+  set_dyn_lds_once(attr_once, (const void*)KERNEL, lds);
+  hipLaunchKernelGGL(KERNEL, l.geo.grid, dim3(l.geo.block), lds, st, l.k);
+  return check_launch(name);
+}
+
+// <KS, VX, SHIFT>: the staging form of l.k.vx and the pad; the kernel of it is conv2d_wgrad_choose's (l.geo.kernel)
 template <int KS, int VX, int SHIFT>
 static int launch_split3(const WgradLaunch& l, hipStream_t st) {
   if constexpr (VX != 0) {
-    // DVSR_WGRAD_S3V=0: the round-4 schedule of the same kernel (A/B switch, read once per process); samples whose byte
-    // offsets do not fit 32 bits keep it too.  l.kys (conv2d_wgrad_prepare): one kernel row per workgroup, two workgroups per CU
-    static const bool s3v = [] { const char* v = getenv("DVSR_WGRAD_S3V"); return !(v && v[0] == '0'); }();
-    const bool fits = (unsigned long long)l.k.Cin * l.k.H * l.k.W < (1ull << 30) && (unsigned long long)l.k.Cout * l.k.Ho * l.k.Wo < (1ull << 30);
-    if (l.kys) {
-      DVSR_REQUIRE(s3v && fits, DVSR_ERR_UNSUPPORTED, "conv2d_wgrad_split3: the row split needs the vector-staging kernel");
-      constexpr size_t lds = (size_t)(3 * S3_GP + 3 * 64 * (2 * S3_XROW + 8)) * 2;
-      auto kv = conv2d_wgrad_split3v_kernel<KS, VX, SHIFT, true>;
-      static PerDeviceOnce attr_once_k;
-      set_dyn_lds_once(attr_once_k, (const void*)kv, lds);
-      hipLaunchKernelGGL(kv, l.grid, dim3(256), lds, st, l.k);
-      return check_launch("conv2d_wgrad_split3v_kernel<kys>");
-    }
-    // the eight-wave form (two waves per SIMD, 16x16x32 MFMAs) for the float4-staged launches that are not row-split: 7 - 14 %
-    // per launch over the four-wave form (profiles/r05_wgrad_s3w.txt); the float2 forms spill there and stay on four waves.
-    // DVSR_WGRAD_S3W=0: A/B switch, read once per process
-    static const bool s3w = [] { const char* v = getenv("DVSR_WGRAD_S3W"); return !(v && v[0] == '0'); }();
-    if (s3v && fits && s3w && VX == 4) {
-      auto kw = conv2d_wgrad_split3w_kernel<KS, VX, SHIFT>;
-      static PerDeviceOnce attr_once_w;
-      set_dyn_lds_once(attr_once_w, (const void*)kw, S3_LDS_BYTES);
-      hipLaunchKernelGGL(kw, l.grid, dim3(512), S3_LDS_BYTES, st, l.k);
-      return check_launch("conv2d_wgrad_split3w_kernel");
-    }
-    if (s3v && fits) {
-      auto kv = conv2d_wgrad_split3v_kernel<KS, VX, SHIFT, false>;
-      static PerDeviceOnce attr_once_v;
-      set_dyn_lds_once(attr_once_v, (const void*)kv, S3_LDS_BYTES);
-      hipLaunchKernelGGL(kv, l.grid, dim3(256), S3_LDS_BYTES, st, l.k);
-      return check_launch("conv2d_wgrad_split3v_kernel");
-    }
+    if (l.geo.kernel == WgradKernel::SPLIT_VECTOR && l.geo.row_split)
+      return launch_wgrad_bf<conv2d_wgrad_split3v_kernel<KS, VX, SHIFT, true>>(l, (size_t)(3 * S3_GP + 3 * 64 * (2 * S3_XROW + 8)) * 2,
+                                                                               "conv2d_wgrad_split3v_kernel<kys>", st);
+    if (l.geo.kernel == WgradKernel::SPLIT_WAVE8)
+      return launch_wgrad_bf<conv2d_wgrad_split3w_kernel<KS, VX, SHIFT>>(l, S3_LDS_BYTES, "conv2d_wgrad_split3w_kernel", st);
+    if (l.geo.kernel == WgradKernel::SPLIT_VECTOR)
+      return launch_wgrad_bf<conv2d_wgrad_split3v_kernel<KS, VX, SHIFT, false>>(l, S3_LDS_BYTES, "conv2d_wgrad_split3v_kernel", st);
   }
-  DVSR_REQUIRE(!l.kys, DVSR_ERR_UNSUPPORTED, "conv2d_wgrad_split3: the row split needs the vector-staging kernel");
-  auto kern = conv2d_wgrad_split3_kernel<KS, VX, SHIFT>;
-  static PerDeviceOnce attr_once;
-  set_dyn_lds_once(attr_once, (const void*)kern, S3_LDS_BYTES);
-  hipLaunchKernelGGL(kern, l.grid, dim3(256), S3_LDS_BYTES, st, l.k);
-  return check_launch("conv2d_wgrad_split3_kernel");
+  return launch_wgrad_bf<conv2d_wgrad_split3_kernel<KS, VX, SHIFT>>(l, S3_LDS_BYTES, "conv2d_wgrad_split3_kernel", st);
 }
 
 int conv2d_wgrad_split3_launch(const WgradLaunch& l, hipStream_t st) {
-  // l.k.vx (conv2d_wgrad_prepare): 4 / 2 when gy rows are float4-loadable and the x rows float4 / float2-loadable
+  // l.k.vx (conv2d_wgrad_choose): 4 / 2 when gy rows are float4-loadable and the x rows float4 / float2-loadable
   const int pad = l.k.pad;
   if (l.ks == 2) {   // (pad 0 or 1: the forward of the space-to-depth form / nothing else; other pads take the scalar staging)
     if (l.k.vx == 4 && pad == 0) return launch_split3<2, 4, 0>(l, st);
@@ -1137,10 +1117,7 @@ int conv2d_wgrad_split3_launch(const WgradLaunch& l, hipStream_t st) {
 }
 
 int conv2d_wgrad_bf16_launch(const WgradLaunch& l, hipStream_t st) {
-  static PerDeviceOnce attr_once;
-  set_dyn_lds_once(attr_once, (const void*)conv2d_wgrad_bf16_kernel, WB_LDS_BYTES);
-  hipLaunchKernelGGL(conv2d_wgrad_bf16_kernel, l.grid, dim3(256), WB_LDS_BYTES, st, l.k);
-  return check_launch("conv2d_wgrad_bf16_kernel");
+  return launch_wgrad_bf<conv2d_wgrad_bf16_kernel>(l, WB_LDS_BYTES, "conv2d_wgrad_bf16_kernel", st);
 }
 
 }  // namespace dvsr

@@ -166,6 +166,20 @@ static T arena_alloc(dvsr_edvr_plan& p, const char* name, size_t numel) {
   return t;
 }
 
+// The weight gradient of input `which` of conv op o, tensors left out: what the plan knows of it (workspace size, plan_work).
+// The one place that turns cfg.bf16_mfma into the operand mode asked for: plain bf16 where the plan runs bf16 operands, else the
+// exact split unless DVSR_WGRAD_SPLIT3=0 (A/B aid: the fp32 MFMA kernel); conv2d_wgrad_choose knows which shapes have such kernels.
+static WgradDesc wgrad_shape(const dvsr_edvr_plan& p, const Op& o, int which) {
+  WgradDesc d;
+  d.x_bs = which ? o.x1_bs : o.x0_bs; d.x_bdiv = which ? o.x1_bdiv : 1; d.gy_ps = o.ps;
+  d.N = o.N; d.Cin = which ? o.c1 : o.c0; d.H = o.H; d.W = o.W; d.Cout = o.Cout;
+  d.Ctot = o.c0 + o.c1; d.c_off = which ? o.c0 : 0;
+  d.ks = o.ks; d.stride = o.stride; d.pad = conv_pad(o);
+  d.groups = p.wgroups; d.dW_gs = (long long)o.Cout * (o.c0 + o.c1) * o.ks * o.ks; d.db_gs = o.Cout;
+  d.mode = (p.cfg.bf16_mfma == 1 && !o.wmap) ? 1 : (wgrad_split3_default() ? 2 : 0);
+  return d;
+}
+
 // ---- launch planning of a conv op: which packed kernel, on which geometry, runs its forward in each mode and its data gradients
 // The hoisted pair of a no-grad forward whose unsplit launch is `whole` (n == 0: the op stays whole): runs the shared half of a
 // batch-broadcast second input once per clip where that is modelled to pay -- the unsplit launch and the main part both on
@@ -653,8 +667,7 @@ static void build_backward(dvsr_edvr_plan& p) {
           // every weight gradient owns its slot region: the slot sums of ALL layers are reduced by one
           // batched launch at the end of the backward (wgrad_reduce_batch)
           BOp& wr = p.bops.back();
-          wr.ws_bytes = (conv2d_wgrad_workspace_bytes(o.N, which ? o.c1 : o.c0, o.H, o.W, o.Cout, o.ks, o.stride,
-                                                      conv_pad(o), p.wgroups) + 255) & ~(size_t)255;
+          wr.ws_bytes = (conv2d_wgrad_workspace_bytes(wgrad_shape(p, o, which)) + 255) & ~(size_t)255;
           wr.ws_off = wscratch;
           wscratch += wr.ws_bytes;
           if (o.wmap) {  // dW of the re-laid-out copy -> gradient of the 4x4 parameter (same stream as the wgrad)
@@ -790,24 +803,15 @@ struct BBases {
   }
 };
 
-// DVSR_WGRAD_SPLIT3=0: the 3x3 stride-1 weight gradients stay on the fp32 MFMA kernel (A/B aid); default: the exact 3-way
-// bf16 split kernel (conv2d_wgrad_bf16.hip)
-static bool wgrad_split3_on() {
-  static const bool on = [] { const char* v = getenv("DVSR_WGRAD_SPLIT3"); return !(v && v[0] == '0'); }();
-  return on;
-}
-
-// Argument marshalling of the two gradient launches of a conv, shared by the separate and the fused paths.
+// Argument marshalling of the two gradient launches of a conv.
 static int prep_wgrad(const dvsr_edvr_plan& p, const BOp& b, float* const* GP, const BBases& bs, void* scratch,
                       size_t scratch_bytes, hipStream_t st, WgradReduceEntry* defer, WgradLaunch* out) {
-  const Op* o = &p.ops[b.fwd];
-  const int ci = b.which ? o->c1 : o->c0;
-  float* dW = o->wmap ? bs.garena + o->w2_off : GP[o->pw];
-  return conv2d_wgrad_prepare(bs.at(b.a), b.which ? o->x1_bs : o->x0_bs, b.which ? o->x1_bdiv : 1, bs.at(b.b), o->ps, dW,
-                              b.which ? nullptr : GP[o->pb], o->N, ci, o->H, o->W, o->Cout, o->c0 + o->c1,
-                              b.which ? o->c0 : 0, o->ks, o->stride, scratch, scratch_bytes, st, 1, conv_pad(*o), defer, out,
-                              (p.cfg.bf16_mfma == 1 && !o->wmap) ? 1 : (wgrad_split3_on() ? 2 : 0), p.wgroups,
-                              (long long)o->Cout * (o->c0 + o->c1) * o->ks * o->ks, o->Cout);
+  const Op& o = p.ops[b.fwd];
+  WgradDesc d = wgrad_shape(p, o, b.which);
+  d.x = bs.at(b.a); d.gy = bs.at(b.b);
+  d.dW = o.wmap ? bs.garena + o.w2_off : GP[o.pw];
+  d.db = b.which ? nullptr : GP[o.pb];
+  return conv2d_wgrad_prepare(d, scratch, scratch_bytes, st, 1, defer, out);
 }
 
 // ConvExtra of a launch whose batch items take per-sample weight sets (plan.wsets > 1)
@@ -835,8 +839,7 @@ static void dgrad_desc(const dvsr_edvr_plan& p, const BOp& b, const float* const
 }
 
 static int run_backward_op(const dvsr_edvr_plan& p, const BOp& b, const float* const* P, float* const* GP,
-                           const BBases& bs, void* scratch, size_t scratch_bytes, hipStream_t st,
-                           int scratch_is_zero = 0, WgradReduceEntry* defer = nullptr) {
+                           const BBases& bs, void* scratch, size_t scratch_bytes, hipStream_t st) {
   const Op* o = b.fwd >= 0 ? &p.ops[b.fwd] : nullptr;
   switch (b.type) {
     case B_MEMSET: {
@@ -854,15 +857,6 @@ static int run_backward_op(const dvsr_edvr_plan& p, const BOp& b, const float* c
     }
     case B_ACT:
       return act_bwd_inplace(bs.at(b.a), bs.at(b.b), b.n, o->act, st);
-    case B_WGRAD: {
-      const int ci = b.which ? o->c1 : o->c0;
-      float* dW = o->wmap ? bs.garena + o->w2_off : GP[o->pw];
-      return conv2d_wgrad_run(bs.at(b.a), b.which ? o->x1_bs : o->x0_bs, b.which ? o->x1_bdiv : 1, bs.at(b.b),
-                              o->ps, dW, b.which ? nullptr : GP[o->pb], o->N, ci, o->H, o->W, o->Cout,
-                              o->c0 + o->c1, b.which ? o->c0 : 0, o->ks, o->stride, scratch, scratch_bytes, st,
-                              scratch_is_zero, conv_pad(*o), defer, p.wgroups,
-                              (long long)o->Cout * (o->c0 + o->c1) * o->ks * o->ks, o->Cout);
-    }
     case B_WUNMAP:   // (the map is per output channel: the stacked per-group gradients are a [wgroups * Cout] tensor)
       return w4_to_s2d(bs.garena + o->w2_off, GP[o->pw], p.wgroups * o->Cout, o->c0 / 4, 1, st);
     case B_PADFOLD: {
@@ -914,6 +908,7 @@ static int run_backward_op(const dvsr_edvr_plan& p, const BOp& b, const float* c
     case B_BLEND:
       return tsa_blend_bwd(bs.arena + o->x0.off, bs.arena + o->x1.off, bs.at(b.b), bs.at(b.a), bs.at(b.c),
                            o->y.numel, b.accum, st);
+    case B_WGRAD: break;   // dvsr_edvr_backward launches the weight gradients itself (prep_wgrad, shared forks, one batched reduce)
   }
   return DVSR_ERR_INVALID;
 }
@@ -1235,7 +1230,7 @@ extern "C" int dvsr_edvr_backward(const dvsr_edvr_plan* p, const float* const* p
       // only SMALL weight gradients wait for company (the small-grid kernel was chosen for them): a large one -- the
       // estimator's at 176x320 run 100-300 us each, longer than its data-gradient chain -- must start at once, or
       // the side stream is still busy long after the main stream has finished (profiles/r02_g_estimator_timeline.txt)
-      if (rc == DVSR_OK && (!use_side || !l.kys)) rc = flush_waiting();
+      if (rc == DVSR_OK && (!use_side || !l.geo.row_split)) rc = flush_waiting();
     } else if (b.type == B_WUNMAP) {
       unmaps.push_back(&b);  // needs the reduced gradient: after the batched reduce below
     } else {
@@ -1410,10 +1405,8 @@ static int plan_work(const dvsr_edvr_plan* p, double* out9, FwdMode mode) {
     if (b.type == B_WGRAD) {
       const double f = conv_part(o, b.which ? o.c1 : o.c0);
       ba += f; be += f;
-      // (conv2d_wgrad_prepare's choice, restated: prep_wgrad's mode, then the kernel's own eligibility)
-      const int mode = (p->cfg.bf16_mfma == 1 && !o.wmap) ? 1 : (wgrad_split3_on() ? 2 : 0);
-      const int bf = (mode && o.stride == 1 && (o.ks == 3 || (o.ks == 2 && mode == 2))) ? mode : 0;
-      if (bf == 2) bfp[1] += 6.0 * f; else if (bf == 1) bfp[1] += f; else f32p[1] += f;
+      const WgradKernel k = conv2d_wgrad_choose(wgrad_shape(*p, o, b.which)).kernel;   // (the pipe does not depend on the tensors' alignment)
+      if (on_bf16_split(k)) bfp[1] += 6.0 * f; else if (on_bf16_pipe(k)) bfp[1] += f; else f32p[1] += f;
     } else if (b.type == B_DGRAD) {
       const double f = conv_part(o, b.which ? o.c1 : o.c0);
       ba += f; issue(o.dgrad[b.which].geo, f, &be, 1);

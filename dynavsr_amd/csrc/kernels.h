@@ -118,7 +118,7 @@ int conv3x3_small_cout_run(const float* x, const float* w, const float* bias, co
                            int C, int H, int W, int Cout, int act, hipStream_t st, int wdiv = 1, long long w_gs = 0,
                            int b_gs = 0);
 
-// Deferred slot reduction of a weight gradient (conv2d_wgrad_run(..., defer = &entry) + wgrad_reduce_batch)
+// Slot reduction of a weight gradient (one entry at once, or deferred: conv2d_wgrad_run(..., defer = &entry) + wgrad_reduce_batch)
 struct WgradReduceEntry {
   float* partial; float* dbp; float* dW; float* db;
   int nslot, KK, OP, CP, Cout, Cin, Ctot, c_off;
@@ -131,14 +131,46 @@ struct WgradReduceTable {
   int n;
   WgradReduceEntry e[WGRAD_REDUCE_BATCH];
 };
-int wgrad_reduce_batch(const WgradReduceEntry* entries, int n, hipStream_t st);
-size_t conv2d_wgrad_workspace_bytes(int N, int Cin, int H, int W, int Cout, int ks, int stride, int pad = -1, int groups = 1);
-// groups > 1: one gradient per group of N / groups consecutive batch items, written to dW + g * dW_gs (db + g * db_gs)
-int conv2d_wgrad_run(const float* x, long long x_bs, int x_bdiv, const float* gy, int gy_ps, float* dW,
-                     float* db, int N, int Cin, int H, int W, int Cout, int Ctot, int c_off, int ks,
-                     int stride, void* ws, size_t ws_bytes, hipStream_t st, int scratch_is_zero = 0,
-                     int pad = -1, WgradReduceEntry* defer = nullptr, int groups = 1, long long dW_gs = 0,
-                     long long db_gs = 0);  // pad < 0: ks / 2
+int wgrad_reduce_batch(const WgradReduceEntry* entries, int n, hipStream_t st, int blocks = 96);   // blocks: per entry and group
+// One weight-gradient launch: dW[:, c_off:c_off+Cin, :, :] of a [Cout][Ctot][ks][ks] gradient (and db when non-null) from
+// x, one input of the conv ([N/x_bdiv][Cin][H][W], batch stride x_bs or dense), and gy, the gradient of the conv's
+// pre-activation output (gy_ps: stored pixel-shuffled).
+struct WgradDesc {
+  const float* x = nullptr; long long x_bs = 0; int x_bdiv = 1;
+  const float* gy = nullptr; int gy_ps = 0;
+  float* dW = nullptr; float* db = nullptr;
+  int N = 0, Cin = 0, H = 0, W = 0, Cout = 0, Ctot = 0, c_off = 0, ks = 0, stride = 1, pad = -1;   // pad < 0: ks / 2
+  // groups > 1: one gradient per group of N / groups consecutive batch items, written to dW + g * dW_gs (db + g * db_gs)
+  int groups = 1; long long dW_gs = 0, db_gs = 0;
+  int mode = 0;   // operands asked for: 0 fp32, 1 bf16, 2 the exact 3-way bf16 split (3x3 stride 1, split also 2x2; fp32 otherwise)
+};
+// The kernel a weight gradient launches on.  The values are ABI: dvsr_conv2d_wgrad_geometry writes them to geo[0].
+enum class WgradKernel : int {
+  SIMPLE = 0,        // conv2d_wgrad_kernel: stride 2
+  PIPE = 1,          // conv2d_wgrad_pipe_kernel: the pipelined fp32 kernel, all taps or one kernel row per workgroup
+  BF16 = 2,          // conv2d_wgrad_bf16_kernel: operands rounded to bf16
+  SPLIT_SCALAR = 3,  // conv2d_wgrad_split3_kernel: the exact split, scalar staging
+  SPLIT_VECTOR = 4,  // conv2d_wgrad_split3v_kernel: vector staging, all taps or one kernel row per workgroup
+  SPLIT_WAVE8 = 5,   // conv2d_wgrad_split3w_kernel: vector staging, eight waves
+};
+constexpr bool on_bf16_pipe(WgradKernel k) { return k >= WgradKernel::BF16; }   // v_mfma_f32_*_bf16; the others v_mfma_f32_32x32x2_f32
+constexpr bool on_bf16_split(WgradKernel k) { return k >= WgradKernel::SPLIT_SCALAR; }   // six bf16 products per fp32 one
+struct WgradGeo {
+  WgradKernel kernel = WgradKernel::PIPE;
+  int row_split = 0;    // one kernel row per workgroup (ks times the workgroups): what the rule picks for SMALL pixel grids
+  int vx = 0;           // WgradK::vx
+  int nsplit = 1, nslot = 1;   // pixel splits / flush slots, per group
+  dim3 grid; int block = 256;
+};
+// THE rule: which kernel a weight gradient runs on and how it is launched (conv2d_wgrad.hip).  Host arithmetic only: no
+// HIP call, and of the pointers it reads the alignment alone.
+WgradGeo conv2d_wgrad_choose(const WgradDesc& d);
+bool wgrad_split3_default();   // DVSR_WGRAD_SPLIT3 (read once with the rule's other switches): plans ask for mode 2
+size_t conv2d_wgrad_workspace_bytes(const WgradDesc& d);   // the slot regions at the most slots the rule gives this shape
+// scratch_is_zero: the slot regions hold zeros (a reduce leaves them so); defer: the caller reduces a batch of layers later
+// (wgrad_reduce_batch) and `ws` stays untouched until then
+int conv2d_wgrad_run(const WgradDesc& d, void* ws, size_t ws_bytes, hipStream_t st, int scratch_is_zero = 0,
+                     WgradReduceEntry* defer = nullptr);
 size_t mdcn_backward_workspace_bytes(int N, int C, int H, int W, int Cout, int stride, int pad, int dil, int groups = 1);
 int mdcn_backward_run(const float* x, const float* off, long long off_bs, const float* msk, long long msk_bs,
                       int mask_logit, const float* w, const float* gout, float* gx, float* goff,

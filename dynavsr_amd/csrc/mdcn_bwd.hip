@@ -956,13 +956,20 @@ __global__ void mdcn_dw_reduce_kernel(const float* __restrict__ dwp, const float
 
 // Workspace: the general path's column buffer [N][C*9][P] + the 1x1 weight gradient's slots; the fused path's per-
 // workgroup weight / bias gradient partials.
+// dW / db of the unfused form: a 1x1 weight gradient over the column buffer [N][C * 9][Ho][Wo] (tensors left out)
+static WgradDesc col_wgrad_shape(int N, int C, int Ho, int Wo, int Cout, int groups) {
+  WgradDesc d;
+  d.N = N; d.Cin = C * 9; d.H = Ho; d.W = Wo; d.Cout = Cout; d.Ctot = C * 9; d.ks = 1; d.stride = 1; d.groups = groups;
+  return d;
+}
+
 size_t mdcn_backward_workspace_bytes(int N, int C, int H, int W, int Cout, int stride, int pad, int dil, int groups) {
   const int Ho = (H + 2 * pad - (dil * 2 + 1)) / stride + 1, Wo = (W + 2 * pad - (dil * 2 + 1)) / stride + 1;
   const size_t col = (size_t)N * C * 9 * Ho * Wo * sizeof(float);
   const size_t ntile = (size_t)ceil_div(Wo, 32) * ceil_div(Ho, 8);
   const size_t fused = ((size_t)N * (C / 8) * ntile * Cout * 72 + (size_t)N * ntile * Cout +
                         (size_t)std::max(groups, 1) * (C / 8) * 3 * (Cout / 2) * 64 * 3 / 2) * sizeof(float);   // + the W^T images (bf16 x 3)
-  return std::max(col + conv2d_wgrad_workspace_bytes(N, C * 9, Ho, Wo, Cout, 1, 1, -1, groups), fused);
+  return std::max(col + conv2d_wgrad_workspace_bytes(col_wgrad_shape(N, C, Ho, Wo, Cout, groups)), fused);
 }
 
 // gout: gradient w.r.t. the PRE-activation output.  gx is accumulated into (atomics) -- zero it
@@ -1092,8 +1099,9 @@ int mdcn_backward_run(const float* x, const float* off, long long off_bs, const 
     hipLaunchKernelGGL(mdcn_im2col_kernel, dim3(grid), dim3(256), 0, st, a, col);
     rc = check_launch("mdcn_im2col_kernel");
     if (rc) return rc;
-    rc = conv2d_wgrad_run(col, 0, 1, gout, 0, gw, gb, N, C * 9, a.Ho, a.Wo, Cout, C * 9, 0, 1, 1, ws2,
-                          ws2_bytes, st, 0, -1, nullptr, groups, gw_gs, gb_gs);
+    WgradDesc d = col_wgrad_shape(N, C, a.Ho, a.Wo, Cout, groups);
+    d.x = col; d.gy = gout; d.dW = gw; d.db = gb; d.dW_gs = gw_gs; d.db_gs = gb_gs;
+    rc = conv2d_wgrad_run(d, ws2, ws2_bytes, st);
   }
   return rc;
 }

@@ -63,24 +63,17 @@ __device__ __forceinline__ WgSpan wg_span(const WgradK& a, int split) {
 
 // host side: fill the argument structs without launching (conv2d_v2.hip / conv2d_wgrad.hip)
 int conv2d_packed_prepare(const dvsr_conv2d_desc& d, const float* wp, const ConvExtra& ex, const ConvGeo& geo, ConvK2* k);
-struct WgradLaunch {
-  WgradK k;
-  dim3 grid;
-  int ks, stride, kys;
-  int bf = 0;  // 1: bf16 operands on v_mfma_f32_32x32x16_bf16 (conv2d_wgrad_bf16.hip; 3x3 stride 1 only); 2: the exact
-               // 3-way split of both operands on the same pipe (fp32 accuracy)
-};
-int conv2d_wgrad_prepare(const float* x, long long x_bs, int x_bdiv, const float* gy, int gy_ps, float* dW, float* db,
-                         int N, int Cin, int H, int W, int Cout, int Ctot, int c_off, int ks, int stride, void* ws,
-                         size_t ws_bytes, hipStream_t st, int scratch_is_zero, int pad, WgradReduceEntry* defer,
-                         WgradLaunch* out, int bf16 = 0, int groups = 1, long long dW_gs = 0, long long db_gs = 0);
-int conv2d_wgrad_launch(const WgradLaunch& l, hipStream_t st);
+struct WgradLaunch { WgradK k; WgradGeo geo; int ks; };
+// (launches nothing -- at most the memset of the slots when !scratch_is_zero; *entry: the slot reduction the caller owes)
+int conv2d_wgrad_prepare(const WgradDesc& d, void* ws, size_t ws_bytes, hipStream_t st, int scratch_is_zero, WgradReduceEntry* entry,
+                         WgradLaunch* out);
+int conv2d_wgrad_launch(const WgradLaunch& l, hipStream_t st);   // dispatch on l.geo.kernel, nothing else
 int conv2d_wino_launch(const ConvK2& k, int th, hipStream_t st);   // conv2d_wino.hip (ConvKernel::WINO_F2)
 int conv2d_wino3_launch(const ConvK2& k, int th, hipStream_t st);  // conv2d_wino3.hip (ConvKernel::WINO_F2_BF16)
 int conv2d_wino4_launch(const ConvK2& k, int th, hipStream_t st);  // conv2d_wino4.hip (the same image, B operand in registers)
 int conv2d_wino5_launch(const ConvK2& k, int th, hipStream_t st);  // conv2d_wino5.hip (ConvKernel::WINO_F4: F(4x4, 3x3), th = 8 | 16)
-int conv2d_wgrad_bf16_launch(const WgradLaunch& l, hipStream_t st);
-int conv2d_wgrad_split3_launch(const WgradLaunch& l, hipStream_t st);   // bf = 2: exact 3-way bf16 split (fp32 accuracy)
+int conv2d_wgrad_bf16_launch(const WgradLaunch& l, hipStream_t st);     // WgradKernel::BF16
+int conv2d_wgrad_split3_launch(const WgradLaunch& l, hipStream_t st);   // WgradKernel::SPLIT_*
 
 // -------------------------------------------------------------------------------------------------
 // K-split variant for SMALL grids (the 44x80 / 22x40 / 11x20 levels of the inner MAML step).

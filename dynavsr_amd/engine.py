@@ -21,8 +21,7 @@ _GEOMETRY_ENV = ("DVSR_CONV_WINO", "DVSR_CONV_WINO3", "DVSR_CONV_WINO5", "DVSR_C
 # ... and the ones the native side reads ONCE PER PROCESS (function-local statics): changing them after the first plan has no
 # effect, so they are deliberately NOT in the key -- set them before the first call (the A/B tools run one process per value).
 _PROCESS_ENV = ("DVSR_CONV_LDS", "DVSR_CONV_LAST_MFMA", "DVSR_SPLIT_TH8_FROM", "DVSR_WGRAD_SPLIT3",
-                "DVSR_WGRAD_SPLITS", "DVSR_WGRAD_SIMPLE", "DVSR_WGRAD_WIDE", "DVSR_WGRAD_S3V", "DVSR_WGRAD_S3_KYS_BELOW", "DVSR_WGRAD_S3_WGS",
-                "DVSR_WGRAD_S3W", "DVSR_WGRAD_KYS_BELOW", "DVSR_WGRAD_KYS_WGS", "DVSR_WGRAD_BF_WGS", "DVSR_DCN_FWD", "DVSR_DCN_BWD",
+                "DVSR_WGRAD_WIDE", "DVSR_WGRAD_S3V", "DVSR_WGRAD_S3_KYS_BELOW", "DVSR_WGRAD_S3_WGS", "DVSR_WGRAD_S3W", "DVSR_DCN_FWD", "DVSR_DCN_BWD",
                 "DVSR_EST_FUSE_PAD", "DVSR_FUSE_RES_BWD", "DVSR_BWD_FORK_EVERY", "DVSR_BWD_PROBE", "DVSR_TSA_DUAL", "DVSR_TSA_V",
                 "DVSR_DEGRADE_GENERIC", "DVSR_UP2")
 _process_env_seen = None   # their values when the first plan of the process was built

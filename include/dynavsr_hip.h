@@ -457,6 +457,18 @@ int dvsr_conv2d_wgrad_bf16(const dvsr_conv2d_desc* d, const float* gy, float* gw
 int dvsr_conv2d_wgrad_split3(const dvsr_conv2d_desc* d, const float* gy, float* gw, float* gb, void* workspace,
                              size_t workspace_bytes, dvsr_stream_t stream);
 
+/* Which kernel a weight gradient runs on and how it is launched: the counterpart of dvsr_conv2d_packed_geometry.  The launch
+ * is the one dvsr_conv2d_wgrad_bf16 (mode 1), dvsr_conv2d_wgrad_split3 (mode 2) or the weight gradient of dvsr_conv2d_backward
+ * (mode 0, with d->pad = ks / 2) makes for d's first input; of d->x0 and d->y -- standing for the gradient, which has its shape --
+ * only the alignment is read (pixel_shuffle: the gradient is stored shuffled, as the EDVR plans have it).  groups >= 1: that
+ * many per-group gradients.  geo = {kernel, row_split, vx, nsplit, nslot, grid x, grid y, grid z}; kernel: 0 the simple fp32
+ * kernel (stride 2), 1 the pipelined fp32 kernel, 2 plain bf16, 3 / 4 / 5 the exact bf16 split with scalar staging / vector
+ * staging / vector staging on eight waves; row_split = 1: one kernel row per workgroup (small pixel grids).  Launches nothing and
+ * needs no device.  dvsr_conv2d_wgrad_workspace_bytes: the workspace such a launch needs (dvsr_conv2d_backward_workspace_bytes
+ * is its groups = 1, pad = ks / 2 case over the wider of the two inputs). */
+int dvsr_conv2d_wgrad_geometry(const dvsr_conv2d_desc* d, int mode, int groups, int geo[8]);
+size_t dvsr_conv2d_wgrad_workspace_bytes(const dvsr_conv2d_desc* d, int groups);
+
 /* ---- TOFlow backbone ops (codes/models/archs/TOF_arch.py:25-140, arch_util.py:55-79) --------
  * The convolutions of SpyNet (7x7) and of the TOFlow head (9x9, 1x1) go through dvsr_conv2d_forward / _backward
  * (ks = 7, 9, 1); the ops below are the rest of the graph.  All fp32 NCHW, HBM-bound streaming kernels.
