@@ -77,6 +77,17 @@ FRAME_F32_CHW, FRAME_U8_HWC_RGB, FRAME_U8_HWC_BGR = 0, 1, 2
 FRAME_PAD_REFLECT, FRAME_PAD_REPLICATE = 0, 1
 
 
+class YuvDesc(Structure):
+    """dvsr_yuv_desc: a YCbCr 4:2:0 frame, every plane at any address and pitch (include/dynavsr_hip.h)."""
+    _fields_ = [("format", c_int), ("h", c_int), ("w", c_int), ("matrix", c_int), ("range", c_int),
+                ("plane", c_void_p * 3), ("row_stride", c_longlong * 3)]
+
+
+YUV_NV12, YUV_I420 = 0, 1
+YUV_BT601, YUV_BT709 = 0, 1
+YUV_LIMITED, YUV_FULL = 0, 1
+
+
 class EstimatorConfig(Structure):
     _fields_ = [(k, c_int) for k in ("kind", "nf", "in_nc", "scale", "nframes")]
 
@@ -190,6 +201,9 @@ def _declare(lib):
         "dvsr_frame_emit": (I, [P, I, I, P, POINTER(FrameDesc), F, F, P]),
         "dvsr_edvr_stream_extract_frame": (I, [P, POINTER(c_void_p), P, POINTER(FrameDesc), I, I, P, c_size_t, P, c_size_t, I,
                                                P]),
+        "dvsr_frame_ingest_yuv": (I, [POINTER(YuvDesc), P, I, I, I, P]),
+        "dvsr_frame_emit_yuv": (I, [P, I, I, POINTER(YuvDesc), F, F, P]),
+        "dvsr_edvr_stream_extract_frame_yuv": (I, [P, POINTER(c_void_p), POINTER(YuvDesc), I, I, P, c_size_t, P, c_size_t, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -798,16 +798,19 @@ def _video_format(frames, layout):
         raise ValueError("super_resolve_frames: no frames")
     first = fio.resolve_layout(frames[0], layout)
     if not torch.is_tensor(frames):
+        def kind(f):        # a tensor's, or those of the planes of a 4:2:0 frame
+            if torch.is_tensor(f):
+                return f.dtype, tuple(f.shape)
+            return [kind(p) for p in f] if isinstance(f, (tuple, list)) else type(f).__name__
         for i, f in enumerate(frames):
-            if torch.is_tensor(f) and (f.dtype != frames[0].dtype or tuple(f.shape) != tuple(frames[0].shape)):
-                raise ValueError("super_resolve_frames: frame %d is %s %s, frame 0 is %s %s" % (
-                    i, f.dtype, tuple(f.shape), frames[0].dtype, tuple(frames[0].shape)))
+            if kind(f) != kind(frames[0]):
+                raise ValueError("super_resolve_frames: frame %d is %s, frame 0 is %s" % (i, kind(f), kind(frames[0])))
             fio.resolve_layout(f, layout)
     return first
 
 
 def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, layout=None, out=None, pad_mode='reflect',
-                         multiple=None):
+                         multiple=None, matrix='bt601', yuv_range='limited'):
     """Super-resolves a VIDEO: `frames` is a [T,3,H,W] tensor or a list of [3,H,W] frames (CPU or GPU); yields the SR frame
     [1,3,sH,sW] of every frame, in order -- what `net(frames[index_generation(i, T, nframes, padding)][None])` gives, the
     sliding-window test of the reference's video datasets (video_test_dataset_int.py:219, `padding: new_info` in the
@@ -835,7 +838,13 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     [sH,sW,3] on the device in the input's channel order for uint8 frames (util.tensor2img's image); 'float', 'hwc_rgb',
     'hwc_bgr' force one.  Float planar frames that need no padding, with `out` unset, take exactly the calls described
     above (the crop / conversion otherwise runs as one more launch on the window's stream, out of a per-stream staging
-    buffer).  Arguments are checked before the first GPU call (ValueError)."""
+    buffer).
+    What a VIDEO decoder delivers is YCbCr 4:2:0 (frames.py, csrc/frame_yuv.hip): with `layout` 'nv12' or 'i420' (never
+    inferred) `frames` is a uint8 [T, H*3/2, W] tensor or a list of packed frames or of plane tuples, converted with `matrix`
+    ('bt601' | 'bt709') and `yuv_range` ('limited' | 'full') in the launch that fills the frame cache; `out` None then
+    yields packed uint8 [sH*3/2, sW] frames of the input's layout on the device, written from the fp32 SR frame in one launch,
+    and 'nv12' / 'i420' force such an output for RGB and float inputs too (sH and sW must be even).
+    Arguments are checked before the first GPU call (ValueError)."""
     from . import frames as fio
     from .data.util import index_generation
     from .models.archs.EDVR_arch import EDVR
@@ -848,7 +857,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         raise ValueError("super_resolve_frames: pad_mode=%r ('reflect' or 'replicate')" % (pad_mode,))
     # float frames with none of the frame arguments given, at a size the network takes as it is: the calls of before
     plain = layout is None and out is None and multiple is None and \
-        not (torch.is_tensor(frames[0]) and frames[0].dtype == torch.uint8)
+        torch.is_tensor(frames[0]) and frames[0].dtype != torch.uint8
     if is_edvr:
         plain = plain and torch.is_tensor(frames[0]) and frames[0].dim() == 3 and frames[0].is_floating_point() and \
             frames[0].shape[-2] % 4 == 0 and frames[0].shape[-1] % 4 == 0
@@ -856,9 +865,15 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         h, w, lay, out_fmt, Hp, Wp = int(frames[0].shape[-2]), int(frames[0].shape[-1]), 'chw', 'float', None, None
     else:
         lay, h, w = _video_format(frames, layout)
-        if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr'):
-            raise ValueError("super_resolve_frames: out=%r (None, 'float', 'hwc_rgb' or 'hwc_bgr')" % (out,))
+        if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') + fio.YUV_LAYOUTS:
+            raise ValueError("super_resolve_frames: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr', 'nv12' or 'i420')" % (out,))
+        fio.check_yuv_names(matrix, yuv_range)
         out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
+        if out_fmt in fio.YUV_LAYOUTS:
+            scale = int(net.scale) if is_edvr else int(opt.get('scale') or 1)
+            if scale * h % 2 or scale * w % 2:
+                raise ValueError("super_resolve_frames: a packed %s output of %d x %d needs an even size" % (
+                    out_fmt, scale * h, scale * w))
         if h < 4 or w < 4:
             raise ValueError("super_resolve_frames: frames of %d x %d (at least 4 x 4)" % (h, w))
         mult = int(multiple) if multiple is not None else (4 if is_edvr else 1)
@@ -884,7 +899,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         def ingested(j):
             x = kept.get(j)
             if x is None:
-                x = kept[j] = fio.ingest(frames[j], lay, mult, pad_mode)
+                x = kept[j] = fio.ingest(frames[j], lay, mult, pad_mode, matrix=matrix, yuv_range=yuv_range)
                 while len(kept) > 2 * n:
                     kept.pop(next(iter(kept)))
             return x
@@ -897,7 +912,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
             if out_fmt == 'float':
                 yield sr if (Hp, Wp) == (h, w) else fio.emit(sr, s * h, s * w, 'chw')[None]
             else:
-                yield fio.emit(sr, s * h, s * w, out_fmt)
+                yield fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
         return
     leaves = net.ordered_parameters()
     dev = leaves[0].device
@@ -934,18 +949,19 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                     x = frames[f]
                     if direct:
                         x = engine._prep(x if x.is_cuda else x.to(dev))
-                    elif not x.is_cuda:
-                        x = x.to(dev, non_blocking=True)             # (8-bit frames travel as bytes)
+                    else:
+                        x = fio.to_device(x, dev)                    # (8-bit frames travel as bytes)
                     for ev in readers.pop(slot, ()):
                         s.wait_event(ev)
                     if direct:
                         plan.extract(leaves, x, slot, cache)
                     else:
-                        x = plan.extract_frame(leaves, x, slot, cache, lay, pad_mode)
+                        x = plan.extract_frame(leaves, x, slot, cache, lay, pad_mode, matrix, yuv_range)
                     extracted[slot] = torch.cuda.Event()
                     extracted[slot].record(s)
                     if s != main:
-                        x.record_stream(s)
+                        for t in (x,) if torch.is_tensor(x) else x:
+                            t.record_stream(s)
                 for slot in set(wslots):
                     s.wait_event(extracted[slot])
                 if direct or (out_fmt == 'float' and (ph, pw) == (h, w)):
@@ -959,7 +975,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                     if out_fmt == 'float':
                         sr = fio.emit(staging[k], net.scale * h, net.scale * w, 'chw')[None]
                     else:
-                        sr = fio.emit(staging[k], net.scale * h, net.scale * w, out_fmt)
+                        sr = fio.emit(staging[k], net.scale * h, net.scale * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
                 ev = torch.cuda.Event()
                 ev.record(s)
             for slot in set(wslots):

@@ -241,6 +241,10 @@ int frame_ingest_check(const char* what, const void* src, const dvsr_frame_desc*
                        int pad_mode);
 int frame_ingest_launch(const void* src, const dvsr_frame_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
 
+// frame_yuv.hip: the same pair for a YCbCr 4:2:0 frame (NV12 / I420 planes at any address / pitch)
+int frame_ingest_yuv_check(const char* what, const dvsr_yuv_desc* sd, const float* dst, int Hp, int Wp, int pad_mode);
+int frame_ingest_yuv_launch(const dvsr_yuv_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
+
 // pad.hip: explicit padding / layout changes of the MFDN estimator and their adjoints
 enum : int { PAD_REFLECT = 0, PAD_REFLECT_S2D = 1, PAD_REPL_T3 = 2 };
 size_t pad_out_numel(int mode, size_t N, int C, int H, int W);

@@ -550,17 +550,28 @@ class StreamPlan:
             ws.numel(), packed, L.stream()))
         self.stats['extracted'] += 1
 
-    def extract_frame(self, leaves, frame, slot, cache, layout=None, pad_mode='reflect'):
-        """A decoder's frame on the GPU -- uint8 [h,w,3|4] ('hwc_rgb' / 'hwc_bgr') or fp32 [3,h,w] ('chw'), h <= H, w <= W,
-        any offset and row pitch -- -> slot `slot` of `cache`, on the current stream: converted and padded to the plan's
-        H x W straight into the slot (frames.ingest's result, without the temporary), then `extract`'s tape."""
+    def extract_frame(self, leaves, frame, slot, cache, layout=None, pad_mode='reflect', matrix='bt601', yuv_range='limited'):
+        """A decoder's frame on the GPU -- uint8 [h,w,3|4] ('hwc_rgb' / 'hwc_bgr'), fp32 [3,h,w] ('chw') or YCbCr 4:2:0
+        ('nv12' / 'i420': packed or planes, frames.py; `matrix`, `yuv_range`), h <= H, w <= W, any offset and row pitch --
+        -> slot `slot` of `cache`, on the current stream: converted and padded to the plan's H x W straight into the slot
+        (frames.ingest's result, without the temporary), then `extract`'s tape.  Returns the tensor(s) the launch reads."""
         from . import frames as F
+        F.check_yuv_names(matrix, yuv_range)
         layout, h, w = F.resolve_layout(frame, layout)
         if h > self.h or w > self.w:
             raise ValueError("EDVR stream of %d x %d frames got a frame of %d x %d" % (self.h, self.w, h, w))
         F.check_pad(h, w, self.h, self.w, pad_mode)
-        if not frame.is_cuda:
-            raise RuntimeError("libdynavsr_hip needs a tensor on the GPU, got device %s" % frame.device)
+        first = frame if torch.is_tensor(frame) else frame[0]
+        if not first.is_cuda:
+            raise RuntimeError("libdynavsr_hip needs a tensor on the GPU, got device %s" % first.device)
+        if layout in F.YUV_LAYOUTS:
+            planes, desc = F.describe_yuv(F.yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range)
+            params, arr = self._params(leaves)
+            self._run('extract', leaves, lambda ws, packed: L.lib().dvsr_edvr_stream_extract_frame_yuv(
+                self._h, arr, ctypes.byref(desc), F._PAD[pad_mode], int(slot), cache.data_ptr(),
+                cache.numel() * cache.element_size(), ws.data_ptr(), ws.numel(), packed, L.stream()))
+            self.stats['extracted'] += 1
+            return planes
         frame, desc = F.describe(frame, layout)
         params, arr = self._params(leaves)
         self._run('extract', leaves, lambda ws, packed: L.lib().dvsr_edvr_stream_extract_frame(

@@ -1,4 +1,5 @@
-"""Frames in and out of the video path (csrc/frame_io.hip: dvsr_frame_ingest / dvsr_frame_emit).
+"""Frames in and out of the video path (csrc/frame_io.hip: dvsr_frame_ingest / dvsr_frame_emit; csrc/frame_yuv.hip:
+dvsr_frame_ingest_yuv / dvsr_frame_emit_yuv).
 
 A decoder delivers 8-bit interleaved RGB or BGR (cv2 order) frames [H,W,3|4] of any size; the networks compute on fp32
 planar [3,Hp,Wp] in [0,1] whose sides are multiples of 4 (EDVR) or 16 (TOFlow), and an encoder or PNG writer wants 8-bit
@@ -14,6 +15,15 @@ interleaved back.  The reference does both on the host (`img.astype(np.float32) 
 `layout` is 'chw' (fp32 planar), 'hwc_rgb' or 'hwc_bgr' (uint8 interleaved); None means 'chw' for a float tensor and
 'hwc_rgb' for a uint8 one.  adapt.super_resolve_frames uses these (and engine.StreamPlan.extract_frame, which ingests
 straight into the frame cache); they are also the building blocks for feeding padded clips to the adaptation loops by hand.
+
+What a video decoder delivers (ffmpeg rawvideo pipes, PyAV) and an encoder takes is 8-bit YCbCr 4:2:0: the layouts 'nv12'
+and 'i420' (yuv420p), never inferred.  Such a frame is PACKED -- one uint8 tensor [H + H/2, W], H and W even: the Y plane
+followed by the interleaved CbCr rows (NV12, any row pitch) or by the Cb and the Cr plane (I420, contiguous) -- or a tuple
+of PLANES on one device: (y [H,W], uv [Hc,Wc,2]) for NV12, (y, u [Hc,Wc], v [Hc,Wc]) for I420, Hc x Wc = ceil(H/2) x
+ceil(W/2), every plane at any offset and row pitch (passed by stride) and H, W of either parity.  `matrix` ('bt601' |
+'bt709') and `yuv_range` ('limited' | 'full') name the conversion; the defaults are the reference's ycbcr2rgb / rgb2ycbcr
+(data/util.py:234-299).  ingest gives the un-rounded fp32 RGB, emit goes from fp32 RGB to 4:2:0 bytes in one launch; the
+arithmetic is written out in csrc/frame_yuv.hip and DESIGN 3.2k.
 """
 import ctypes
 
@@ -22,6 +32,10 @@ import torch
 from . import _lib as L
 
 LAYOUTS = ('chw', 'hwc_rgb', 'hwc_bgr')
+YUV_LAYOUTS = ('nv12', 'i420')
+_YUV_FORMAT = {'nv12': L.YUV_NV12, 'i420': L.YUV_I420}
+_YUV_MATRIX = {'bt601': L.YUV_BT601, 'bt709': L.YUV_BT709}
+_YUV_RANGE = {'limited': L.YUV_LIMITED, 'full': L.YUV_FULL}
 _FORMAT = {'chw': L.FRAME_F32_CHW, 'hwc_rgb': L.FRAME_U8_HWC_RGB, 'hwc_bgr': L.FRAME_U8_HWC_BGR}
 _PAD = {'reflect': L.FRAME_PAD_REFLECT, 'replicate': L.FRAME_PAD_REPLICATE}
 
@@ -35,13 +49,17 @@ def padded_size(h, w, multiple):
 
 
 def resolve_layout(frame, layout=None):
-    """Checks one frame tensor against `layout` (None: by dtype) and returns (layout, h, w).  No GPU call."""
+    """Checks one frame against `layout` (None: by dtype; the 4:2:0 layouts are never inferred) and returns
+    (layout, h, w).  No GPU call."""
+    if layout in YUV_LAYOUTS:
+        _, h, w = yuv_planes(frame, layout)
+        return layout, h, w
     if not torch.is_tensor(frame):
         raise ValueError("a frame must be a tensor, got %s" % type(frame).__name__)
     if layout is None:
         layout = 'hwc_rgb' if frame.dtype == torch.uint8 else 'chw'
     if layout not in LAYOUTS:
-        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS)))
+        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + YUV_LAYOUTS)))
     if frame.dtype == torch.uint8:
         if layout == 'chw':
             raise ValueError("a uint8 frame is interleaved ('hwc_rgb' / 'hwc_bgr'), not 'chw'")
@@ -89,17 +107,92 @@ def describe(frame, layout):
     return frame, L.FrameDesc(_FORMAT[layout], h, w, st[0], 0, st[1])
 
 
+def check_yuv_names(matrix, yuv_range):
+    if matrix not in _YUV_MATRIX:
+        raise ValueError("unknown YCbCr matrix %r ('bt601' or 'bt709')" % (matrix,))
+    if yuv_range not in _YUV_RANGE:
+        raise ValueError("unknown YCbCr range %r ('limited' or 'full')" % (yuv_range,))
+
+
+def yuv_planes(frame, layout):
+    """(planes, h, w) of a 4:2:0 frame -- a packed uint8 [H*3/2, W] tensor or a tuple of plane tensors: the planes as views
+    (y, uv) / (y, u, v), nothing copied.  ValueError for anything else.  No GPU call."""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError("unknown YCbCr layout %r (one of %s)" % (layout, ', '.join(YUV_LAYOUTS)))
+    n = 2 if layout == 'nv12' else 3
+    if torch.is_tensor(frame):
+        if frame.dtype != torch.uint8 or frame.dim() != 2:
+            raise ValueError("a packed %s frame must be uint8 [H*3/2, W], got %s %s" % (layout, frame.dtype, tuple(frame.shape)))
+        rows, w = int(frame.shape[0]), int(frame.shape[1])
+        h = rows * 2 // 3
+        if rows < 3 or rows % 3 or h % 2 or w < 2 or w % 2:
+            raise ValueError("a packed %s frame is [H*3/2, W] with H and W even, got %s (pass planes for odd sizes)"
+                             % (layout, tuple(frame.shape)))
+        if layout == 'nv12':
+            return (frame[:h], frame[h:].unflatten(1, (w // 2, 2))), h, w
+        if not frame.is_contiguous():
+            raise ValueError("a packed i420 frame must be contiguous (its chroma rows are half as long); pass planes")
+        flat, n_c = frame.view(-1), (h // 2) * (w // 2)
+        return (frame[:h], flat[h * w:h * w + n_c].view(h // 2, w // 2), flat[h * w + n_c:].view(h // 2, w // 2)), h, w
+    if not isinstance(frame, (tuple, list)) or len(frame) != n or not all(torch.is_tensor(p) for p in frame):
+        raise ValueError("a %s frame is a packed uint8 tensor or %d plane tensors, got %s" % (
+            layout, n, type(frame).__name__ if not isinstance(frame, (tuple, list)) else "%d items" % len(frame)))
+    planes = tuple(frame)
+    y = planes[0]
+    if any(p.dtype != torch.uint8 for p in planes) or any(p.device != y.device for p in planes):
+        raise ValueError("the planes of a %s frame must be uint8 tensors on one device" % layout)
+    if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
+        raise ValueError("the Y plane must be [H,W], got %s" % (tuple(y.shape),))
+    h, w = int(y.shape[0]), int(y.shape[1])
+    want = ((h + 1) // 2, (w + 1) // 2) + ((2,) if layout == 'nv12' else ())
+    for p in planes[1:]:
+        if tuple(p.shape) != want:
+            raise ValueError("a chroma plane of a %d x %d %s frame must be %s, got %s" % (h, w, layout, list(want), tuple(p.shape)))
+    return planes, h, w
+
+
+def describe_yuv(planes, layout, h, w, matrix='bt601', yuv_range='limited', copy=True):
+    """(planes', dvsr_yuv_desc) of what yuv_planes returned.  A plane that the descriptor can express -- any offset, any row
+    pitch -- is passed by stride; any other is copied first (copy = False: ValueError, for a destination)."""
+    check_yuv_names(matrix, yuv_range)
+    desc = L.YuvDesc(_YUV_FORMAT[layout], h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
+    kept = []
+    for i, p in enumerate(planes):
+        row = p.shape[1] * (p.shape[2] if p.dim() == 3 else 1)          # bytes of a row
+        st = p.stride()
+        inner = st[1:] == ((2, 1) if p.dim() == 3 else (1,)) or row == 1
+        if not (inner and (st[0] >= row or p.shape[0] == 1)):
+            if not copy:
+                raise ValueError("plane %d must have contiguous rows that do not overlap" % i)
+            p = p.contiguous()
+            st = p.stride()
+        kept.append(p)
+        desc.plane[i] = p.data_ptr()
+        desc.row_stride[i] = max(int(st[0]), row)
+    return tuple(kept), desc
+
+
+def to_device(frame, device):
+    """A frame (tensor or tuple of planes) on `device`; a CPU frame is copied as it is -- 8-bit frames travel as bytes."""
+    if torch.is_tensor(frame):
+        return frame if frame.is_cuda else frame.to(device, non_blocking=True)
+    return tuple(to_device(p, device) for p in frame)
+
+
 def _planar_ok(t):
     return t.is_contiguous() and t.shape[-1] % 4 == 0 and t.data_ptr() % 16 == 0
 
 
-def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None):
+def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix='bt601', yuv_range='limited'):
     """One frame -> fp32 [3,Hp,Wp] on the GPU, (Hp, Wp) = padded_size(h, w, multiple).
 
     frame: uint8 [H,W,3|4] ('hwc_rgb' / 'hwc_bgr'; a fourth byte is ignored) or float [3,H,W] ('chw'), on the CPU or the
     GPU; a CPU frame is copied to the device as it is -- 8-bit frames travel as bytes.  out: an fp32 contiguous [3,Hp,Wp]
     GPU tensor to fill (Wp a multiple of 4).  When Wp is not a multiple of 4 (multiple = 1, 2) the result is a
-    [3,Hp,Wp] view of a buffer whose rows are."""
+    [3,Hp,Wp] view of a buffer whose rows are.
+    'nv12' / 'i420': frame is a packed uint8 [H*3/2, W] tensor or a tuple of planes (module docstring), converted with
+    `matrix` / `yuv_range` to un-rounded RGB in [0,1] -- one launch, like the other layouts."""
+    check_yuv_names(matrix, yuv_range)
     layout, h, w = resolve_layout(frame, layout)
     Hp, Wp = padded_size(h, w, multiple)
     Wb = -(-Wp // 4) * 4
@@ -111,24 +204,36 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None):
             raise RuntimeError("ingest: out must be on the GPU (libdynavsr_hip); there is no CPU path")
         if not _planar_ok(out):
             raise ValueError("ingest: out must be contiguous and 16-byte aligned")
-    dev = out.device if out is not None else (frame.device if frame.is_cuda else torch.device('cuda', torch.cuda.current_device()))
-    if not frame.is_cuda:
-        frame = frame.to(dev, non_blocking=True)
-    frame, desc = describe(frame, layout)
+    first = frame if torch.is_tensor(frame) else frame[0]
+    dev = out.device if out is not None else (first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+    frame = to_device(frame, dev)
+    if layout in YUV_LAYOUTS:
+        planes, desc = describe_yuv(yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range)
+    else:
+        frame, desc = describe(frame, layout)
     with torch.cuda.device(dev):
         buf = out if out is not None else torch.empty((3, Hp, Wb), dtype=torch.float32, device=dev)
-        L.check(L.lib().dvsr_frame_ingest(frame.data_ptr(), ctypes.byref(desc), buf.data_ptr(), Hp, Wb, _PAD[pad_mode],
-                                          L.stream()), "dvsr_frame_ingest")
+        if layout in YUV_LAYOUTS:
+            L.check(L.lib().dvsr_frame_ingest_yuv(ctypes.byref(desc), buf.data_ptr(), Hp, Wb, _PAD[pad_mode], L.stream()),
+                    "dvsr_frame_ingest_yuv")
+        else:
+            L.check(L.lib().dvsr_frame_ingest(frame.data_ptr(), ctypes.byref(desc), buf.data_ptr(), Hp, Wb, _PAD[pad_mode],
+                                              L.stream()), "dvsr_frame_ingest")
     return buf if Wb == Wp else buf[:, :, :Wp]
 
 
-def emit(sr, h, w, layout, min_max=(0, 1), out=None):
+def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='limited'):
     """The top-left h x w crop of sr (fp32 [3,Hs,Ws] or [1,3,Hs,Ws] on the GPU) as uint8 [h,w,3] ('hwc_rgb' / 'hwc_bgr':
     clamp to min_max, rescale, x 255, round half to even -- util.tensor2img's image, and dvsr_frame_metrics') or as fp32
     [3,h,w] ('chw').  out: the tensor to write (any offset and row pitch; what lies outside the crop is not touched).
-    A source whose rows are not 16-byte aligned (Ws not a multiple of 4) is copied into one that is, first."""
-    if layout not in LAYOUTS:
-        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS)))
+    A source whose rows are not 16-byte aligned (Ws not a multiple of 4) is copied into one that is, first.
+    'nv12' / 'i420': the crop as YCbCr 4:2:0 bytes (`matrix`, `yuv_range`; chroma filtered inside the crop alone).  With h and
+    w even and no `out` the result is a packed uint8 [h*3/2, w] tensor; otherwise `out` is a packed tensor of that shape or a
+    tuple of planes (module docstring; needed for an odd h or w) and is returned; bytes outside the planes' rows are not
+    touched."""
+    if layout not in LAYOUTS + YUV_LAYOUTS:
+        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + YUV_LAYOUTS)))
+    check_yuv_names(matrix, yuv_range)
     if sr.dim() == 4 and sr.shape[0] == 1:
         sr = sr[0]
     if sr.dim() != 3 or sr.shape[0] != 3:
@@ -137,6 +242,15 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None):
     h, w = int(h), int(w)
     if not (1 <= h <= Hs and 1 <= w <= Ws):
         raise ValueError("emit: crop %d x %d outside the frame %d x %d" % (h, w, Hs, Ws))
+    if layout in YUV_LAYOUTS:
+        if out is None and (h % 2 or w % 2):
+            raise ValueError("emit: a packed %s frame needs an even size, got %d x %d: pass `out` as planes" % (layout, h, w))
+        if out is not None:
+            planes, ho, wo = yuv_planes(out, layout)
+            if (ho, wo) != (h, w):
+                raise ValueError("emit: out is a %d x %d frame, the crop is %d x %d" % (ho, wo, h, w))
+            if planes[0].device != sr.device:
+                raise ValueError("emit: out must be on %s" % sr.device)
     if not sr.is_cuda:
         raise RuntimeError("emit runs on the GPU (libdynavsr_hip); there is no CPU path")
     if sr.dtype != torch.float32:
@@ -144,6 +258,15 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None):
     if not _planar_ok(sr):
         sr = torch.nn.functional.pad(sr, (0, -Ws % 4)).contiguous()
         Ws = int(sr.shape[2])
+    if layout in YUV_LAYOUTS:
+        with torch.cuda.device(sr.device):
+            if out is None:
+                out = torch.empty((h * 3 // 2, w), dtype=torch.uint8, device=sr.device)
+                planes = yuv_planes(out, layout)[0]
+            _, desc = describe_yuv(planes, layout, h, w, matrix, yuv_range, copy=False)
+            L.check(L.lib().dvsr_frame_emit_yuv(sr.data_ptr(), Hs, Ws, ctypes.byref(desc), float(min_max[0]), float(min_max[1]),
+                                                L.stream()), "dvsr_frame_emit_yuv")
+        return out
     with torch.cuda.device(sr.device):
         if out is None:
             out = (torch.empty((3, h, w), dtype=torch.float32, device=sr.device) if layout == 'chw' else

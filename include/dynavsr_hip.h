@@ -354,6 +354,46 @@ int dvsr_edvr_stream_extract_frame(const dvsr_edvr_stream* stream_plan, const fl
                                    const dvsr_frame_desc* fd, int pad_mode, int slot, void* cache, size_t cache_bytes,
                                    void* workspace, size_t workspace_bytes, int packed, dvsr_stream_t stream);
 
+/* ---- YCbCr 4:2:0 frames in and out of the video path -----------------------------------------------
+ * What a video decoder really delivers and an encoder takes: 8-bit YCbCr 4:2:0 as NV12 or planar I420 (yuv420p), every plane
+ * at any address and row pitch (row_stride in BYTES), chroma planes Hc x Wc = ceil(h/2) x ceil(w/2).  Converted on the
+ * device, to and from the fp32 planar RGB [3][H][W] in [0,1] of the section above, without an 8-bit RGB frame in between.
+ *   matrix  DVSR_YUV_BT601: Kr = 0.299, Kb = 0.114; DVSR_YUV_BT709: Kr = 0.2126, Kb = 0.0722; Kg = 1 - Kr - Kb
+ *   range   DVSR_YUV_LIMITED: y0 = 16, ys = 219, cs = 224; DVSR_YUV_FULL: y0 = 0, ys = 255, cs = 255
+ *   (BT601 + LIMITED: the reference's ycbcr2rgb / rgb2ycbcr, data/util.py:234-299.)  Chroma siting is the MPEG-2 / H.264
+ *   default: chroma sample (j, k) on luma column 2k, midway between luma rows 2j and 2j+1.
+ * dvsr_frame_ingest_yuv: sd (h x w) -> dst fp32 planar [3][Hp][Wp] RGB (as dvsr_frame_ingest: Wp % 4 == 0, 16-byte aligned,
+ *   the same two pad modes, defined on the source index).  Chroma is brought to the luma grid by [1,1]/2 between two chroma
+ *   columns (odd x) and 0.75 / 0.25 between the two nearest chroma rows, edges clamped; then yn = (Y - y0) / ys,
+ *   c = (C - 128) / cs, R = yn + 2(1-Kr) cr, G = yn - (2 Kb (1-Kb) / Kg) cb - (2 Kr (1-Kr) / Kg) cr, B = yn + 2(1-Kb) cb,
+ *   clamped to [0,1] and NOT rounded to 8 bits.
+ * dvsr_frame_emit_yuv: src fp32 planar [3][Hs][Ws] -> its top-left dd->h x dd->w crop as 4:2:0 bytes: t = (clamp(v, lo, hi)
+ *   - lo) / (hi - lo), y = Kr R + Kg G + Kb B, cb = (B - y) / (2(1-Kb)), cr = (R - y) / (2(1-Kr)); luma byte = clamp(rint(y0 +
+ *   ys y), 0, 255); chroma sample (j, k) = taps [1,2,1]/4 on columns 2k-1 .. 2k+1, mean of rows 2j and 2j+1, indices clamped
+ *   to the crop; chroma byte = clamp(rint(128 + cs c), 0, 255).  Bytes outside the rows of the planes are not written.
+ * dvsr_edvr_stream_extract_frame_yuv: dvsr_edvr_stream_extract_frame for such a frame (no temporary, no device copy).
+ * Bad arguments (null descriptor / plane, unknown format / matrix / range / pad mode, h or w < 1 or beyond the target, a row
+ * stride shorter than a row, a reflect pad not smaller than the dimension, a misaligned fp32 side) return DVSR_ERR_INVALID
+ * before any launch. */
+#define DVSR_YUV_NV12 0      /* plane[0] = Y [h][w], plane[1] = CbCr interleaved [Hc][Wc][2]; plane[2] ignored */
+#define DVSR_YUV_I420 1      /* plane[0] = Y, plane[1] = Cb [Hc][Wc], plane[2] = Cr [Hc][Wc] */
+#define DVSR_YUV_BT601 0
+#define DVSR_YUV_BT709 1
+#define DVSR_YUV_LIMITED 0
+#define DVSR_YUV_FULL 1
+typedef struct dvsr_yuv_desc {
+  int format;   /* DVSR_YUV_NV12 / _I420 */
+  int h, w;     /* the frame's own (luma) size */
+  int matrix, range;
+  void* plane[3];
+  long long row_stride[3];   /* bytes */
+} dvsr_yuv_desc;
+int dvsr_frame_ingest_yuv(const dvsr_yuv_desc* sd, float* dst, int Hp, int Wp, int pad_mode, dvsr_stream_t stream);
+int dvsr_frame_emit_yuv(const float* src, int Hs, int Ws, const dvsr_yuv_desc* dd, float lo, float hi, dvsr_stream_t stream);
+int dvsr_edvr_stream_extract_frame_yuv(const dvsr_edvr_stream* stream_plan, const float* const* params, const dvsr_yuv_desc* fd,
+                                       int pad_mode, int slot, void* cache, size_t cache_bytes, void* workspace,
+                                       size_t workspace_bytes, int packed, dvsr_stream_t stream);
+
 /* ---- Down-scaling estimators MFDN / SFDN as one launch tape ------------------------------------
  * Replaces DirectKernelEstimatorVideo.forward (models/archs/LRimg_estimator.py:92-117, "MFDN":
  * Conv3d(k3)+ReplicationPad3d, ReflectionPad2d + 3x3 / 4x4-stride-2 Conv2d, Conv3d, 1x1, per-frame

@@ -10,9 +10,19 @@
      baseline  the float path wrapped in torch ops: .float() / 255 + permute on the device in front,
                clamp * 255 round to(uint8) permute behind
    Accepted if the new path's median is not below the baseline's median by more than the baseline's own max - min spread.
+3. the YCbCr 4:2:0 pair (csrc/frame_yuv.hip) next to the unchanged 8-bit HWC kernels, on the same frames in this process:
+   frame_ingest_yuv (NV12, I420; 180x320) and frame_emit_yuv (720x1280) against frame_ingest / frame_emit, each as `--calls`
+   back-to-back launches through the C ABI captured into one graph, whose replay is timed by hipEvents (device time per launch,
+   without the host's call rate), `--yuv-repeats` repetitions alternated; effective bytes/s from the algorithmic bytes (ingest
+   1.5 B read + 12 B written per padded pixel, emit 12 B read + 1.5 B written; HWC: 3 B).  Then frames/s of a pinned NV12
+   video -> NV12 frames on the host against the same video through the HWC path of 2.  The HWC path of the same build is the
+   yardstick, not code under test: a YUV figure is expected not to be slower than its HWC counterpart by more than that
+   counterpart's own max - min spread.
 
-usage (GPU box): python tools/frame_io_bench.py [--h 180 --w 320 --frames 100 --repeats 5 --calls 200] > profiles/r08_frame_io.txt"""
+usage (GPU box): python tools/frame_io_bench.py [--h 180 --w 320 --frames 100 --repeats 5 --calls 200 --yuv-repeats 10]
+                 > profiles/r10_yuv_io.txt   (round 8's profiles/r08_frame_io.txt: parts 1 and 2)"""
 import argparse
+import ctypes
 import os
 import statistics
 import sys
@@ -34,6 +44,7 @@ ap.add_argument("--frames", type=int, default=100)
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--calls", type=int, default=200)
 ap.add_argument("--in-flight", type=int, default=2)
+ap.add_argument("--yuv-repeats", type=int, default=10)
 args = ap.parse_args()
 H, W, T = args.h, args.w, args.frames
 OPT = {'scale': 4, 'network_G': {'which_model_G': 'EDVR', 'nframes': 5}}
@@ -123,3 +134,116 @@ print("  baseline (torch ops around the float path)           median %7.1f frame
     mb, sb, " ".join("%.1f" % v for v in fb)))
 print("  new - baseline = %+.1f frames/s (%+.1f %%); baseline spread %.1f -> %s" % (
     mn - mb, 100 * (mn - mb) / mb, sb, "ACCEPTED (not below the baseline by more than its spread)" if mn >= mb - sb else "REJECTED"))
+
+
+# ---- 3. the YCbCr 4:2:0 pair next to the HWC kernels
+from dynavsr_amd import _lib as L  # noqa: E402
+
+lib = L.lib()
+
+
+def graph_us(launch, n):
+    """Device time per launch: `n` back-to-back launches captured into one graph; returns a function that replays and times it."""
+    for _ in range(3):
+        launch()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(n):
+            launch()
+    g.replay()
+    torch.cuda.synchronize()
+
+    def timed_replay():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return 1e3 * e0.elapsed_time(e1) / n
+    return timed_replay
+
+
+def c_launch(fn, *a):
+    def go():
+        L.check(fn(*a, L.stream()), fn.__name__)
+    return go
+
+
+def compare(title, entries, reps):
+    """entries: [(name, launch, algorithmic bytes)], the first one the yardstick; alternated `reps` times."""
+    timers = [(name, graph_us(launch, args.calls), nbytes) for name, launch, nbytes in entries]
+    us = {name: [] for name, _, _ in timers}
+    for _ in range(reps):
+        for name, t, _ in timers:
+            us[name].append(t())
+    print(title)
+    base = timers[0][0]
+    mb, sb = statistics.median(us[base]), max(us[base]) - min(us[base])
+    for name, _, nbytes in timers:
+        m, sp = statistics.median(us[name]), max(us[name]) - min(us[name])
+        verdict = "yardstick" if name == base else ("not slower than %s by more than its spread %.2f us: %s" % (
+            base, sb, "MET" if m <= mb + sb else "MISSED"))
+        print("  %-22s median %7.2f us per launch  spread %5.2f  %6.2f MB algorithmic -> %6.3f TB/s effective  (%s)" % (
+            name, m, sp, nbytes / 1e6, nbytes / m / 1e6, verdict))
+
+
+h, w = 180, 320
+rgb = torch.from_numpy(r.randint(0, 256, (h, w, 3)).astype(np.uint8)).cuda()
+packed = torch.from_numpy(r.randint(0, 256, (h * 3 // 2, w)).astype(np.uint8)).cuda()
+dst = torch.empty((3, h, w), device='cuda')
+_, d_rgb = frames.describe(rgb, 'hwc_rgb')
+entries = [("frame_ingest HWC RGB", c_launch(lib.dvsr_frame_ingest, rgb.data_ptr(), ctypes.byref(d_rgb), dst.data_ptr(), h, w,
+                                               L.FRAME_PAD_REFLECT), 15 * h * w)]
+keep = []
+for lay in ('nv12', 'i420'):
+    planes, d = frames.describe_yuv(frames.yuv_planes(packed, lay)[0], lay, h, w)
+    keep.append((planes, d))
+    entries.append(("frame_ingest_yuv " + lay.upper(), c_launch(lib.dvsr_frame_ingest_yuv, ctypes.byref(d), dst.data_ptr(), h, w,
+                                                                  L.FRAME_PAD_REFLECT), int(13.5 * h * w)))
+compare("ingest %dx%d -> fp32 [3,%d,%d], %d launches per replay, %d repetitions alternated" % (h, w, h, w, args.calls,
+                                                                                               args.yuv_repeats), entries, args.yuv_repeats)
+h, w = 720, 1280
+sr = torch.rand((3, h, w), device='cuda')
+img = torch.empty((h, w, 3), dtype=torch.uint8, device='cuda')
+out = torch.empty((h * 3 // 2, w), dtype=torch.uint8, device='cuda')
+_, d_img = frames.describe(img, 'hwc_rgb')
+entries = [("frame_emit HWC RGB", c_launch(lib.dvsr_frame_emit, sr.data_ptr(), h, w, img.data_ptr(), ctypes.byref(d_img),
+                                             ctypes.c_float(0.0), ctypes.c_float(1.0)), 15 * h * w)]
+for lay in ('nv12', 'i420'):
+    planes, d = frames.describe_yuv(frames.yuv_planes(out, lay)[0], lay, h, w, copy=False)
+    keep.append((planes, d))
+    entries.append(("frame_emit_yuv " + lay.upper(), c_launch(lib.dvsr_frame_emit_yuv, sr.data_ptr(), h, w, ctypes.byref(d),
+                                                                ctypes.c_float(0.0), ctypes.c_float(1.0)), int(13.5 * h * w)))
+compare("emit fp32 [3,%d,%d] -> %dx%d, %d launches per replay, %d repetitions alternated" % (h, w, h, w, args.calls,
+                                                                                             args.yuv_repeats), entries, args.yuv_repeats)
+del sr, img, out, keep
+
+if H % 2 or W % 2:
+    sys.exit("the NV12 video needs an even --h and --w")
+yuv_video = torch.from_numpy(r.randint(16, 236, (T, H * 3 // 2, W)).astype(np.uint8)).pin_memory()     # [T,H*3/2,W] uint8, pinned
+yuv_out = torch.empty((T, 6 * H, 4 * W), dtype=torch.uint8).pin_memory()
+
+
+def yuv_path():
+    for i, y in enumerate(adapt.super_resolve_frames(OPT, net, yuv_video, in_flight=args.in_flight, layout='nv12')):
+        yuv_out[i].copy_(y, non_blocking=True)
+    torch.cuda.synchronize()
+
+
+yuv_path()
+new_path()
+fy, fh = [], []
+for _ in range(args.yuv_repeats):
+    fy.append(timed(yuv_path))
+    fh.append(timed(new_path))
+my, mh = statistics.median(fy), statistics.median(fh)
+sh = max(fh) - min(fh)
+print("video %d frames %dx%d pinned host -> %dx%d host, in_flight %d, %d repetitions alternated" % (T, H, W, 4 * H, 4 * W,
+                                                                                                   args.in_flight, args.yuv_repeats))
+print("  NV12 in, NV12 out (%.2f MB back per frame)   median %7.1f frames/s  spread %5.1f  (%s)" % (
+    6 * H * 4 * W / 1e6, my, max(fy) - min(fy), " ".join("%.1f" % v for v in fy)))
+print("  HWC RGB in, HWC RGB out (%.2f MB back)        median %7.1f frames/s  spread %5.1f  (%s)" % (
+    12 * H * 4 * W / 1e6, mh, sh, " ".join("%.1f" % v for v in fh)))
+print("  NV12 - HWC = %+.1f frames/s (%+.1f %%); HWC spread %.1f -> expectation %s" % (
+    my - mh, 100 * (my - mh) / mh, sh, "MET (not below the HWC path by more than its spread)" if my >= mh - sh else "MISSED"))
