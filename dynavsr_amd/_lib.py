@@ -73,7 +73,7 @@ class FrameDesc(Structure):
                 ("pixel_stride", c_int)]
 
 
-FRAME_F32_CHW, FRAME_U8_HWC_RGB, FRAME_U8_HWC_BGR = 0, 1, 2
+FRAME_F32_CHW, FRAME_U8_HWC_RGB, FRAME_U8_HWC_BGR, FRAME_U8_Y = 0, 1, 2, 3
 FRAME_PAD_REFLECT, FRAME_PAD_REPLICATE = 0, 1
 
 
@@ -204,6 +204,7 @@ def _declare(lib):
         "dvsr_frame_ingest_yuv": (I, [POINTER(YuvDesc), P, I, I, I, P]),
         "dvsr_frame_emit_yuv": (I, [P, I, I, POINTER(YuvDesc), F, F, P]),
         "dvsr_edvr_stream_extract_frame_yuv": (I, [P, POINTER(c_void_p), POINTER(YuvDesc), I, I, P, c_size_t, P, c_size_t, I, P]),
+        "dvsr_frame_luma_sad": (I, [P, P, POINTER(FrameDesc), LL, I, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

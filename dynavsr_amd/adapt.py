@@ -762,7 +762,62 @@ def _adapt_video_batched(opt, model, est_model, modelcp, est_modelcp, est_model_
         yield from hand_out(pending)
 
 
-def stream_schedule(T, nframes, padding='new_info', in_flight=2):
+def scene_bounds(T, cuts):
+    """The scenes [(a, b), ...] of a video of T frames cut at `cuts`: a strictly increasing sequence of ints in (0, T), k
+    meaning that frame k is the first frame of a new scene ([] = one scene).  Anything else is a ValueError."""
+    import numbers
+    T = int(T)
+    if isinstance(cuts, (str, bytes)) or not hasattr(cuts, '__iter__'):
+        raise ValueError("cuts=%r: a sequence of frame numbers (or None)" % (cuts,))
+    ks = list(cuts)
+    for k in ks:
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+            raise ValueError("cuts: %r is not an int" % (k,))
+    ks = [int(k) for k in ks]
+    for i, k in enumerate(ks):
+        if not 0 < k < T:
+            raise ValueError("cuts: %d is outside (0, %d) -- a cut names the first frame of a new scene" % (k, T))
+        if i and k <= ks[i - 1]:
+            raise ValueError("cuts: %s is not strictly increasing" % (ks,))
+    edges = [0] + ks + [T]
+    return list(zip(edges[:-1], edges[1:]))
+
+
+def video_windows(T, nframes, padding='new_info', cuts=None):
+    """(windows, scenes): the window (list of nframes frame numbers) of every centre 0 .. T - 1, and the number of scenes.
+
+    cuts=None: one scene, data.util.index_generation(centre, T, nframes, padding); ValueError where a window leaves [0, T).
+    Scene mode (any other `cuts`, see scene_bounds): the window of centre c in the scene [a, b) is
+    a + index_generation(c - a, b - a, nframes, padding) -- what the reference's datasets give, which read one folder per
+    scene -- and a scene too short for `padding` (some window would leave [a, b)) takes 'replicate', which never leaves it,
+    for all of its windows.  Nothing is raised for a short scene."""
+    from .data.util import index_generation
+    T, nframes = int(T), int(nframes)
+    if cuts is None:
+        windows = [index_generation(c, T, nframes, padding) for c in range(T)]
+        for c, win in enumerate(windows):
+            if min(win) < 0 or max(win) >= T:
+                raise ValueError("stream_schedule: %d frames are too few for windows of %d under padding %r (centre %d would "
+                                 "read frames %s)" % (T, nframes, padding, c, win))
+        return windows, 1
+    scenes = scene_bounds(T, cuts)
+    windows = []
+    for a, b in scenes:
+        wins = [index_generation(c, b - a, nframes, padding) for c in range(b - a)]
+        if any(min(win) < 0 or max(win) >= b - a for win in wins):
+            wins = [index_generation(c, b - a, nframes, 'replicate') for c in range(b - a)]
+        windows += [[a + i for i in win] for win in wins]
+    return windows, len(scenes)
+
+
+def stream_slots(nframes, in_flight, scenes=1):
+    """The capacity of the frame cache that stream_schedule assumes (see there)."""
+    if scenes > 1 and in_flight > 1:
+        return 2 * nframes + in_flight - 2
+    return nframes + in_flight - 1
+
+
+def stream_schedule(T, nframes, padding='new_info', in_flight=2, cuts=None):
     """The frame-cache schedule of super_resolve_frames, as pure Python: for every centre frame 0 .. T - 1 yields
     (centre, frames_to_extract, [(frame, slot), ...], window_slots).
 
@@ -773,17 +828,22 @@ def stream_schedule(T, nframes, padding='new_info', in_flight=2):
     nor the in_flight - 1 before it that may still be running, nor any later one names it (tests/test_stream_schedule.py
     simulates it).  window_slots are the cache slots of the window's frames, in window order.
     T < nframes is accepted only where every window stays inside [0, T); otherwise ValueError, where the reference would
-    index past the end of its frame list."""
-    from .data.util import index_generation
+    index past the end of its frame list.
+
+    cuts (None: all of the above, unchanged): scene mode, the windows of video_windows -- no window names a frame of
+    another scene, and a short scene raises nothing.  The properties are the same; the capacity is not.  With more than
+    one scene the windows that end a scene reach nframes frames back while the first window of the next one reaches
+    nframes - 1 frames ahead, and the smallest cache that always works with slot = frame % slots is
+        slots = nframes                        for in_flight == 1,
+        slots = 2 * nframes + in_flight - 2    otherwise
+    (stream_slots; found and held by simulation over nframes 3, 5, 7, in_flight 1 .. 4, the four modes, T <= 29 and cut
+    sets of every single cut, a cut at every frame and random ones: tests/test_scene_schedule.py, which also shows that
+    one slot fewer fails).  One scene (cuts=[]) keeps nframes + in_flight - 1."""
     T, nframes, in_flight = int(T), int(nframes), int(in_flight)
     if T < 1 or nframes < 1 or in_flight < 1:
         raise ValueError("stream_schedule: T=%d, nframes=%d, in_flight=%d must be positive" % (T, nframes, in_flight))
-    windows = [index_generation(c, T, nframes, padding) for c in range(T)]
-    for c, win in enumerate(windows):
-        if min(win) < 0 or max(win) >= T:
-            raise ValueError("stream_schedule: %d frames are too few for windows of %d under padding %r (centre %d would "
-                             "read frames %s)" % (T, nframes, padding, c, win))
-    slots = nframes + in_flight - 1
+    windows, scenes = video_windows(T, nframes, padding, cuts)
+    slots = stream_slots(nframes, in_flight, scenes)
     done = 0                       # frames 0 .. done - 1 are extracted
     for c, win in enumerate(windows):
         new = list(range(done, max(done, max(win) + 1)))
@@ -810,7 +870,7 @@ def _video_format(frames, layout):
 
 
 def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, layout=None, out=None, pad_mode='reflect',
-                         multiple=None, matrix='bt601', yuv_range='limited'):
+                         multiple=None, matrix='bt601', yuv_range='limited', cuts=None, cut_threshold=10.0):
     """Super-resolves a VIDEO: `frames` is a [T,3,H,W] tensor or a list of [3,H,W] frames (CPU or GPU); yields the SR frame
     [1,3,sH,sW] of every frame, in order -- what `net(frames[index_generation(i, T, nframes, padding)][None])` gives, the
     sliding-window test of the reference's video datasets (video_test_dataset_int.py:219, `padding: new_info` in the
@@ -844,9 +904,11 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     ('bt601' | 'bt709') and `yuv_range` ('limited' | 'full') in the launch that fills the frame cache; `out` None then
     yields packed uint8 [sH*3/2, sW] frames of the input's layout on the device, written from the fp32 SR frame in one launch,
     and 'nv12' / 'i420' force such an output for RGB and float inputs too (sH and sW must be even).
+    A video of several scenes: `cuts` (None: one scene, the calls of before) lists the first frame of every new scene, or is
+    'auto' for frames.detect_cuts(frames, layout, threshold=cut_threshold); no window then crosses a cut (video_windows), so
+    every scene comes out as if it had been passed alone, and the frame cache has stream_slots' capacity.
     Arguments are checked before the first GPU call (ValueError)."""
     from . import frames as fio
-    from .data.util import index_generation
     from .models.archs.EDVR_arch import EDVR
     T = len(frames)
     if T < 1:
@@ -885,13 +947,20 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         fio.check_pad(h, w, Hp, -(-Wp // 4) * 4, pad_mode)
         if lay == 'chw' and out_fmt == 'float' and (Hp, Wp) == (h, w):
             Hp = Wp = None                            # nothing to convert, pad or crop: today's calls
+    n = int(net.nframes) if is_edvr or not (opt.get('network_G') or {}).get('nframes') else int(opt['network_G']['nframes'])
+    if isinstance(cuts, str):
+        if cuts != 'auto':
+            raise ValueError("super_resolve_frames: cuts=%r (None, 'auto' or a sequence of frame numbers)" % (cuts,))
+        video_windows(T, n, padding, [])                           # (the mode, before the first GPU call)
+        cuts = fio.detect_cuts(frames, lay, threshold=cut_threshold)
+    elif cuts is not None:
+        cuts = [a for a, _ in scene_bounds(T, cuts)][1:]
     if not is_edvr:
-        n = int(opt['network_G']['nframes']) if (opt.get('network_G') or {}).get('nframes') else int(net.nframes)
-        sched = list(stream_schedule(T, n, padding, 1))            # (validates T and the mode)
+        windows, _ = video_windows(T, n, padding, cuts)            # (validates T, the mode and the cuts)
         if Hp is None:
             def clips():
-                for c, _, _, _ in sched:
-                    yield torch.stack([frames[j] for j in index_generation(c, T, n, padding)])[None]
+                for win in windows:
+                    yield torch.stack([frames[j] for j in win])[None]
             yield from super_resolve_video(opt, net, clips(), in_flight)
             return
         kept = {}                                      # frame -> its ingested tensor; the last 2n are kept
@@ -905,8 +974,8 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
             return x
 
         def padded_clips():
-            for c, _, _, _ in sched:
-                yield torch.stack([ingested(j) for j in index_generation(c, T, n, padding)])[None]
+            for win in windows:
+                yield torch.stack([ingested(j) for j in win])[None]
         for sr in super_resolve_video(opt, net, padded_clips(), in_flight):
             s = sr.shape[-2] // Hp
             if out_fmt == 'float':
@@ -918,12 +987,13 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     dev = leaves[0].device
     if dev.type != 'cuda':
         raise RuntimeError("dynavsr_amd EDVR runs on the MI355X only (the network is on %s); there is no CPU fallback" % dev)
-    sched = list(stream_schedule(T, net.nframes, padding, in_flight))
+    sched = list(stream_schedule(T, net.nframes, padding, in_flight, cuts))
     if Hp is None and tuple(frames[0].shape[-3:-2]) != (3,):
         raise RuntimeError("super_resolve_frames expects frames [3,H,W], got %s" % (tuple(frames[0].shape),))
     direct = Hp is None                               # fp32 planar frames of the plan's size in, the fuse tape's tensor out
     ph, pw = (h, w) if direct else (Hp, Wp)
-    plan = engine.get_stream_plan(net._cfg(), ph, pw, net.nframes + in_flight - 1, dev)
+    slots = stream_slots(net.nframes, in_flight, 1 if cuts is None else len(cuts) + 1)
+    plan = engine.get_stream_plan(net._cfg(), ph, pw, slots, dev)
     main = torch.cuda.current_stream(dev)
     streams = _clip_streams(dev, in_flight)
     with torch.cuda.device(dev):

@@ -24,6 +24,12 @@ ceil(W/2), every plane at any offset and row pitch (passed by stride) and H, W o
 'bt709') and `yuv_range` ('limited' | 'full') name the conversion; the defaults are the reference's ycbcr2rgb / rgb2ycbcr
 (data/util.py:234-299).  ingest gives the un-rounded fp32 RGB, emit goes from fp32 RGB to 4:2:0 bytes in one launch; the
 arithmetic is written out in csrc/frame_yuv.hip and DESIGN 3.2k.
+
+Scene cuts (csrc/frame_cut.hip: dvsr_frame_luma_sad), for any of the layouts above:
+
+    luma_sad(frames, layout)             -> int64 [T-1]: sum over the frame of |Y8_t - Y8_(t-1)|, exact, in one pass on the device
+    scene_scores(sad, h, w)              -> float64 [T]: min(mafd_t, |mafd_t - mafd_(t-1)|), mafd = 100 SAD / (255 h w); host code
+    detect_cuts(frames, layout, threshold) -> the frames whose score reaches the threshold: the `cuts` of super_resolve_frames
 """
 import ctypes
 
@@ -281,3 +287,118 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
         L.check(L.lib().dvsr_frame_emit(sr.data_ptr(), Hs, Ws, out.data_ptr(), ctypes.byref(desc), float(min_max[0]),
                                         float(min_max[1]), L.stream()), "dvsr_frame_emit")
     return out
+
+
+def _luma_part(frame, layout):
+    """The tensor of a frame that carries its luma: the Y plane of a 4:2:0 frame (a view), the frame itself otherwise."""
+    if layout in YUV_LAYOUTS:
+        return yuv_planes(frame, layout)[0][0]
+    return frame if layout != 'chw' or frame.dtype == torch.float32 else frame.float()
+
+
+def _describe_luma(x, layout):
+    """(x', the fields of its dvsr_frame_desc) of what _luma_part returned; a view that the descriptor cannot express is
+    copied first."""
+    if layout in YUV_LAYOUTS:
+        h, w = x.shape
+        st = x.stride()
+        if not ((st[1] == 1 or w == 1) and (st[0] >= w or h == 1)):
+            x = x.contiguous()
+            st = x.stride()
+        return x, (L.FRAME_U8_Y, h, w, max(int(st[0]), w), 0, 1)
+    x, d = describe(x, layout)
+    return x, (d.format, d.h, d.w, d.row_stride, d.plane_stride, d.pixel_stride)
+
+
+def _luma_sad_launch(a, b, fields, frame_stride, pairs, sad):
+    desc = L.FrameDesc(*fields)
+    L.check(L.lib().dvsr_frame_luma_sad(a.data_ptr(), b.data_ptr(), ctypes.byref(desc), int(frame_stride), int(pairs),
+                                        sad.data_ptr(), L.stream()), "dvsr_frame_luma_sad")
+
+
+def luma_sad(frames, layout=None):
+    """SAD_t = sum over the h x w frame of |Y8_t(p) - Y8_(t-1)(p)| for t = 1 .. T - 1, as an int64 CPU tensor [T - 1].
+
+    `frames` is what adapt.super_resolve_frames accepts: a [T,...] tensor or a list of frames of one kind and size, on the CPU
+    or the GPU, in any `layout` (None: by dtype).  Y8, the luma of a pixel, is an 8-bit integer: the Y-plane byte of an
+    'nv12' / 'i420' frame as it is (`matrix` and `yuv_range` play no part), (77 R + 150 G + 29 B + 128) >> 8 of an 8-bit
+    RGB / BGR pixel, and the same formula on the 8-bit values emit() would write (clamp to [0,1], x 255, round half to
+    even) of a float frame.  The sums are exact.
+    A video tensor on the GPU is one launch over all pairs; a list takes one launch per pair.  CPU frames travel as bytes
+    (the Y plane alone of a 4:2:0 frame) through two staging buffers on the device, so a long video is never resident as a
+    whole.  One device-to-host copy at the end carries the sums."""
+    T = len(frames)
+    if T < 1:
+        raise ValueError("luma_sad: no frames")
+    lay, h, w = resolve_layout(frames[0], layout)
+    first = _luma_part(frames[0], lay)
+    dev = first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    if T == 1:
+        return torch.zeros((0,), dtype=torch.int64)
+    with torch.cuda.device(dev):
+        sad = torch.empty((T - 1,), dtype=torch.int64, device=dev)
+        if torch.is_tensor(frames) and frames.is_cuda:
+            video = frames if lay != 'chw' or frames.dtype == torch.float32 else frames.float()
+            for attempt in (0, 1):
+                p0, p1 = _luma_part(video[0], lay), _luma_part(video[1], lay)
+                (x0, d0), (x1, d1) = _describe_luma(p0, lay), _describe_luma(p1, lay)
+                step = x1.data_ptr() - x0.data_ptr()
+                if x0.data_ptr() == p0.data_ptr() and x1.data_ptr() == p1.data_ptr() and d0 == d1 and \
+                        step == video.stride(0) * video.element_size():
+                    break
+                if attempt:
+                    raise RuntimeError("luma_sad: a contiguous video must be expressible by stride")
+                video = video.contiguous()                 # (a view the descriptor cannot express)
+            _luma_sad_launch(x0, x1, d0, video.stride(0), T - 1, sad)
+            return sad.cpu()
+        stage, prev, kind = [None, None], None, None
+        for t in range(T):
+            ht, wt = resolve_layout(frames[t], lay)[1:]
+            if (ht, wt) != (h, w):
+                raise ValueError("luma_sad: frame %d is %d x %d, frame 0 is %d x %d" % (t, ht, wt, h, w))
+            x = _luma_part(frames[t], lay)
+            if kind is None:
+                kind = (x.dtype, tuple(x.shape))
+            if (x.dtype, tuple(x.shape)) != kind:
+                raise ValueError("luma_sad: frame %d is %s, frame 0 is %s" % (t, (x.dtype, tuple(x.shape)), kind))
+            if x.device != dev:
+                if stage[t % 2] is None:
+                    stage[t % 2] = torch.empty(x.shape, dtype=x.dtype, device=dev)
+                stage[t % 2].copy_(x, non_blocking=True)    # (behind the launch that last read this buffer, on one stream)
+                x = stage[t % 2]
+            cur = _describe_luma(x, lay)
+            if prev is not None:
+                a, b = prev, cur
+                if a[1] != b[1]:                            # two views of different pitch: one descriptor serves copies
+                    a, b = _describe_luma(a[0].contiguous(), lay), _describe_luma(b[0].contiguous(), lay)
+                _luma_sad_launch(a[0], b[0], a[1], 0, 1, sad[t - 1:])
+            prev = cur
+        return sad.cpu()
+
+
+def scene_scores(sad, h, w):
+    """The scene-change score of every frame, float64 [T], from luma_sad's [T - 1] sums -- pure host code.
+    mafd_t = 100 * SAD_t / (255 h w) for t = 1 .. T - 1 (the mean absolute luma difference in percent of full scale),
+    mafd_0 = 0, and score_t = min(mafd_t, |mafd_t - mafd_(t-1)|): the form of the score of ffmpeg's scene-change filter.
+    The min with the CHANGE of the difference keeps sustained fast motion from reading as a cut."""
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError("scene_scores: h=%d, w=%d must be positive" % (h, w))
+    sad = torch.as_tensor(sad).to(torch.float64).reshape(-1)
+    mafd = torch.cat([torch.zeros(1, dtype=torch.float64), 100.0 * sad / (255.0 * h * w)])
+    prev = torch.cat([torch.zeros(1, dtype=torch.float64), mafd[:-1]])
+    return torch.minimum(mafd, (mafd - prev).abs())
+
+
+def detect_cuts(frames, layout=None, threshold=10.0):
+    """The hard cuts of a video: the list of t with scene_scores(luma_sad(frames, layout))[t] >= threshold, frame t being
+    the first of a new scene -- the `cuts` of adapt.super_resolve_frames.  The default threshold is a policy default that
+    callers override; it has not been tuned on real footage.  Fades and dissolves are not found."""
+    threshold = float(threshold)
+    if not threshold > 0:
+        raise ValueError("detect_cuts: threshold=%r must be positive" % (threshold,))
+    if len(frames) < 1:
+        raise ValueError("detect_cuts: no frames")
+    _, h, w = resolve_layout(frames[0], layout)
+    scores = scene_scores(luma_sad(frames, layout), h, w)
+    return [t for t in range(1, len(scores)) if float(scores[t]) >= threshold]

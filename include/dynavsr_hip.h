@@ -354,6 +354,25 @@ int dvsr_edvr_stream_extract_frame(const dvsr_edvr_stream* stream_plan, const fl
                                    const dvsr_frame_desc* fd, int pad_mode, int slot, void* cache, size_t cache_bytes,
                                    void* workspace, size_t workspace_bytes, int packed, dvsr_stream_t stream);
 
+/* ---- Scene cuts: the luma difference of consecutive frames ----------------------------------------
+ * dvsr_frame_luma_sad: sad[i] = sum over the h x w frame of |Y8_b(p) - Y8_a(p)| for pair i = 0 .. pairs - 1, frame a of
+ *   the pair at a + i * frame_stride and frame b at b + i * frame_stride (frame_stride in the descriptor's own units: bytes
+ *   for the 8-bit formats, floats for F32_CHW; any value).  A device-resident video [T][...] is ONE call: b = a +
+ *   frame_stride, pairs = T - 1.  Both frames of every pair share the descriptor.  Y8, the luma of a pixel, is an 8-bit integer:
+ *     DVSR_FRAME_U8_Y                a single 8-bit plane (the Y plane of an NV12 / I420 frame, any address and row pitch,
+ *                                    pixel_stride 1): the byte itself
+ *     DVSR_FRAME_U8_HWC_RGB / _BGR   (pixel_stride 3 or 4)  Y8 = (77 R + 150 G + 29 B + 128) >> 8
+ *     DVSR_FRAME_F32_CHW             the same formula on the 8-bit values of dvsr_frame_emit with lo = 0, hi = 1 (clamp, x 255,
+ *                                    round half to even) of the three channels
+ *   The sums are exact unsigned 64-bit integers and do not depend on the launch geometry.  The function zeroes sad[0 .. pairs)
+ *   on `stream` itself, then launches (one launch per 65535 pairs); sad must be 8-byte aligned device memory.
+ *   DVSR_FRAME_U8_Y is accepted here alone: dvsr_frame_ingest / _emit keep rejecting it.
+ * Bad arguments (null pointer, unknown format, h or w < 1, pairs < 1, a pixel stride the format does not have, a row or
+ * plane stride shorter than a row / plane, a misaligned fp32 frame or result) return DVSR_ERR_INVALID before any launch. */
+#define DVSR_FRAME_U8_Y 3
+int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_frame_desc* desc, long long frame_stride, int pairs,
+                        unsigned long long* sad, dvsr_stream_t stream);
+
 /* ---- YCbCr 4:2:0 frames in and out of the video path -----------------------------------------------
  * What a video decoder really delivers and an encoder takes: 8-bit YCbCr 4:2:0 as NV12 or planar I420 (yuv420p), every plane
  * at any address and row pitch (row_stride in BYTES), chroma planes Hc x Wc = ceil(h/2) x ceil(w/2).  Converted on the
