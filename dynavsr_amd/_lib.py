@@ -74,6 +74,7 @@ class FrameDesc(Structure):
 
 
 FRAME_F32_CHW, FRAME_U8_HWC_RGB, FRAME_U8_HWC_BGR, FRAME_U8_Y = 0, 1, 2, 3
+FRAME_U16_Y_MSB, FRAME_U16_Y_10, FRAME_U16_Y_12 = 4, 5, 6          # dvsr_frame_luma_sad alone
 FRAME_PAD_REFLECT, FRAME_PAD_REPLICATE = 0, 1
 
 
@@ -86,6 +87,15 @@ class YuvDesc(Structure):
 YUV_NV12, YUV_I420 = 0, 1
 YUV_BT601, YUV_BT709 = 0, 1
 YUV_LIMITED, YUV_FULL = 0, 1
+
+
+class Yuv16Desc(Structure):
+    """dvsr_yuv16_desc: a 10- / 12-bit YCbCr 4:2:0 frame in 16-bit words, every plane at any even address and pitch."""
+    _fields_ = [("format", c_int), ("depth", c_int), ("h", c_int), ("w", c_int), ("matrix", c_int), ("range", c_int),
+                ("plane", c_void_p * 3), ("row_stride", c_longlong * 3)]
+
+
+YUV16_SEMI_MSB, YUV16_PLANAR_LSB = 0, 1
 
 
 class EstimatorConfig(Structure):
@@ -205,6 +215,10 @@ def _declare(lib):
         "dvsr_frame_emit_yuv": (I, [P, I, I, POINTER(YuvDesc), F, F, P]),
         "dvsr_edvr_stream_extract_frame_yuv": (I, [P, POINTER(c_void_p), POINTER(YuvDesc), I, I, P, c_size_t, P, c_size_t, I, P]),
         "dvsr_frame_luma_sad": (I, [P, P, POINTER(FrameDesc), LL, I, P, P]),
+        "dvsr_frame_ingest_yuv16": (I, [POINTER(Yuv16Desc), P, I, I, I, P]),
+        "dvsr_frame_emit_yuv16": (I, [P, I, I, POINTER(Yuv16Desc), F, F, P]),
+        "dvsr_edvr_stream_extract_frame_yuv16": (I, [P, POINTER(c_void_p), POINTER(Yuv16Desc), I, I, P, c_size_t, P, c_size_t, I,
+                                                     P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -904,6 +904,11 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     ('bt601' | 'bt709') and `yuv_range` ('limited' | 'full') in the launch that fills the frame cache; `out` None then
     yields packed uint8 [sH*3/2, sW] frames of the input's layout on the device, written from the fp32 SR frame in one launch,
     and 'nv12' / 'i420' force such an output for RGB and float inputs too (sH and sW must be even).
+    High-bit-depth video (HEVC Main10, AV1, VP9 profile 2): `layout` 'p010' / 'p012' (semi-planar, the level in the top bits of a
+    16-bit word) or 'i420p10' / 'i420p12' (yuv420p10le / yuv420p12le), as uint16 or int16 tensors shaped like their 8-bit
+    counterparts (csrc/frame_yuv16.hip); `out` None then yields packed torch.uint16 frames of the input's layout, quantised
+    from the fp32 SR frame to 1024 / 4096 levels, and the four names force such an output for any input -- an 8-bit source can
+    leave with 10 bits.
     A video of several scenes: `cuts` (None: one scene, the calls of before) lists the first frame of every new scene, or is
     'auto' for frames.detect_cuts(frames, layout, threshold=cut_threshold); no window then crosses a cut (video_windows), so
     every scene comes out as if it had been passed alone, and the frame cache has stream_slots' capacity.
@@ -919,7 +924,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         raise ValueError("super_resolve_frames: pad_mode=%r ('reflect' or 'replicate')" % (pad_mode,))
     # float frames with none of the frame arguments given, at a size the network takes as it is: the calls of before
     plain = layout is None and out is None and multiple is None and \
-        torch.is_tensor(frames[0]) and frames[0].dtype != torch.uint8
+        torch.is_tensor(frames[0]) and frames[0].dtype not in (torch.uint8, torch.uint16, torch.int16)
     if is_edvr:
         plain = plain and torch.is_tensor(frames[0]) and frames[0].dim() == 3 and frames[0].is_floating_point() and \
             frames[0].shape[-2] % 4 == 0 and frames[0].shape[-1] % 4 == 0
@@ -927,11 +932,13 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         h, w, lay, out_fmt, Hp, Wp = int(frames[0].shape[-2]), int(frames[0].shape[-1]), 'chw', 'float', None, None
     else:
         lay, h, w = _video_format(frames, layout)
-        if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') + fio.YUV_LAYOUTS:
-            raise ValueError("super_resolve_frames: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr', 'nv12' or 'i420')" % (out,))
+        yuv_all = fio.YUV_LAYOUTS + fio.YUV16_LAYOUTS
+        if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') + yuv_all:
+            raise ValueError("super_resolve_frames: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (
+                out, ', '.join(yuv_all)))
         fio.check_yuv_names(matrix, yuv_range)
         out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
-        if out_fmt in fio.YUV_LAYOUTS:
+        if out_fmt in yuv_all:
             scale = int(net.scale) if is_edvr else int(opt.get('scale') or 1)
             if scale * h % 2 or scale * w % 2:
                 raise ValueError("super_resolve_frames: a packed %s output of %d x %d needs an even size" % (

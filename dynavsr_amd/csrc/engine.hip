@@ -1620,6 +1620,26 @@ extern "C" int dvsr_edvr_stream_extract_frame_yuv(const dvsr_edvr_stream* s, con
   return stream_extract_tape(s, params, raw, dst, ws, packed, st);
 }
 
+// ... and a 10- / 12-bit one (frame_yuv16.hip)
+extern "C" int dvsr_edvr_stream_extract_frame_yuv16(const dvsr_edvr_stream* s, const float* const* params,
+                                                    const dvsr_yuv16_desc* fd, int pad_mode, int slot, void* cache,
+                                                    size_t cache_bytes, void* ws, size_t ws_bytes, int packed,
+                                                    dvsr_stream_t stream) {
+  int rc = stream_check(s, params, cache, cache_bytes, ws, ws_bytes, "edvr_stream_extract_frame_yuv16");
+  if (rc != DVSR_OK) return rc;
+  DVSR_REQUIRE(slot >= 0 && slot < s->slots, DVSR_ERR_INVALID, "edvr_stream_extract_frame_yuv16: slot %d outside [0, %d)", slot,
+               s->slots);
+  const dvsr_edvr_plan& p = s->extract;
+  hipStream_t st = (hipStream_t)stream;
+  float* dst = (float*)cache + (size_t)slot * s->sl.floats;
+  float* raw = dst + s->sl.raw;
+  rc = frame_ingest_yuv16_check("edvr_stream_extract_frame_yuv16", fd, raw, p.H, p.W, pad_mode);
+  if (rc != DVSR_OK) return rc;
+  rc = frame_ingest_yuv16_launch(*fd, raw, p.H, p.W, pad_mode, st);
+  if (rc != DVSR_OK) return rc;
+  return stream_extract_tape(s, params, raw, dst, ws, packed, st);
+}
+
 extern "C" int dvsr_edvr_stream_fuse(const dvsr_edvr_stream* s, const float* const* params, const int* slots, const void* cache,
                                      size_t cache_bytes, float* out, void* ws, size_t ws_bytes, int packed,
                                      dvsr_stream_t stream) {

@@ -5,11 +5,13 @@
 // frame in temporaries; here one pass reads every byte of both frames once:
 //   luma of a pixel, an 8-bit integer
 //     Y plane (NV12 / I420)     the byte itself
+//     16-bit Y plane            the top 8 bits of the level: word >> 8 (P010 / P012), (word & 1023) >> 2 (yuv420p10le),
+//                               (word & 4095) >> 4 (yuv420p12le) -- scores mean what they mean for 8-bit video
 //     8-bit RGB / BGR (3 | 4 B) Y8 = (77 R + 150 G + 29 B + 128) >> 8
 //     fp32 planar               the same formula on quant_u8(v, 0, 1) of each channel (quant.h: the library's one quantiser)
 //   sad[pair] = sum over the h x w frame of |Y8_b(p) - Y8_a(p)|, an exact unsigned 64-bit integer: integer sums are
 //   associative, so the result does not depend on the order in which lanes, waves and workgroups add.
-// One thread = 4 consecutive pixels (Y plane: 16) of a row of BOTH frames, in SAD_ROWS rows; a workgroup is 64 x 4 threads, so a
+// One thread = 4 consecutive pixels (Y plane: 16; 16-bit Y plane: 8) of a row of BOTH frames, in SAD_ROWS rows; a workgroup is 64 x 4 threads, so a
 // wave works on one row at a time and a row's misalignment is wave-uniform.  The byte side follows frame_io.hip: a row that
 // starts on a dword boundary moves as dwords, any other is assembled from the aligned dwords around it (v_alignbyte_b32) -- no load is wider than its
 // address is aligned and only aligned dwords that hold a needed byte are read; the ragged end of a row goes pixel by pixel.
@@ -29,7 +31,7 @@ namespace dvsr {
 
 constexpr int SAD_X = 64, SAD_Y = 4;   // threads of a workgroup along a row (one wave) / rows of a workgroup at a time
 constexpr int SAD_ROWS = 8;            // rows of a wave: a workgroup covers SAD_Y * SAD_ROWS rows
-enum : int { SAD_F32 = 0, SAD_YPLANE = 1, SAD_HWC3 = 3, SAD_HWC4 = 4 };
+enum : int { SAD_F32 = 0, SAD_YPLANE = 1, SAD_HWC3 = 3, SAD_HWC4 = 4, SAD_Y16_MSB = 5, SAD_Y16_10 = 6, SAD_Y16_12 = 7 };
 
 struct SadArgs {
   const void* a;
@@ -109,6 +111,39 @@ __device__ __forceinline__ void luma16_plane(const unsigned char* row, int x0, i
   }
 }
 
+// the top 8 bits of the levels of the two 16-bit words of a dword, in bytes 0 and 1 of the result
+template <int KIND>
+__device__ __forceinline__ unsigned luma2_w16(unsigned v) {
+  constexpr unsigned MASK = KIND == SAD_Y16_MSB ? 0xffffu : (KIND == SAD_Y16_10 ? 1023u : 4095u);
+  constexpr int SH = KIND == SAD_Y16_MSB ? 8 : (KIND == SAD_Y16_10 ? 2 : 4);
+  return (((v & 0xffffu) & MASK) >> SH) | ((((v >> 16) & MASK) >> SH) << 8);
+}
+
+// words x0 .. x0 + 7 of a 16-bit Y row (2-byte aligned) as the two dwords of their lumas (0 for a word beyond w)
+template <int KIND>
+__device__ __forceinline__ void luma8_plane16(const unsigned char* row, int x0, int w, unsigned e[2]) {
+  unsigned d4[4];
+  if (x0 + 7 < w) {
+    const unsigned char* p = row + 2 * (long long)x0;  // x0 * 2 is a multiple of 16: m (0 or 2) is the row's
+    const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3);
+    const unsigned* q = reinterpret_cast<const unsigned*>(p - m);
+    unsigned d[5];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = q[k];
+    d[4] = m ? q[4] : 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d4[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], m);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d4[k] = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (x0 + i < w) d4[i >> 1] |= (unsigned)reinterpret_cast<const unsigned short*>(row)[x0 + i] << (16 * (i & 1));
+  }
+  e[0] = luma2_w16<KIND>(d4[0]) | (luma2_w16<KIND>(d4[1]) << 16);
+  e[1] = luma2_w16<KIND>(d4[2]) | (luma2_w16<KIND>(d4[3]) << 16);
+}
+
 // the lumas of pixels x0 .. x0 + 3 of an fp32 planar row, one per byte (0 for a pixel beyond w)
 __device__ __forceinline__ unsigned luma4_f32(const float* row, long long plane, int x0, int w) {
   float v[3][4];
@@ -145,7 +180,8 @@ __device__ __forceinline__ unsigned luma4_f32(const float* row, long long plane,
 
 template <int KIND>
 __global__ __launch_bounds__(SAD_X * SAD_Y) void frame_luma_sad_kernel(SadArgs a) {
-  constexpr int PX = KIND == SAD_YPLANE ? 16 : 4;
+  constexpr bool Y16 = KIND == SAD_Y16_MSB || KIND == SAD_Y16_10 || KIND == SAD_Y16_12;
+  constexpr int PX = KIND == SAD_YPLANE ? 16 : (Y16 ? 8 : 4);
   const int x0 = (blockIdx.x * SAD_X + threadIdx.x) * PX;
   unsigned s = 0;
 #pragma unroll
@@ -163,6 +199,12 @@ __global__ __launch_bounds__(SAD_X * SAD_Y) void frame_luma_sad_kernel(SadArgs a
       luma16_plane(static_cast<const unsigned char*>(a.b) + off, x0, a.w, eb);
 #pragma unroll
       for (int k = 0; k < 4; ++k) s = __builtin_amdgcn_sad_u8(ea[k], eb[k], s);
+    } else if constexpr (Y16) {
+      unsigned ea[2], eb[2];
+      luma8_plane16<KIND>(static_cast<const unsigned char*>(a.a) + off, x0, a.w, ea);
+      luma8_plane16<KIND>(static_cast<const unsigned char*>(a.b) + off, x0, a.w, eb);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) s = __builtin_amdgcn_sad_u8(ea[k], eb[k], s);
     } else {
       const unsigned ya = luma4_hwc<KIND>(static_cast<const unsigned char*>(a.a) + off, x0, a.w, a.swap);
       const unsigned yb = luma4_hwc<KIND>(static_cast<const unsigned char*>(a.b) + off, x0, a.w, a.swap);
@@ -190,8 +232,9 @@ using namespace dvsr;
 extern "C" int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_frame_desc* d, long long frame_stride, int pairs,
                                    unsigned long long* sad, dvsr_stream_t stream) {
   DVSR_REQUIRE(a && b && d && sad, DVSR_ERR_INVALID, "frame_luma_sad: null frame / descriptor / result");
+  const bool y16 = d->format == DVSR_FRAME_U16_Y_MSB || d->format == DVSR_FRAME_U16_Y_10 || d->format == DVSR_FRAME_U16_Y_12;
   DVSR_REQUIRE(d->format == DVSR_FRAME_F32_CHW || d->format == DVSR_FRAME_U8_HWC_RGB || d->format == DVSR_FRAME_U8_HWC_BGR ||
-                   d->format == DVSR_FRAME_U8_Y,
+                   d->format == DVSR_FRAME_U8_Y || y16,
                DVSR_ERR_INVALID, "frame_luma_sad: unknown frame format %d", d->format);
   DVSR_REQUIRE(d->h >= 1 && d->w >= 1 && d->h <= (1 << 20) && d->w <= (1 << 24), DVSR_ERR_INVALID,
                "frame_luma_sad: frame size h=%d w=%d outside [1, %d] x [1, %d]", d->h, d->w, 1 << 20, 1 << 24);
@@ -210,6 +253,14 @@ extern "C" int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_fram
     if (d->format == DVSR_FRAME_U8_Y) {
       DVSR_REQUIRE(d->pixel_stride == 1, DVSR_ERR_INVALID, "frame_luma_sad: pixel stride %d of a Y plane (1)", d->pixel_stride);
       kind = SAD_YPLANE;
+    } else if (y16) {
+      DVSR_REQUIRE(d->pixel_stride == 2, DVSR_ERR_INVALID, "frame_luma_sad: pixel stride %d of a 16-bit Y plane (2)",
+                   d->pixel_stride);
+      DVSR_REQUIRE(reinterpret_cast<uintptr_t>(a) % 2 == 0 && reinterpret_cast<uintptr_t>(b) % 2 == 0, DVSR_ERR_INVALID,
+                   "frame_luma_sad: odd address of a 16-bit Y plane");
+      DVSR_REQUIRE(d->row_stride % 2 == 0 && frame_stride % 2 == 0, DVSR_ERR_INVALID,
+                   "frame_luma_sad: odd row stride %lld / frame stride %lld of a 16-bit Y plane", d->row_stride, frame_stride);
+      kind = d->format == DVSR_FRAME_U16_Y_MSB ? SAD_Y16_MSB : (d->format == DVSR_FRAME_U16_Y_10 ? SAD_Y16_10 : SAD_Y16_12);
     } else {
       DVSR_REQUIRE(d->pixel_stride == 3 || d->pixel_stride == 4, DVSR_ERR_INVALID, "frame_luma_sad: pixel stride %d (3 or 4)",
                    d->pixel_stride);
@@ -226,7 +277,7 @@ extern "C" int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_fram
     return DVSR_ERR_HIP;
   }
   const long long unit = kind == SAD_F32 ? 4 : 1;
-  const int per_thread = kind == SAD_YPLANE ? 16 : 4;
+  const int per_thread = kind == SAD_YPLANE ? 16 : (y16 ? 8 : 4);
   const dim3 block(SAD_X, SAD_Y);
   for (int first = 0; first < pairs; first += 65535) {               // grid.z is the pair: at most 65535 per launch
     const int n = pairs - first < 65535 ? pairs - first : 65535;
@@ -238,6 +289,9 @@ extern "C" int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_fram
       case SAD_F32: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_F32>, grid, block, 0, st, args); break;
       case SAD_YPLANE: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_YPLANE>, grid, block, 0, st, args); break;
       case SAD_HWC3: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_HWC3>, grid, block, 0, st, args); break;
+      case SAD_Y16_MSB: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_Y16_MSB>, grid, block, 0, st, args); break;
+      case SAD_Y16_10: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_Y16_10>, grid, block, 0, st, args); break;
+      case SAD_Y16_12: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_Y16_12>, grid, block, 0, st, args); break;
       default: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_HWC4>, grid, block, 0, st, args); break;
     }
     const int rc = check_launch("frame_luma_sad_kernel");

@@ -245,6 +245,10 @@ int frame_ingest_launch(const void* src, const dvsr_frame_desc& sd, float* dst, 
 int frame_ingest_yuv_check(const char* what, const dvsr_yuv_desc* sd, const float* dst, int Hp, int Wp, int pad_mode);
 int frame_ingest_yuv_launch(const dvsr_yuv_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
 
+// frame_yuv16.hip: ... and for a 10- / 12-bit one (P010 / P012, yuv420p10le / yuv420p12le)
+int frame_ingest_yuv16_check(const char* what, const dvsr_yuv16_desc* sd, const float* dst, int Hp, int Wp, int pad_mode);
+int frame_ingest_yuv16_launch(const dvsr_yuv16_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
+
 // pad.hip: explicit padding / layout changes of the MFDN estimator and their adjoints
 enum : int { PAD_REFLECT = 0, PAD_REFLECT_S2D = 1, PAD_REPL_T3 = 2 };
 size_t pad_out_numel(int mode, size_t N, int C, int H, int W);

@@ -552,7 +552,8 @@ class StreamPlan:
 
     def extract_frame(self, leaves, frame, slot, cache, layout=None, pad_mode='reflect', matrix='bt601', yuv_range='limited'):
         """A decoder's frame on the GPU -- uint8 [h,w,3|4] ('hwc_rgb' / 'hwc_bgr'), fp32 [3,h,w] ('chw') or YCbCr 4:2:0
-        ('nv12' / 'i420': packed or planes, frames.py; `matrix`, `yuv_range`), h <= H, w <= W, any offset and row pitch --
+        ('nv12' / 'i420', or 'p010' / 'p012' / 'i420p10' / 'i420p12' in 16-bit words: packed or planes, frames.py; `matrix`,
+        `yuv_range`), h <= H, w <= W, any offset and row pitch --
         -> slot `slot` of `cache`, on the current stream: converted and padded to the plan's H x W straight into the slot
         (frames.ingest's result, without the temporary), then `extract`'s tape.  Returns the tensor(s) the launch reads."""
         from . import frames as F
@@ -564,10 +565,11 @@ class StreamPlan:
         first = frame if torch.is_tensor(frame) else frame[0]
         if not first.is_cuda:
             raise RuntimeError("libdynavsr_hip needs a tensor on the GPU, got device %s" % first.device)
-        if layout in F.YUV_LAYOUTS:
+        if layout in F.YUV_LAYOUTS + F.YUV16_LAYOUTS:
             planes, desc = F.describe_yuv(F.yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range)
             params, arr = self._params(leaves)
-            self._run('extract', leaves, lambda ws, packed: L.lib().dvsr_edvr_stream_extract_frame_yuv(
+            fn = F._yuv_entry(layout, 'edvr_stream_extract_frame')[0]
+            self._run('extract', leaves, lambda ws, packed: fn(
                 self._h, arr, ctypes.byref(desc), F._PAD[pad_mode], int(slot), cache.data_ptr(),
                 cache.numel() * cache.element_size(), ws.data_ptr(), ws.numel(), packed, L.stream()))
             self.stats['extracted'] += 1

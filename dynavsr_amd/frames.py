@@ -25,6 +25,14 @@ ceil(W/2), every plane at any offset and row pitch (passed by stride) and H, W o
 (data/util.py:234-299).  ingest gives the un-rounded fp32 RGB, emit goes from fp32 RGB to 4:2:0 bytes in one launch; the
 arithmetic is written out in csrc/frame_yuv.hip and DESIGN 3.2k.
 
+High-bit-depth video (HEVC Main10, AV1, VP9 profile 2) decodes to 16-bit little-endian words that hold 10 or 12 bits: the
+layouts 'p010' / 'p012' (semi-planar like NV12, the level in the TOP bits of the word) and 'i420p10' / 'i420p12'
+(yuv420p10le / yuv420p12le: planar like I420, the level in the LOW bits), never inferred either.  Frames come packed or as
+planes exactly as above, as torch.uint16 or torch.int16 tensors (the same bits; numpy and PyAV hand over uint16); the bits of a
+word that carry no level are ignored on the way in and written as 0, and emit returns torch.uint16.  The same matrices, ranges,
+siting and filters apply with H.273's level scale at that depth, nothing is rounded to 8 bits on the way, and an 8-bit or RGB
+source may leave with 10 bits (csrc/frame_yuv16.hip).
+
 Scene cuts (csrc/frame_cut.hip: dvsr_frame_luma_sad), for any of the layouts above:
 
     luma_sad(frames, layout)             -> int64 [T-1]: sum over the frame of |Y8_t - Y8_(t-1)|, exact, in one pass on the device
@@ -39,6 +47,12 @@ from . import _lib as L
 
 LAYOUTS = ('chw', 'hwc_rgb', 'hwc_bgr')
 YUV_LAYOUTS = ('nv12', 'i420')
+YUV16_LAYOUTS = ('p010', 'p012', 'i420p10', 'i420p12')
+_YUV16 = {'p010': (L.YUV16_SEMI_MSB, 10), 'p012': (L.YUV16_SEMI_MSB, 12),          # layout -> (storage, depth)
+          'i420p10': (L.YUV16_PLANAR_LSB, 10), 'i420p12': (L.YUV16_PLANAR_LSB, 12)}
+_SEMI_PLANAR = ('nv12', 'p010', 'p012')
+_WORD_DTYPES = (torch.uint16, torch.int16)
+_LUMA16 = {'p010': L.FRAME_U16_Y_MSB, 'p012': L.FRAME_U16_Y_MSB, 'i420p10': L.FRAME_U16_Y_10, 'i420p12': L.FRAME_U16_Y_12}
 _YUV_FORMAT = {'nv12': L.YUV_NV12, 'i420': L.YUV_I420}
 _YUV_MATRIX = {'bt601': L.YUV_BT601, 'bt709': L.YUV_BT709}
 _YUV_RANGE = {'limited': L.YUV_LIMITED, 'full': L.YUV_FULL}
@@ -57,7 +71,7 @@ def padded_size(h, w, multiple):
 def resolve_layout(frame, layout=None):
     """Checks one frame against `layout` (None: by dtype; the 4:2:0 layouts are never inferred) and returns
     (layout, h, w).  No GPU call."""
-    if layout in YUV_LAYOUTS:
+    if layout in YUV_LAYOUTS + YUV16_LAYOUTS:
         _, h, w = yuv_planes(frame, layout)
         return layout, h, w
     if not torch.is_tensor(frame):
@@ -65,7 +79,7 @@ def resolve_layout(frame, layout=None):
     if layout is None:
         layout = 'hwc_rgb' if frame.dtype == torch.uint8 else 'chw'
     if layout not in LAYOUTS:
-        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + YUV_LAYOUTS)))
+        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + YUV_LAYOUTS + YUV16_LAYOUTS)))
     if frame.dtype == torch.uint8:
         if layout == 'chw':
             raise ValueError("a uint8 frame is interleaved ('hwc_rgb' / 'hwc_bgr'), not 'chw'")
@@ -121,36 +135,39 @@ def check_yuv_names(matrix, yuv_range):
 
 
 def yuv_planes(frame, layout):
-    """(planes, h, w) of a 4:2:0 frame -- a packed uint8 [H*3/2, W] tensor or a tuple of plane tensors: the planes as views
-    (y, uv) / (y, u, v), nothing copied.  ValueError for anything else.  No GPU call."""
-    if layout not in YUV_LAYOUTS:
-        raise ValueError("unknown YCbCr layout %r (one of %s)" % (layout, ', '.join(YUV_LAYOUTS)))
-    n = 2 if layout == 'nv12' else 3
+    """(planes, h, w) of a 4:2:0 frame -- a packed [H*3/2, W] tensor or a tuple of plane tensors, uint8 for 'nv12' / 'i420',
+    uint16 or int16 for the 10- / 12-bit layouts: the planes as views (y, uv) / (y, u, v), nothing copied.  ValueError for
+    anything else.  No GPU call."""
+    if layout not in YUV_LAYOUTS + YUV16_LAYOUTS:
+        raise ValueError("unknown YCbCr layout %r (one of %s)" % (layout, ', '.join(YUV_LAYOUTS + YUV16_LAYOUTS)))
+    semi = layout in _SEMI_PLANAR
+    n = 2 if semi else 3
+    dtypes, kind = ((torch.uint8,), 'uint8') if layout in YUV_LAYOUTS else (_WORD_DTYPES, 'uint16 / int16')
     if torch.is_tensor(frame):
-        if frame.dtype != torch.uint8 or frame.dim() != 2:
-            raise ValueError("a packed %s frame must be uint8 [H*3/2, W], got %s %s" % (layout, frame.dtype, tuple(frame.shape)))
+        if frame.dtype not in dtypes or frame.dim() != 2:
+            raise ValueError("a packed %s frame must be %s [H*3/2, W], got %s %s" % (layout, kind, frame.dtype, tuple(frame.shape)))
         rows, w = int(frame.shape[0]), int(frame.shape[1])
         h = rows * 2 // 3
         if rows < 3 or rows % 3 or h % 2 or w < 2 or w % 2:
             raise ValueError("a packed %s frame is [H*3/2, W] with H and W even, got %s (pass planes for odd sizes)"
                              % (layout, tuple(frame.shape)))
-        if layout == 'nv12':
+        if semi:
             return (frame[:h], frame[h:].unflatten(1, (w // 2, 2))), h, w
         if not frame.is_contiguous():
-            raise ValueError("a packed i420 frame must be contiguous (its chroma rows are half as long); pass planes")
+            raise ValueError("a packed %s frame must be contiguous (its chroma rows are half as long); pass planes" % layout)
         flat, n_c = frame.view(-1), (h // 2) * (w // 2)
         return (frame[:h], flat[h * w:h * w + n_c].view(h // 2, w // 2), flat[h * w + n_c:].view(h // 2, w // 2)), h, w
     if not isinstance(frame, (tuple, list)) or len(frame) != n or not all(torch.is_tensor(p) for p in frame):
-        raise ValueError("a %s frame is a packed uint8 tensor or %d plane tensors, got %s" % (
-            layout, n, type(frame).__name__ if not isinstance(frame, (tuple, list)) else "%d items" % len(frame)))
+        raise ValueError("a %s frame is a packed %s tensor or %d plane tensors, got %s" % (
+            layout, kind, n, type(frame).__name__ if not isinstance(frame, (tuple, list)) else "%d items" % len(frame)))
     planes = tuple(frame)
     y = planes[0]
-    if any(p.dtype != torch.uint8 for p in planes) or any(p.device != y.device for p in planes):
-        raise ValueError("the planes of a %s frame must be uint8 tensors on one device" % layout)
+    if any(p.dtype not in dtypes for p in planes) or any(p.device != y.device for p in planes):
+        raise ValueError("the planes of a %s frame must be %s tensors on one device" % (layout, kind))
     if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
         raise ValueError("the Y plane must be [H,W], got %s" % (tuple(y.shape),))
     h, w = int(y.shape[0]), int(y.shape[1])
-    want = ((h + 1) // 2, (w + 1) // 2) + ((2,) if layout == 'nv12' else ())
+    want = ((h + 1) // 2, (w + 1) // 2) + ((2,) if semi else ())
     for p in planes[1:]:
         if tuple(p.shape) != want:
             raise ValueError("a chroma plane of a %d x %d %s frame must be %s, got %s" % (h, w, layout, list(want), tuple(p.shape)))
@@ -158,28 +175,40 @@ def yuv_planes(frame, layout):
 
 
 def describe_yuv(planes, layout, h, w, matrix='bt601', yuv_range='limited', copy=True):
-    """(planes', dvsr_yuv_desc) of what yuv_planes returned.  A plane that the descriptor can express -- any offset, any row
-    pitch -- is passed by stride; any other is copied first (copy = False: ValueError, for a destination)."""
+    """(planes', dvsr_yuv_desc) of what yuv_planes returned (a dvsr_yuv16_desc for the 10- / 12-bit layouts).  A plane that the
+    descriptor can express -- any offset, any row pitch -- is passed by stride; any other is copied first (copy = False:
+    ValueError, for a destination)."""
     check_yuv_names(matrix, yuv_range)
-    desc = L.YuvDesc(_YUV_FORMAT[layout], h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
+    if layout in YUV16_LAYOUTS:
+        desc = L.Yuv16Desc(_YUV16[layout][0], _YUV16[layout][1], h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
+    else:
+        desc = L.YuvDesc(_YUV_FORMAT[layout], h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
     kept = []
     for i, p in enumerate(planes):
-        row = p.shape[1] * (p.shape[2] if p.dim() == 3 else 1)          # bytes of a row
+        es = p.element_size()                                           # 1, or 2 for 16-bit words
+        row = p.shape[1] * (p.shape[2] if p.dim() == 3 else 1)          # samples of a row
         st = p.stride()
         inner = st[1:] == ((2, 1) if p.dim() == 3 else (1,)) or row == 1
-        if not (inner and (st[0] >= row or p.shape[0] == 1)):
+        if not (inner and (st[0] >= row or p.shape[0] == 1) and p.data_ptr() % es == 0):
             if not copy:
                 raise ValueError("plane %d must have contiguous rows that do not overlap" % i)
-            p = p.contiguous()
+            p = p.clone(memory_format=torch.contiguous_format)
             st = p.stride()
         kept.append(p)
         desc.plane[i] = p.data_ptr()
-        desc.row_stride[i] = max(int(st[0]), row)
+        desc.row_stride[i] = max(int(st[0]), row) * es                  # bytes
     return tuple(kept), desc
 
 
+def _yuv_entry(layout, name):
+    """The C entry point `name` ('frame_ingest' / 'frame_emit' / 'edvr_stream_extract_frame') of a 4:2:0 layout."""
+    name = "dvsr_%s_%s" % (name, 'yuv16' if layout in YUV16_LAYOUTS else 'yuv')
+    return getattr(L.lib(), name), name
+
+
 def to_device(frame, device):
-    """A frame (tensor or tuple of planes) on `device`; a CPU frame is copied as it is -- 8-bit frames travel as bytes."""
+    """A frame (tensor or tuple of planes) on `device`; a CPU frame is copied as it is -- 8-bit frames travel as bytes, 10- and
+    12-bit ones as 16-bit words."""
     if torch.is_tensor(frame):
         return frame if frame.is_cuda else frame.to(device, non_blocking=True)
     return tuple(to_device(p, device) for p in frame)
@@ -197,7 +226,8 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix=
     GPU tensor to fill (Wp a multiple of 4).  When Wp is not a multiple of 4 (multiple = 1, 2) the result is a
     [3,Hp,Wp] view of a buffer whose rows are.
     'nv12' / 'i420': frame is a packed uint8 [H*3/2, W] tensor or a tuple of planes (module docstring), converted with
-    `matrix` / `yuv_range` to un-rounded RGB in [0,1] -- one launch, like the other layouts."""
+    `matrix` / `yuv_range` to un-rounded RGB in [0,1] -- one launch, like the other layouts.  'p010' / 'p012' / 'i420p10' /
+    'i420p12': the same for uint16 / int16 words of 10 or 12 bits."""
     check_yuv_names(matrix, yuv_range)
     layout, h, w = resolve_layout(frame, layout)
     Hp, Wp = padded_size(h, w, multiple)
@@ -213,15 +243,16 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix=
     first = frame if torch.is_tensor(frame) else frame[0]
     dev = out.device if out is not None else (first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device()))
     frame = to_device(frame, dev)
-    if layout in YUV_LAYOUTS:
+    yuv = layout in YUV_LAYOUTS + YUV16_LAYOUTS
+    if yuv:
         planes, desc = describe_yuv(yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range)
     else:
         frame, desc = describe(frame, layout)
     with torch.cuda.device(dev):
         buf = out if out is not None else torch.empty((3, Hp, Wb), dtype=torch.float32, device=dev)
-        if layout in YUV_LAYOUTS:
-            L.check(L.lib().dvsr_frame_ingest_yuv(ctypes.byref(desc), buf.data_ptr(), Hp, Wb, _PAD[pad_mode], L.stream()),
-                    "dvsr_frame_ingest_yuv")
+        if yuv:
+            fn, name = _yuv_entry(layout, 'frame_ingest')
+            L.check(fn(ctypes.byref(desc), buf.data_ptr(), Hp, Wb, _PAD[pad_mode], L.stream()), name)
         else:
             L.check(L.lib().dvsr_frame_ingest(frame.data_ptr(), ctypes.byref(desc), buf.data_ptr(), Hp, Wb, _PAD[pad_mode],
                                               L.stream()), "dvsr_frame_ingest")
@@ -236,9 +267,11 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     'nv12' / 'i420': the crop as YCbCr 4:2:0 bytes (`matrix`, `yuv_range`; chroma filtered inside the crop alone).  With h and
     w even and no `out` the result is a packed uint8 [h*3/2, w] tensor; otherwise `out` is a packed tensor of that shape or a
     tuple of planes (module docstring; needed for an odd h or w) and is returned; bytes outside the planes' rows are not
-    touched."""
-    if layout not in LAYOUTS + YUV_LAYOUTS:
-        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + YUV_LAYOUTS)))
+    touched.  'p010' / 'p012' / 'i420p10' / 'i420p12': the same as 10- / 12-bit words, a packed torch.uint16 [h*3/2, w] tensor
+    (`out`: uint16 or int16); the bits of a word that carry no level are written as 0."""
+    yuv_all = YUV_LAYOUTS + YUV16_LAYOUTS
+    if layout not in LAYOUTS + yuv_all:
+        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + yuv_all)))
     check_yuv_names(matrix, yuv_range)
     if sr.dim() == 4 and sr.shape[0] == 1:
         sr = sr[0]
@@ -248,7 +281,7 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     h, w = int(h), int(w)
     if not (1 <= h <= Hs and 1 <= w <= Ws):
         raise ValueError("emit: crop %d x %d outside the frame %d x %d" % (h, w, Hs, Ws))
-    if layout in YUV_LAYOUTS:
+    if layout in yuv_all:
         if out is None and (h % 2 or w % 2):
             raise ValueError("emit: a packed %s frame needs an even size, got %d x %d: pass `out` as planes" % (layout, h, w))
         if out is not None:
@@ -264,14 +297,14 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     if not _planar_ok(sr):
         sr = torch.nn.functional.pad(sr, (0, -Ws % 4)).contiguous()
         Ws = int(sr.shape[2])
-    if layout in YUV_LAYOUTS:
+    if layout in yuv_all:
         with torch.cuda.device(sr.device):
             if out is None:
-                out = torch.empty((h * 3 // 2, w), dtype=torch.uint8, device=sr.device)
+                out = torch.empty((h * 3 // 2, w), dtype=torch.uint16 if layout in YUV16_LAYOUTS else torch.uint8, device=sr.device)
                 planes = yuv_planes(out, layout)[0]
             _, desc = describe_yuv(planes, layout, h, w, matrix, yuv_range, copy=False)
-            L.check(L.lib().dvsr_frame_emit_yuv(sr.data_ptr(), Hs, Ws, ctypes.byref(desc), float(min_max[0]), float(min_max[1]),
-                                                L.stream()), "dvsr_frame_emit_yuv")
+            fn, name = _yuv_entry(layout, 'frame_emit')
+            L.check(fn(sr.data_ptr(), Hs, Ws, ctypes.byref(desc), float(min_max[0]), float(min_max[1]), L.stream()), name)
         return out
     with torch.cuda.device(sr.device):
         if out is None:
@@ -291,7 +324,7 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
 
 def _luma_part(frame, layout):
     """The tensor of a frame that carries its luma: the Y plane of a 4:2:0 frame (a view), the frame itself otherwise."""
-    if layout in YUV_LAYOUTS:
+    if layout in YUV_LAYOUTS + YUV16_LAYOUTS:
         return yuv_planes(frame, layout)[0][0]
     return frame if layout != 'chw' or frame.dtype == torch.float32 else frame.float()
 
@@ -299,13 +332,14 @@ def _luma_part(frame, layout):
 def _describe_luma(x, layout):
     """(x', the fields of its dvsr_frame_desc) of what _luma_part returned; a view that the descriptor cannot express is
     copied first."""
-    if layout in YUV_LAYOUTS:
+    if layout in YUV_LAYOUTS + YUV16_LAYOUTS:
         h, w = x.shape
+        es = x.element_size()
         st = x.stride()
-        if not ((st[1] == 1 or w == 1) and (st[0] >= w or h == 1)):
-            x = x.contiguous()
+        if not ((st[1] == 1 or w == 1) and (st[0] >= w or h == 1) and x.data_ptr() % es == 0):
+            x = x.clone(memory_format=torch.contiguous_format)
             st = x.stride()
-        return x, (L.FRAME_U8_Y, h, w, max(int(st[0]), w), 0, 1)
+        return x, (_LUMA16[layout] if layout in YUV16_LAYOUTS else L.FRAME_U8_Y, h, w, max(int(st[0]), w) * es, 0, es)
     x, d = describe(x, layout)
     return x, (d.format, d.h, d.w, d.row_stride, d.plane_stride, d.pixel_stride)
 
@@ -321,7 +355,9 @@ def luma_sad(frames, layout=None):
 
     `frames` is what adapt.super_resolve_frames accepts: a [T,...] tensor or a list of frames of one kind and size, on the CPU
     or the GPU, in any `layout` (None: by dtype).  Y8, the luma of a pixel, is an 8-bit integer: the Y-plane byte of an
-    'nv12' / 'i420' frame as it is (`matrix` and `yuv_range` play no part), (77 R + 150 G + 29 B + 128) >> 8 of an 8-bit
+    'nv12' / 'i420' frame as it is (`matrix` and `yuv_range` play no part), the top 8 bits of the level of a 10- / 12-bit
+    Y-plane word (so that scores and thresholds mean what they mean for 8-bit video), (77 R + 150 G + 29 B + 128) >> 8 of an
+    8-bit
     RGB / BGR pixel, and the same formula on the 8-bit values emit() would write (clamp to [0,1], x 255, round half to
     even) of a float frame.  The sums are exact.
     A video tensor on the GPU is one launch over all pairs; a list takes one launch per pair.  CPU frames travel as bytes
@@ -349,7 +385,8 @@ def luma_sad(frames, layout=None):
                 if attempt:
                     raise RuntimeError("luma_sad: a contiguous video must be expressible by stride")
                 video = video.contiguous()                 # (a view the descriptor cannot express)
-            _luma_sad_launch(x0, x1, d0, video.stride(0), T - 1, sad)
+            # (the frame stride in the descriptor's units: floats for 'chw', bytes for everything else)
+            _luma_sad_launch(x0, x1, d0, video.stride(0) * (1 if lay == 'chw' else video.element_size()), T - 1, sad)
             return sad.cpu()
         stage, prev, kind = [None, None], None, None
         for t in range(T):

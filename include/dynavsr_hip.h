@@ -366,10 +366,18 @@ int dvsr_edvr_stream_extract_frame(const dvsr_edvr_stream* stream_plan, const fl
  *                                    round half to even) of the three channels
  *   The sums are exact unsigned 64-bit integers and do not depend on the launch geometry.  The function zeroes sad[0 .. pairs)
  *   on `stream` itself, then launches (one launch per 65535 pairs); sad must be 8-byte aligned device memory.
- *   DVSR_FRAME_U8_Y is accepted here alone: dvsr_frame_ingest / _emit keep rejecting it.
+ *     DVSR_FRAME_U16_Y_MSB / _10 / _12  a single plane of 16-bit little-endian words (the Y plane of a P010 / P012, a
+ *                                    yuv420p10le, a yuv420p12le frame; 2-byte aligned, pixel_stride 2, row_stride and
+ *                                    frame_stride in BYTES and even): the top 8 bits of the level, word >> 8,
+ *                                    (word & 1023) >> 2, (word & 4095) >> 4 -- scores mean what they mean for 8-bit video
+ *   DVSR_FRAME_U8_Y and DVSR_FRAME_U16_Y_* are accepted here alone: dvsr_frame_ingest / _emit keep rejecting them.
  * Bad arguments (null pointer, unknown format, h or w < 1, pairs < 1, a pixel stride the format does not have, a row or
- * plane stride shorter than a row / plane, a misaligned fp32 frame or result) return DVSR_ERR_INVALID before any launch. */
+ * plane stride shorter than a row / plane, a misaligned fp32 frame or result, an odd address or stride of a 16-bit plane)
+ * return DVSR_ERR_INVALID before any launch. */
 #define DVSR_FRAME_U8_Y 3
+#define DVSR_FRAME_U16_Y_MSB 4
+#define DVSR_FRAME_U16_Y_10 5
+#define DVSR_FRAME_U16_Y_12 6
 int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_frame_desc* desc, long long frame_stride, int pairs,
                         unsigned long long* sad, dvsr_stream_t stream);
 
@@ -412,6 +420,37 @@ int dvsr_frame_emit_yuv(const float* src, int Hs, int Ws, const dvsr_yuv_desc* d
 int dvsr_edvr_stream_extract_frame_yuv(const dvsr_edvr_stream* stream_plan, const float* const* params, const dvsr_yuv_desc* fd,
                                        int pad_mode, int slot, void* cache, size_t cache_bytes, void* workspace,
                                        size_t workspace_bytes, int packed, dvsr_stream_t stream);
+
+/* ---- 10- and 12-bit YCbCr 4:2:0 frames in and out of the video path --------------------------------
+ * What an HEVC Main10 / AV1 / VP9 profile 2 decoder delivers and a 10-bit encoder takes: 16-bit little-endian words holding
+ * depth = 10 or 12 bits, every plane at any 2-byte aligned address and any even row pitch (row_stride in BYTES), chroma planes
+ * Hc x Wc = ceil(h/2) x ceil(w/2):
+ *   DVSR_YUV16_SEMI_MSB    P010 / P012: word = level << (16 - depth); the low bits are ignored on the way in and written as 0
+ *   DVSR_YUV16_PLANAR_LSB  yuv420p10le / yuv420p12le: word = level; the high bits are ignored on the way in and written as 0
+ * The arithmetic is that of the 8-bit section above (matrix, siting, the two resampling filters, padding on the source index,
+ * RGB clamped to [0,1], round half to even) with the level scale of H.273 at that depth, s = 2^(depth-8):
+ *   DVSR_YUV_LIMITED: y0 = 16 s, ys = 219 s, cs = 224 s, chroma mid 128 s;  DVSR_YUV_FULL: y0 = 0, ys = cs = 2^depth - 1,
+ *   chroma mid 2^(depth-1);  an emitted level is clamped to [0, 2^depth - 1].
+ * dvsr_frame_ingest_yuv16 / dvsr_frame_emit_yuv16 / dvsr_edvr_stream_extract_frame_yuv16 are dvsr_frame_ingest_yuv /
+ * dvsr_frame_emit_yuv / dvsr_edvr_stream_extract_frame_yuv for such a frame: one launch each, nothing rounded to 8 bits in
+ * between, no temporary and no device copy on the way into the frame cache.
+ * Bad arguments (null descriptor / plane, unknown format / depth / matrix / range / pad mode, h or w < 1 or beyond the target, a
+ * row stride shorter than a row or odd, an odd plane address, a reflect pad not smaller than the dimension, a misaligned fp32
+ * side) return DVSR_ERR_INVALID before any launch.  depth 16, a BT.2020 matrix and transfer functions are not provided. */
+#define DVSR_YUV16_SEMI_MSB 0     /* plane[0] = Y [h][w], plane[1] = CbCr interleaved [Hc][Wc][2]; plane[2] ignored */
+#define DVSR_YUV16_PLANAR_LSB 1   /* plane[0] = Y, plane[1] = Cb [Hc][Wc], plane[2] = Cr [Hc][Wc] */
+typedef struct dvsr_yuv16_desc {
+  int format, depth;         /* DVSR_YUV16_*; depth 10 or 12 */
+  int h, w;                  /* the frame's own (luma) size */
+  int matrix, range;         /* DVSR_YUV_BT601 / _BT709, DVSR_YUV_LIMITED / _FULL */
+  void* plane[3];
+  long long row_stride[3];   /* bytes, even */
+} dvsr_yuv16_desc;
+int dvsr_frame_ingest_yuv16(const dvsr_yuv16_desc* sd, float* dst, int Hp, int Wp, int pad_mode, dvsr_stream_t stream);
+int dvsr_frame_emit_yuv16(const float* src, int Hs, int Ws, const dvsr_yuv16_desc* dd, float lo, float hi, dvsr_stream_t stream);
+int dvsr_edvr_stream_extract_frame_yuv16(const dvsr_edvr_stream* stream_plan, const float* const* params,
+                                         const dvsr_yuv16_desc* fd, int pad_mode, int slot, void* cache, size_t cache_bytes,
+                                         void* workspace, size_t workspace_bytes, int packed, dvsr_stream_t stream);
 
 /* ---- Down-scaling estimators MFDN / SFDN as one launch tape ------------------------------------
  * Replaces DirectKernelEstimatorVideo.forward (models/archs/LRimg_estimator.py:92-117, "MFDN":

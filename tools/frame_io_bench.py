@@ -19,8 +19,15 @@
    yardstick, not code under test: a YUV figure is expected not to be slower than its HWC counterpart by more than that
    counterpart's own max - min spread.
 
+4. the 10- / 12-bit pair (csrc/frame_yuv16.hip) next to the 8-bit 4:2:0 kernels of 3, by the method of 3: frame_ingest_yuv16
+   (P010, yuv420p10le; 180x320) and frame_emit_yuv16 (720x1280) against frame_ingest_yuv / frame_emit_yuv NV12.  A 16-bit
+   frame is twice the bytes on its side (ingest 3 B read + 12 B written per pixel, emit 12 B read + 3 B written, against
+   13.5), so the comparison is PER BYTE MOVED: a 16-bit kernel's us per MB is expected not to exceed the 8-bit yardstick's by
+   more than that yardstick's own max - min spread.  Then frames/s of a pinned P010 video -> P010 frames on the host against
+   the same video through the HWC uint8 path of 2, which moves the same 3 bytes per output pixel back to the host.
+
 usage (GPU box): python tools/frame_io_bench.py [--h 180 --w 320 --frames 100 --repeats 5 --calls 200 --yuv-repeats 10]
-                 > profiles/r10_yuv_io.txt   (round 8's profiles/r08_frame_io.txt: parts 1 and 2)"""
+                 > profiles/r12_yuv16_io.txt   (profiles/r10_yuv_io.txt: parts 1 to 3; profiles/r08_frame_io.txt: 1 and 2)"""
 import argparse
 import ctypes
 import os
@@ -170,8 +177,9 @@ def c_launch(fn, *a):
     return go
 
 
-def compare(title, entries, reps):
-    """entries: [(name, launch, algorithmic bytes)], the first one the yardstick; alternated `reps` times."""
+def compare(title, entries, reps, per_byte=False):
+    """entries: [(name, launch, algorithmic bytes)], the first one the yardstick; alternated `reps` times.  per_byte: the
+    verdict is on us per MB moved, not on us per launch."""
     timers = [(name, graph_us(launch, args.calls), nbytes) for name, launch, nbytes in entries]
     us = {name: [] for name, _, _ in timers}
     for _ in range(reps):
@@ -180,10 +188,16 @@ def compare(title, entries, reps):
     print(title)
     base = timers[0][0]
     mb, sb = statistics.median(us[base]), max(us[base]) - min(us[base])
+    nb = timers[0][2]
     for name, _, nbytes in timers:
         m, sp = statistics.median(us[name]), max(us[name]) - min(us[name])
-        verdict = "yardstick" if name == base else ("not slower than %s by more than its spread %.2f us: %s" % (
-            base, sb, "MET" if m <= mb + sb else "MISSED"))
+        if name == base:
+            verdict = "yardstick"
+        elif per_byte:
+            verdict = "%.3f us/MB against %.3f + spread %.3f of %s: %s" % (
+                1e6 * m / nbytes, 1e6 * mb / nb, 1e6 * sb / nb, base, "MET" if m / nbytes <= (mb + sb) / nb else "MISSED")
+        else:
+            verdict = "not slower than %s by more than its spread %.2f us: %s" % (base, sb, "MET" if m <= mb + sb else "MISSED")
         print("  %-22s median %7.2f us per launch  spread %5.2f  %6.2f MB algorithmic -> %6.3f TB/s effective  (%s)" % (
             name, m, sp, nbytes / 1e6, nbytes / m / 1e6, verdict))
 
@@ -247,3 +261,66 @@ print("  HWC RGB in, HWC RGB out (%.2f MB back)        median %7.1f frames/s  sp
     12 * H * 4 * W / 1e6, mh, sh, " ".join("%.1f" % v for v in fh)))
 print("  NV12 - HWC = %+.1f frames/s (%+.1f %%); HWC spread %.1f -> expectation %s" % (
     my - mh, 100 * (my - mh) / mh, sh, "MET (not below the HWC path by more than its spread)" if my >= mh - sh else "MISSED"))
+
+
+# ---- 4. the 10- / 12-bit pair next to the 8-bit 4:2:0 kernels
+h, w = 180, 320
+packed = torch.from_numpy(r.randint(0, 256, (h * 3 // 2, w)).astype(np.uint8)).cuda()
+packed16 = torch.from_numpy((r.randint(0, 1024, (h * 3 // 2, w)) << 6).astype(np.uint16)).cuda()
+planar16 = torch.from_numpy(r.randint(0, 1024, (h * 3 // 2, w)).astype(np.uint16)).cuda()
+dst = torch.empty((3, h, w), device='cuda')
+keep = []
+planes, d = frames.describe_yuv(frames.yuv_planes(packed, 'nv12')[0], 'nv12', h, w)
+keep.append((planes, d))
+entries = [("frame_ingest_yuv NV12", c_launch(lib.dvsr_frame_ingest_yuv, ctypes.byref(d), dst.data_ptr(), h, w,
+                                                L.FRAME_PAD_REFLECT), int(13.5 * h * w))]
+for lay, src in (('p010', packed16), ('i420p10', planar16)):
+    planes, d = frames.describe_yuv(frames.yuv_planes(src, lay)[0], lay, h, w)
+    keep.append((planes, d))
+    entries.append(("frame_ingest_yuv16 " + lay, c_launch(lib.dvsr_frame_ingest_yuv16, ctypes.byref(d), dst.data_ptr(), h, w,
+                                                            L.FRAME_PAD_REFLECT), 15 * h * w))
+compare("16-bit ingest %dx%d -> fp32 [3,%d,%d], %d launches per replay, %d repetitions alternated" % (
+    h, w, h, w, args.calls, args.yuv_repeats), entries, args.yuv_repeats, per_byte=True)
+h, w = 720, 1280
+sr = torch.rand((3, h, w), device='cuda')
+out = torch.empty((h * 3 // 2, w), dtype=torch.uint8, device='cuda')
+out16 = torch.empty((h * 3 // 2, w), dtype=torch.uint16, device='cuda')
+planes, d = frames.describe_yuv(frames.yuv_planes(out, 'nv12')[0], 'nv12', h, w, copy=False)
+keep.append((planes, d))
+entries = [("frame_emit_yuv NV12", c_launch(lib.dvsr_frame_emit_yuv, sr.data_ptr(), h, w, ctypes.byref(d), ctypes.c_float(0.0),
+                                              ctypes.c_float(1.0)), int(13.5 * h * w))]
+for lay in ('p010', 'i420p10'):
+    planes, d = frames.describe_yuv(frames.yuv_planes(out16, lay)[0], lay, h, w, copy=False)
+    keep.append((planes, d))
+    entries.append(("frame_emit_yuv16 " + lay, c_launch(lib.dvsr_frame_emit_yuv16, sr.data_ptr(), h, w, ctypes.byref(d),
+                                                          ctypes.c_float(0.0), ctypes.c_float(1.0)), 15 * h * w))
+compare("16-bit emit fp32 [3,%d,%d] -> %dx%d, %d launches per replay, %d repetitions alternated" % (
+    h, w, h, w, args.calls, args.yuv_repeats), entries, args.yuv_repeats, per_byte=True)
+del sr, out, out16, keep
+
+p010_video = torch.from_numpy((r.randint(64, 941, (T, H * 3 // 2, W)) << 6).astype(np.uint16)).pin_memory()   # [T,H*3/2,W] pinned
+p010_out = torch.empty((T, 6 * H, 4 * W), dtype=torch.uint16).pin_memory()
+
+
+def p010_path():
+    for i, y in enumerate(adapt.super_resolve_frames(OPT, net, p010_video, in_flight=args.in_flight, layout='p010')):
+        p010_out[i].copy_(y, non_blocking=True)
+    torch.cuda.synchronize()
+
+
+p010_path()
+new_path()
+fp, fh = [], []
+for _ in range(args.yuv_repeats):
+    fp.append(timed(p010_path))
+    fh.append(timed(new_path))
+mp, mh = statistics.median(fp), statistics.median(fh)
+sh = max(fh) - min(fh)
+print("video %d frames %dx%d pinned host -> %dx%d host, in_flight %d, %d repetitions alternated" % (T, H, W, 4 * H, 4 * W,
+                                                                                                   args.in_flight, args.yuv_repeats))
+print("  P010 in, P010 out (%.2f MB back per frame)   median %7.1f frames/s  spread %5.1f  (%s)" % (
+    12 * H * 4 * W / 1e6, mp, max(fp) - min(fp), " ".join("%.1f" % v for v in fp)))
+print("  HWC RGB in, HWC RGB out (%.2f MB back)        median %7.1f frames/s  spread %5.1f  (%s)" % (
+    12 * H * 4 * W / 1e6, mh, sh, " ".join("%.1f" % v for v in fh)))
+print("  P010 - HWC = %+.1f frames/s (%+.1f %%); HWC spread %.1f -> expectation %s" % (
+    mp - mh, 100 * (mp - mh) / mh, sh, "MET (not below the HWC path by more than its spread)" if mp >= mh - sh else "MISSED"))
