@@ -98,6 +98,11 @@ class Yuv16Desc(Structure):
 YUV16_SEMI_MSB, YUV16_PLANAR_LSB = 0, 1
 
 
+class ResizeAxis(Structure):
+    """dvsr_resize_axis: the table of one axis of dvsr_frame_resize, in device memory (include/dynavsr_hip.h)."""
+    _fields_ = [("first", c_void_p), ("weights", c_void_p), ("taps", c_int)]
+
+
 class EstimatorConfig(Structure):
     _fields_ = [(k, c_int) for k in ("kind", "nf", "in_nc", "scale", "nframes")]
 
@@ -219,6 +224,9 @@ def _declare(lib):
         "dvsr_frame_emit_yuv16": (I, [P, I, I, POINTER(Yuv16Desc), F, F, P]),
         "dvsr_edvr_stream_extract_frame_yuv16": (I, [P, POINTER(c_void_p), POINTER(Yuv16Desc), I, I, P, c_size_t, P, c_size_t, I,
                                                      P]),
+        "dvsr_frame_resize_taps": (I, [I, I]),
+        "dvsr_frame_resize_table": (I, [I, I, I, P, P]),
+        "dvsr_frame_resize": (I, [P, I, I, I, I, P, I, I, I, I, POINTER(ResizeAxis), POINTER(ResizeAxis), P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

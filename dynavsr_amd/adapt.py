@@ -870,7 +870,7 @@ def _video_format(frames, layout):
 
 
 def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, layout=None, out=None, pad_mode='reflect',
-                         multiple=None, matrix='bt601', yuv_range='limited', cuts=None, cut_threshold=10.0):
+                         multiple=None, matrix='bt601', yuv_range='limited', cuts=None, cut_threshold=10.0, out_size=None):
     """Super-resolves a VIDEO: `frames` is a [T,3,H,W] tensor or a list of [3,H,W] frames (CPU or GPU); yields the SR frame
     [1,3,sH,sW] of every frame, in order -- what `net(frames[index_generation(i, T, nframes, padding)][None])` gives, the
     sliding-window test of the reference's video datasets (video_test_dataset_int.py:219, `padding: new_info` in the
@@ -912,6 +912,11 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     A video of several scenes: `cuts` (None: one scene, the calls of before) lists the first frame of every new scene, or is
     'auto' for frames.detect_cuts(frames, layout, threshold=cut_threshold); no window then crosses a cut (video_windows), so
     every scene comes out as if it had been passed alone, and the frame cache has stream_slots' capacity.
+    A target output size: with `out_size` = (oh, ow) every yielded frame is oh x ow instead of sH x sW, for every network and
+    every `out` ('float': [1,3,oh,ow]; a packed 4:2:0 output needs oh and ow even, sH and sW no longer).  The SR frame's
+    sH x sW crop -- never the padding around it -- is resampled on the device (frames.resize: separable antialiased bicubic,
+    torch's interpolate(mode='bicubic', antialias=True); per axis sH / oh <= 4 and oh / sH <= 2) by one more launch on the
+    window's stream, in front of the conversion.  None, or (sH, sW) itself, takes exactly the calls described above.
     Arguments are checked before the first GPU call (ValueError)."""
     from . import frames as fio
     from .models.archs.EDVR_arch import EDVR
@@ -928,6 +933,10 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     if is_edvr:
         plain = plain and torch.is_tensor(frames[0]) and frames[0].dim() == 3 and frames[0].is_floating_point() and \
             frames[0].shape[-2] % 4 == 0 and frames[0].shape[-1] % 4 == 0
+    sr_scale = int(net.scale) if is_edvr else int(opt.get('scale') or 1)
+    if out_size is not None:
+        out_size = fio.check_size(out_size, "super_resolve_frames: out_size")
+    plain = plain and out_size is None
     if plain:
         h, w, lay, out_fmt, Hp, Wp = int(frames[0].shape[-2]), int(frames[0].shape[-1]), 'chw', 'float', None, None
     else:
@@ -938,11 +947,15 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                 out, ', '.join(yuv_all)))
         fio.check_yuv_names(matrix, yuv_range)
         out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
+        if out_size == (sr_scale * h, sr_scale * w):
+            out_size = None                           # the SR frame's own size: today's calls
+        if out_size is not None:
+            fio.check_resize(sr_scale * h, sr_scale * w, out_size, "super_resolve_frames: out_size")
         if out_fmt in yuv_all:
-            scale = int(net.scale) if is_edvr else int(opt.get('scale') or 1)
-            if scale * h % 2 or scale * w % 2:
-                raise ValueError("super_resolve_frames: a packed %s output of %d x %d needs an even size" % (
-                    out_fmt, scale * h, scale * w))
+            oh, ow = out_size if out_size is not None else (sr_scale * h, sr_scale * w)
+            if oh % 2 or ow % 2:
+                raise ValueError("super_resolve_frames: a packed %s output of %d x %d needs an even size%s" % (
+                    out_fmt, oh, ow, " (out_size)" if out_size is not None else ""))
         if h < 4 or w < 4:
             raise ValueError("super_resolve_frames: frames of %d x %d (at least 4 x 4)" % (h, w))
         mult = int(multiple) if multiple is not None else (4 if is_edvr else 1)
@@ -952,7 +965,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
             mult *= 4 // math.gcd(mult, 4)            # the EDVR plans take multiples of 4 only
         Hp, Wp = fio.padded_size(h, w, mult)
         fio.check_pad(h, w, Hp, -(-Wp // 4) * 4, pad_mode)
-        if lay == 'chw' and out_fmt == 'float' and (Hp, Wp) == (h, w):
+        if lay == 'chw' and out_fmt == 'float' and (Hp, Wp) == (h, w) and out_size is None:
             Hp = Wp = None                            # nothing to convert, pad or crop: today's calls
     n = int(net.nframes) if is_edvr or not (opt.get('network_G') or {}).get('nframes') else int(opt['network_G']['nframes'])
     if isinstance(cuts, str):
@@ -985,7 +998,14 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                 yield torch.stack([ingested(j) for j in win])[None]
         for sr in super_resolve_video(opt, net, padded_clips(), in_flight):
             s = sr.shape[-2] // Hp
-            if out_fmt == 'float':
+            if out_size is not None:
+                if s != sr_scale:
+                    raise RuntimeError("super_resolve_frames: the network scales by %d, opt['scale'] says %d" % (s, sr_scale))
+                if out_fmt == 'float':
+                    yield fio.resize(sr, s * h, s * w, out_size)[None]
+                else:
+                    yield fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range, size=out_size)
+            elif out_fmt == 'float':
                 yield sr if (Hp, Wp) == (h, w) else fio.emit(sr, s * h, s * w, 'chw')[None]
             else:
                 yield fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
@@ -1009,6 +1029,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         cache.record_stream(s)
     extracted, readers, pending = {}, {}, []   # slot -> event of its extraction; slot -> events of the windows reading it
     staging = {}                               # stream index -> the fuse tape's output when a crop / conversion follows it
+    resized = {}                               # stream index -> the resampled frame when a conversion follows it
     was_training = net.training
     net.eval()
     try:
@@ -1041,7 +1062,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                             t.record_stream(s)
                 for slot in set(wslots):
                     s.wait_event(extracted[slot])
-                if direct or (out_fmt == 'float' and (ph, pw) == (h, w)):
+                if direct or (out_fmt == 'float' and (ph, pw) == (h, w) and out_size is None):
                     sr = torch.empty((1, 3, net.scale * ph, net.scale * pw), dtype=torch.float32, device=dev)
                     plan.fuse(leaves, wslots, cache, sr)
                 else:
@@ -1049,7 +1070,14 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                     if k not in staging:
                         staging[k] = torch.empty((1, 3, net.scale * ph, net.scale * pw), dtype=torch.float32, device=dev)
                     plan.fuse(leaves, wslots, cache, staging[k])
-                    if out_fmt == 'float':
+                    if out_size is not None and out_fmt == 'float':
+                        sr = fio.resize(staging[k], net.scale * h, net.scale * w, out_size)[None]
+                    elif out_size is not None:
+                        if k not in resized:
+                            resized[k] = fio.resize_buffer(out_size, dev)
+                        fio.resize(staging[k], net.scale * h, net.scale * w, out_size, out=resized[k])
+                        sr = fio.emit(resized[k], out_size[0], out_size[1], out_fmt, matrix=matrix, yuv_range=yuv_range)
+                    elif out_fmt == 'float':
                         sr = fio.emit(staging[k], net.scale * h, net.scale * w, 'chw')[None]
                     else:
                         sr = fio.emit(staging[k], net.scale * h, net.scale * w, out_fmt, matrix=matrix, yuv_range=yuv_range)

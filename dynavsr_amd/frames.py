@@ -38,8 +38,18 @@ Scene cuts (csrc/frame_cut.hip: dvsr_frame_luma_sad), for any of th
     luma_sad(frames, layout)             -> int64 [T-1]: sum over the frame of |Y8_t - Y8_(t-1)|, exact, in one pass on the device
     scene_scores(sad, h, w)              -> float64 [T]: min(mafd_t, |mafd_t - mafd_(t-1)|), mafd = 100 SAD / (255 h w); host code
     detect_cuts(frames, layout, threshold) -> the frames whose score reaches the threshold: the `cuts` of super_resolve_frames
+
+A target output size (csrc/frame_resize.hip: dvsr_frame_resize):
+
+    resize_table(n_in, n_out)            -> (first int32 [n_out], weights fp32 [n_out, taps]) on the CPU: one axis of the resampler
+    resize(sr, h, w, (oh, ow))           -> the top-left h x w crop of sr resampled to fp32 [3,oh,ow] on the GPU, one launch
+    emit(sr, h, w, layout, size=(oh, ow)) = emit(resize(sr, h, w, (oh, ow)), oh, ow, layout)
+
+The resampler is separable antialiased bicubic, torch.nn.functional.interpolate(.., mode='bicubic', antialias=True,
+align_corners=False); per axis n_in / n_out <= 4 and n_out / n_in <= 2.
 """
 import ctypes
+import numbers
 
 import torch
 
@@ -259,7 +269,104 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix=
     return buf if Wb == Wp else buf[:, :, :Wp]
 
 
-def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='limited'):
+def check_size(size, what="size"):
+    """(oh, ow) of a target size: a pair of positive ints, ValueError otherwise.  No GPU call."""
+    if isinstance(size, (str, bytes)) or not isinstance(size, (tuple, list, torch.Size)) or len(size) != 2 or \
+            any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in size) or size[0] < 1 or size[1] < 1:
+        raise ValueError("%s=%r must be a pair of positive ints (oh, ow)" % (what, size))
+    return int(size[0]), int(size[1])
+
+
+def check_resize(h, w, size, what="size"):
+    """(oh, ow) of a target size that the resampler takes from h x w (per axis n_in / n_out <= 4 and n_out / n_in <= 2),
+    ValueError otherwise.  No GPU call."""
+    oh, ow = check_size(size, what)
+    for n_in, n_out in ((int(h), oh), (int(w), ow)):
+        if n_in < 1 or n_in > 4 * n_out or n_out > 2 * n_in:
+            raise ValueError("%s=%r: %d -> %d is outside the accepted ratios (n_in / n_out <= 4, n_out / n_in <= 2) of %d x %d"
+                             % (what, tuple(size), n_in, n_out, h, w))
+    return oh, ow
+
+
+def resize_table(n_in, n_out):
+    """One axis of the resampler, n_in -> n_out samples: (first int32 [n_out], weights fp32 [n_out, taps]) CPU tensors from
+    dvsr_frame_resize_taps / dvsr_frame_resize_table -- output i is sum_t weights[i, t] * x[first[i] + t]; rows shorter than
+    taps are zero-padded.  No GPU call."""
+    n_in, n_out = int(n_in), int(n_out)
+    taps = L.lib().dvsr_frame_resize_taps(n_in, n_out)
+    if taps < 1:
+        raise ValueError("resize_table: " + L.lib().dvsr_last_error().decode("utf-8", "replace"))
+    first = torch.empty((n_out,), dtype=torch.int32)
+    weights = torch.empty((n_out, taps), dtype=torch.float32)
+    L.check(L.lib().dvsr_frame_resize_table(n_in, n_out, taps, first.data_ptr(), weights.data_ptr()), "dvsr_frame_resize_table")
+    return first, weights
+
+
+_resize_tables = {}      # (n_in, n_out, device) -> (first, weights) on the device + the dvsr_resize_axis that points at them
+
+
+def _resize_axis(n_in, n_out, device):
+    key = (int(n_in), int(n_out), str(device))
+    hit = _resize_tables.get(key)
+    if hit is None:
+        first, weights = resize_table(n_in, n_out)
+        first, weights = first.to(device), weights.to(device)       # (blocking copies: usable from any stream afterwards)
+        hit = _resize_tables[key] = (first, weights, L.ResizeAxis(first.data_ptr(), weights.data_ptr(), int(weights.shape[1])))
+    return hit[2]
+
+
+def resize_buffer(size, device):
+    """The fp32 [3, oh, Wb] buffer that resize() fills, Wb = ow rounded up to a multiple of 4 (its `out`)."""
+    oh, ow = check_size(size)
+    return torch.empty((3, oh, -(-ow // 4) * 4), dtype=torch.float32, device=device)
+
+
+def resize(sr, h, w, size, out=None):
+    """The top-left h x w crop of sr (fp32 [3,Hs,Ws] or [1,3,Hs,Ws] on the GPU) resampled to size = (oh, ow): fp32
+    [3,oh,ow], a view of a contiguous [3,oh,Wb] buffer whose rows are a multiple of 4 floats (columns ow .. Wb-1 are 0) --
+    what emit() takes without a copy.  Separable antialiased bicubic, torch.nn.functional.interpolate(crop, size,
+    mode='bicubic', antialias=True, align_corners=False) at fp32 rounding; what lies outside the crop is never read.
+    out: that buffer (resize_buffer), to fill.  One launch (dvsr_frame_resize); the tables of an axis are built once per
+    (n_in, n_out, device) and kept on the device."""
+    buf, ow = _resize(sr, h, w, size, out)
+    return buf if buf.shape[2] == ow else buf[:, :, :ow]
+
+
+def _resize(sr, h, w, size, out=None):
+    """resize(): (the whole [3,oh,Wb] buffer, ow)."""
+    if sr.dim() == 4 and sr.shape[0] == 1:
+        sr = sr[0]
+    if sr.dim() != 3 or sr.shape[0] != 3:
+        raise ValueError("resize expects [3,Hs,Ws] or [1,3,Hs,Ws], got %s" % (tuple(sr.shape),))
+    Hs, Ws = int(sr.shape[1]), int(sr.shape[2])
+    h, w = int(h), int(w)
+    if not (1 <= h <= Hs and 1 <= w <= Ws):
+        raise ValueError("resize: crop %d x %d outside the frame %d x %d" % (h, w, Hs, Ws))
+    oh, ow = check_resize(h, w, size)
+    Wb = -(-ow // 4) * 4
+    if out is not None:
+        if not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (3, oh, Wb)):
+            raise ValueError("resize: out must be an fp32 [3,%d,%d] tensor" % (oh, Wb))
+        if out.device != sr.device:
+            raise ValueError("resize: out must be on %s" % sr.device)
+        if not _planar_ok(out):
+            raise ValueError("resize: out must be contiguous and 16-byte aligned")
+    if not sr.is_cuda:
+        raise RuntimeError("resize runs on the GPU (libdynavsr_hip); there is no CPU path")
+    if sr.dtype != torch.float32:
+        sr = sr.float()
+    if not _planar_ok(sr):
+        sr = torch.nn.functional.pad(sr, (0, -Ws % 4)).contiguous()
+        Ws = int(sr.shape[2])
+    with torch.cuda.device(sr.device):
+        rows, cols = _resize_axis(h, oh, sr.device), _resize_axis(w, ow, sr.device)
+        buf = out if out is not None else resize_buffer((oh, ow), sr.device)
+        L.check(L.lib().dvsr_frame_resize(sr.data_ptr(), Hs, Ws, h, w, buf.data_ptr(), oh, Wb, oh, ow, ctypes.byref(rows),
+                                          ctypes.byref(cols), L.stream()), "dvsr_frame_resize")
+    return buf, ow
+
+
+def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='limited', size=None):
     """The top-left h x w crop of sr (fp32 [3,Hs,Ws] or [1,3,Hs,Ws] on the GPU) as uint8 [h,w,3] ('hwc_rgb' / 'hwc_bgr':
     clamp to min_max, rescale, x 255, round half to even -- util.tensor2img's image, and dvsr_frame_metrics') or as fp32
     [3,h,w] ('chw').  out: the tensor to write (any offset and row pitch; what lies outside the crop is not touched).
@@ -268,11 +375,19 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     w even and no `out` the result is a packed uint8 [h*3/2, w] tensor; otherwise `out` is a packed tensor of that shape or a
     tuple of planes (module docstring; needed for an odd h or w) and is returned; bytes outside the planes' rows are not
     touched.  'p010' / 'p012' / 'i420p10' / 'i420p12': the same as 10- / 12-bit words, a packed torch.uint16 [h*3/2, w] tensor
-    (`out`: uint16 or int16); the bits of a word that carry no level are written as 0."""
+    (`out`: uint16 or int16); the bits of a word that carry no level are written as 0.
+    size = (oh, ow): the crop is first resampled to oh x ow (resize(): one more launch into a buffer of its own), and
+    everything above holds for the oh x ow image -- emit(resize(sr, h, w, size), oh, ow, layout, ...), bit for bit."""
     yuv_all = YUV_LAYOUTS + YUV16_LAYOUTS
     if layout not in LAYOUTS + yuv_all:
         raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + yuv_all)))
     check_yuv_names(matrix, yuv_range)
+    if size is not None:
+        oh, ow = check_resize(h, w, size)
+        if layout in yuv_all and out is None and (oh % 2 or ow % 2):
+            raise ValueError("emit: a packed %s frame needs an even size, got %d x %d: pass `out` as planes" % (layout, oh, ow))
+        # (the whole buffer goes on: its rows are 16-byte aligned, those of resize()'s view are not when ow % 4)
+        return emit(_resize(sr, h, w, (oh, ow))[0], oh, ow, layout, min_max, out, matrix, yuv_range)
     if sr.dim() == 4 and sr.shape[0] == 1:
         sr = sr[0]
     if sr.dim() != 3 or sr.shape[0] != 3:

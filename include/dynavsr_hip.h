@@ -452,6 +452,37 @@ int dvsr_edvr_stream_extract_frame_yuv16(const dvsr_edvr_stream* stream_plan, co
                                          const dvsr_yuv16_desc* fd, int pad_mode, int slot, void* cache, size_t cache_bytes,
                                          void* workspace, size_t workspace_bytes, int packed, dvsr_stream_t stream);
 
+/* ---- SR frames at a target output size: the resampler in front of the emit functions -----------------
+ * Separable antialiased bicubic: Keys' kernel with a = -0.5, half-pixel centres, the support widened by the down-scale
+ * ratio -- torch.nn.functional.interpolate(x, size=(oh, ow), mode='bicubic', antialias=True, align_corners=False).
+ * Per axis, n_in -> n_out:  scale = n_in / n_out;  support = 2 scale and inv = 1 / scale if scale >= 1, else 2 and 1.  Output
+ * i: c = scale (i + 0.5), first = max(0, int(c - support + 0.5)), end = min(n_in, int(c + support + 0.5)), and
+ * w_j = k((j - c + 0.5) inv) for j in [first, end), divided by their sum;  k(x) = ((a+2)|x| - (a+3)) x^2 + 1 for |x| < 1,
+ * a (((|x| - 5)|x| + 8)|x| - 4) for 1 <= |x| < 2, 0 otherwise.  The window is cut at the edge of the image and renormalised.
+ * Accepted per axis: n_in / n_out <= 4 and n_out / n_in <= 2 (at most 18 taps).
+ * dvsr_frame_resize_taps: the longest window end - first of the axis.  Host code, no device call.
+ * dvsr_frame_resize_table: first[n_out] and weights[n_out][taps] (HOST memory), taps >= dvsr_frame_resize_taps and <= 18;
+ *   weights are computed in double, rounded to fp32 and zero-padded to taps.  Host code, no device call.
+ * dvsr_frame_resize: src fp32 planar [3][Hs][Ws] (16-byte aligned, Ws % 4 == 0: the fuse tape's output), of which ONLY the
+ *   top-left h x w is the image -- the padding around it is never read -- -> dst fp32 planar [3][Ho][Wo] (16-byte aligned,
+ *   Wo % 4 == 0, Ho >= oh, Wo >= ow): rows 0 .. oh-1 hold the oh x ow image in columns 0 .. ow-1 and 0 in columns ow .. Wo-1,
+ *   rows oh .. Ho-1 are not written.  dst is what dvsr_frame_emit / _emit_yuv / _emit_yuv16 take as src.  Columns are
+ *   resampled first, then rows, in fp32.  rows / cols: the tables of h -> oh / w -> ow as dvsr_frame_resize_table fills
+ *   them, copied to DEVICE memory.  The kernel clamps every index into the image: a table with other contents gives a wrong
+ *   picture, never an access outside src's h x w or dst's oh x Wo.  One launch, no atomics, deterministic.
+ * Bad arguments (null pointer, a size < 1, h x w or oh x ow beyond its tensor, Ws or Wo no multiple of 4, a ratio outside
+ * the bounds, taps outside [1, 18] or shorter than the axis needs, a misaligned tensor or table) return DVSR_ERR_INVALID
+ * before any launch. */
+typedef struct dvsr_resize_axis {
+  const int* first;       /* [n_out]        device memory */
+  const float* weights;   /* [n_out][taps]  device memory */
+  int taps;
+} dvsr_resize_axis;
+int dvsr_frame_resize_taps(int n_in, int n_out);
+int dvsr_frame_resize_table(int n_in, int n_out, int taps, int* first, float* weights);
+int dvsr_frame_resize(const float* src, int Hs, int Ws, int h, int w, float* dst, int Ho, int Wo, int oh, int ow,
+                      const dvsr_resize_axis* rows, const dvsr_resize_axis* cols, dvsr_stream_t stream);
+
 /* ---- Down-scaling estimators MFDN / SFDN as one launch tape ------------------------------------
  * Replaces DirectKernelEstimatorVideo.forward (models/archs/LRimg_estimator.py:92-117, "MFDN":
  * Conv3d(k3)+ReplicationPad3d, ReflectionPad2d + 3x3 / 4x4-stride-2 Conv2d, Conv3d, 1x1, per-frame
