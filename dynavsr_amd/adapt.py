@@ -906,7 +906,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     and 'nv12' / 'i420' force such an output for RGB and float inputs too (sH and sW must be even).
     High-bit-depth video (HEVC Main10, AV1, VP9 profile 2): `layout` 'p010' / 'p012' (semi-planar, the level in the top bits of a
     16-bit word) or 'i420p10' / 'i420p12' (yuv420p10le / yuv420p12le), as uint16 or int16 tensors shaped like their 8-bit
-    counterparts (csrc/frame_yuv16.hip); `out` None then yields packed torch.uint16 frames of the input's layout, quantised
+    counterparts (csrc/frame_yuv.hip too); `out` None then yields packed torch.uint16 frames of the input's layout, quantised
     from the fp32 SR frame to 1024 / 4096 levels, and the four names force such an output for any input -- an 8-bit source can
     leave with 10 bits.
     A video of several scenes: `cuts` (None: one scene, the calls of before) lists the first frame of every new scene, or is
@@ -941,17 +941,16 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         h, w, lay, out_fmt, Hp, Wp = int(frames[0].shape[-2]), int(frames[0].shape[-1]), 'chw', 'float', None, None
     else:
         lay, h, w = _video_format(frames, layout)
-        yuv_all = fio.YUV_LAYOUTS + fio.YUV16_LAYOUTS
-        if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') + yuv_all:
+        if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') and not fio.is_yuv(out):
             raise ValueError("super_resolve_frames: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (
-                out, ', '.join(yuv_all)))
+                out, ', '.join(fio.YUV_LAYOUTS + fio.YUV16_LAYOUTS)))
         fio.check_yuv_names(matrix, yuv_range)
         out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
         if out_size == (sr_scale * h, sr_scale * w):
             out_size = None                           # the SR frame's own size: today's calls
         if out_size is not None:
             fio.check_resize(sr_scale * h, sr_scale * w, out_size, "super_resolve_frames: out_size")
-        if out_fmt in yuv_all:
+        if fio.is_yuv(out_fmt):
             oh, ow = out_size if out_size is not None else (sr_scale * h, sr_scale * w)
             if oh % 2 or ow % 2:
                 raise ValueError("super_resolve_frames: a packed %s output of %d x %d needs an even size%s" % (

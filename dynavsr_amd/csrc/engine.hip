@@ -1581,63 +1581,58 @@ extern "C" int dvsr_edvr_stream_extract(const dvsr_edvr_stream* s, const float* 
   return DVSR_OK;
 }
 
-// A decoder's frame (frame_io.hip) goes straight into the slot's raw-frame section, padded to the plan's H x W, and the tape
-// reads it there: no temporary, no device copy behind the tape.
+// A decoder's frame goes straight into the slot's raw-frame section, padded to the plan's H x W, and the tape reads it there:
+// no temporary, no device copy behind the tape.  ingest(what, raw, H, W, st) checks the frame against that section and launches.
+template <class Ingest>
+static int stream_extract_frame(const char* what, const dvsr_edvr_stream* s, const float* const* params, int slot, void* cache,
+                                size_t cache_bytes, void* ws, size_t ws_bytes, int packed, dvsr_stream_t stream, Ingest ingest) {
+  int rc = stream_check(s, params, cache, cache_bytes, ws, ws_bytes, what);
+  if (rc != DVSR_OK) return rc;
+  DVSR_REQUIRE(slot >= 0 && slot < s->slots, DVSR_ERR_INVALID, "%s: slot %d outside [0, %d)", what, slot, s->slots);
+  const dvsr_edvr_plan& p = s->extract;
+  hipStream_t st = (hipStream_t)stream;
+  float* dst = (float*)cache + (size_t)slot * s->sl.floats;
+  float* raw = dst + s->sl.raw;
+  rc = ingest(what, raw, p.H, p.W, st);
+  if (rc != DVSR_OK) return rc;
+  return stream_extract_tape(s, params, raw, dst, ws, packed, st);
+}
+
+// the ingest step of a YCbCr 4:2:0 frame of either descriptor (frame_yuv.hip)
+template <class Desc>
+static auto yuv_ingest_step(const Desc* fd, int pad_mode) {
+  return [=](const char* what, float* raw, int H, int W, hipStream_t st) {
+    Yuv420 f;
+    int rc = yuv420_from(what, fd, &f);
+    if (rc == DVSR_OK) rc = frame_ingest_yuv_check(what, f, raw, H, W, pad_mode);
+    return rc != DVSR_OK ? rc : frame_ingest_yuv_launch(f, raw, H, W, pad_mode, st);
+  };
+}
+
+// an 8-bit RGB / BGR or fp32 frame (frame_io.hip)
 extern "C" int dvsr_edvr_stream_extract_frame(const dvsr_edvr_stream* s, const float* const* params, const void* frame,
                                               const dvsr_frame_desc* fd, int pad_mode, int slot, void* cache,
                                               size_t cache_bytes, void* ws, size_t ws_bytes, int packed, dvsr_stream_t stream) {
-  int rc = stream_check(s, params, cache, cache_bytes, ws, ws_bytes, "edvr_stream_extract_frame");
-  if (rc != DVSR_OK) return rc;
-  DVSR_REQUIRE(slot >= 0 && slot < s->slots, DVSR_ERR_INVALID, "edvr_stream_extract_frame: slot %d outside [0, %d)", slot,
-               s->slots);
-  const dvsr_edvr_plan& p = s->extract;
-  hipStream_t st = (hipStream_t)stream;
-  float* dst = (float*)cache + (size_t)slot * s->sl.floats;
-  float* raw = dst + s->sl.raw;
-  rc = frame_ingest_check("edvr_stream_extract_frame", frame, fd, raw, p.H, p.W, pad_mode);
-  if (rc != DVSR_OK) return rc;
-  rc = frame_ingest_launch(frame, *fd, raw, p.H, p.W, pad_mode, st);
-  if (rc != DVSR_OK) return rc;
-  return stream_extract_tape(s, params, raw, dst, ws, packed, st);
+  return stream_extract_frame("edvr_stream_extract_frame", s, params, slot, cache, cache_bytes, ws, ws_bytes, packed, stream,
+                              [=](const char* what, float* raw, int H, int W, hipStream_t st) {
+                                int rc = frame_ingest_check(what, frame, fd, raw, H, W, pad_mode);
+                                return rc != DVSR_OK ? rc : frame_ingest_launch(frame, *fd, raw, H, W, pad_mode, st);
+                              });
 }
 
-// ... and a decoder's YCbCr 4:2:0 frame (frame_yuv.hip) the same way
 extern "C" int dvsr_edvr_stream_extract_frame_yuv(const dvsr_edvr_stream* s, const float* const* params, const dvsr_yuv_desc* fd,
                                                   int pad_mode, int slot, void* cache, size_t cache_bytes, void* ws,
                                                   size_t ws_bytes, int packed, dvsr_stream_t stream) {
-  int rc = stream_check(s, params, cache, cache_bytes, ws, ws_bytes, "edvr_stream_extract_frame_yuv");
-  if (rc != DVSR_OK) return rc;
-  DVSR_REQUIRE(slot >= 0 && slot < s->slots, DVSR_ERR_INVALID, "edvr_stream_extract_frame_yuv: slot %d outside [0, %d)", slot,
-               s->slots);
-  const dvsr_edvr_plan& p = s->extract;
-  hipStream_t st = (hipStream_t)stream;
-  float* dst = (float*)cache + (size_t)slot * s->sl.floats;
-  float* raw = dst + s->sl.raw;
-  rc = frame_ingest_yuv_check("edvr_stream_extract_frame_yuv", fd, raw, p.H, p.W, pad_mode);
-  if (rc != DVSR_OK) return rc;
-  rc = frame_ingest_yuv_launch(*fd, raw, p.H, p.W, pad_mode, st);
-  if (rc != DVSR_OK) return rc;
-  return stream_extract_tape(s, params, raw, dst, ws, packed, st);
+  return stream_extract_frame("edvr_stream_extract_frame_yuv", s, params, slot, cache, cache_bytes, ws, ws_bytes, packed, stream,
+                              yuv_ingest_step(fd, pad_mode));
 }
 
-// ... and a 10- / 12-bit one (frame_yuv16.hip)
 extern "C" int dvsr_edvr_stream_extract_frame_yuv16(const dvsr_edvr_stream* s, const float* const* params,
                                                     const dvsr_yuv16_desc* fd, int pad_mode, int slot, void* cache,
                                                     size_t cache_bytes, void* ws, size_t ws_bytes, int packed,
                                                     dvsr_stream_t stream) {
-  int rc = stream_check(s, params, cache, cache_bytes, ws, ws_bytes, "edvr_stream_extract_frame_yuv16");
-  if (rc != DVSR_OK) return rc;
-  DVSR_REQUIRE(slot >= 0 && slot < s->slots, DVSR_ERR_INVALID, "edvr_stream_extract_frame_yuv16: slot %d outside [0, %d)", slot,
-               s->slots);
-  const dvsr_edvr_plan& p = s->extract;
-  hipStream_t st = (hipStream_t)stream;
-  float* dst = (float*)cache + (size_t)slot * s->sl.floats;
-  float* raw = dst + s->sl.raw;
-  rc = frame_ingest_yuv16_check("edvr_stream_extract_frame_yuv16", fd, raw, p.H, p.W, pad_mode);
-  if (rc != DVSR_OK) return rc;
-  rc = frame_ingest_yuv16_launch(*fd, raw, p.H, p.W, pad_mode, st);
-  if (rc != DVSR_OK) return rc;
-  return stream_extract_tape(s, params, raw, dst, ws, packed, st);
+  return stream_extract_frame("edvr_stream_extract_frame_yuv16", s, params, slot, cache, cache_bytes, ws, ws_bytes, packed, stream,
+                              yuv_ingest_step(fd, pad_mode));
 }
 
 extern "C" int dvsr_edvr_stream_fuse(const dvsr_edvr_stream* s, const float* const* params, const int* slots, const void* cache,

@@ -19,8 +19,7 @@
 // loop (stream_gather.hip: gfx9 counts stores in vmcnt too, in order).
 #include <cstdint>
 
-#include "common.h"
-#include "kernels.h"
+#include "frame_common.h"
 #include "quant.h"
 
 namespace dvsr {
@@ -44,11 +43,6 @@ struct EmitArgs {
   int swap;
   float lo, hi;
 };
-
-// index i of a padded axis -> index of the frame's own axis of length n (i < 2n - 1 under REFLECT: checked by the host)
-__device__ __forceinline__ int pad_index(int i, int n, int mode) {
-  return i < n ? i : (mode == DVSR_FRAME_PAD_REFLECT ? 2 * (n - 1) - i : n - 1);
-}
 
 __device__ __forceinline__ void store_planes(float* dst, long long plane, const f32x4 o[3], int swap) {
   *reinterpret_cast<f32x4*>(dst) = swap ? o[2] : o[0];
@@ -235,26 +229,13 @@ static int frame_desc_check(const char* what, const void* ptr, const dvsr_frame_
   return DVSR_OK;
 }
 
-// the planar fp32 side: [3][H][W], 16-byte accesses
-static int planar_check(const char* what, const float* ptr, int H, int W) {
-  DVSR_REQUIRE(ptr, DVSR_ERR_INVALID, "%s: null planar tensor", what);
-  DVSR_REQUIRE(H >= 1 && W >= 4 && W % 4 == 0 && H <= FIO_Y * 65535, DVSR_ERR_INVALID,
-               "%s: planar tensor H=%d W=%d (W must be a positive multiple of 4)", what, H, W);
-  DVSR_REQUIRE(reinterpret_cast<uintptr_t>(ptr) % 16 == 0, DVSR_ERR_INVALID, "%s: misaligned planar fp32 tensor (16 bytes)", what);
-  return DVSR_OK;
-}
-
 int frame_ingest_check(const char* what, const void* src, const dvsr_frame_desc* sd, const float* dst, int Hp, int Wp,
                        int pad_mode) {
-  int rc = planar_check(what, dst, Hp, Wp);
+  int rc = frame_planar_check(what, dst, Hp, Wp, FIO_Y);
   if (rc != DVSR_OK) return rc;
   rc = frame_desc_check(what, src, sd, Hp, Wp, false);
   if (rc != DVSR_OK) return rc;
-  DVSR_REQUIRE(pad_mode == DVSR_FRAME_PAD_REFLECT || pad_mode == DVSR_FRAME_PAD_REPLICATE, DVSR_ERR_INVALID,
-               "%s: unknown pad mode %d", what, pad_mode);
-  DVSR_REQUIRE(pad_mode != DVSR_FRAME_PAD_REFLECT || (Hp - sd->h < sd->h && Wp - sd->w < sd->w), DVSR_ERR_INVALID,
-               "%s: reflect pad %d x %d not smaller than the frame %d x %d", what, Hp - sd->h, Wp - sd->w, sd->h, sd->w);
-  return DVSR_OK;
+  return frame_pad_check(what, pad_mode, sd->h, sd->w, Hp, Wp);
 }
 
 // (arguments checked by frame_ingest_check)
@@ -280,7 +261,7 @@ extern "C" int dvsr_frame_ingest(const void* src, const dvsr_frame_desc* sd, flo
 
 extern "C" int dvsr_frame_emit(const float* src, int Hs, int Ws, void* dst, const dvsr_frame_desc* dd, float lo, float hi,
                                dvsr_stream_t stream) {
-  int rc = planar_check("frame_emit", src, Hs, Ws);
+  int rc = frame_planar_check("frame_emit", src, Hs, Ws, FIO_Y);
   if (rc != DVSR_OK) return rc;
   rc = frame_desc_check("frame_emit", dst, dd, Hs, Ws, true);
   if (rc != DVSR_OK) return rc;

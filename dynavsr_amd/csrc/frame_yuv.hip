@@ -1,58 +1,74 @@
-// YCbCr 4:2:0 frames in and out of the video path (dvsr_frame_ingest_yuv / dvsr_frame_emit_yuv, engine.hip:
-// dvsr_edvr_stream_extract_frame_yuv), beside the 8-bit RGB / BGR frames of frame_io.hip.
+// YCbCr 4:2:0 frames of 8, 10 and 12 bits in and out of the video path (dvsr_frame_ingest_yuv / dvsr_frame_emit_yuv and their
+// _yuv16 counterparts, engine.hip: dvsr_edvr_stream_extract_frame_yuv / _yuv16), beside the RGB / BGR frames of frame_io.hip.
 //
-// What a video decoder delivers and an encoder takes is 8-bit YCbCr 4:2:0, as NV12 (a Y plane [h][w] and one plane of
-// interleaved Cb, Cr pairs [Hc][Wc][2]) or planar I420 (Y, Cb [Hc][Wc], Cr [Hc][Wc]), Hc x Wc = ceil(h/2) x ceil(w/2), every
-// plane at any address and row pitch.  The network computes on fp32 planar RGB [3][Hp][Wp] in [0,1].
+// What a video decoder delivers and an encoder takes: a Y plane [h][w] and either one plane of interleaved Cb, Cr pairs
+// [Hc][Wc][2] (semi-planar) or a Cb and a Cr plane [Hc][Wc] (planar), Hc x Wc = ceil(h/2) x ceil(w/2), every plane at any
+// sample-aligned address and row pitch.  A sample holds a level of d bits:
+//   descriptor        format                         sample          level <-> sample
+//   dvsr_yuv_desc     NV12 (semi) | I420 (planar)    a byte, d = 8   level = byte
+//   dvsr_yuv16_desc   SEMI_MSB (P010 / P012)         a 16-bit word   word = level << (16 - d); the low bits: ignored in, 0 out
+//   dvsr_yuv16_desc   PLANAR_LSB (yuv420p10le/12le)  a 16-bit word   word = level, & (2^d - 1);   the high bits: ignored in, 0 out
+// 16-bit words are little-endian, d = 10 or 12 is an argument (a shift, a mask and the coefficients), not a template parameter.
+// The network computes on fp32 planar RGB [3][Hp][Wp] in [0,1].
 //
-// The arithmetic (DESIGN 3.2k says the same):
+// The arithmetic (DESIGN 3.2k and 3.2m say the same), s = 2^(d-8):
 //   matrix  BT601: Kr = 0.299, Kb = 0.114;  BT709: Kr = 0.2126, Kb = 0.0722;  Kg = 1 - Kr - Kb
-//   range   LIMITED: y0 = 16, ys = 219, cs = 224;  FULL: y0 = 0, ys = 255, cs = 255
-//   BT601 + LIMITED are the reference's ycbcr2rgb / rgb2ycbcr ("same as matlab", data/util.py:234-299).
+//   range   H.273 at depth d.  LIMITED: y0 = 16 s, ys = 219 s, cs = 224 s;  FULL: y0 = 0, ys = cs = 2^d - 1;  chroma mid cm = 128 s
+//   BT601 + LIMITED at d = 8 are the reference's ycbcr2rgb / rgb2ycbcr ("same as matlab", data/util.py:234-299).
 //   siting  MPEG-2 / H.264 "left": chroma sample (j, k) sits on luma column 2k, midway between luma rows 2j and 2j+1.
-//   ingest, per luma pixel (y, x) of the frame, C one of the two chroma planes, j = y / 2:
+//   ingest, per luma pixel (y, x) of the frame, C one of the two chroma planes (levels), j = y / 2:
 //     Ch(j, x) = C[j][x/2] (x even) | (C[j][k] + C[j][min(k+1, Wc-1)]) / 2, k = (x-1)/2 (x odd)
 //     C'       = 0.75 Ch(j, x) + 0.25 Ch(max(j-1, 0), x) (y even) | 0.75 Ch(j, x) + 0.25 Ch(min(j+1, Hc-1), x) (y odd)
-//                (multiples of 1/8 of a level: exact in fp32)
-//     yn = (Y - y0) / ys, cb = (Cb' - 128) / cs, cr = (Cr' - 128) / cs
+//                (multiples of 1/8 of a level below 2^12: exact in fp32)
+//     yn = (Y - y0) / ys, cb = (Cb' - cm) / cs, cr = (Cr' - cm) / cs
 //     R = yn + 2(1-Kr) cr,  G = yn - (2 Kb (1-Kb) / Kg) cb - (2 Kr (1-Kr) / Kg) cr,  B = yn + 2(1-Kb) cb, each clamped to
-//     [0,1]; nothing is rounded to 8 bits.  Output pixel (y, x) of the padded [3][Hp][Wp] tensor is the converted pixel at
+//     [0,1]; nothing is rounded to d bits.  Output pixel (y, x) of the padded [3][Hp][Wp] tensor is the converted pixel at
 //     (pad_index(y, h), pad_index(x, w)): ingest(yuv, pad) = F.pad(convert(yuv), .., mode).
 //   emit, of the top-left h x w crop of fp32 planar [3][Hs][Ws]:
 //     t = (clamp(v, lo, hi) - lo) / (hi - lo) per channel (quant.h's first line)
 //     y = Kr R + Kg G + Kb B, cb = (B - y) / (2(1-Kb)), cr = (R - y) / (2(1-Kr))
-//     luma byte = clamp(rint(y0 + ys y), 0, 255), round half to even
+//     luma level = clamp(rint(y0 + ys y), 0, 2^d - 1), round half to even
 //     chroma sample (j, k): taps [1,2,1]/4 on columns 2k-1, 2k, 2k+1, the mean of rows 2j and min(2j+1, h-1), indices clamped to
-//     the crop -- nothing outside it influences a byte; chroma byte = clamp(rint(128 + cs c), 0, 255)
+//     the crop -- nothing outside it influences a sample; chroma level = clamp(rint(cm + cs c), 0, 2^d - 1)
+//   The five quotients -- by ys, cs, 2(1-Kb), 2(1-Kr), hi - lo -- are IEEE divisions for bytes (hi - lo formed in fp32 on the
+//   device) and multiplications by reciprocals formed on the host in double and rounded once to fp32 for 16-bit words: one more
+//   rounding of 2^-24 relative per quotient, inside the tests' bars.  They differ in the last bit and in emitted
+//   samples near ties, so they stay apart (Sample8::quot / Sample16::quot).
 //
 // One thread = a 4 x 2 luma block (two rows, four columns): one chroma row, two chroma columns, and the neighbours the filters
 // need.  A workgroup is 64 x 4 threads, so a wave owns whole rows and whatever depends on a row's address is wave-uniform.
-// The fp32 side moves as 16-byte accesses.  On the byte side no access is wider than its address is aligned and no byte
-// outside the rows of a plane is read or written: a group of 4 (2) bytes moves as a dword (a short) where its address allows
-// it and in naturally aligned pieces otherwise -- relaxed atomics, which are plain sub-dword accesses that are never merged
-// into wider, possibly misaligned ones.  Blocks that hold padded rows / columns or the ragged end of the frame work pixel by
-// pixel.  Pure streaming: all of a lane's loads come ahead of its first store, no grid-stride loop (frame_io.hip).
+// The fp32 side moves as 16-byte accesses.  On the sample side a group of 4 (2) samples -- four luma samples, two CbCr pairs --
+// moves as one access where its address is aligned to the group's size and in naturally aligned pieces otherwise: 1 + 2 + 1
+// or 2 + 2 samples; the offset of a lane's group inside its row is a multiple of the group's size, so that choice is the row's:
+// per wave.  No access is wider than its address is aligned (relaxed atomics of wavefront scope: plain accesses that are never
+// merged into wider, possibly misaligned ones), no access is narrower than a sample, and nothing outside the rows of a plane is
+// read or written.  Blocks that hold padded rows / columns or the ragged end of the frame work sample by sample.  Pure
+// streaming: all of a lane's loads come ahead of its first store, no grid-stride loop (frame_io.hip).
 #include <cstdint>
 
-#include "common.h"
-#include "kernels.h"
+#include "frame_common.h"
 
 namespace dvsr {
 
 constexpr int YUV_X = 64, YUV_Y = 4;   // threads of a workgroup along a row (one wave) / block rows of a workgroup
 
+// (what the 8-bit kernels read comes first and together: their scalar loads of it stay few)
 struct YuvCoef {
-  float y0, ys, cs;
+  float y0, ys, cs;                 // luma offset, luma / chroma scale (levels)
   float kr, kg, kb;
-  float r_cr, g_cb, g_cr, b_cb;   // 2(1-Kr), 2 Kb (1-Kb) / Kg, 2 Kr (1-Kr) / Kg, 2(1-Kb)
+  float r_cr, g_cb, g_cr, b_cb;     // 2(1-Kr), 2 Kb (1-Kb) / Kg, 2 Kr (1-Kr) / Kg, 2(1-Kb)
+  float cm, top;                    // chroma mid, 2^d - 1 (levels)
+  float inv_ys, inv_cs;             // (double) 1 / ys, 1 / cs
+  float inv_r_cr, inv_b_cb;         // (double) 1 / (2(1-Kr)), 1 / (2(1-Kb))
 };
 
 struct YuvIngestArgs {
   const unsigned char* p[3];
-  long long rs[3];
+  long long rs[3];                  // bytes
   float* dst;
   int h, w, Hp, Wp, pad;
   YuvCoef k;
+  unsigned shift, mask;             // 16-bit words: level = (word >> shift) & mask
 };
 
 struct YuvEmitArgs {
@@ -60,94 +76,165 @@ struct YuvEmitArgs {
   unsigned char* p[3];
   long long rs[3];
   int Hs, Ws, h, w;
-  float lo, hi;
+  float lo, inv_scale, hi;          // inv_scale = (double) 1 / (hi - lo)
+  unsigned shift;                   // 16-bit words: word = level << shift
   YuvCoef k;
 };
 
-// (frame_io.hip's) index i of a padded axis -> index of the frame's own axis of length n
-__device__ __forceinline__ int yuv_pad_index(int i, int n, int mode) {
-  return i < n ? i : (mode == DVSR_FRAME_PAD_REFLECT ? 2 * (n - 1) - i : n - 1);
+template <typename T>
+__device__ __forceinline__ T ld_plain(const unsigned char* p) {
+  return __hip_atomic_load(reinterpret_cast<const T*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+template <typename T>
+__device__ __forceinline__ void st_plain(unsigned char* p, T v) {
+  __hip_atomic_store(reinterpret_cast<T*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 
-// ---- the byte side: little-endian groups of 1, 2, 4 bytes at any address, in naturally aligned pieces
-__device__ __forceinline__ unsigned ld1(const unsigned char* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ unsigned ld2a(const unsigned char* p) {   // p even
-  return __hip_atomic_load(reinterpret_cast<const unsigned short*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ unsigned ld2(const unsigned char* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 1) ? (ld1(p) | (ld1(p + 1) << 8)) : ld2a(p);
-}
-__device__ __forceinline__ unsigned ld4(const unsigned char* p) {
-  const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3);
-  if (m == 0) return *reinterpret_cast<const unsigned*>(p);
-  if (m == 2) return ld2a(p) | (ld2a(p + 2) << 16);
-  return ld1(p) | (ld2a(p + 1) << 8) | (ld1(p + 3) << 24);
-}
-__device__ __forceinline__ void st1(unsigned char* p, unsigned v) {
-  __hip_atomic_store(p, (unsigned char)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ void st2a(unsigned char* p, unsigned v) {   // p even
-  __hip_atomic_store(reinterpret_cast<unsigned short*>(p), (unsigned short)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ void st2(unsigned char* p, unsigned v) {
-  if (reinterpret_cast<uintptr_t>(p) & 1) {
-    st1(p, v);
-    st1(p + 1, v >> 8);
-  } else {
-    st2a(p, v);
+// ---- a sample trait S: B bytes per sample; little-endian groups of 1, 2, 4 samples at any sample-aligned address, loaded (a
+// group stays packed, G4 for four; lev(a, group, i) is the level of its sample i) and stored (from words, one per sample) in
+// naturally aligned pieces; word(a, level); the chroma midpoint; the quotient x / d given d and its reciprocal.
+
+struct Sample8 {
+  static constexpr int B = 1;
+  struct G4 { unsigned d[1]; };
+  // (a literal, as 255 is not: read from the argument struct it costs the planar ingest kernel 35 VGPRs and a wave of occupancy)
+  static __device__ __forceinline__ float cm(const YuvCoef&) { return 128.0f; }
+  static __device__ __forceinline__ float quot(float x, float d, float) { return x / d; }   // IEEE division
+  static __device__ __forceinline__ float lev(const YuvIngestArgs&, unsigned v, int i) { return (float)((v >> (8 * i)) & 0xffu); }
+  static __device__ __forceinline__ float lev(const YuvIngestArgs& a, const G4& g, int i) { return lev(a, g.d[0], i); }
+  static __device__ __forceinline__ unsigned word(const YuvEmitArgs&, unsigned level) { return level; }
+  static __device__ __forceinline__ unsigned ld1(const unsigned char* p) { return ld_plain<unsigned char>(p); }
+  static __device__ __forceinline__ unsigned ld2a(const unsigned char* p) { return ld_plain<unsigned short>(p); }   // p even
+  static __device__ __forceinline__ unsigned ld2(const unsigned char* p) {
+    return (reinterpret_cast<uintptr_t>(p) & 1) ? (ld1(p) | (ld1(p + 1) << 8)) : ld2a(p);
   }
-}
-__device__ __forceinline__ void st4(unsigned char* p, unsigned v) {
-  const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3);
-  if (m == 0) {
-    *reinterpret_cast<unsigned*>(p) = v;
-  } else if (m == 2) {
-    st2a(p, v);
-    st2a(p + 2, v >> 16);
-  } else {
-    st1(p, v);
-    st2a(p + 1, v >> 8);
-    st1(p + 3, v >> 24);
+  static __device__ __forceinline__ G4 ld4(const unsigned char* p) {
+    const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3);
+    if (m == 0) return G4{{*reinterpret_cast<const unsigned*>(p)}};
+    if (m == 2) return G4{{ld2a(p) | (ld2a(p + 2) << 16)}};
+    return G4{{ld1(p) | (ld2a(p + 1) << 8) | (ld1(p + 3) << 24)}};
   }
-}
+  static __device__ __forceinline__ void st1(unsigned char* p, unsigned v) { st_plain<unsigned char>(p, (unsigned char)v); }
+  static __device__ __forceinline__ void st2a(unsigned char* p, unsigned v) { st_plain<unsigned short>(p, (unsigned short)v); }
+  static __device__ __forceinline__ void st2(unsigned char* p, const unsigned s[2]) {
+    const unsigned v = s[0] | (s[1] << 8);
+    if (reinterpret_cast<uintptr_t>(p) & 1) {
+      st1(p, v);
+      st1(p + 1, v >> 8);
+    } else {
+      st2a(p, v);
+    }
+  }
+  static __device__ __forceinline__ void st4(unsigned char* p, const unsigned s[4]) {
+    const unsigned v = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
+    const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3);
+    if (m == 0) {
+      *reinterpret_cast<unsigned*>(p) = v;
+    } else if (m == 2) {
+      st2a(p, v);
+      st2a(p + 2, v >> 16);
+    } else {
+      st1(p, v);
+      st2a(p + 1, v >> 8);
+      st1(p + 3, v >> 24);
+    }
+  }
+};
+
+struct Sample16 {
+  static constexpr int B = 2;
+  struct G4 { unsigned d[2]; };
+  static __device__ __forceinline__ float cm(const YuvCoef& k) { return k.cm; }
+  static __device__ __forceinline__ float quot(float x, float, float inv) { return x * inv; }
+  static __device__ __forceinline__ float lev(const YuvIngestArgs& a, unsigned v, int i) {   // the two words of a dword
+    return i ? (float)((v >> (16 + a.shift)) & a.mask) : (float)(((v & 0xffffu) >> a.shift) & a.mask);
+  }
+  static __device__ __forceinline__ float lev(const YuvIngestArgs& a, const G4& g, int i) { return lev(a, g.d[i >> 1], i & 1); }
+  static __device__ __forceinline__ unsigned word(const YuvEmitArgs& a, unsigned level) { return level << a.shift; }
+  static __device__ __forceinline__ unsigned ld1(const unsigned char* p) { return ld_plain<unsigned short>(p); }
+  static __device__ __forceinline__ unsigned ld2a(const unsigned char* p) { return ld_plain<unsigned>(p); }   // p 4-aligned
+  static __device__ __forceinline__ unsigned ld2(const unsigned char* p) {
+    return (reinterpret_cast<uintptr_t>(p) & 2) ? (ld1(p) | (ld1(p + 2) << 16)) : ld2a(p);
+  }
+  static __device__ __forceinline__ G4 ld4(const unsigned char* p) {
+    const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 7);
+    unsigned lo, hi;
+    if (m == 0) {
+      const unsigned long long v = ld_plain<unsigned long long>(p);
+      lo = (unsigned)v;
+      hi = (unsigned)(v >> 32);
+    } else if (m == 4) {
+      lo = ld2a(p);
+      hi = ld2a(p + 4);
+    } else {
+      const unsigned a = ld1(p), b = ld2a(p + 2), c = ld1(p + 6);
+      lo = a | (b << 16);
+      hi = (b >> 16) | (c << 16);
+    }
+    return G4{{lo, hi}};
+  }
+  static __device__ __forceinline__ void st1(unsigned char* p, unsigned v) { st_plain<unsigned short>(p, (unsigned short)v); }
+  static __device__ __forceinline__ void st2a(unsigned char* p, unsigned v) { st_plain<unsigned>(p, v); }
+  static __device__ __forceinline__ void st2(unsigned char* p, const unsigned s[2]) {
+    const unsigned v = s[0] | (s[1] << 16);
+    if (reinterpret_cast<uintptr_t>(p) & 2) {
+      st1(p, v);
+      st1(p + 2, v >> 16);
+    } else {
+      st2a(p, v);
+    }
+  }
+  static __device__ __forceinline__ void st4(unsigned char* p, const unsigned s[4]) {
+    const unsigned lo = s[0] | (s[1] << 16), hi = s[2] | (s[3] << 16);
+    const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 7);
+    if (m == 0) {
+      st_plain<unsigned long long>(p, (unsigned long long)lo | ((unsigned long long)hi << 32));
+    } else if (m == 4) {
+      st2a(p, lo);
+      st2a(p + 4, hi);
+    } else {
+      st1(p, lo);
+      st2a(p + 2, (lo >> 16) | (hi << 16));
+      st1(p + 6, hi >> 16);
+    }
+  }
+};
 
 // chroma sample (j, k) of both planes
-template <int FMT>
+template <class S, bool SEMI>
 __device__ __forceinline__ void chroma1(const YuvIngestArgs& a, int j, int k, float& cb, float& cr) {
-  if (FMT == DVSR_YUV_NV12) {
-    const unsigned v = ld2(a.p[1] + (long long)j * a.rs[1] + 2 * k);
-    cb = (float)(v & 0xffu);
-    cr = (float)(v >> 8);
+  if (SEMI) {
+    const unsigned v = S::ld2(a.p[1] + (long long)j * a.rs[1] + 2 * S::B * k);
+    cb = S::lev(a, v, 0);
+    cr = S::lev(a, v, 1);
   } else {
-    cb = (float)ld1(a.p[1] + (long long)j * a.rs[1] + k);
-    cr = (float)ld1(a.p[2] + (long long)j * a.rs[2] + k);
+    cb = S::lev(a, S::ld1(a.p[1] + (long long)j * a.rs[1] + S::B * k), 0);
+    cr = S::lev(a, S::ld1(a.p[2] + (long long)j * a.rs[2] + S::B * k), 0);
   }
 }
 
 // chroma samples (j, k0), (j, k0 + 1), (j, k2) of both planes; k0 is even and k0 + 1 < Wc
-template <int FMT>
+template <class S, bool SEMI>
 __device__ __forceinline__ void chroma3(const YuvIngestArgs& a, int j, int k0, int k2, float cb[3], float cr[3]) {
-  if (FMT == DVSR_YUV_NV12) {
-    const unsigned v = ld4(a.p[1] + (long long)j * a.rs[1] + 2 * k0);
-    cb[0] = (float)(v & 0xffu);
-    cr[0] = (float)((v >> 8) & 0xffu);
-    cb[1] = (float)((v >> 16) & 0xffu);
-    cr[1] = (float)(v >> 24);
+  if (SEMI) {
+    const typename S::G4 g = S::ld4(a.p[1] + (long long)j * a.rs[1] + 2 * S::B * k0);
+    cb[0] = S::lev(a, g, 0);
+    cr[0] = S::lev(a, g, 1);
+    cb[1] = S::lev(a, g, 2);
+    cr[1] = S::lev(a, g, 3);
   } else {
-    const unsigned u = ld2(a.p[1] + (long long)j * a.rs[1] + k0), v = ld2(a.p[2] + (long long)j * a.rs[2] + k0);
-    cb[0] = (float)(u & 0xffu);
-    cb[1] = (float)(u >> 8);
-    cr[0] = (float)(v & 0xffu);
-    cr[1] = (float)(v >> 8);
+    const unsigned u = S::ld2(a.p[1] + (long long)j * a.rs[1] + S::B * k0), v = S::ld2(a.p[2] + (long long)j * a.rs[2] + S::B * k0);
+    cb[0] = S::lev(a, u, 0);
+    cb[1] = S::lev(a, u, 1);
+    cr[0] = S::lev(a, v, 0);
+    cr[1] = S::lev(a, v, 1);
   }
-  chroma1<FMT>(a, j, k2, cb[2], cr[2]);
+  chroma1<S, SEMI>(a, j, k2, cb[2], cr[2]);
 }
 
 __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
-template <int FMT>
+template <class S, bool SEMI>
 __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvIngestArgs a) {
   const int x0 = (blockIdx.x * YUV_X + threadIdx.x) * 4;
   const int y0 = (blockIdx.y * YUV_Y + threadIdx.y) * 2;
@@ -159,16 +246,16 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
     // k0, k0 + 1 and reach to k0 + 2 for the last (odd) one
     const int j = y0 >> 1, k0 = x0 >> 1, k2 = min(k0 + 2, Wc - 1);
     const int jr[3] = {max(j - 1, 0), j, min(j + 1, Hc - 1)};
-    unsigned yl[2];
+    typename S::G4 yl[2];
 #pragma unroll
-    for (int r = 0; r < 2; ++r) yl[r] = ld4(a.p[0] + (long long)(y0 + r) * a.rs[0] + x0);
+    for (int r = 0; r < 2; ++r) yl[r] = S::ld4(a.p[0] + (long long)(y0 + r) * a.rs[0] + S::B * x0);
     float cb[3][3], cr[3][3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) chroma3<FMT>(a, jr[r], k0, k2, cb[r], cr[r]);
+    for (int r = 0; r < 3; ++r) chroma3<S, SEMI>(a, jr[r], k0, k2, cb[r], cr[r]);
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) Y[r][i] = (float)((yl[r] >> (8 * i)) & 0xffu);
+      for (int i = 0; i < 4; ++i) Y[r][i] = S::lev(a, yl[r], i);
     float hb[3][4], hr[3][4];           // the horizontal step, per chroma row
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -189,21 +276,21 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
       Cr[1][i] = 0.75f * hr[1][i] + 0.25f * hr[2][i];
     }
   } else {
-    // padded rows / columns, the ragged end of a row, the last row of an odd height: pixel by pixel, every index clamped
+    // padded rows / columns, the ragged end of a row, the last row of an odd height: sample by sample, every index clamped
     float cbv[2][4][4], crv[2][4][4];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-      const int sy = yuv_pad_index(min(y0 + r, a.Hp - 1), a.h, a.pad);
+      const int sy = pad_index(min(y0 + r, a.Hp - 1), a.h, a.pad);
       const int j = sy >> 1, jn = (sy & 1) ? min(j + 1, Hc - 1) : max(j - 1, 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int sx = yuv_pad_index(x0 + i, a.w, a.pad);
+        const int sx = pad_index(x0 + i, a.w, a.pad);
         const int ka = sx >> 1, kb = (sx & 1) ? min(ka + 1, Wc - 1) : ka;
-        Y[r][i] = (float)ld1(a.p[0] + (long long)sy * a.rs[0] + sx);
-        chroma1<FMT>(a, j, ka, cbv[r][i][0], crv[r][i][0]);
-        chroma1<FMT>(a, j, kb, cbv[r][i][1], crv[r][i][1]);
-        chroma1<FMT>(a, jn, ka, cbv[r][i][2], crv[r][i][2]);
-        chroma1<FMT>(a, jn, kb, cbv[r][i][3], crv[r][i][3]);
+        Y[r][i] = S::lev(a, S::ld1(a.p[0] + (long long)sy * a.rs[0] + S::B * sx), 0);
+        chroma1<S, SEMI>(a, j, ka, cbv[r][i][0], crv[r][i][0]);
+        chroma1<S, SEMI>(a, j, kb, cbv[r][i][1], crv[r][i][1]);
+        chroma1<S, SEMI>(a, jn, ka, cbv[r][i][2], crv[r][i][2]);
+        chroma1<S, SEMI>(a, jn, kb, cbv[r][i][3], crv[r][i][3]);
       }
     }
 #pragma unroll
@@ -219,7 +306,8 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
   for (int r = 0; r < 2; ++r)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float yn = (Y[r][i] - a.k.y0) / a.k.ys, cb = (Cb[r][i] - 128.0f) / a.k.cs, cr = (Cr[r][i] - 128.0f) / a.k.cs;
+      const float yn = S::quot(Y[r][i] - a.k.y0, a.k.ys, a.k.inv_ys), cb = S::quot(Cb[r][i] - S::cm(a.k), a.k.cs, a.k.inv_cs),
+                  cr = S::quot(Cr[r][i] - S::cm(a.k), a.k.cs, a.k.inv_cs);
       o[r][0][i] = clamp01(yn + a.k.r_cr * cr);
       o[r][1][i] = clamp01(yn - a.k.g_cb * cb - a.k.g_cr * cr);
       o[r][2][i] = clamp01(yn + a.k.b_cb * cb);
@@ -234,9 +322,9 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
     }
 }
 
-__device__ __forceinline__ unsigned quant_level(float v) { return (unsigned)(int)fminf(fmaxf(rintf(v), 0.0f), 255.0f); }
+__device__ __forceinline__ unsigned quant_level(float v, float top) { return (unsigned)(int)fminf(fmaxf(rintf(v), 0.0f), top); }
 
-template <int FMT>
+template <class S, bool SEMI>
 __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitArgs a) {
   const int x0 = (blockIdx.x * YUV_X + threadIdx.x) * 4;
   const int y0 = (blockIdx.y * YUV_Y + threadIdx.y) * 2;
@@ -270,18 +358,18 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitAr
           if (i > 1 && x0 + i - 1 >= a.w) v[r][c][i - 1] = v[r][c][i - 2];
           s = v[r][c][i - 1];
         }
-        t[c] = (fminf(fmaxf(s, a.lo), a.hi) - a.lo) / scale;
+        t[c] = S::quot(fminf(fmaxf(s, a.lo), a.hi) - a.lo, scale, a.inv_scale);
       }
       const float y = a.k.kr * t[0] + a.k.kg * t[1] + a.k.kb * t[2];
-      cbv[r][i] = (t[2] - y) / a.k.b_cb;
-      crv[r][i] = (t[0] - y) / a.k.r_cr;
+      cbv[r][i] = S::quot(t[2] - y, a.k.b_cb, a.k.inv_b_cb);
+      crv[r][i] = S::quot(t[0] - y, a.k.r_cr, a.k.inv_r_cr);
       if (i > 0) yv[r][i - 1] = y;
     }
-  unsigned yb[2] = {0u, 0u}, cbb[2], crb[2];
+  unsigned yw[2][4], cbw[2], crw[2];      // samples as they are stored
 #pragma unroll
   for (int r = 0; r < 2; ++r)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) yb[r] |= quant_level(a.k.y0 + a.k.ys * yv[r][i]) << (8 * i);
+    for (int i = 0; i < 4; ++i) yw[r][i] = S::word(a, quant_level(a.k.y0 + a.k.ys * yv[r][i], a.k.top));
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int i = 2 * k;               // columns 2k - 1, 2k, 2k + 1 of this lane's chroma column k
@@ -289,106 +377,157 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitAr
                              0.25f * (cbv[1][i] + 2.0f * cbv[1][i + 1] + cbv[1][i + 2]));
     const float fr = 0.5f * (0.25f * (crv[0][i] + 2.0f * crv[0][i + 1] + crv[0][i + 2]) +
                              0.25f * (crv[1][i] + 2.0f * crv[1][i + 1] + crv[1][i + 2]));
-    cbb[k] = quant_level(128.0f + a.k.cs * fb);
-    crb[k] = quant_level(128.0f + a.k.cs * fr);
+    cbw[k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fb, a.k.top));
+    crw[k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fr, a.k.top));
   }
   // ---- stores
 #pragma unroll
   for (int r = 0; r < 2; ++r)
     if (y0 + r < a.h) {
-      unsigned char* q = a.p[0] + (long long)(y0 + r) * a.rs[0] + x0;
+      unsigned char* q = a.p[0] + (long long)(y0 + r) * a.rs[0] + S::B * x0;
       if (x0 + 3 < a.w) {
-        st4(q, yb[r]);
+        S::st4(q, yw[r]);
       } else {
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-          if (x0 + i < a.w) st1(q + i, yb[r] >> (8 * i));
+          if (x0 + i < a.w) S::st1(q + S::B * i, yw[r][i]);
       }
     }
   const int j = y0 >> 1;
   const bool two = x0 + 2 < a.w;        // this lane's second chroma column exists
-  if (FMT == DVSR_YUV_NV12) {
-    unsigned char* q = a.p[1] + (long long)j * a.rs[1] + x0;
-    if (two) st4(q, cbb[0] | (crb[0] << 8) | (cbb[1] << 16) | (crb[1] << 24));
-    else st2(q, cbb[0] | (crb[0] << 8));
+  if (SEMI) {
+    unsigned char* q = a.p[1] + (long long)j * a.rs[1] + S::B * x0;   // pair k0 = x0 / 2 is 2 k0 samples into the row
+    const unsigned s[4] = {cbw[0], crw[0], cbw[1], crw[1]};
+    if (two) S::st4(q, s);
+    else S::st2(q, s);
   } else {
-    unsigned char* qb = a.p[1] + (long long)j * a.rs[1] + (x0 >> 1);
-    unsigned char* qr = a.p[2] + (long long)j * a.rs[2] + (x0 >> 1);
+    unsigned char* qb = a.p[1] + (long long)j * a.rs[1] + S::B * (x0 >> 1);
+    unsigned char* qr = a.p[2] + (long long)j * a.rs[2] + S::B * (x0 >> 1);
     if (two) {
-      st2(qb, cbb[0] | (cbb[1] << 8));
-      st2(qr, crb[0] | (crb[1] << 8));
+      S::st2(qb, cbw);
+      S::st2(qr, crw);
     } else {
-      st1(qb, cbb[0]);
-      st1(qr, crb[0]);
+      S::st1(qb, cbw[0]);
+      S::st1(qr, crw[0]);
     }
   }
 }
 
-static YuvCoef yuv_coef(int matrix, int range) {
-  const double kr = matrix == DVSR_YUV_BT709 ? 0.2126 : 0.299, kb = matrix == DVSR_YUV_BT709 ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
-  const bool full = range == DVSR_YUV_FULL;
-  return YuvCoef{full ? 0.0f : 16.0f, full ? 255.0f : 219.0f, full ? 255.0f : 224.0f, (float)kr, (float)kg, (float)kb,
-                 (float)(2.0 * (1.0 - kr)), (float)(2.0 * kb * (1.0 - kb) / kg), (float)(2.0 * kr * (1.0 - kr) / kg),
-                 (float)(2.0 * (1.0 - kb))};
-}
+// ---- the host side, on the one internal frame (kernels.h: Yuv420)
 
-// the 4:2:0 frame on the "any address, any pitch" side, against the h x w it may have at most
-static int yuv_desc_check(const char* what, const dvsr_yuv_desc* d, int Ht, int Wt) {
+int yuv420_from(const char* what, const dvsr_yuv_desc* d, Yuv420* f) {
   DVSR_REQUIRE(d, DVSR_ERR_INVALID, "%s: null descriptor", what);
   DVSR_REQUIRE(d->format == DVSR_YUV_NV12 || d->format == DVSR_YUV_I420, DVSR_ERR_INVALID, "%s: unknown YUV format %d", what,
                d->format);
-  DVSR_REQUIRE(d->matrix == DVSR_YUV_BT601 || d->matrix == DVSR_YUV_BT709, DVSR_ERR_INVALID, "%s: unknown YUV matrix %d", what,
-               d->matrix);
-  DVSR_REQUIRE(d->range == DVSR_YUV_LIMITED || d->range == DVSR_YUV_FULL, DVSR_ERR_INVALID, "%s: unknown YUV range %d", what,
-               d->range);
-  DVSR_REQUIRE(d->h >= 1 && d->w >= 1 && d->h <= Ht && d->w <= Wt, DVSR_ERR_INVALID,
-               "%s: frame size h=%d w=%d outside [1, %d] x [1, %d]", what, d->h, d->w, Ht, Wt);
-  const int np = d->format == DVSR_YUV_NV12 ? 2 : 3;
-  const long long Wc = (d->w + 1) / 2;
-  for (int i = 0; i < np; ++i) {
-    DVSR_REQUIRE(d->plane[i], DVSR_ERR_INVALID, "%s: null plane %d", what, i);
-    const long long need = i == 0 ? d->w : (d->format == DVSR_YUV_NV12 ? 2 * Wc : Wc);
-    DVSR_REQUIRE(d->row_stride[i] >= need, DVSR_ERR_INVALID, "%s: row stride %lld of plane %d shorter than a row of %lld bytes",
-                 what, d->row_stride[i], i, need);
+  *f = Yuv420{{d->plane[0], d->plane[1], d->plane[2]}, {d->row_stride[0], d->row_stride[1], d->row_stride[2]},
+              d->h, d->w, d->matrix, d->range, d->format == DVSR_YUV_NV12, 1, 8};
+  return DVSR_OK;
+}
+
+int yuv420_from(const char* what, const dvsr_yuv16_desc* d, Yuv420* f) {
+  DVSR_REQUIRE(d, DVSR_ERR_INVALID, "%s: null descriptor", what);
+  DVSR_REQUIRE(d->format == DVSR_YUV16_SEMI_MSB || d->format == DVSR_YUV16_PLANAR_LSB, DVSR_ERR_INVALID,
+               "%s: unknown 16-bit YUV format %d", what, d->format);
+  DVSR_REQUIRE(d->depth == 10 || d->depth == 12, DVSR_ERR_INVALID, "%s: unknown depth %d (10 or 12)", what, d->depth);
+  *f = Yuv420{{d->plane[0], d->plane[1], d->plane[2]}, {d->row_stride[0], d->row_stride[1], d->row_stride[2]},
+              d->h, d->w, d->matrix, d->range, d->format == DVSR_YUV16_SEMI_MSB, 2, d->depth};
+  return DVSR_OK;
+}
+
+// (arguments checked by yuv_frame_check)
+static YuvCoef yuv_coef(const Yuv420& f) {
+  const bool bt709 = f.matrix == DVSR_YUV_BT709, full = f.range == DVSR_YUV_FULL;
+  const double kr = bt709 ? 0.2126 : 0.299, kb = bt709 ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
+  const double s = (double)(1 << (f.depth - 8)), top = (double)((1 << f.depth) - 1);
+  const double y0 = full ? 0.0 : 16.0 * s, ys = full ? top : 219.0 * s, cs = full ? top : 224.0 * s, cm = 128.0 * s;
+  const double r_cr = 2.0 * (1.0 - kr), b_cb = 2.0 * (1.0 - kb);
+  return YuvCoef{(float)y0, (float)ys, (float)cs, (float)kr, (float)kg, (float)kb, (float)r_cr,
+                 (float)(2.0 * kb * (1.0 - kb) / kg), (float)(2.0 * kr * (1.0 - kr) / kg), (float)b_cb, (float)cm, (float)top,
+                 (float)(1.0 / ys), (float)(1.0 / cs), (float)(1.0 / r_cr), (float)(1.0 / b_cb)};
+}
+
+// the frame on the "any address, any pitch" side, against the h x w it may have at most
+static int yuv_frame_check(const char* what, const Yuv420& f, int Ht, int Wt) {
+  DVSR_REQUIRE(f.matrix == DVSR_YUV_BT601 || f.matrix == DVSR_YUV_BT709, DVSR_ERR_INVALID, "%s: unknown YUV matrix %d", what,
+               f.matrix);
+  DVSR_REQUIRE(f.range == DVSR_YUV_LIMITED || f.range == DVSR_YUV_FULL, DVSR_ERR_INVALID, "%s: unknown YUV range %d", what,
+               f.range);
+  DVSR_REQUIRE(f.h >= 1 && f.w >= 1 && f.h <= Ht && f.w <= Wt, DVSR_ERR_INVALID,
+               "%s: frame size h=%d w=%d outside [1, %d] x [1, %d]", what, f.h, f.w, Ht, Wt);
+  const long long Wc = (f.w + 1) / 2;
+  for (int i = 0; i < (f.semi ? 2 : 3); ++i) {   // (the two "16-bit samples" checks cannot fail for bytes: % 1)
+    DVSR_REQUIRE(f.plane[i], DVSR_ERR_INVALID, "%s: null plane %d", what, i);
+    DVSR_REQUIRE(reinterpret_cast<uintptr_t>(f.plane[i]) % f.bytes == 0, DVSR_ERR_INVALID,
+                 "%s: odd address of plane %d (16-bit samples)", what, i);
+    const long long need = f.bytes * (i == 0 ? f.w : (f.semi ? 2 * Wc : Wc));
+    DVSR_REQUIRE(f.rs[i] >= need, DVSR_ERR_INVALID, "%s: row stride %lld of plane %d shorter than a row of %lld bytes", what,
+                 f.rs[i], i, need);
+    DVSR_REQUIRE(f.rs[i] % f.bytes == 0, DVSR_ERR_INVALID, "%s: odd row stride %lld of plane %d (16-bit samples)", what, f.rs[i], i);
   }
   return DVSR_OK;
 }
 
-// the planar fp32 side: [3][H][W], 16-byte accesses; a workgroup covers 2 * YUV_Y rows
-static int yuv_planar_check(const char* what, const float* ptr, int H, int W) {
-  DVSR_REQUIRE(ptr, DVSR_ERR_INVALID, "%s: null planar tensor", what);
-  DVSR_REQUIRE(H >= 1 && W >= 4 && W % 4 == 0 && H <= 2 * YUV_Y * 65535, DVSR_ERR_INVALID,
-               "%s: planar tensor H=%d W=%d (W must be a positive multiple of 4)", what, H, W);
-  DVSR_REQUIRE(reinterpret_cast<uintptr_t>(ptr) % 16 == 0, DVSR_ERR_INVALID, "%s: misaligned planar fp32 tensor (16 bytes)", what);
-  return DVSR_OK;
+// a workgroup covers 2 * YUV_Y rows
+static dim3 yuv_grid(int h, int w) { return dim3(ceil_div(ceil_div(w, 4), YUV_X), ceil_div(ceil_div(h, 2), YUV_Y)); }
+
+// the instantiation that takes a frame
+static auto ingest_kernel(const Yuv420& f) {
+  if (f.bytes == 2) return f.semi ? frame_ingest_yuv_kernel<Sample16, true> : frame_ingest_yuv_kernel<Sample16, false>;
+  return f.semi ? frame_ingest_yuv_kernel<Sample8, true> : frame_ingest_yuv_kernel<Sample8, false>;
+}
+static auto emit_kernel(const Yuv420& f) {
+  if (f.bytes == 2) return f.semi ? frame_emit_yuv_kernel<Sample16, true> : frame_emit_yuv_kernel<Sample16, false>;
+  return f.semi ? frame_emit_yuv_kernel<Sample8, true> : frame_emit_yuv_kernel<Sample8, false>;
 }
 
-int frame_ingest_yuv_check(const char* what, const dvsr_yuv_desc* sd, const float* dst, int Hp, int Wp, int pad_mode) {
-  int rc = yuv_planar_check(what, dst, Hp, Wp);
+int frame_ingest_yuv_check(const char* what, const Yuv420& f, const float* dst, int Hp, int Wp, int pad_mode) {
+  int rc = frame_planar_check(what, dst, Hp, Wp, 2 * YUV_Y);
   if (rc != DVSR_OK) return rc;
-  rc = yuv_desc_check(what, sd, Hp, Wp);
+  rc = yuv_frame_check(what, f, Hp, Wp);
   if (rc != DVSR_OK) return rc;
-  DVSR_REQUIRE(pad_mode == DVSR_FRAME_PAD_REFLECT || pad_mode == DVSR_FRAME_PAD_REPLICATE, DVSR_ERR_INVALID,
-               "%s: unknown pad mode %d", what, pad_mode);
-  DVSR_REQUIRE(pad_mode != DVSR_FRAME_PAD_REFLECT || (Hp - sd->h < sd->h && Wp - sd->w < sd->w), DVSR_ERR_INVALID,
-               "%s: reflect pad %d x %d not smaller than the frame %d x %d", what, Hp - sd->h, Wp - sd->w, sd->h, sd->w);
-  return DVSR_OK;
+  return frame_pad_check(what, pad_mode, f.h, f.w, Hp, Wp);
 }
 
 // (arguments checked by frame_ingest_yuv_check)
-int frame_ingest_yuv_launch(const dvsr_yuv_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st) {
+int frame_ingest_yuv_launch(const Yuv420& f, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st) {
   YuvIngestArgs a{};
   for (int i = 0; i < 3; ++i) {
-    a.p[i] = static_cast<const unsigned char*>(sd.plane[i]);
-    a.rs[i] = sd.row_stride[i];
+    a.p[i] = static_cast<const unsigned char*>(f.plane[i]);
+    a.rs[i] = f.rs[i];
   }
   a.dst = dst;
-  a.h = sd.h, a.w = sd.w, a.Hp = Hp, a.Wp = Wp, a.pad = pad_mode;
-  a.k = yuv_coef(sd.matrix, sd.range);
-  const dim3 grid(ceil_div(Wp / 4, YUV_X), ceil_div(ceil_div(Hp, 2), YUV_Y)), block(YUV_X, YUV_Y);
-  if (sd.format == DVSR_YUV_NV12) hipLaunchKernelGGL(frame_ingest_yuv_kernel<DVSR_YUV_NV12>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(frame_ingest_yuv_kernel<DVSR_YUV_I420>, grid, block, 0, st, a);
-  return check_launch("frame_ingest_yuv_kernel");
+  a.h = f.h, a.w = f.w, a.Hp = Hp, a.Wp = Wp, a.pad = pad_mode;
+  a.shift = f.semi ? 16u - (unsigned)f.depth : 0u;   // (bytes: unused)
+  a.mask = (1u << f.depth) - 1u;
+  a.k = yuv_coef(f);
+  hipLaunchKernelGGL(ingest_kernel(f), yuv_grid(Hp, Wp), dim3(YUV_X, YUV_Y), 0, st, a);
+  return check_launch(f.bytes == 2 ? "frame_ingest_yuv16_kernel" : "frame_ingest_yuv_kernel");
+}
+
+static int frame_ingest_yuv(const char* what, const Yuv420& f, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st) {
+  int rc = frame_ingest_yuv_check(what, f, dst, Hp, Wp, pad_mode);
+  if (rc != DVSR_OK) return rc;
+  return frame_ingest_yuv_launch(f, dst, Hp, Wp, pad_mode, st);
+}
+
+static int frame_emit_yuv(const char* what, const Yuv420& f, const float* src, int Hs, int Ws, float lo, float hi, hipStream_t st) {
+  int rc = frame_planar_check(what, src, Hs, Ws, 2 * YUV_Y);
+  if (rc != DVSR_OK) return rc;
+  rc = yuv_frame_check(what, f, Hs, Ws);
+  if (rc != DVSR_OK) return rc;
+  DVSR_REQUIRE(hi > lo, DVSR_ERR_INVALID, "%s: range [%g, %g]", what, (double)lo, (double)hi);
+  YuvEmitArgs a{};
+  a.src = src;
+  for (int i = 0; i < 3; ++i) {
+    a.p[i] = static_cast<unsigned char*>(f.plane[i]);
+    a.rs[i] = f.rs[i];
+  }
+  a.Hs = Hs, a.Ws = Ws, a.h = f.h, a.w = f.w, a.lo = lo, a.hi = hi;
+  a.inv_scale = (float)(1.0 / ((double)hi - (double)lo));
+  a.shift = f.semi ? 16u - (unsigned)f.depth : 0u;
+  a.k = yuv_coef(f);
+  hipLaunchKernelGGL(emit_kernel(f), yuv_grid(f.h, f.w), dim3(YUV_X, YUV_Y), 0, st, a);
+  return check_launch(f.bytes == 2 ? "frame_emit_yuv16_kernel" : "frame_emit_yuv_kernel");
 }
 
 }  // namespace dvsr
@@ -396,28 +535,27 @@ int frame_ingest_yuv_launch(const dvsr_yuv_desc& sd, float* dst, int Hp, int Wp,
 using namespace dvsr;
 
 extern "C" int dvsr_frame_ingest_yuv(const dvsr_yuv_desc* sd, float* dst, int Hp, int Wp, int pad_mode, dvsr_stream_t stream) {
-  int rc = frame_ingest_yuv_check("frame_ingest_yuv", sd, dst, Hp, Wp, pad_mode);
-  if (rc != DVSR_OK) return rc;
-  return frame_ingest_yuv_launch(*sd, dst, Hp, Wp, pad_mode, (hipStream_t)stream);
+  Yuv420 f;
+  int rc = yuv420_from("frame_ingest_yuv", sd, &f);
+  return rc != DVSR_OK ? rc : frame_ingest_yuv("frame_ingest_yuv", f, dst, Hp, Wp, pad_mode, (hipStream_t)stream);
+}
+
+extern "C" int dvsr_frame_ingest_yuv16(const dvsr_yuv16_desc* sd, float* dst, int Hp, int Wp, int pad_mode, dvsr_stream_t stream) {
+  Yuv420 f;
+  int rc = yuv420_from("frame_ingest_yuv16", sd, &f);
+  return rc != DVSR_OK ? rc : frame_ingest_yuv("frame_ingest_yuv16", f, dst, Hp, Wp, pad_mode, (hipStream_t)stream);
 }
 
 extern "C" int dvsr_frame_emit_yuv(const float* src, int Hs, int Ws, const dvsr_yuv_desc* dd, float lo, float hi,
                                    dvsr_stream_t stream) {
-  int rc = yuv_planar_check("frame_emit_yuv", src, Hs, Ws);
-  if (rc != DVSR_OK) return rc;
-  rc = yuv_desc_check("frame_emit_yuv", dd, Hs, Ws);
-  if (rc != DVSR_OK) return rc;
-  DVSR_REQUIRE(hi > lo, DVSR_ERR_INVALID, "frame_emit_yuv: range [%g, %g]", (double)lo, (double)hi);
-  YuvEmitArgs a{};
-  a.src = src;
-  for (int i = 0; i < 3; ++i) {
-    a.p[i] = static_cast<unsigned char*>(dd->plane[i]);
-    a.rs[i] = dd->row_stride[i];
-  }
-  a.Hs = Hs, a.Ws = Ws, a.h = dd->h, a.w = dd->w, a.lo = lo, a.hi = hi;
-  a.k = yuv_coef(dd->matrix, dd->range);
-  const dim3 grid(ceil_div(ceil_div(dd->w, 4), YUV_X), ceil_div(ceil_div(dd->h, 2), YUV_Y)), block(YUV_X, YUV_Y);
-  if (dd->format == DVSR_YUV_NV12) hipLaunchKernelGGL(frame_emit_yuv_kernel<DVSR_YUV_NV12>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(frame_emit_yuv_kernel<DVSR_YUV_I420>, grid, block, 0, (hipStream_t)stream, a);
-  return check_launch("frame_emit_yuv_kernel");
+  Yuv420 f;
+  int rc = yuv420_from("frame_emit_yuv", dd, &f);
+  return rc != DVSR_OK ? rc : frame_emit_yuv("frame_emit_yuv", f, src, Hs, Ws, lo, hi, (hipStream_t)stream);
+}
+
+extern "C" int dvsr_frame_emit_yuv16(const float* src, int Hs, int Ws, const dvsr_yuv16_desc* dd, float lo, float hi,
+                                     dvsr_stream_t stream) {
+  Yuv420 f;
+  int rc = yuv420_from("frame_emit_yuv16", dd, &f);
+  return rc != DVSR_OK ? rc : frame_emit_yuv("frame_emit_yuv16", f, src, Hs, Ws, lo, hi, (hipStream_t)stream);
 }

@@ -565,7 +565,7 @@ class StreamPlan:
         first = frame if torch.is_tensor(frame) else frame[0]
         if not first.is_cuda:
             raise RuntimeError("libdynavsr_hip needs a tensor on the GPU, got device %s" % first.device)
-        if layout in F.YUV_LAYOUTS + F.YUV16_LAYOUTS:
+        if F.is_yuv(layout):
             planes, desc = F.describe_yuv(F.yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range)
             params, arr = self._params(leaves)
             fn = F._yuv_entry(layout, 'edvr_stream_extract_frame')[0]

@@ -1,5 +1,5 @@
 """Frames in and out of the video path (csrc/frame_io.hip: dvsr_frame_ingest / dvsr_frame_emit; csrc/frame_yuv.hip:
-dvsr_frame_ingest_yuv / dvsr_frame_emit_yuv).
+dvsr_frame_ingest_yuv / dvsr_frame_emit_yuv and their _yuv16 counterparts).
 
 A decoder delivers 8-bit interleaved RGB or BGR (cv2 order) frames [H,W,3|4] of any size; the networks compute on fp32
 planar [3,Hp,Wp] in [0,1] whose sides are multiples of 4 (EDVR) or 16 (TOFlow), and an encoder or PNG writer wants 8-bit
@@ -31,7 +31,7 @@ layouts 'p010' / 'p012' (semi-planar like NV12, the level in the TOP bits of the
 planes exactly as above, as torch.uint16 or torch.int16 tensors (the same bits; numpy and PyAV hand over uint16); the bits of a
 word that carry no level are ignored on the way in and written as 0, and emit returns torch.uint16.  The same matrices, ranges,
 siting and filters apply with H.273's level scale at that depth, nothing is rounded to 8 bits on the way, and an 8-bit or RGB
-source may leave with 10 bits (csrc/frame_yuv16.hip).
+source may leave with 10 bits (the same kernels of csrc/frame_yuv.hip on 16-bit samples).
 
 Scene cuts (csrc/frame_cut.hip: dvsr_frame_luma_sad), for any of the layouts above:
 
@@ -56,14 +56,14 @@ import torch
 from . import _lib as L
 
 LAYOUTS = ('chw', 'hwc_rgb', 'hwc_bgr')
-YUV_LAYOUTS = ('nv12', 'i420')
-YUV16_LAYOUTS = ('p010', 'p012', 'i420p10', 'i420p12')
-_YUV16 = {'p010': (L.YUV16_SEMI_MSB, 10), 'p012': (L.YUV16_SEMI_MSB, 12),          # layout -> (storage, depth)
-          'i420p10': (L.YUV16_PLANAR_LSB, 10), 'i420p12': (L.YUV16_PLANAR_LSB, 12)}
-_SEMI_PLANAR = ('nv12', 'p010', 'p012')
-_WORD_DTYPES = (torch.uint16, torch.int16)
-_LUMA16 = {'p010': L.FRAME_U16_Y_MSB, 'p012': L.FRAME_U16_Y_MSB, 'i420p10': L.FRAME_U16_Y_10, 'i420p12': L.FRAME_U16_Y_12}
-_YUV_FORMAT = {'nv12': L.YUV_NV12, 'i420': L.YUV_I420}
+_BYTES, _WORDS = (torch.uint8,), (torch.uint16, torch.int16)
+# 4:2:0 layout -> (semi-planar, depth, the format of its descriptor, the format of its Y plane for luma_sad, its dtypes)
+_YUV = {'nv12': (True, 8, L.YUV_NV12, L.FRAME_U8_Y, _BYTES), 'i420': (False, 8, L.YUV_I420, L.FRAME_U8_Y, _BYTES),
+        'p010': (True, 10, L.YUV16_SEMI_MSB, L.FRAME_U16_Y_MSB, _WORDS), 'p012': (True, 12, L.YUV16_SEMI_MSB, L.FRAME_U16_Y_MSB, _WORDS),
+        'i420p10': (False, 10, L.YUV16_PLANAR_LSB, L.FRAME_U16_Y_10, _WORDS),
+        'i420p12': (False, 12, L.YUV16_PLANAR_LSB, L.FRAME_U16_Y_12, _WORDS)}
+YUV_LAYOUTS = tuple(k for k, v in _YUV.items() if v[1] == 8)
+YUV16_LAYOUTS = tuple(k for k, v in _YUV.items() if v[1] > 8)
 _YUV_MATRIX = {'bt601': L.YUV_BT601, 'bt709': L.YUV_BT709}
 _YUV_RANGE = {'limited': L.YUV_LIMITED, 'full': L.YUV_FULL}
 _FORMAT = {'chw': L.FRAME_F32_CHW, 'hwc_rgb': L.FRAME_U8_HWC_RGB, 'hwc_bgr': L.FRAME_U8_HWC_BGR}
@@ -78,12 +78,16 @@ def padded_size(h, w, multiple):
     return -(-h // m) * m, -(-w // m) * m
 
 
+def is_yuv(layout):
+    """`layout` is one of the 4:2:0 layouts, of any depth."""
+    return layout in YUV_LAYOUTS + YUV16_LAYOUTS
+
+
 def resolve_layout(frame, layout=None):
     """Checks one frame against `layout` (None: by dtype; the 4:2:0 layouts are never inferred) and returns
     (layout, h, w).  No GPU call."""
-    if layout in YUV_LAYOUTS + YUV16_LAYOUTS:
-        _, h, w = yuv_planes(frame, layout)
-        return layout, h, w
+    if is_yuv(layout):
+        return (layout,) + yuv_planes(frame, layout)[1:]
     if not torch.is_tensor(frame):
         raise ValueError("a frame must be a tensor, got %s" % type(frame).__name__)
     if layout is None:
@@ -148,11 +152,10 @@ def yuv_planes(frame, layout):
     """(planes, h, w) of a 4:2:0 frame -- a packed [H*3/2, W] tensor or a tuple of plane tensors, uint8 for 'nv12' / 'i420',
     uint16 or int16 for the 10- / 12-bit layouts: the planes as views (y, uv) / (y, u, v), nothing copied.  ValueError for
     anything else.  No GPU call."""
-    if layout not in YUV_LAYOUTS + YUV16_LAYOUTS:
+    if not is_yuv(layout):
         raise ValueError("unknown YCbCr layout %r (one of %s)" % (layout, ', '.join(YUV_LAYOUTS + YUV16_LAYOUTS)))
-    semi = layout in _SEMI_PLANAR
-    n = 2 if semi else 3
-    dtypes, kind = ((torch.uint8,), 'uint8') if layout in YUV_LAYOUTS else (_WORD_DTYPES, 'uint16 / int16')
+    semi, depth, _, _, dtypes = _YUV[layout]
+    n, kind = (2 if semi else 3), ('uint8' if depth == 8 else 'uint16 / int16')
     if torch.is_tensor(frame):
         if frame.dtype not in dtypes or frame.dim() != 2:
             raise ValueError("a packed %s frame must be %s [H*3/2, W], got %s %s" % (layout, kind, frame.dtype, tuple(frame.shape)))
@@ -189,10 +192,8 @@ def describe_yuv(planes, layout, h, w, matrix='bt601', yuv_range='limited', copy
     descriptor can express -- any offset, any row pitch -- is passed by stride; any other is copied first (copy = False:
     ValueError, for a destination)."""
     check_yuv_names(matrix, yuv_range)
-    if layout in YUV16_LAYOUTS:
-        desc = L.Yuv16Desc(_YUV16[layout][0], _YUV16[layout][1], h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
-    else:
-        desc = L.YuvDesc(_YUV_FORMAT[layout], h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
+    (_, depth, fmt, _, _), rest = _YUV[layout], (h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
+    desc = L.Yuv16Desc(fmt, depth, *rest) if depth > 8 else L.YuvDesc(fmt, *rest)
     kept = []
     for i, p in enumerate(planes):
         es = p.element_size()                                           # 1, or 2 for 16-bit words
@@ -212,7 +213,7 @@ def describe_yuv(planes, layout, h, w, matrix='bt601', yuv_range='limited', copy
 
 def _yuv_entry(layout, name):
     """The C entry point `name` ('frame_ingest' / 'frame_emit' / 'edvr_stream_extract_frame') of a 4:2:0 layout."""
-    name = "dvsr_%s_%s" % (name, 'yuv16' if layout in YUV16_LAYOUTS else 'yuv')
+    name = "dvsr_%s_%s" % (name, 'yuv16' if _YUV[layout][1] > 8 else 'yuv')
     return getattr(L.lib(), name), name
 
 
@@ -253,7 +254,7 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix=
     first = frame if torch.is_tensor(frame) else frame[0]
     dev = out.device if out is not None else (first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device()))
     frame = to_device(frame, dev)
-    yuv = layout in YUV_LAYOUTS + YUV16_LAYOUTS
+    yuv = is_yuv(layout)
     if yuv:
         planes, desc = describe_yuv(yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range)
     else:
@@ -378,13 +379,12 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     (`out`: uint16 or int16); the bits of a word that carry no level are written as 0.
     size = (oh, ow): the crop is first resampled to oh x ow (resize(): one more launch into a buffer of its own), and
     everything above holds for the oh x ow image -- emit(resize(sr, h, w, size), oh, ow, layout, ...), bit for bit."""
-    yuv_all = YUV_LAYOUTS + YUV16_LAYOUTS
-    if layout not in LAYOUTS + yuv_all:
-        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + yuv_all)))
+    if layout not in LAYOUTS and not is_yuv(layout):
+        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + YUV_LAYOUTS + YUV16_LAYOUTS)))
     check_yuv_names(matrix, yuv_range)
     if size is not None:
         oh, ow = check_resize(h, w, size)
-        if layout in yuv_all and out is None and (oh % 2 or ow % 2):
+        if is_yuv(layout) and out is None and (oh % 2 or ow % 2):
             raise ValueError("emit: a packed %s frame needs an even size, got %d x %d: pass `out` as planes" % (layout, oh, ow))
         # (the whole buffer goes on: its rows are 16-byte aligned, those of resize()'s view are not when ow % 4)
         return emit(_resize(sr, h, w, (oh, ow))[0], oh, ow, layout, min_max, out, matrix, yuv_range)
@@ -396,7 +396,7 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     h, w = int(h), int(w)
     if not (1 <= h <= Hs and 1 <= w <= Ws):
         raise ValueError("emit: crop %d x %d outside the frame %d x %d" % (h, w, Hs, Ws))
-    if layout in yuv_all:
+    if is_yuv(layout):
         if out is None and (h % 2 or w % 2):
             raise ValueError("emit: a packed %s frame needs an even size, got %d x %d: pass `out` as planes" % (layout, h, w))
         if out is not None:
@@ -412,10 +412,10 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     if not _planar_ok(sr):
         sr = torch.nn.functional.pad(sr, (0, -Ws % 4)).contiguous()
         Ws = int(sr.shape[2])
-    if layout in yuv_all:
+    if is_yuv(layout):
         with torch.cuda.device(sr.device):
             if out is None:
-                out = torch.empty((h * 3 // 2, w), dtype=torch.uint16 if layout in YUV16_LAYOUTS else torch.uint8, device=sr.device)
+                out = torch.empty((h * 3 // 2, w), dtype=_YUV[layout][4][0], device=sr.device)
                 planes = yuv_planes(out, layout)[0]
             _, desc = describe_yuv(planes, layout, h, w, matrix, yuv_range, copy=False)
             fn, name = _yuv_entry(layout, 'frame_emit')
@@ -439,7 +439,7 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
 
 def _luma_part(frame, layout):
     """The tensor of a frame that carries its luma: the Y plane of a 4:2:0 frame (a view), the frame itself otherwise."""
-    if layout in YUV_LAYOUTS + YUV16_LAYOUTS:
+    if is_yuv(layout):
         return yuv_planes(frame, layout)[0][0]
     return frame if layout != 'chw' or frame.dtype == torch.float32 else frame.float()
 
@@ -447,14 +447,14 @@ def _luma_part(frame, layout):
 def _describe_luma(x, layout):
     """(x', the fields of its dvsr_frame_desc) of what _luma_part returned; a view that the descriptor cannot express is
     copied first."""
-    if layout in YUV_LAYOUTS + YUV16_LAYOUTS:
+    if is_yuv(layout):
         h, w = x.shape
         es = x.element_size()
         st = x.stride()
         if not ((st[1] == 1 or w == 1) and (st[0] >= w or h == 1) and x.data_ptr() % es == 0):
             x = x.clone(memory_format=torch.contiguous_format)
             st = x.stride()
-        return x, (_LUMA16[layout] if layout in YUV16_LAYOUTS else L.FRAME_U8_Y, h, w, max(int(st[0]), w) * es, 0, es)
+        return x, (_YUV[layout][3], h, w, max(int(st[0]), w) * es, 0, es)
     x, d = describe(x, layout)
     return x, (d.format, d.h, d.w, d.row_stride, d.plane_stride, d.pixel_stride)
 

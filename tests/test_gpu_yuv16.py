@@ -1,4 +1,4 @@
-"""GPU: 10- and 12-bit YCbCr 4:2:0 frames in and out of the video path (csrc/frame_yuv16.hip, the 'p010' / 'p012' / 'i420p10' /
+"""GPU: 10- and 12-bit YCbCr 4:2:0 frames in and out of the video path (csrc/frame_yuv.hip, the 'p010' / 'p012' / 'i420p10' /
 'i420p12' layouts of dynavsr_amd/frames.py, StreamPlan.extract_frame, adapt.super_resolve_frames) and the 16-bit Y planes of
 dvsr_frame_luma_sad (csrc/frame_cut.hip).
 

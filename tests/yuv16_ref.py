@@ -1,4 +1,4 @@
-"""The YCbCr 4:2:0 arithmetic of csrc/frame_yuv16.hip restated in fp64 numpy at a depth d: the yardstick of
+"""The YCbCr 4:2:0 arithmetic of csrc/frame_yuv.hip restated in fp64 numpy at a depth d: the yardstick of
 test_yuv16_host.py and test_gpu_yuv16.py.  A helper, not a conftest.  The up-sampling, down-sampling, padding and packing are
 tests/yuv_ref.py's; only the level scale and the storage of a level in a 16-bit word are defined here.
 

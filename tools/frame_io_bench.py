@@ -19,7 +19,7 @@
    yardstick, not code under test: a YUV figure is expected not to be slower than its HWC counterpart by more than that
    counterpart's own max - min spread.
 
-4. the 10- / 12-bit pair (csrc/frame_yuv16.hip) next to the 8-bit 4:2:0 kernels of 3, by the method of 3: frame_ingest_yuv16
+4. the 10- / 12-bit pair (csrc/frame_yuv.hip too) next to the 8-bit 4:2:0 kernels of 3, by the method of 3: frame_ingest_yuv16
    (P010, yuv420p10le; 180x320) and frame_emit_yuv16 (720x1280) against frame_ingest_yuv / frame_emit_yuv NV12.  A 16-bit
    frame is twice the bytes on its side (ingest 3 B read + 12 B written per pixel, emit 12 B read + 3 B written, against
    13.5), so the comparison is PER BYTE MOVED: a 16-bit kernel's us per MB is expected not to exceed the 8-bit yardstick's by
