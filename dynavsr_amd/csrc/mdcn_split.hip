@@ -20,8 +20,28 @@
 //     the fragment layout), read straight from global memory one tap ahead (A1 = (hi | hi), A2 = (mid | hi), A3 = (lo | mid)
 //     by lane half) -- no weight image in the LDS (54 KB per workgroup instead of 72), no weight DMA;
 //   * per tap and wave: acc[mt][nt] += A1 B1 + A3 B1 + A2 B2 on the 2 x 2 blocks = 12 MFMAs.
-// Window / offset / mask staging, the sampler's pieces, the exact global fix-up for samples outside the window and the
-// epilogue are those of mdcn_fwd_dma_kernel.
+// The sampler's pieces, the exact global fix-up for samples outside the window and the epilogue are those of
+// mdcn_fwd_dma_kernel.
+//
+// Staging (round 10).  mdcn_fwd_dma_kernel's chunk opens with barrier, DMA issue of window + offset / mask image, barrier
+// (the drain) and a tap-0 sampler with nothing to hide behind: 6.4 k of a 19.9 k-cycle chunk here, which the co-resident
+// workgroup covers only partly (profiles/r06_dcn_dma_trace.txt).  This kernel keeps no offset / mask image -- it was a
+// transposition aid exactly the size of one window --, and spends the LDS on a second window buffer instead (the same
+// 55 296 bytes, two workgroups per CU):
+//   * a lane reads (dh, dw, mask) of ITS pixel with three dword buffer loads per tap, three taps ahead, across the chunk
+//     boundary (a ring of three triples); a wave's pixels are two runs of 32 consecutive floats per plane, a lane without a
+//     pixel is rejected by the resource's range and gets the 0.0 the zero-filled image rows used to deliver;
+//   * the window of chunk kc + 1 moves into buffer (kc + 1) & 1 under the taps of chunk kc: seven DMA instructions per wave
+//     behind the loads of taps 0-5 (two under tap 0), every one issued by every wave (out-of-image groups and the chunk past
+//     the last are rejected by the resource, not branched around), so the VM instructions behind the last DMA are a constant;
+//   * ONE raw s_barrier per chunk, ahead of tap 8, behind s_waitcnt vmcnt(VM_BEHIND_DMA) lgkmcnt(0): the wave's own DMA
+//     pieces have landed (VM loads retire in order) and its LDS reads of this chunk's buffer are done (tap 7 made the last:
+//     the refill of that buffer starts a tap later), while the A fragments and triples requested since stay in flight; the
+//     first read of the new window comes after that barrier;
+//   * tap 8 has no successor in its chunk, so the sampler of the NEXT chunk's tap 0 sits between its MFMAs (the new window is
+//     visible by then) and writes the odd operand sets, which the next chunk's top copies to the even ones (32 v_mov): only
+//     the first chunk's tap 0 has nothing to hide behind.  Under the last chunk's tap 8 it samples a chunk that does not
+//     exist (addresses clamped to the last chunk, results unused) rather than branch inside a tap.
 #include <type_traits>
 
 #include "common.h"
@@ -91,11 +111,14 @@ struct DcnSplitShape {
   static constexpr int CPG = 8, KK = 9, TH = 8, TW = 32, HALO = 4, X0 = 8;
   static constexpr int XH = TH + 2 + 2 * HALO, XW = 48, XG = XW / 4, XCH = XH * XW;
   static constexpr int NXG = CPG * XH * XG, NXI = (NXG + 255) / 256;
-  static constexpr int OMP = 27, NOI = (OMP + 3) / 4;
-  static constexpr int X_FLOATS = CPG * XCH, OM_FLOATS = OMP * TH * TW;
+  static constexpr int X_FLOATS = CPG * XCH;
   static constexpr int PACK_BYTES = 9 * 3 * 64 * 8 * 2;   // one (cout block, chunk) of the weight pack
-  static constexpr size_t LDS_BYTES = (size_t)(X_FLOATS + OM_FLOATS) * sizeof(float);
+  static constexpr size_t LDS_BYTES = (size_t)(2 * X_FLOATS) * sizeof(float);   // two window buffers
+  // VM instructions a wave issues between the last window DMA of a chunk (under tap 5) and the chunk's barrier (ahead of
+  // tap 8): the six A fragments and the offset / mask triple of taps 6 and 7
+  static constexpr int VM_BEHIND_DMA = 2 * (6 + 3);
 };
+static_assert(DcnSplitShape::NXG == 27 * 64 && DcnSplitShape::NXI == 7, "window DMA: 27 wave instructions, seven per wave (wave 3 has six)");
 
 __device__ __forceinline__ unsigned dcs_cvt_pk(float a, float b) {   // {bf16(a) in bits 15:0, bf16(b) in bits 31:16}, RNE
   return __builtin_bit_cast(unsigned, __builtin_convertvector(ds2f{a, b}, dsbf2));
@@ -103,14 +126,19 @@ __device__ __forceinline__ unsigned dcs_cvt_pk(float a, float b) {   // {bf16(a)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t dcs_rsrc(const float* base) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, -1, 0x00020000);
 }
+// a resource whose range rejects byte offset DCS_REJECT: such a lane loads 0.0 / moves nothing into the image (records = 0:
+// every lane)
+constexpr unsigned DCS_REJECT = 0x80000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dcs_rsrc_ranged(const float* base, bool live) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, live ? 0x7fffffff : 0, 0x00020000);
+}
 
 template <bool MASK_LOGIT>
 __global__ __launch_bounds__(256, 2) void mdcn_fwd_split_kernel(DcnK2 a) {
   using Sh = DcnSplitShape;
   constexpr int KK = Sh::KK, TH = Sh::TH, TW = Sh::TW, XH = Sh::XH, XW = Sh::XW, XG = Sh::XG, XCH = Sh::XCH;
   extern __shared__ __attribute__((aligned(16))) float smem_dcs[];
-  float* const s_x = smem_dcs;
-  float* const s_om = smem_dcs + Sh::X_FLOATS;
+  float* const s_x = smem_dcs;   // window buffer b at + b X_FLOATS: chunk kc samples buffer kc & 1
 
   const int id = blockIdx.x;
   const int tpx = (a.ntiles + 7) >> 3;
@@ -134,33 +162,37 @@ __global__ __launch_bounds__(256, 2) void mdcn_fwd_split_kernel(DcnK2 a) {
   const int px = ox0 + lo;
   const int py = oy0 + 2 * wave + hi;          // this lane's pixel row (lane halves = the wave's two rows)
   const bool pv = py < a.H && px < a.W;
-  const int prow = (2 * wave + hi) * TW + lo;
+  const unsigned omo = pv ? (unsigned)(((size_t)py * a.W + px) * 4) : DCS_REJECT;   // this lane's pixel in an offset / mask plane
 
   // window groups of this lane: L = 64 (wave + 4 jj) + lane = (row, channel, column group) -- the window is laid out
   // [row][channel][column]: the two corners of a row are neighbours and the four channels x two corners of a row lie within
   // 255 dwords of one base address, i.e. ONE ds_read2_b32 per (channel, row) instead of two ds_read_b32
+  // Every wave issues all seven pieces, so that the VM instructions of a chunk can be counted: the 28th piece (wave 3,
+  // jj 6) does not exist and repeats wave 3's piece jj 5 instead; out-of-image groups are rejected by the resource's range
+  // and their slots, zeroed here in both buffers, are never written again.
   unsigned xo[Sh::NXI];
-  bool xv[Sh::NXI];
+  int xp[Sh::NXI];   // the piece (= 256-float slab of a buffer) of instruction jj
 #pragma unroll
   for (int jj = 0; jj < Sh::NXI; ++jj) {
-    const int L = 64 * (wave + 4 * jj) + lane;
+    xp[jj] = (jj == Sh::NXI - 1 && wave == 3) ? wave + 4 * (jj - 1) : wave + 4 * jj;
+    const int L = 64 * xp[jj] + lane;   // < NXG
     const int y = L / (Sh::CPG * XG), r = L - y * (Sh::CPG * XG);
     const int c = r / XG, g4 = r - c * XG;
     const int gy = wy0 + y, gx = wx0 + 4 * g4;
-    const bool ok = L < Sh::NXG && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-    xo[jj] = ok ? (unsigned)(((size_t)c * HW + (size_t)gy * a.W + gx) * 4) : 0u;
-    xv[jj] = ok;
-    if (L < Sh::NXG && !ok) *reinterpret_cast<f32x4*>(s_x + L * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bool ok = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
+    xo[jj] = ok ? (unsigned)(((size_t)c * HW + (size_t)gy * a.W + gx) * 4) : DCS_REJECT;
+    if (!ok) {
+      *reinterpret_cast<f32x4*>(s_x + L * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(s_x + Sh::X_FLOATS + L * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
   }
-  // offset / mask planes: plane p = wave + 4 jj is ONE instruction; this lane moves (row lane / 8, columns 4 (lane % 8) ..)
-  const int omy = oy0 + (lane >> 3), omx = ox0 + 4 * (lane & 7);
-  const bool omv = omy < a.H && omx < a.W;
-  const unsigned omo = omv ? (unsigned)(((size_t)omy * a.W + omx) * 4) : 0u;
-  if (!omv) {
-#pragma unroll
-    for (int jj = 0; jj < Sh::NOI; ++jj)
-      if (wave + 4 * jj < Sh::OMP) *reinterpret_cast<f32x4*>(s_om + (wave + 4 * jj) * 256 + lane * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+  // window of chunk k -> buffer k & 1, piece by piece (past the last chunk: nothing moves, the instruction is still issued)
+  auto x_dma = [&](int k, int jj) __attribute__((always_inline)) {
+    const bool live = k < a.nchunks;
+    const __amdgpu_buffer_rsrc_t rs = dcs_rsrc_ranged(a.x + ((size_t)n * a.C + (live ? k : 0) * Sh::CPG) * HW, live);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(s_x + (k & 1) * Sh::X_FLOATS + 256 * xp[jj]),
+                                             16, xo[jj], 0, 0, 0);
+  };
 
   f32x16 acc[2][2];
 #pragma unroll
@@ -172,8 +204,7 @@ __global__ __launch_bounds__(256, 2) void mdcn_fwd_split_kernel(DcnK2 a) {
 
   // LDS byte addresses of this lane's operands (inline-asm reads of the tap loop)
   auto lds_addr = [](const float* p) { return (unsigned)(size_t)((__attribute__((address_space(3))) const float*)p); };
-  const unsigned a_x = lds_addr(s_x);          // channel c: + c XCH floats
-  const unsigned a_om = lds_addr(s_om) + (unsigned)prow * 4u;
+  const unsigned a_x0 = lds_addr(s_x);
 
   // A fragments: [tap][piece][cout][8 ch] bf16; lane halves read the pieces A1: hi|hi, A2: mid|hi, A3: lo|mid
   const float* wp_cb = wset_ptr(a.wp, a.w_gs, n, a.wdiv) + (size_t)cb * a.nchunks * (Sh::PACK_BYTES / 4);
@@ -192,50 +223,44 @@ __global__ __launch_bounds__(256, 2) void mdcn_fwd_split_kernel(DcnK2 a) {
   };
 
   const int sub = a.nchunks / a.dg;  // 8-channel chunks per deformable group (they share its offsets and masks)
+  // (dh, dw, mask) of this lane's pixel for tap `tap` of group g: three dwords straight from the planes (a wave's 64 pixels are
+  // two runs of 32 consecutive floats per plane); a lane without a pixel is rejected and gets 0.0.  The plane goes into the
+  // resource's base, so the offsets stay 32-bit at any image size.
+  float om[3][3];              // [tap % 3][dh, dw, mask]: a ring, loaded three taps ahead across the chunk boundary
+  auto om_load = [&](int g, int tap, float (&o)[3]) __attribute__((always_inline)) {
+    const __amdgpu_buffer_rsrc_t ro = dcs_rsrc_ranged(offn + (size_t)(g * 18 + 2 * tap) * HW, true);
+    const __amdgpu_buffer_rsrc_t rm = dcs_rsrc_ranged(mskn + (size_t)(g * 9 + tap) * HW, true);
+    o[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ro, (int)omo, 0, 0));
+    o[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ro, (int)omo, (int)(HW * 4), 0));
+    o[2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rm, (int)omo, 0, 0));
+  };
+  // Prologue: taps 0-2 of chunk 0 and its window.  The one full drain of the kernel: nothing is there to hide it behind.
   DCS_STAMP(0);
+  om_load(0, 0, om[0]); om_load(0, 1, om[1]); om_load(0, 2, om[2]);
+#pragma unroll
+  for (int jj = Sh::NXI - 1; jj >= 0; --jj) x_dma(0, jj);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  int g = 0;
+  // Per chunk ONE barrier, ahead of tap 8 (chunk 0 has a second one at its top, for the prologue's window and zero fill).
+  // Before it every wave has finished its LDS reads of chunk kc (the last s_waitcnt lgkmcnt(0) is in tap 7; the DMAs of chunk
+  // kc + 2 into that buffer are issued from tap 0 of chunk kc + 1 on) and has waited for its own DMA pieces of chunk kc + 1
+  // (issued under taps 0-5): VM loads retire in order, the newest VM_BEHIND_DMA instructions are all that may be outstanding.
+  // The first read of buffer (kc + 1) & 1 comes after the barrier.  A raw s_barrier: __syncthreads() would drain the counter
+  // (an LDS-DMA in flight makes its fence vmcnt(0)).  Every thread of a workgroup executes every barrier: the early return of
+  // surplus workgroups is ahead of all of them, and kc == 0 is uniform.
   for (int kc = 0; kc < a.nchunks; ++kc) {
-    const int g = kc / sub;
+    const int kcn = min(kc + 1, a.nchunks - 1), gn = kcn / sub;   // the chunk whose first taps are prefetched under taps 6-8
     if (kc < 2) DCS_STAMP(1 + 30 * kc);
-    __syncthreads();  // the previous chunk's taps are done with s_x / s_om
+    // the sampler's window and planes: this chunk's for taps 0-7 (they prepare taps 1-8), the next chunk's from tap 8 on
     const float* xg = a.x + ((size_t)n * a.C + kc * Sh::CPG) * HW;
-    {
-      const char* xb = reinterpret_cast<const char*>(xg);
-#pragma unroll
-      for (int jj = 0; jj < Sh::NXI; ++jj)
-        if (xv[jj])
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xb + xo[jj]),
-                                           (__attribute__((address_space(3))) void*)(s_x + 256 * (wave + 4 * jj)), 16, 0, 0);
-    }
-    if (kc % sub == 0) {
-#pragma unroll
-      for (int jj = 0; jj < Sh::NOI; ++jj) {
-        const int p = wave + 4 * jj;
-        if (p < Sh::OMP) {
-          const float* pb = p < 18 ? offn + (size_t)(g * 18 + p) * HW : mskn + (size_t)(g * 9 + p - 18) * HW;
-          if (omv)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(pb) + omo),
-                                             (__attribute__((address_space(3))) void*)(s_om + 256 * p), 16, 0, 0);
-        }
-      }
-    }
-    a_load(0, kc, 0);
-    if (kc < 2) DCS_STAMP(2 + 30 * kc);
-    __syncthreads();  // everything landed (the barrier's vmcnt(0) covers the DMAs)
-    if (kc < 2) DCS_STAMP(3 + 30 * kc);
+    unsigned a_x = a_x0 + (unsigned)(kc & 1) * (unsigned)(Sh::X_FLOATS * 4);   // channel c: + c XCH floats
 
     // ---- the nine taps, software-pipelined by hand as in mdcn_fwd_dma_kernel: the sampler of tap t + 1 is cut into pieces
     // that sit between the twelve MFMAs of tap t; LDS reads are inline asm, their results pass through one s_waitcnt asm
-    // before the blends; operands ping-pong between two register sets by tap parity.
+    // before the blends; operands ping-pong between two register sets by tap parity.  Tap t also issues, in this order, the A
+    // fragments of tap t + 1, the offset / mask triple of tap t + 3 and, t < 6, piece 5 - t of the next chunk's window (tap 0:
+    // piece 6 as well); tap 8's "tap t + 1" is tap 0 of the next chunk.
     struct Geo { ds2f w12, w34; float h_im, w_im, m, lh, lw; int ry, rx; unsigned addr; bool inwin; };
-    auto om_issue = [&](auto TAP, float (&o)[3]) {
-      constexpr int tap = decltype(TAP)::value;
-      const unsigned ad = a_om;  // (a local: asm operands of a generic lambda do not capture)
-      f32x2 hw2;  // (dh, dw): planes 2 tap and 2 tap + 1, 1 KiB = 4 x 64 dwords apart
-      asm volatile("ds_read2st64_b32 %0, %2 offset0:%3 offset1:%4\n\tds_read_b32 %1, %2 offset:%5"
-                   : "=&v"(hw2), "=&v"(o[2])
-                   : "v"(ad), "i"(2 * tap * 4), "i"((2 * tap + 1) * 4), "i"((18 + tap) * 1024));
-      o[0] = hw2[0]; o[1] = hw2[1];
-    };
     // cp[2 ch] = ((y,x), (y,x+1)), cp[2 ch + 1] = ((y+1,x), (y+1,x+1)) of channel ch; half h = channels 4 h .. 4 h + 3.
     // Bases: addr (row y, channels 0-3), + 768 B (channels 4-7), + 1536 B (row y + 1), + 2304 B
     auto corners_issue = [&](unsigned addr, ds2f (&cp)[16], int h) {
@@ -259,15 +284,13 @@ __global__ __launch_bounds__(256, 2) void mdcn_fwd_split_kernel(DcnK2 a) {
     };
     static_assert(XW == 48 && Sh::CPG == 8, "corners_issue hard-codes the window pitch");
 #define DCS_PIN8(c, o) asm volatile("" : "+v"(c[o]), "+v"(c[o + 1]), "+v"(c[o + 2]), "+v"(c[o + 3]), "+v"(c[o + 4]), "+v"(c[o + 5]), "+v"(c[o + 6]), "+v"(c[o + 7]))
-    // the first half: everything but the 10 newest LDS reads has returned (the other 8 corner pairs and the offsets / masks
-    // follow them)
+    // the first half: everything but the 8 newest LDS reads has returned (the other 8 corner pairs follow them)
     auto landed_a = [&](ds2f (&cp)[16]) {
-      asm volatile("s_waitcnt lgkmcnt(10)" : "+v"(cp[0]), "+v"(cp[1]), "+v"(cp[2]), "+v"(cp[3]), "+v"(cp[4]), "+v"(cp[5]), "+v"(cp[6]), "+v"(cp[7]));
+      asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(cp[0]), "+v"(cp[1]), "+v"(cp[2]), "+v"(cp[3]), "+v"(cp[4]), "+v"(cp[5]), "+v"(cp[6]), "+v"(cp[7]));
     };
     auto landed_b = [&](ds2f (&cp)[16]) {
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cp[8]), "+v"(cp[9]), "+v"(cp[10]), "+v"(cp[11]), "+v"(cp[12]), "+v"(cp[13]), "+v"(cp[14]), "+v"(cp[15]));
     };
-    auto landed_om = [&](float (&o)[3]) { asm volatile("" : "+v"(o[0]), "+v"(o[1]), "+v"(o[2])); };
     auto geom_a = [&](auto TAP, const float (&o)[3], Geo& q) {
       constexpr int tap = decltype(TAP)::value;
       constexpr int ki = tap / 3, kj = tap - ki * 3;
@@ -353,18 +376,18 @@ __global__ __launch_bounds__(256, 2) void mdcn_fwd_split_kernel(DcnK2 a) {
       Bq[par][1][1] = dsu4{l1[0], l1[1], l1[2], l1[3]};
     };
 
-    float om[2][3];              // [tap parity][dh, dw, mask]
     float Bf[8];                 // the blended fp32 values of the tap being prepared
     using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    {  // tap 0 of the chunk: nothing to hide behind
+    if (kc == 0) {  // tap 0 of the first chunk: nothing to hide behind
+      a_load(0, 0, 0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the zero fill; the prologue has drained the DMAs)
+      DCS_STAMP(2);
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      DCS_STAMP(3);
       Geo gq;
       ds2f c[16];
       int fix = 0;
-      om_issue(I0{}, om[0]);
-      om_issue(I1{}, om[1]);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(om[0][0]), "+v"(om[0][1]), "+v"(om[0][2]));
-      landed_om(om[1]);
       geom_a(I0{}, om[0], gq);
       geom_b1(gq); geom_b2(gq, fix);
       corners_issue(gq.addr, c, 0); corners_issue(gq.addr, c, 1);
@@ -374,6 +397,16 @@ __global__ __launch_bounds__(256, 2) void mdcn_fwd_split_kernel(DcnK2 a) {
       if (fix) fixup(gq, Bf);
       split_pair(0, Bf); split_pair(1, Bf); split_pair(2, Bf); split_pair(3, Bf);
       frags(0);
+    } else {  // prepared under tap 8 of the previous chunk, in the odd register sets
+      if (kc < 2) { DCS_STAMP(2 + 30 * kc); DCS_STAMP(3 + 30 * kc); }   // (no wait, no barrier here: they are in tap 8)
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Aop[0][mt][j] = Aop[1][mt][j];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) Bq[0][r][j] = Bq[1][r][j];
     }
     if (kc < 2) DCS_STAMP(4 + 30 * kc);
 #define DCS_SB __builtin_amdgcn_sched_barrier(0)
@@ -386,45 +419,51 @@ __global__ __launch_bounds__(256, 2) void mdcn_fwd_split_kernel(DcnK2 a) {
     auto tap_body = [&](auto TAP) {
       constexpr int tap = decltype(TAP)::value;
       constexpr int cur = tap & 1, nxt = cur ^ 1;
-      constexpr bool nx = tap + 1 < KK;
-      using TN = std::integral_constant<int, (tap + 1 < KK ? tap + 1 : tap)>;
-      using TNN = std::integral_constant<int, (tap + 2 < KK ? tap + 2 : tap)>;
+      using TN = std::integral_constant<int, (tap + 1) % KK>;   // tap 8 prepares tap 0 of the next chunk
       Geo gq;
       ds2f c[16];
       int fix = 0;
       DCS_SB;
-      if (nx) a_load(nxt, kc, tap + 1);
-      if (nx) geom_a(TN{}, om[nxt], gq);
+      if (tap == KK - 1) {
+        // the chunk's barrier (see the top of the loop): the next chunk's window is complete, this chunk's is free
+        static_assert(Sh::VM_BEHIND_DMA == 18, "the wait below is written out");
+        asm volatile("s_waitcnt vmcnt(18) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        xg = a.x + ((size_t)n * a.C + kcn * Sh::CPG) * HW;
+        a_x = a_x0 + (unsigned)((kc + 1) & 1) * (unsigned)(Sh::X_FLOATS * 4);
+        DCS_SB;
+      }
+      if (tap + 1 < KK) a_load(nxt, kc, tap + 1);
+      else a_load(nxt, kcn, 0);
+      if (tap + 3 < KK) om_load(g, tap + 3, om[tap % 3]);   // (om[tap % 3] held this tap's values: consumed one tap ago)
+      else om_load(gn, tap + 3 - KK, om[tap % 3]);
+      if (tap == 0) x_dma(kc + 1, Sh::NXI - 1);
+      if (tap < Sh::NXI - 1) x_dma(kc + 1, Sh::NXI - 2 - tap);    // the last one, under tap 5, is a piece every wave has
+      geom_a(TN{}, om[(tap + 1) % 3], gq);
       DCS_MF(0, 0, 0);
-      if (nx) { geom_b1(gq); geom_b2(gq, fix); }
+      geom_b1(gq); geom_b2(gq, fix);
       DCS_MF(0, 0, 1);
-      if (nx) corners_issue(gq.addr, c, 0);
+      corners_issue(gq.addr, c, 0);
       DCS_MF(0, 1, 0);
-      if (nx) corners_issue(gq.addr, c, 1);
+      corners_issue(gq.addr, c, 1);
       DCS_MF(0, 1, 1);
-      if (tap + 2 < KK) om_issue(TNN{}, om[cur]);  // (om[cur] held this tap's values: consumed one tap ago)
       DCS_MF(2, 0, 0);
-      if (nx) { landed_a(c); blend2(gq, c, 0, Bf); blend2(gq, c, 2, Bf); }
+      landed_a(c); blend2(gq, c, 0, Bf); blend2(gq, c, 2, Bf);
       DCS_MF(2, 0, 1);
-      if (nx) {
-        landed_b(c);
-        if (tap + 2 < KK) landed_om(om[cur]);
-        blend2(gq, c, 4, Bf); blend2(gq, c, 6, Bf);
-      }
+      landed_b(c); blend2(gq, c, 4, Bf); blend2(gq, c, 6, Bf);
       DCS_MF(2, 1, 0);
-      if (nx) {
-        if (fix) fixup(gq, Bf);
-      }
+      if (fix) fixup(gq, Bf);
       DCS_MF(2, 1, 1);
-      if (nx) split_pair(0, Bf);
+      split_pair(0, Bf);
       DCS_MF(1, 0, 0);
-      if (nx) split_pair(1, Bf);
+      split_pair(1, Bf);
       DCS_MF(1, 0, 1);
-      if (nx) split_pair(2, Bf);
+      split_pair(2, Bf);
       DCS_MF(1, 1, 0);
-      if (nx) split_pair(3, Bf);
+      split_pair(3, Bf);
       DCS_MF(1, 1, 1);
-      if (nx) frags(nxt);
+      frags(nxt);
       if (kc < 2) DCS_STAMP(5 + 30 * kc + tap);
     };
     tap_body(std::integral_constant<int, 0>{}); tap_body(std::integral_constant<int, 1>{});
@@ -435,7 +474,9 @@ __global__ __launch_bounds__(256, 2) void mdcn_fwd_split_kernel(DcnK2 a) {
 #undef DCS_MF
 #undef DCS_SB
 #undef DCS_PIN8
+    g = gn;
   }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last chunk's (empty) window DMAs: none outlives the workgroup's LDS
 
   DCS_STAMP(62);
   const TileOut t{a.out, wset_ptr(a.bias, a.b_gs, n, a.wdiv), nullptr, a.act, 0, 0, a.Cout, a.H, a.W};
