@@ -103,6 +103,9 @@ class ResizeAxis(Structure):
     _fields_ = [("first", c_void_p), ("weights", c_void_p), ("taps", c_int)]
 
 
+FLIP_W, FLIP_H = 1, 2                                             # dvsr_frame_flip's flags
+
+
 class EstimatorConfig(Structure):
     _fields_ = [(k, c_int) for k in ("kind", "nf", "in_nc", "scale", "nframes")]
 
@@ -227,6 +230,8 @@ def _declare(lib):
         "dvsr_frame_resize_taps": (I, [I, I]),
         "dvsr_frame_resize_table": (I, [I, I, I, P, P]),
         "dvsr_frame_resize": (I, [P, I, I, I, I, P, I, I, I, I, POINTER(ResizeAxis), POINTER(ResizeAxis), P]),
+        "dvsr_frame_flip": (I, [P, P, LL, I, I, I, P]),
+        "dvsr_frame_flip_mean": (I, [P, P, P, P, P, LL, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

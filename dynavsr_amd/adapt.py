@@ -526,7 +526,22 @@ def _clip_streams(device, n):
     return [torch.cuda.current_stream(key)] + have[:n - 1]
 
 
-def super_resolve_video(opt, net, clips, in_flight=2):
+def _check_flip_test(flip_test, who):
+    if not isinstance(flip_test, bool):
+        raise ValueError("%s: flip_test=%r must be a bool" % (who, flip_test))
+
+
+def _flip_test_forward(opt, net, lq):
+    """flipx4_forward of the reference (utils/util.py:232-254) on one clip [B,N,3,H,W], on the current stream: the forward
+    on the clip and on its three mirror images (frames.flip), then the un-flips and the mean in one launch (frames.flip_mean)."""
+    from . import frames as fio
+    if lq.dtype != torch.float32 or not lq.is_contiguous() or lq.data_ptr() % 16:
+        lq = lq.float().clone(memory_format=torch.contiguous_format)
+    ys = [net(backbone_input(opt, lq if v == 0 else fio.flip(lq, v))) for v in range(4)]
+    return fio.flip_mean(*[y if y.is_contiguous() else y.contiguous() for y in ys])
+
+
+def super_resolve_video(opt, net, clips, in_flight=2, flip_test=False):
     """The un-adapted forward of test_dynavsr.py:200-204 (`model.feed_data(val_data, need_GT=False); model.test()`) over a
     stream of clips, as a generator: yields the SR frame [B, 3, sH, sW] of every clip [B, N, 3, H, W], in order.
 
@@ -538,7 +553,13 @@ def super_resolve_video(opt, net, clips, in_flight=2):
     by the stream) except the weight packing, which only the first clip on a stream does (the workspace and the packs in it
     are kept for the video; an in-place update of the weights between clips re-packs), so the outputs are bit-identical to
     `net(clip)`.  A yielded frame stays valid until the generator is
-    advanced `in_flight` times; clips and results are ordered against the caller's current stream."""
+    advanced `in_flight` times; clips and results are ordered against the caller's current stream.
+
+    flip_test=True: the reference's x4 self-ensemble (`flip_test` of test_Vid4_REDS4_with_GT.py, util.flipx4_forward) -- per
+    clip four forwards, on the clip and on frames.flip of it in W, in H and in both, and one frames.flip_mean that un-flips
+    and averages them in the reference's order, all on the clip's stream; the clip's and the output's width must be
+    multiples of 4.  False takes exactly the calls above.  (The x8 ensemble with transposes is not provided.)"""
+    _check_flip_test(flip_test, "super_resolve_video")
     main = None
     streams = None
     pending = []
@@ -565,7 +586,7 @@ def super_resolve_video(opt, net, clips, in_flight=2):
             if s != main:
                 s.wait_stream(main)                  # the clip (and the weights) were produced on the caller's stream
             with torch.cuda.stream(s), torch.no_grad(), frozen:
-                sr = net(backbone_input(opt, lq))
+                sr = _flip_test_forward(opt, net, lq) if flip_test else net(backbone_input(opt, lq))
                 ev = torch.cuda.Event()
                 ev.record(s)
             if s != main:
@@ -870,7 +891,8 @@ def _video_format(frames, layout):
 
 
 def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, layout=None, out=None, pad_mode='reflect',
-                         multiple=None, matrix='bt601', yuv_range='limited', cuts=None, cut_threshold=10.0, out_size=None):
+                         multiple=None, matrix='bt601', yuv_range='limited', cuts=None, cut_threshold=10.0, out_size=None,
+                         flip_test=False):
     """Super-resolves a VIDEO: `frames` is a [T,3,H,W] tensor or a list of [3,H,W] frames (CPU or GPU); yields the SR frame
     [1,3,sH,sW] of every frame, in order -- what `net(frames[index_generation(i, T, nframes, padding)][None])` gives, the
     sliding-window test of the reference's video datasets (video_test_dataset_int.py:219, `padding: new_info` in the
@@ -917,12 +939,25 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     sH x sW crop -- never the padding around it -- is resampled on the device (frames.resize: separable antialiased bicubic,
     torch's interpolate(mode='bicubic', antialias=True); per axis sH / oh <= 4 and oh / sH <= 2) by one more launch on the
     window's stream, in front of the conversion.  None, or (sH, sW) itself, takes exactly the calls described above.
+    More GPU time for a better frame: `flip_test` = True is the reference's x4 self-ensemble (`flip_test` of
+    test_Vid4_REDS4_with_GT.py, util.flipx4_forward; EDVR's published "with self-ensemble" numbers) -- the network runs on
+    every window as it is, mirrored in W, in H and in both, and the un-flipped outputs are averaged, (((y0 + flipW(y1)) +
+    flipH(y2)) + flipHW(y3)) / 4 in this order (frames.flip / frames.flip_mean, csrc/frame_flip.hip).  EDVR: the
+    frame cache holds 4 x stream_slots slots, variant v (0 none, 1 W, 2 H, 3 both) of frame f in slot v * slots + f % slots;
+    a frame is still extracted once per variant -- variant 0 by the call above, the others from frames.flip of the PADDED
+    fp32 frame (the network sees flip(pad(x)): the padding stays at the bottom and right of the source) -- and a window runs
+    four fuse tapes and one flip_mean that writes the tensor the single fuse tape writes otherwise, so crop, `out_size`,
+    every `out` and `cuts` work as described.  Other networks: super_resolve_video(flip_test=True), which needs a (padded)
+    width that is a multiple of 4.  False takes exactly the calls described above: no further plan, buffer or launch.  Not
+    provided: the x8 ensemble with transposes (a transposed frame needs a second plan of W x H), and flip-test inside
+    Video_base_model.test() or the adaptation loops.
     Arguments are checked before the first GPU call (ValueError)."""
     from . import frames as fio
     from .models.archs.EDVR_arch import EDVR
     T = len(frames)
     if T < 1:
         raise ValueError("super_resolve_frames: no frames")
+    _check_flip_test(flip_test, "super_resolve_frames")
     in_flight = max(1, int(in_flight))
     is_edvr = isinstance(net, EDVR)
     if pad_mode not in ('reflect', 'replicate'):
@@ -976,11 +1011,14 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         cuts = [a for a, _ in scene_bounds(T, cuts)][1:]
     if not is_edvr:
         windows, _ = video_windows(T, n, padding, cuts)            # (validates T, the mode and the cuts)
+        if flip_test and (w if Hp is None else Wp) % 4:
+            raise ValueError("super_resolve_frames: flip_test needs a width that is a multiple of 4, got %d (pass multiple=4)"
+                             % (w if Hp is None else Wp))
         if Hp is None:
             def clips():
                 for win in windows:
                     yield torch.stack([frames[j] for j in win])[None]
-            yield from super_resolve_video(opt, net, clips(), in_flight)
+            yield from super_resolve_video(opt, net, clips(), in_flight, flip_test)
             return
         kept = {}                                      # frame -> its ingested tensor; the last 2n are kept
 
@@ -995,7 +1033,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         def padded_clips():
             for win in windows:
                 yield torch.stack([ingested(j) for j in win])[None]
-        for sr in super_resolve_video(opt, net, padded_clips(), in_flight):
+        for sr in super_resolve_video(opt, net, padded_clips(), in_flight, flip_test):
             s = sr.shape[-2] // Hp
             if out_size is not None:
                 if s != sr_scale:
@@ -1019,7 +1057,8 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     direct = Hp is None                               # fp32 planar frames of the plan's size in, the fuse tape's tensor out
     ph, pw = (h, w) if direct else (Hp, Wp)
     slots = stream_slots(net.nframes, in_flight, 1 if cuts is None else len(cuts) + 1)
-    plan = engine.get_stream_plan(net._cfg(), ph, pw, slots, dev)
+    nv = 4 if flip_test else 1                        # variants of a frame in the cache: slot v * slots + f % slots
+    plan = engine.get_stream_plan(net._cfg(), ph, pw, nv * slots, dev)
     main = torch.cuda.current_stream(dev)
     streams = _clip_streams(dev, in_flight)
     with torch.cuda.device(dev):
@@ -1029,6 +1068,20 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     extracted, readers, pending = {}, {}, []   # slot -> event of its extraction; slot -> events of the windows reading it
     staging = {}                               # stream index -> the fuse tape's output when a crop / conversion follows it
     resized = {}                               # stream index -> the resampled frame when a conversion follows it
+    flipped = {}                               # flip_test: stream index -> [the padded frame, one mirror image of it]
+    fused = {}                                 # flip_test: stream index -> the four fuse tapes' outputs
+
+    def fuse(k, wslots, dst):
+        """The window in `wslots` -> dst [1,3,s ph,s pw] on the current stream (of index k): the fuse tape, or, with
+        flip_test, the four variants' fuse tapes and the launch that un-flips and averages them."""
+        if not flip_test:
+            plan.fuse(leaves, wslots, cache, dst)
+            return
+        if k not in fused:
+            fused[k] = [torch.empty_like(dst) for _ in range(nv)]
+        for v in range(nv):
+            plan.fuse(leaves, [v * slots + slot for slot in wslots], cache, fused[k][v])
+        fio.flip_mean(*fused[k], out=dst)
     was_training = net.training
     net.eval()
     try:
@@ -1048,27 +1101,40 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                         x = engine._prep(x if x.is_cuda else x.to(dev))
                     else:
                         x = fio.to_device(x, dev)                    # (8-bit frames travel as bytes)
-                    for ev in readers.pop(slot, ()):
-                        s.wait_event(ev)
+                    for v in range(nv):
+                        for ev in readers.pop(v * slots + slot, ()):
+                            s.wait_event(ev)
+                    if flip_test:                     # the padded fp32 frame, then its mirror images one at a time
+                        k = step % len(streams)
+                        if k not in flipped:
+                            flipped[k] = [torch.empty((3, ph, pw), dtype=torch.float32, device=dev) for _ in range(2)]
+                        if direct:
+                            padded = x if x.data_ptr() % 16 == 0 else flipped[k][0].copy_(x)
+                        else:
+                            padded = fio.ingest(x, lay, mult, pad_mode, out=flipped[k][0], matrix=matrix, yuv_range=yuv_range)
                     if direct:
                         plan.extract(leaves, x, slot, cache)
                     else:
                         x = plan.extract_frame(leaves, x, slot, cache, lay, pad_mode, matrix, yuv_range)
-                    extracted[slot] = torch.cuda.Event()
-                    extracted[slot].record(s)
+                    for v in range(1, nv):
+                        plan.extract(leaves, fio.flip(padded, v, out=flipped[k][1]), v * slots + slot, cache)
+                    ev = torch.cuda.Event()
+                    ev.record(s)
+                    for v in range(nv):
+                        extracted[v * slots + slot] = ev
                     if s != main:
                         for t in (x,) if torch.is_tensor(x) else x:
                             t.record_stream(s)
-                for slot in set(wslots):
-                    s.wait_event(extracted[slot])
+                for ev in set(extracted[v * slots + slot] for v in range(nv) for slot in set(wslots)):
+                    s.wait_event(ev)
                 if direct or (out_fmt == 'float' and (ph, pw) == (h, w) and out_size is None):
                     sr = torch.empty((1, 3, net.scale * ph, net.scale * pw), dtype=torch.float32, device=dev)
-                    plan.fuse(leaves, wslots, cache, sr)
+                    fuse(step % len(streams), wslots, sr)
                 else:
                     k = step % len(streams)
                     if k not in staging:
                         staging[k] = torch.empty((1, 3, net.scale * ph, net.scale * pw), dtype=torch.float32, device=dev)
-                    plan.fuse(leaves, wslots, cache, staging[k])
+                    fuse(k, wslots, staging[k])
                     if out_size is not None and out_fmt == 'float':
                         sr = fio.resize(staging[k], net.scale * h, net.scale * w, out_size)[None]
                     elif out_size is not None:
@@ -1083,7 +1149,8 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                 ev = torch.cuda.Event()
                 ev.record(s)
             for slot in set(wslots):
-                readers.setdefault(slot, []).append(ev)
+                for v in range(nv):
+                    readers.setdefault(v * slots + slot, []).append(ev)
             pending.append((sr, ev))
         while pending:
             sr, ev = pending.pop(0)

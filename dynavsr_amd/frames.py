@@ -47,6 +47,11 @@ A target output size (csrc/frame_resize.hip: dvsr_frame_resize):
 
 The resampler is separable antialiased bicubic, torch.nn.functional.interpolate(.., mode='bicubic', antialias=True,
 align_corners=False); per axis n_in / n_out <= 4 and n_out / n_in <= 2.
+
+The flip-test x4 self-ensemble (csrc/frame_flip.hip: dvsr_frame_flip / dvsr_frame_flip_mean):
+
+    flip(x, flags)                       -> fp32 [..., H, W] mirrored in W (flags & 1) and / or H (flags & 2), one launch
+    flip_mean(y0, yw, yh, yhw)           -> (((y0 + yw.flip(-1)) + yh.flip(-2)) + yhw.flip((-2, -1))) * 0.25, one launch
 """
 import ctypes
 import numbers
@@ -365,6 +370,74 @@ def _resize(sr, h, w, size, out=None):
         L.check(L.lib().dvsr_frame_resize(sr.data_ptr(), Hs, Ws, h, w, buf.data_ptr(), oh, Wb, oh, ow, ctypes.byref(rows),
                                           ctypes.byref(cols), L.stream()), "dvsr_frame_resize")
     return buf, ow
+
+
+def _flip_operand(x, what):
+    """The checks of flip() / flip_mean() on one tensor; no GPU call."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() < 2:
+        raise ValueError("%s must be an fp32 [..., H, W] tensor, got %s" % (
+            what, "%s %s" % (x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x).__name__))
+    if x.numel() < 1 or x.shape[-1] % 4:
+        raise ValueError("%s: %s must be non-empty with a width that is a multiple of 4" % (what, tuple(x.shape)))
+    if not x.is_contiguous() or x.data_ptr() % 16:
+        raise ValueError("%s must be contiguous and 16-byte aligned" % what)
+
+
+def _flip_out(out, like, what):
+    if out is None:
+        return
+    if not (torch.is_tensor(out) and out.dtype == torch.float32 and out.shape == like.shape and out.device == like.device):
+        raise ValueError("%s: out must be an fp32 %s tensor on %s" % (what, list(like.shape), like.device))
+    if not out.is_contiguous() or out.data_ptr() % 16:
+        raise ValueError("%s: out must be contiguous and 16-byte aligned" % what)
+
+
+def flip(x, flags, out=None):
+    """x (fp32 [..., H, W] on the GPU, contiguous, 16-byte aligned, W a multiple of 4) mirrored in W (flags & 1), in H
+    (flags & 2), in both (3) or copied (0): torch.flip(x, (-1,)) / (-2,) / (-2, -1), one launch with 16-byte accesses only
+    (dvsr_frame_flip).  out: the tensor to fill, of x's shape -- never x itself.  Arguments are checked before the GPU call
+    (ValueError)."""
+    if isinstance(flags, bool) or not isinstance(flags, numbers.Integral) or not 0 <= flags <= 3:
+        raise ValueError("flip: flags=%r (0, or FLIP_W = 1 | FLIP_H = 2)" % (flags,))
+    _flip_operand(x, "flip: x")
+    _flip_out(out, x, "flip")
+    if out is not None and out.data_ptr() == x.data_ptr():
+        raise ValueError("flip: out is x (flipping in place is not provided)")
+    if not x.is_cuda:
+        raise RuntimeError("flip runs on the GPU (libdynavsr_hip); there is no CPU path")
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty_like(x)
+        L.check(L.lib().dvsr_frame_flip(x.data_ptr(), out.data_ptr(), x.numel() // (H * W), H, W, int(flags), L.stream()),
+                "dvsr_frame_flip")
+    return out
+
+
+def flip_mean(y0, yw, yh, yhw, out=None):
+    """The mean of the flip-test x4 self-ensemble: y0, yw, yh, yhw are the network's outputs on a clip as it is, mirrored in W,
+    in H and in both (fp32 [..., H, W] on one GPU, one shape, contiguous, 16-byte aligned, W a multiple of 4) ->
+    (((y0 + yw.flip(-1)) + yh.flip(-2)) + yhw.flip((-2, -1))) * 0.25, the additions in this order: the reference's
+    flipx4_forward (utils/util.py:232-254) bit for bit, in one launch that reads each input once (dvsr_frame_flip_mean).
+    out: the tensor to fill -- none of the inputs.  Arguments are checked before the GPU call (ValueError)."""
+    ys = (y0, yw, yh, yhw)
+    for i, y in enumerate(ys):
+        _flip_operand(y, "flip_mean: input %d" % i)
+        if y.shape != y0.shape or y.device != y0.device:
+            raise ValueError("flip_mean: input %d is %s on %s, input 0 is %s on %s" % (i, tuple(y.shape), y.device, tuple(y0.shape),
+                                                                                     y0.device))
+    _flip_out(out, y0, "flip_mean")
+    if out is not None and any(out.data_ptr() == y.data_ptr() for y in ys):
+        raise ValueError("flip_mean: out is one of the inputs (averaging in place is not provided)")
+    if not y0.is_cuda:
+        raise RuntimeError("flip_mean runs on the GPU (libdynavsr_hip); there is no CPU path")
+    H, W = int(y0.shape[-2]), int(y0.shape[-1])
+    with torch.cuda.device(y0.device):
+        if out is None:
+            out = torch.empty_like(y0)
+        L.check(L.lib().dvsr_frame_flip_mean(y0.data_ptr(), yw.data_ptr(), yh.data_ptr(), yhw.data_ptr(), out.data_ptr(),
+                                             y0.numel() // (H * W), H, W, L.stream()), "dvsr_frame_flip_mean")
+    return out
 
 
 def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='limited', size=None):

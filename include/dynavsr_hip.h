@@ -483,6 +483,26 @@ int dvsr_frame_resize_table(int n_in, int n_out, int taps, int* first, float* we
 int dvsr_frame_resize(const float* src, int Hs, int Ws, int h, int w, float* dst, int Ho, int Wo, int oh, int ow,
                       const dvsr_resize_axis* rows, const dvsr_resize_axis* cols, dvsr_stream_t stream);
 
+/* ---- Flip-test x4 self-ensemble: the flips in front of the network and the mean of the un-flipped outputs behind it ----
+ * The reference's flipx4_forward (utils/util.py:232-254; `flip_test` of test_Vid4_REDS4_with_GT.py) runs the network on a clip
+ * as it is, flipped in W, flipped in H and flipped in both, un-flips the three outputs and averages the four.
+ * Both functions work on contiguous fp32 planar [planes][H][W] with W % 4 == 0 and 16-byte aligned pointers -- an ingested
+ * frame, a clip (planes = B N 3), the fuse tape's output.
+ * dvsr_frame_flip: dst[p][y][x] = src[p][fy(y)][fx(x)], fx(x) = W-1-x if flags & DVSR_FLIP_W (else x), fy(y) = H-1-y if
+ *   flags & DVSR_FLIP_H (else y); flags = 0 is a copy.
+ * dvsr_frame_flip_mean: dst[p][y][x] = (((y0[p][y][x] + yw[p][y][W-1-x]) + yh[p][H-1-y][x]) + yhw[p][H-1-y][W-1-x]) * 0.25f,
+ *   the additions in exactly this order (the reference's statements), in fp32 and never contracted: the bits of the torch
+ *   composition.
+ * One launch each, 16-byte loads and stores only, no atomics, deterministic; every element of dst is written and nothing else.
+ * dst must not be one of the sources (nor overlap one): nothing works in place.
+ * Bad arguments (null pointer, planes / H / W < 1, W no multiple of 4, a misaligned pointer, flags outside 0 .. 3, dst equal
+ * to a source) return DVSR_ERR_INVALID before any launch. */
+#define DVSR_FLIP_W 1
+#define DVSR_FLIP_H 2
+int dvsr_frame_flip(const float* src, float* dst, long long planes, int H, int W, int flags, dvsr_stream_t stream);
+int dvsr_frame_flip_mean(const float* y0, const float* yw, const float* yh, const float* yhw, float* dst,
+                         long long planes, int H, int W, dvsr_stream_t stream);
+
 /* ---- Down-scaling estimators MFDN / SFDN as one launch tape ------------------------------------
  * Replaces DirectKernelEstimatorVideo.forward (models/archs/LRimg_estimator.py:92-117, "MFDN":
  * Conv3d(k3)+ReplicationPad3d, ReflectionPad2d + 3x3 / 4x4-stride-2 Conv2d, Conv3d, 1x1, per-frame
