@@ -876,23 +876,41 @@ extern "C" size_t dvsr_mdcn_forward_fast_workspace_bytes(int C, int Cout, int dg
   return dvsr::conv2_pack_floats(3, Cout, C, 8, 0, dvsr::PackLayout::DCN_SPLIT) * sizeof(float);   // (the larger layout: either fits)
 }
 
-extern "C" int dvsr_mdcn_forward_fast(const float* x, const float* offset, const float* mask, const float* w,
-                                      const float* b, float* out, int N, int C, int H, int W, int Cout, int dg,
-                                      int act, void* workspace, size_t workspace_bytes, dvsr_stream_t stream) {
+// The pack form of the same entry: om = [N, 27 dg, H, W], offsets then mask LOGITS (the sigmoid is taken in the kernel) -- the
+// call the engine's DCN op makes, with the same kernel selection.
+static int mdcn_forward_fast_run(const float* x, const float* offset, long long off_bs, const float* mask, long long msk_bs,
+                                 int mask_logit, const float* w, const float* b, float* out, int N, int C, int H, int W,
+                                 int Cout, int dg, int act, void* workspace, size_t workspace_bytes, hipStream_t st,
+                                 const char* who) {
   using namespace dvsr;
-  DVSR_REQUIRE(x && offset && mask && w && out && workspace, DVSR_ERR_INVALID, "mdcn_forward_fast: null pointer");
-  DVSR_REQUIRE(dg > 0 && C % (dg * 8) == 0, DVSR_ERR_UNSUPPORTED, "mdcn_forward_fast: needs C/dg to be a multiple of 8");
+  DVSR_REQUIRE(x && offset && mask && w && out && workspace, DVSR_ERR_INVALID, "%s: null pointer", who);
+  DVSR_REQUIRE(dg > 0 && C % (dg * 8) == 0, DVSR_ERR_UNSUPPORTED, "%s: needs C/dg to be a multiple of 8", who);
   DVSR_REQUIRE(workspace_bytes >= dvsr_mdcn_forward_fast_workspace_bytes(C, Cout, dg), DVSR_ERR_WORKSPACE,
-               "mdcn_forward_fast: workspace too small");
+               "%s: workspace too small", who);
   const bool aligned = (((uintptr_t)x | (uintptr_t)offset | (uintptr_t)mask) & 15) == 0 && ((size_t)H * W) % 4 == 0;
   // (unaligned tensors: the register-staged fp32 kernel and its pack)
   const PackLayout layout = aligned ? mdcn_pack_layout(W) : PackLayout::INTERLEAVED;
   PackTable t;
   t.n = 1;
   t.e[0] = conv2_pack_entry(w, (float*)workspace, 3, Cout, C, 8, 0, layout);
-  int rc = pack_weights_run(t, (hipStream_t)stream);
+  int rc = pack_weights_run(t, st);
   if (rc) return rc;
+  return mdcn_forward_packed_run(x, offset, off_bs, mask, msk_bs, mask_logit, (const float*)workspace, b, out, N, C, H, W, Cout,
+                                 dg, act, st, 1, 0, 0, layout);
+}
+
+extern "C" int dvsr_mdcn_forward_fast(const float* x, const float* offset, const float* mask, const float* w,
+                                      const float* b, float* out, int N, int C, int H, int W, int Cout, int dg,
+                                      int act, void* workspace, size_t workspace_bytes, dvsr_stream_t stream) {
   const long long P = (long long)H * W;
-  return mdcn_forward_packed_run(x, offset, (long long)dg * 18 * P, mask, (long long)dg * 9 * P, 0,
-                                 (const float*)workspace, b, out, N, C, H, W, Cout, dg, act, (hipStream_t)stream, 1, 0, 0, layout);
+  return mdcn_forward_fast_run(x, offset, (long long)dg * 18 * P, mask, (long long)dg * 9 * P, 0, w, b, out, N, C, H, W, Cout,
+                               dg, act, workspace, workspace_bytes, (hipStream_t)stream, "mdcn_forward_fast");
+}
+
+extern "C" int dvsr_mdcn_pack_forward_fast(const float* x, const float* om, const float* w, const float* b, float* out,
+                                           int N, int C, int H, int W, int Cout, int dg, int act, void* workspace,
+                                           size_t workspace_bytes, dvsr_stream_t stream) {
+  const long long P = (long long)H * W, bs = (long long)dg * 27 * P;
+  return mdcn_forward_fast_run(x, om, bs, om ? om + (size_t)dg * 18 * P : nullptr, bs, 1, w, b, out, N, C, H, W, Cout, dg, act,
+                               workspace, workspace_bytes, (hipStream_t)stream, "mdcn_pack_forward_fast");
 }

@@ -444,7 +444,16 @@ __global__ __launch_bounds__(256, 2) void mdcn_bwd_fused_kernel(DcnF a) {
   // (round 6: the scale is set from max |dcol| x max |mask| -- an upper bound of the largest product, so the sums still cannot
   // overflow; a sigmoid mask is at most 1 and costs nothing here, plain masks are read once for their maximum.  Against the
   // exact maximum this gives away log2(max |mask| / the mask at the largest |dcol|) of the 16 spare bits.)
+  // The window's own domain:
+  //  * precision is relative to the WORKGROUP's maximum -- 8 channels, one tile --, not per channel: a channel whose |dcol| is
+  //    2^-k of its chunk's largest keeps 40 - k bits;
+  //  * the scale's exponent is clamped so that 2^qexp and 2^-qexp are normal fp32 numbers (unclamped, 2^(40 - aexp) is +inf for
+  //    a maximum below 2^-87, and 0 x inf = NaN on the lanes that own no sample): a maximum below 2^-86 lands at
+  //    2^(126 + aexp) instead of 2^40, one bit fewer per halving -- 27 bits at 2^-100, 17 at 2^-110, none below 2^-126;
+  //  * fixed point holds no inf / NaN: when the workgroup's largest |dcol| x |mask| is not finite the flush writes NaN to its
+  //    whole window (the maximum is taken on the bit patterns, so that a NaN wins it: fmaxf would drop it).
   float amax = 0.f, mmax = 1.f;
+  unsigned abits = 0u;   // max |dcol| as a bit pattern: ordered like the values, inf and NaN above every finite one
   if (!a.mask_logit) {
     mmax = 0.f;
 #pragma unroll
@@ -457,18 +466,21 @@ __global__ __launch_bounds__(256, 2) void mdcn_bwd_fused_kernel(DcnF a) {
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-      for (int cq = 0; cq < 4; ++cq) amax = fmaxf(amax, fabsf(acc[tap >> 2][nt][(tap & 3) * 4 + cq]));
+      for (int cq = 0; cq < 4; ++cq) abits = max(abits, __float_as_uint(acc[tap >> 2][nt][(tap & 3) * 4 + cq]) & 0x7fffffffu);
   for (int o = 32; o > 0; o >>= 1) {
-    amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    abits = max(abits, (unsigned)__shfl_xor((int)abits, o, 64));
     mmax = fmaxf(mmax, __shfl_xor(mmax, o, 64));
   }
-  if (lane == 0) { s_max[wave] = amax; s_max[4 + wave] = mmax; }
+  if (lane == 0) { s_max[wave] = __uint_as_float(abits); s_max[4 + wave] = mmax; }
   __syncthreads();  // all waves are done with s_wt
-  amax = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3])) * fmaxf(fmaxf(s_max[4], s_max[5]), fmaxf(s_max[6], s_max[7]));
+  abits = max(max(__float_as_uint(s_max[0]), __float_as_uint(s_max[1])), max(__float_as_uint(s_max[2]), __float_as_uint(s_max[3])));
+  amax = __uint_as_float(abits) * fmaxf(fmaxf(s_max[4], s_max[5]), fmaxf(s_max[6], s_max[7]));
+  const bool nonfin = !(amax <= 3.402823466e+38f);   // inf or NaN: the same for every lane of the workgroup
   int aexp = 0;
   (void)frexpf(amax, &aexp);  // amax = f * 2^aexp, f in [0.5, 1)
-  const float qscale = amax > 0.f ? ldexpf(1.f, 40 - aexp) : 1.f;
-  const float qinv = amax > 0.f ? ldexpf(1.f, aexp - 40) : 1.f;
+  const int qexp = max(min(40 - aexp, 126), -126);
+  const float qscale = amax > 0.f ? ldexpf(1.f, qexp) : 1.f;
+  const float qinv = amax > 0.f ? ldexpf(1.f, -qexp) : 1.f;
   for (int idx = tid; idx < 8 * XPX; idx += 256) s_gq[idx] = 0ull;
   __syncthreads();
   DCNB_STAMP(4);
@@ -568,7 +580,9 @@ __global__ __launch_bounds__(256, 2) void mdcn_bwd_fused_kernel(DcnF a) {
           // (a sample that left the window keeps d: loop 2b needs it, and stores the exact sample instead)
           COLR(tap, nt, cq) = ((int)pv[nt] & (inwin ^ 1)) ? d : val * mk;
         }
-        gm = ok ? gm : 0.f; gh *= mk; gw *= mk;
+        // (selects, not products with mk = 0: a sample this path does not own has read a clamped cell, and 0 x inf = NaN would
+        // reach goffset through the atomics of the two-chunk form, which loop 2b cannot overwrite)
+        gm = ok ? gm : 0.f; gh = ok ? gh * m : 0.f; gw = ok ? gw * m : 0.f;
         // the partner lane (other 4 channels of the same pixel) completes the sums
         gm += __shfl_xor(gm, 32, 64);
         gh += __shfl_xor(gh, 32, 64);
@@ -668,8 +682,8 @@ __global__ __launch_bounds__(256, 2) void mdcn_bwd_fused_kernel(DcnF a) {
   if (gxg)
   for (int idx = tid; idx < 8 * XPX; idx += 256) {
     const long long q = (long long)s_gq[idx];
-    if (q == 0) continue;
-    const float v = (float)q * qinv;
+    if (q == 0 && !nonfin) continue;
+    const float v = nonfin ? __builtin_nanf("") : (float)q * qinv;   // (a non-finite contribution left some integer behind)
     const int c = idx / XPX, r = idx - c * XPX;
     const int ry = r / XW, rx = r - ry * XW;
     const int gy_ = wy0 + ry, gx_ = wx0 + rx;

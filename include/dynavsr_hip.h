@@ -93,6 +93,14 @@ int dvsr_mdcn_pack_forward(const float* x, const float* om, const float* w, cons
                            int stride, int pad, int dil, int groups, int dg, int act,
                            dvsr_stream_t stream);
 
+/* dvsr_mdcn_forward_fast on `om` (offsets, then mask logits: the sigmoid is taken in the sampler): the kernels and the
+ * kernel selection of the engine's DCN op -- on aligned tensors with W % 4 == 0 the bf16-pipe kernel under the exact 3-way
+ * split, otherwise the register-staged fp32 one.  dvsr_mdcn_pack_forward above runs the generic gather kernel on every shape.
+ * Workspace: dvsr_mdcn_forward_fast_workspace_bytes(). */
+int dvsr_mdcn_pack_forward_fast(const float* x, const float* om, const float* w, const float* b, float* out, int N,
+                                int C, int H, int W, int Cout, int dg, int act, void* workspace,
+                                size_t workspace_bytes, dvsr_stream_t stream);
+
 /* ---- dense convolution ------------------------------------------------------------------------
  * Replaces nn.Conv2d (+ the torch.cat feeding it, + the activation / residual add /
  * nn.PixelShuffle(2) following it) everywhere in EDVR_arch.py / arch_util.py:34-52.

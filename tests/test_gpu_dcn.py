@@ -126,9 +126,12 @@ def _finite(name, t):
         "before writing)" % (name, int((~torch.isfinite(t)).sum()))
 
 
-def gpu_forward(cs, kind):
-    """kind: 'plain' = dvsr_mdcn_forward, 'pack' = dvsr_mdcn_pack_forward on cat(offset, logit(mask)), 'fast' =
-    dvsr_mdcn_forward_fast (stride = pad = dil = 1 only).  The output starts as NaN."""
+def gpu_forward(cs, kind, finite=True):
+    """kind: 'plain' = dvsr_mdcn_forward, 'pack' = dvsr_mdcn_pack_forward on cat(offset, logit(mask)) (both: the generic
+    gather kernel, fp32 MFMAs, any geometry), 'fast' = dvsr_mdcn_forward_fast, 'packfast' = dvsr_mdcn_pack_forward_fast on
+    the same cat(offset, logit(mask)) (stride = pad = dil = 1 only: the LDS-window kernels the engine runs -- the split kernel
+    on aligned W % 4 == 0, reading masks / mask logits).  The output starts as NaN and must come back finite
+    (finite=False: the caller feeds non-finite inputs and checks where the output is finite itself)."""
     from dynavsr_amd import _lib as L
     n, c, dg, cout, h, w, stride, pad, dil = cs["shape"]
     x, wt, b = dev(cs["x"]), dev(cs["wt"]), dev(cs["b"])
@@ -143,6 +146,14 @@ def gpu_forward(cs, kind):
         L.check(L.lib().dvsr_mdcn_pack_forward(L.ptr(x), L.ptr(om), L.ptr(wt), L.ptr(b), L.ptr(out), n, c, h, w, cout,
                                                3, 3, stride, pad, dil, 1, dg, L.ACT_NONE, L.stream()),
                 "dvsr_mdcn_pack_forward")
+    elif kind == "packfast":
+        assert (stride, pad, dil) == (1, 1, 1)
+        om = dev(torch.cat([cs["off"], cs["lg"]], 1))
+        nbytes = int(L.lib().dvsr_mdcn_forward_fast_workspace_bytes(c, cout, dg))
+        ws = nan_bytes(nbytes)
+        L.check(L.lib().dvsr_mdcn_pack_forward_fast(L.ptr(x), L.ptr(om), L.ptr(wt), L.ptr(b), L.ptr(out), n, c, h, w,
+                                                    cout, dg, L.ACT_NONE, ws.data_ptr(), nbytes, L.stream()),
+                "dvsr_mdcn_pack_forward_fast")
     else:
         assert kind == "fast" and (stride, pad, dil) == (1, 1, 1)
         off, m = dev(cs["off"]), dev(cs["m"])
@@ -152,13 +163,15 @@ def gpu_forward(cs, kind):
                                                h, w, cout, dg, L.ACT_NONE, ws.data_ptr(), nbytes, L.stream()),
                 "dvsr_mdcn_forward_fast")
     torch.cuda.synchronize()
-    _finite("out (%s)" % kind, out)
+    if finite:
+        _finite("out (%s)" % kind, out)
     return out
 
 
-def gpu_backward(cs, want_gx=True, want_gw=True, want_gb=True, gx_init=None):
+def gpu_backward(cs, want_gx=True, want_gw=True, want_gb=True, gx_init=None, finite=True):
     """dvsr_mdcn_backward with NaN in goffset / gmask / gw / gb and in the workspace; gx starts as zeros (or gx_init: the
-    op accumulates into it).  Returns a dict of the outputs that were asked for."""
+    op accumulates into it).  Returns a dict of the outputs that were asked for; all of them must be finite (finite=False:
+    the caller feeds non-finite inputs and checks where the outputs are finite itself)."""
     from dynavsr_amd import _lib as L
     n, c, dg, cout, h, w, stride, pad, dil = cs["shape"]
     x, off, m, wt, go = (dev(cs[k]) for k in ("x", "off", "m", "wt", "go"))
@@ -175,8 +188,9 @@ def gpu_backward(cs, want_gx=True, want_gw=True, want_gb=True, gx_init=None):
                                        ws.data_ptr(), nbytes, L.stream()), "dvsr_mdcn_backward")
     torch.cuda.synchronize()
     got = {k: v for k, v in zip(GRADS, (gx, goff, gm, gw, gb)) if v is not None}
-    for k, v in got.items():
-        _finite(k, v)
+    if finite:
+        for k, v in got.items():
+            _finite(k, v)
     return got
 
 
@@ -190,7 +204,7 @@ def check(tag, got, ref):
 
 
 def check_forwards(tag, cs, kinds):
-    ref = {"plain": cs["out"], "fast": cs["out"], "pack": cs["out_pack"]}
+    ref = {"plain": cs["out"], "fast": cs["out"], "pack": cs["out_pack"], "packfast": cs["out_pack"]}
     check(tag, {k: gpu_forward(cs, k) for k in kinds}, ref)
 
 
@@ -269,10 +283,11 @@ def test_gate_backward(case):
 
 @pytest.mark.parametrize("case", GATE, ids=_id)
 def test_gate_forward(case):
-    """The same inputs through the three forward entries; dvsr_mdcn_forward_fast takes the split kernel at W = 36 and the
-    register-staged one at W = 35 (DVSR_DCN_FWD=dma / reg move W = 36 to the other two kernels, see below)."""
+    """The same inputs through the four forward entries; dvsr_mdcn_forward_fast and dvsr_mdcn_pack_forward_fast take the split
+    kernel at W = 36 and the register-staged one at W = 35 (DVSR_DCN_FWD=dma / reg move W = 36 to the other two kernels, see
+    below)."""
     cs = make_case(*case, 1, 1, 1, gate=True)
-    check_forwards("gate " + _id(case) + " fwd", cs, ("plain", "fast", "pack"))
+    check_forwards("gate " + _id(case) + " fwd", cs, ("plain", "fast", "pack", "packfast"))
 
 
 # ---- 4. kernels behind process-wide switches (read once per process: each in a fresh child) ---------------------------

@@ -9,7 +9,8 @@ blocks, windows whose halo is in the image on one side only, and the sampling-ga
 sample of two rows through the global fix-up.
 
 Reference: the fp64 oracle each case of tests/test_gpu_dcn.py carries; bar: that file's TOL (relative L2).  Both
-instantiations run: 'fast' reads masks, 'pack' reads mask logits.  Offsets are N(0, 2^2) against a 4-pixel halo, so a
+instantiations run: 'fast' reads masks, 'packfast' reads mask logits ('pack', the generic gather kernel on the same logits,
+runs beside them).  Offsets are N(0, 2^2) against a 4-pixel halo, so a
 wrong group index, buffer parity or stale window shows as an error of order 1.
 """
 import pytest
@@ -42,15 +43,15 @@ def _case(case, gate):
 def test_window_forward(case, gate):
     cs = _case(case, gate)
     assert TOL == 2e-5
-    check("window " + _id(case) + (" gate" if gate else ""), {k: gpu_forward(cs, k) for k in ("fast", "pack")},
-          {"fast": cs["out"], "pack": cs["out_pack"]})
+    check("window " + _id(case) + (" gate" if gate else ""), {k: gpu_forward(cs, k) for k in ("fast", "pack", "packfast")},
+          {"fast": cs["out"], "pack": cs["out_pack"], "packfast": cs["out_pack"]})
 
 
 def test_window_forward_repeatable():
     """A, B, A again: the three results of A are bit-equal, so nothing depends on what an earlier launch left in the LDS
     (both window buffers' out-of-image slots are zeroed by every workgroup, every other slot is written before it is read)."""
     a, b = _case(*CASES[2]), _case(*CASES[8])
-    for kind in ("fast", "pack"):
+    for kind in ("fast", "pack", "packfast"):
         first = gpu_forward(a, kind)
         second = gpu_forward(a, kind)
         gpu_forward(b, kind)
