@@ -74,7 +74,7 @@ class FrameDesc(Structure):
 
 
 FRAME_F32_CHW, FRAME_U8_HWC_RGB, FRAME_U8_HWC_BGR, FRAME_U8_Y = 0, 1, 2, 3
-FRAME_U16_Y_MSB, FRAME_U16_Y_10, FRAME_U16_Y_12 = 4, 5, 6          # dvsr_frame_luma_sad alone
+FRAME_U16_Y_MSB, FRAME_U16_Y_10, FRAME_U16_Y_12 = 4, 5, 6          # (U8_Y and these: dvsr_frame_luma_sad and dvsr_frame_score)
 FRAME_PAD_REFLECT, FRAME_PAD_REPLICATE = 0, 1
 
 
@@ -104,6 +104,14 @@ class ResizeAxis(Structure):
 
 
 FLIP_W, FLIP_H = 1, 2                                             # dvsr_frame_flip's flags
+
+
+class ScoreArgs(Structure):
+    """dvsr_score_args: what dvsr_frame_score compares and where (include/dynavsr_hip.h)."""
+    _fields_ = [("channel", c_int), ("crop_border", c_int), ("depth", c_int), ("lo", c_float), ("hi", c_float)]
+
+
+SCORE_RGB, SCORE_Y = 0, 1
 
 
 class EstimatorConfig(Structure):
@@ -233,6 +241,8 @@ def _declare(lib):
         "dvsr_frame_resize": (I, [P, I, I, I, I, P, I, I, I, I, POINTER(ResizeAxis), POINTER(ResizeAxis), P]),
         "dvsr_frame_flip": (I, [P, P, LL, I, I, I, P]),
         "dvsr_frame_flip_mean": (I, [P, P, P, P, P, LL, I, I, P]),
+        "dvsr_frame_score_workspace_bytes": (c_size_t, [I, I, I]),
+        "dvsr_frame_score": (I, [P, POINTER(FrameDesc), P, POINTER(FrameDesc), POINTER(ScoreArgs), P, P, c_size_t, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

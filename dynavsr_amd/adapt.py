@@ -892,7 +892,7 @@ def _video_format(frames, layout):
 
 def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, layout=None, out=None, pad_mode='reflect',
                          multiple=None, matrix='bt601', yuv_range='limited', cuts=None, cut_threshold=10.0, out_size=None,
-                         flip_test=False):
+                         flip_test=False, gt=None, gt_layout=None, score='rgb', crop_border=0, scores=None):
     """Super-resolves a VIDEO: `frames` is a [T,3,H,W] tensor or a list of [3,H,W] frames (CPU or GPU); yields the SR frame
     [1,3,sH,sW] of every frame, in order -- what `net(frames[index_generation(i, T, nframes, padding)][None])` gives, the
     sliding-window test of the reference's video datasets (video_test_dataset_int.py:219, `padding: new_info` in the
@@ -951,6 +951,16 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     width that is a multiple of 4.  False takes exactly the calls described above: no further plan, buffer or launch.  Not
     provided: the x8 ensemble with transposes (a transposed frame needs a second plan of W x H), and flip-test inside
     Video_base_model.test() or the adaptation loops.
+    How good the frames are: `gt` is a video of T ground-truth frames of the OUTPUT's size (sH x sW, or `out_size`), a tensor or
+    a list like `frames`, in any layout frames.score takes (`gt_layout`; None: by dtype), on the CPU or the GPU, and `scores` a
+    float64 [T, 2] tensor on the GPU (required with `gt`).  Row i becomes [mse, ssim] of frames.score(yielded frame i, gt[i],
+    channel=`score`, crop_border=`crop_border`) (csrc/frame_score.hip), launched on the window's stream behind the
+    launch that produced the frame and ordered against the caller's stream exactly like the frame: what is scored is the frame
+    the caller gets -- the bytes of a uint8 output, emit()'s 8-bit image of a 'float' one, the Y plane of a 4:2:0 output
+    (`score` = 'y' alone; the 10- / 12-bit levels of a 16-bit one, against a GT of that depth).  A 4:2:0 output scored in 'y'
+    against an RGB GT needs matrix='bt601', yuv_range='limited': the only pair for which the Y plane is the Y8 of the GT.
+    score_summary turns `scores` into the reference's per-scene PSNR / SSIM means.  The yielded frames are what they are
+    without `gt`; None takes exactly the calls described above.
     Arguments are checked before the first GPU call (ValueError)."""
     from . import frames as fio
     from .models.archs.EDVR_arch import EDVR
@@ -1001,6 +1011,27 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         fio.check_pad(h, w, Hp, -(-Wp // 4) * 4, pad_mode)
         if lay == 'chw' and out_fmt == 'float' and (Hp, Wp) == (h, w) and out_size is None:
             Hp = Wp = None                            # nothing to convert, pad or crop: today's calls
+    score_into = None
+    if gt is None:
+        if scores is not None:
+            raise ValueError("super_resolve_frames: scores without gt")
+    else:
+        if len(gt) != T:
+            raise ValueError("super_resolve_frames: gt has %d frames, the video %d" % (len(gt), T))
+        glay, gh, gw = _video_format(gt, gt_layout)
+        olay = 'chw' if out_fmt == 'float' else out_fmt
+        oh, ow = out_size if out_size is not None else (sr_scale * h, sr_scale * w)
+        fio.check_score((olay, oh, ow), (glay, gh, gw), score, crop_border, (0, 1), "super_resolve_frames: gt")
+        if fio.is_yuv(olay) and not fio.is_yuv(glay) and (matrix, yuv_range) != ('bt601', 'limited'):
+            raise ValueError("super_resolve_frames: the Y plane of a %s output is the Y8 of an RGB gt for matrix='bt601', "
+                             "yuv_range='limited' alone, not for %r, %r" % (olay, matrix, yuv_range))
+        if not (torch.is_tensor(scores) and scores.dtype == torch.float64 and tuple(scores.shape) == (T, 2)
+                and scores.is_cuda and scores.is_contiguous()):
+            raise ValueError("super_resolve_frames: gt needs scores, a contiguous float64 [%d, 2] tensor on the GPU" % T)
+
+        def score_into(i, sr):
+            """Row i of `scores` from the frame about to be yielded, on the current stream."""
+            fio.score(sr[0] if olay == 'chw' else sr, gt[i], olay, glay, channel=score, crop_border=crop_border, out=scores[i])
     n = int(net.nframes) if is_edvr or not (opt.get('network_G') or {}).get('nframes') else int(opt['network_G']['nframes'])
     if isinstance(cuts, str):
         if cuts != 'auto':
@@ -1018,7 +1049,12 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
             def clips():
                 for win in windows:
                     yield torch.stack([frames[j] for j in win])[None]
-            yield from super_resolve_video(opt, net, clips(), in_flight, flip_test)
+            if score_into is None:
+                yield from super_resolve_video(opt, net, clips(), in_flight, flip_test)
+                return
+            for i, sr in enumerate(super_resolve_video(opt, net, clips(), in_flight, flip_test)):
+                score_into(i, sr)                      # (on the caller's stream, which the frame is ordered against)
+                yield sr
             return
         kept = {}                                      # frame -> its ingested tensor; the last 2n are kept
 
@@ -1033,19 +1069,22 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         def padded_clips():
             for win in windows:
                 yield torch.stack([ingested(j) for j in win])[None]
-        for sr in super_resolve_video(opt, net, padded_clips(), in_flight, flip_test):
+        for i, sr in enumerate(super_resolve_video(opt, net, padded_clips(), in_flight, flip_test)):
             s = sr.shape[-2] // Hp
             if out_size is not None:
                 if s != sr_scale:
                     raise RuntimeError("super_resolve_frames: the network scales by %d, opt['scale'] says %d" % (s, sr_scale))
                 if out_fmt == 'float':
-                    yield fio.resize(sr, s * h, s * w, out_size)[None]
+                    sr = fio.resize(sr, s * h, s * w, out_size)[None]
                 else:
-                    yield fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range, size=out_size)
+                    sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range, size=out_size)
             elif out_fmt == 'float':
-                yield sr if (Hp, Wp) == (h, w) else fio.emit(sr, s * h, s * w, 'chw')[None]
+                sr = sr if (Hp, Wp) == (h, w) else fio.emit(sr, s * h, s * w, 'chw')[None]
             else:
-                yield fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
+                sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
+            if score_into is not None:
+                score_into(i, sr)                      # (behind the conversion, on the caller's stream like it)
+            yield sr
         return
     leaves = net.ordered_parameters()
     dev = leaves[0].device
@@ -1146,6 +1185,8 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                         sr = fio.emit(staging[k], net.scale * h, net.scale * w, 'chw')[None]
                     else:
                         sr = fio.emit(staging[k], net.scale * h, net.scale * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
+                if score_into is not None:
+                    score_into(centre, sr)             # (behind the launch that wrote sr; the event below covers the row too)
                 ev = torch.cuda.Event()
                 ev.record(s)
             for slot in set(wslots):
@@ -1164,3 +1205,67 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
             main.wait_event(ev)
             sr.record_stream(main)
         net.train(was_training)
+
+
+def score_summary(scores, nframes, cuts=None, peak=255):
+    """The reference's per-folder report (test_Vid4_REDS4_with_GT.py) from the [T, 2] rows [mse, ssim] that
+    super_resolve_frames(gt=...) wrote: one device-to-host copy, then host arithmetic.
+
+    A scene (scene_bounds(T, cuts); cuts=None: the whole video) plays the part of a folder.  With border_frame = nframes // 2,
+    frame i of a scene of N frames is a centre frame when border_frame <= i < N - border_frame and a border frame otherwise.
+    Per scene: 'psnr' / 'ssim' are the means of the per-frame values over all frames, '_center' / '_border' those over the two
+    groups; a border mean over no frames is 0, like the reference, and a centre mean over no frames (a scene shorter than
+    2 * border_frame, where the reference would divide by zero) is NaN.  The per-frame PSNR is frames.psnr(mse, peak): inf for
+    identical frames.  Returns {'scenes': [{'first', 'frames', 'center_frames', 'border_frames', 'psnr', 'psnr_center',
+    'psnr_border', 'ssim', 'ssim_center', 'ssim_border'}, ...], 'mean': the plain mean over scenes of the six values}."""
+    from . import frames as fio
+    rows = torch.as_tensor(scores).detach().to('cpu', torch.float64)
+    if rows.dim() != 2 or rows.shape[1] != 2 or rows.shape[0] < 1:
+        raise ValueError("score_summary: scores must be [T, 2], got %s" % (tuple(rows.shape),))
+    nframes = int(nframes)
+    if nframes < 1:
+        raise ValueError("score_summary: nframes=%d must be positive" % nframes)
+    rows = rows.tolist()
+    border = nframes // 2
+
+    def mean(v, empty):
+        return sum(v) / len(v) if v else empty
+    keys = ('psnr', 'psnr_center', 'psnr_border', 'ssim', 'ssim_center', 'ssim_border')
+    scenes = []
+    for a, b in scene_bounds(len(rows), [] if cuts is None else cuts):
+        p = [fio.psnr(m, peak) for m, _ in rows[a:b]]
+        s = [v for _, v in rows[a:b]]
+        centre = [border <= i < (b - a) - border for i in range(b - a)]
+        pc, pb = [v for v, c in zip(p, centre) if c], [v for v, c in zip(p, centre) if not c]
+        sc, sb = [v for v, c in zip(s, centre) if c], [v for v, c in zip(s, centre) if not c]
+        scenes.append({'first': a, 'frames': b - a, 'center_frames': len(pc), 'border_frames': len(pb),
+                       'psnr': mean(p, 0.0), 'psnr_center': mean(pc, float('nan')), 'psnr_border': mean(pb, 0.0),
+                       'ssim': mean(s, 0.0), 'ssim_center': mean(sc, float('nan')), 'ssim_border': mean(sb, 0.0)})
+    return {'scenes': scenes, 'mean': {k: sum(sc[k] for sc in scenes) / len(scenes) for k in keys}}
+
+
+def evaluate_frames(opt, net, frames, gt, **kw):
+    """Drains super_resolve_frames(opt, net, frames, gt=gt, **kw) and returns (score_summary(scores, nframes, cuts, peak),
+    scores): the evaluation scripts of the reference for one video.  `scores` (a float64 [T, 2] GPU tensor) is allocated on the
+    network's device unless passed; cuts='auto' is resolved here, so that the summary has the scenes the windows had; `peak`
+    (None: 255, or 2^d - 1 for a 10- / 12-bit output) goes to score_summary."""
+    from . import frames as fio
+    from .models.archs.EDVR_arch import EDVR
+    kw = dict(kw)
+    peak = kw.pop('peak', None)
+    T = len(frames)
+    if isinstance(kw.get('cuts'), str) and kw['cuts'] == 'auto':
+        kw['cuts'] = fio.detect_cuts(frames, kw.get('layout'), threshold=kw.get('cut_threshold', 10.0))
+    if kw.get('scores') is None:
+        p = next(iter(net.parameters()), None)
+        dev = p.device if p is not None and p.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        kw['scores'] = torch.zeros((T, 2), dtype=torch.float64, device=dev)
+    scores = kw['scores']
+    for _ in super_resolve_frames(opt, net, frames, gt=gt, **kw):
+        pass
+    n = int(net.nframes) if isinstance(net, EDVR) or not (opt.get('network_G') or {}).get('nframes') else \
+        int(opt['network_G']['nframes'])
+    if peak is None:
+        o = kw.get('out') if kw.get('out') is not None else kw.get('layout')
+        peak = 2 ** fio.layout_depth(o) - 1 if fio.is_yuv(o) else 255
+    return score_summary(scores, n, kw.get('cuts'), peak), scores

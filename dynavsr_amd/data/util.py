@@ -24,3 +24,55 @@ def index_generation(crt_i, max_n, N, padding='reflection'):
     after = {'replicate': lambda p: last, 'reflection': lambda p: 2 * last - p, 'new_info': lambda p: lo - (p - last),
              'circle': lambda p: p - N}[padding]
     return [before(p) if p < 0 else (after(p) if p > last else p) for p in range(lo, hi + 1)]
+
+
+# ---- YCbCr (BT.601, limited range: MATLAB's rgb2ycbcr / ycbcr2rgb), as the reference's data/util.py offers them ------------------
+# An image is [..., 3] in the named channel order: uint8 in [0, 255] (the result is rounded half to even and cast back) or float
+# in [0, 1] (the result is in [0, 1], in the input's dtype).  Unlike the reference's, these never scale the caller's array in
+# place.  The arithmetic runs in numpy's promotion of (image dtype, float64) in the order written here, which is the order
+# whose results tests/golden/ycbcr_reference.npz and score_reference.npz record.
+_Y_FROM_RGB = (65.481, 128.553, 24.966)
+_YCBCR_FROM_RGB = ((65.481, -37.797, 112.0), (128.553, -74.203, -93.786), (24.966, 112.0, -18.214))
+_RGB_FROM_YCBCR = ((0.00456621, 0.00456621, 0.00456621), (0, -0.00153632, 0.00791071), (0.00625893, -0.00318811, 0))
+
+
+def _colour_levels(img):
+    """(the image on the 0 .. 255 scale -- a new array unless it is uint8 --, it is uint8, its dtype)"""
+    import numpy as np
+    img = np.asarray(img)
+    is_u8 = img.dtype == np.uint8
+    return (img if is_u8 else img * 255.), is_u8, img.dtype
+
+
+def _colour_result(levels, is_u8, dtype):
+    return (levels.round() if is_u8 else levels / 255.).astype(dtype)
+
+
+def rgb2ycbcr(img, only_y=True):
+    """RGB [..., 3] -> Y [...] (only_y) or YCbCr [..., 3]: Y = (65.481 R + 128.553 G + 24.966 B) / 255 + 16 on the 0 .. 255 scale."""
+    import numpy as np
+    x, is_u8, dtype = _colour_levels(img)
+    if only_y:
+        levels = np.dot(x, list(_Y_FROM_RGB)) / 255.0 + 16.0
+    else:
+        levels = np.matmul(x, [list(r) for r in _YCBCR_FROM_RGB]) / 255.0 + [16, 128, 128]
+    return _colour_result(levels, is_u8, dtype)
+
+
+def bgr2ycbcr(img, only_y=True):
+    """rgb2ycbcr for an image in BGR order (cv2's)."""
+    import numpy as np
+    x, is_u8, dtype = _colour_levels(img)
+    if only_y:
+        levels = np.dot(x, list(_Y_FROM_RGB[::-1])) / 255.0 + 16.0
+    else:
+        levels = np.matmul(x, [list(r) for r in _YCBCR_FROM_RGB[::-1]]) / 255.0 + [16, 128, 128]
+    return _colour_result(levels, is_u8, dtype)
+
+
+def ycbcr2rgb(img):
+    """YCbCr [..., 3] -> RGB [..., 3], the inverse of rgb2ycbcr(only_y=False) with MATLAB's rounded coefficients."""
+    import numpy as np
+    x, is_u8, dtype = _colour_levels(img)
+    levels = np.matmul(x, [list(r) for r in _RGB_FROM_YCBCR]) * 255.0 + [-222.921, 135.576, -276.836]
+    return _colour_result(levels, is_u8, dtype)

@@ -52,6 +52,11 @@ The flip-test x4 self-ensemble (csrc/frame_flip.hip: dvsr_frame_flip / dvsr_fram
 
     flip(x, flags)                       -> fp32 [..., H, W] mirrored in W (flags & 1) and / or H (flags & 2), one launch
     flip_mean(y0, yw, yh, yhw)           -> (((y0 + yw.flip(-1)) + yh.flip(-2)) + yhw.flip((-2, -1))) * 0.25, one launch
+
+PSNR / SSIM against ground truth, RGB or Y (csrc/frame_score.hip: dvsr_frame_score), for any two of the layouts:
+
+    score(a, b, layout_a, layout_b, channel='rgb' | 'y', crop_border=k) -> float64 [mse, ssim] on the device, no host sync
+    psnr(mse, peak=255)                  -> 20 log10(peak / sqrt(mse)) on the host, inf at 0
 """
 import ctypes
 import numbers
@@ -599,6 +604,103 @@ def luma_sad(frames, layout=None):
                 _luma_sad_launch(a[0], b[0], a[1], 0, 1, sad[t - 1:])
             prev = cur
         return sad.cpu()
+
+
+_SCORE_CHANNEL = {'rgb': L.SCORE_RGB, 'y': L.SCORE_Y}
+SCORE_MAX_SIDE = 32768
+
+
+def layout_depth(layout):
+    """The bits of a sample of `layout`: 10 or 12 for the 16-bit 4:2:0 layouts, 8 for everything else (a float frame is scored
+    as the 8-bit image emit() would write)."""
+    return _YUV[layout][1] if is_yuv(layout) else 8
+
+
+def check_score(side_a, side_b, channel='rgb', crop_border=0, min_max=(0, 1), who="score"):
+    """The checks of score() on two sides given as (layout, h, w), the layouts resolved: ValueError for everything
+    dvsr_frame_score refuses.  Returns (lo, hi, depth).  No GPU call."""
+    (la, ha, wa), (lb, hb, wb) = side_a, side_b
+    if channel not in _SCORE_CHANNEL:
+        raise ValueError("%s: channel=%r ('rgb' or 'y')" % (who, channel))
+    if isinstance(crop_border, bool) or not isinstance(crop_border, numbers.Integral) or crop_border < 0:
+        raise ValueError("%s: crop_border=%r must be an int >= 0" % (who, crop_border))
+    try:
+        lo, hi = (float(v) for v in min_max)
+    except (TypeError, ValueError):
+        raise ValueError("%s: min_max=%r must be a pair (lo, hi)" % (who, min_max))
+    if not hi > lo:
+        raise ValueError("%s: min_max=%r needs hi > lo" % (who, min_max))
+    if (ha, wa) != (hb, wb):
+        raise ValueError("%s: frame a is %d x %d, frame b is %d x %d" % (who, ha, wa, hb, wb))
+    if ha > SCORE_MAX_SIDE or wa > SCORE_MAX_SIDE:
+        raise ValueError("%s: frames of %d x %d (at most %d a side)" % (who, ha, wa, SCORE_MAX_SIDE))
+    if ha - 2 * crop_border < 1 or wa - 2 * crop_border < 1:
+        raise ValueError("%s: crop_border=%d leaves nothing of %d x %d" % (who, crop_border, ha, wa))
+    for lay in (la, lb):
+        if channel == 'rgb' and is_yuv(lay):
+            raise ValueError("%s: channel='rgb' on the Y plane of a %s frame (use channel='y')" % (who, lay))
+    da, db = layout_depth(la), layout_depth(lb)
+    if da != db:
+        raise ValueError("%s: %s has %d-bit samples, %s has %d-bit samples: scoring at mixed bit depths is not provided"
+                         % (who, la, da, lb, db))
+    return lo, hi, da
+
+
+def _check_score_out(out, who="score"):
+    if out is None:
+        return
+    if not (torch.is_tensor(out) and out.dtype == torch.float64 and tuple(out.shape) == (2,) and out.is_contiguous()):
+        raise ValueError("%s: out must be a contiguous float64 [2] tensor" % who)
+    if not out.is_cuda:
+        raise ValueError("%s: out must be on the GPU" % who)
+
+
+def score(a, b, layout_a=None, layout_b=None, *, channel='rgb', crop_border=0, min_max=(0, 1), out=None):
+    """[mse, ssim] of frame `a` against frame `b` as a float64 [2] tensor on the device (or written into `out`), without a
+    host synchronisation: what the reference's evaluation scripts compute per frame -- tensor2img, optionally
+    bgr2ycbcr(only_y=True) (channel='y', the Vid4 protocol), util.crop_border(crop_border), calculate_psnr's mean squared
+    difference and calculate_ssim -- for two frames in the formats they come in (csrc/frame_score.hip: dvsr_frame_score, one
+    tile launch and one finalize launch on the current stream).
+
+    a, b: frames in any layout ingest / luma_sad take, each with its own (`layout_a`, `layout_b`; None: by dtype, the 4:2:0
+    layouts are never inferred), on the CPU or the GPU, of one size; views are passed by stride, CPU frames go to the device as
+    bytes (the Y plane alone of a 4:2:0 frame).  Samples: channel='rgb' compares the three 8-bit values of a pixel -- the bytes
+    of a uint8 frame in RGB order, emit()'s quantisation (clamp to `min_max`, rescale, x 255, round half to even) of a float
+    frame; channel='y' compares one: Y8 = (65.481 R + 128.553 G + 24.966 B) / 255 + 16 of those, rounded half to even
+    (evaluated exactly in integers), the byte of the Y plane of an 'nv12' / 'i420' frame (packed or planes), or the 10- / 12-bit
+    level of the Y plane of a 16-bit layout.  Both frames must have samples of one depth.  mse is the exact integer sum of
+    squared differences over the crop divided once; ssim uses L = 255 (or 2^d - 1) and is NaN when the crop has no valid region
+    (a side <= 10).  psnr(mse) converts on the host.  ValueError before the first GPU call for every bad argument."""
+    la, ha, wa = resolve_layout(a, layout_a)
+    lb, hb, wb = resolve_layout(b, layout_b)
+    lo, hi, depth = check_score((la, ha, wa), (lb, hb, wb), channel, crop_border, min_max)
+    _check_score_out(out)
+    pa, pb = _luma_part(a, la), _luma_part(b, lb)
+    dev = out.device if out is not None else next((p.device for p in (pa, pb) if p.is_cuda),
+                                                   torch.device('cuda', torch.cuda.current_device()))
+    for p in (pa, pb):
+        if p.is_cuda and p.device != dev:
+            raise ValueError("score: the frames and out must be on one device, got %s and %s" % (p.device, dev))
+    with torch.cuda.device(dev):
+        (xa, fa), (xb, fb) = _describe_luma(to_device(pa, dev), la), _describe_luma(to_device(pb, dev), lb)
+        if out is None:
+            out = torch.empty((2,), dtype=torch.float64, device=dev)
+        k = int(crop_border)
+        nbytes = L.lib().dvsr_frame_score_workspace_bytes(3 if channel == 'rgb' else 1, ha - 2 * k, wa - 2 * k)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        da, db = L.FrameDesc(*fa), L.FrameDesc(*fb)
+        args = L.ScoreArgs(_SCORE_CHANNEL[channel], k, depth, lo, hi)
+        L.check(L.lib().dvsr_frame_score(xa.data_ptr(), ctypes.byref(da), xb.data_ptr(), ctypes.byref(db), ctypes.byref(args),
+                                         out.data_ptr(), ws.data_ptr(), nbytes, L.stream()), "dvsr_frame_score")
+    return out
+
+
+def psnr(mse, peak=255):
+    """20 log10(peak / sqrt(mse)) of a mean squared difference (a number, or a one-element tensor: that is a device-to-host
+    copy), inf at 0 like the reference's calculate_psnr.  peak: 255, or 2^d - 1 for d-bit samples."""
+    import math
+    mse = float(mse)
+    return float('inf') if mse == 0 else 20 * math.log10(float(peak) / math.sqrt(mse))
 
 
 def scene_scores(sad, h, w):

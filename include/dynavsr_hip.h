@@ -378,7 +378,8 @@ int dvsr_edvr_stream_extract_frame(const dvsr_edvr_stream* stream_plan, const fl
  *                                    yuv420p10le, a yuv420p12le frame; 2-byte aligned, pixel_stride 2, row_stride and
  *                                    frame_stride in BYTES and even): the top 8 bits of the level, word >> 8,
  *                                    (word & 1023) >> 2, (word & 4095) >> 4 -- scores mean what they mean for 8-bit video
- *   DVSR_FRAME_U8_Y and DVSR_FRAME_U16_Y_* are accepted here alone: dvsr_frame_ingest / _emit keep rejecting them.
+ *   DVSR_FRAME_U8_Y and DVSR_FRAME_U16_Y_* are accepted here and by dvsr_frame_score alone: dvsr_frame_ingest / _emit keep
+ *   rejecting them.
  * Bad arguments (null pointer, unknown format, h or w < 1, pairs < 1, a pixel stride the format does not have, a row or
  * plane stride shorter than a row / plane, a misaligned fp32 frame or result, an odd address or stride of a 16-bit plane)
  * return DVSR_ERR_INVALID before any launch. */
@@ -758,6 +759,48 @@ size_t dvsr_frame_metrics_workspace_bytes(int C, int H, int W);
 int dvsr_frame_metrics(const float* sr, const float* gt, int C, int H, int W, float lo, float hi,
                        unsigned char* sr_hwc_u8, double* out, void* workspace, size_t workspace_bytes,
                        dvsr_stream_t stream);
+
+/* ---- PSNR / SSIM of an emitted frame against its ground truth, RGB or Y ----------------------------
+ * What the reference's evaluation scripts end in (test_Vid4_REDS4_with_GT*.py, calc_psnr_ssim.py): tensor2img, optionally
+ * bgr2ycbcr(only_y=True) (the Vid4 protocol), util.crop_border, calculate_psnr / calculate_ssim -- for two frames that are
+ * each described by a dvsr_frame_desc (any address, any pitch, their own format), in one tile launch and one fixed-order
+ * finalize launch: no quantised plane in global memory, no second pass, no floating-point atomics (bit-identical from run to
+ * run).  Samples of a pixel:
+ *     format                                   channel DVSR_SCORE_RGB (3 samples)     channel DVSR_SCORE_Y (1 sample)
+ *     DVSR_FRAME_U8_HWC_RGB / _BGR (3 | 4 B)   the bytes, in RGB order                Y8(R, G, B)
+ *     DVSR_FRAME_F32_CHW (3 planes)            the quantiser of dvsr_frame_emit /     Y8 of those
+ *                                              dvsr_frame_metrics on v, lo, hi
+ *     DVSR_FRAME_U8_Y                          refused                                the byte
+ *     DVSR_FRAME_U16_Y_MSB / _10 / _12         refused                                the d-bit level, d = depth in {10, 12}:
+ *                                                                                     word >> (16 - d) (MSB), word & (2^d - 1)
+ *   Y8 is rgb2ycbcr(only_y=True) of the reference (data/util.py), (65.481 R + 128.553 G + 24.966 B) / 255 + 16 rounded half to
+ *   even, evaluated exactly in integers: num = 65481 R + 128553 G + 24966 B + 16 * 255000, num / 255000, an exact tie to the
+ *   even level.  Over all 2^24 triples this equals both branches of the reference (uint8 image, float image) off the 194
+ *   exact ties, num = 127500 mod 255000; on those the reference's float64 sum lands beside the tie and it differs from half-even
+ *   by one level on 24 (RGB order) / 21 (BGR order) of them for an [H,W,3] image (31 / 26 for pixels passed as [N,3]).
+ *   Both frames must reduce to ONE sample domain: 8-bit with 8-bit (depth 8), depth d with depth d.
+ * Region: crop_border = k >= 0 removes k pixels on every side first (util.crop_border), H' x W' = (h - 2k) x (w - 2k) >= 1 x 1;
+ *   the SSIM "valid" region is taken inside the crop.
+ * out (DEVICE, 2 doubles, 8-byte aligned): out[0] = the exact integer sum of squared sample differences over the crop divided
+ *   once by the number of samples; out[1] = the mean of the SSIM map (11-tap Gaussian, sigma 1.5, float64, separable) over
+ *   channels and valid pixels with C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = 255 or 2^d - 1 -- NaN when H' <= 10 or W' <= 10.
+ * workspace: dvsr_frame_score_workspace_bytes(channels, h, w) bytes for `channels` (3 for RGB, 1 for Y) samples per pixel
+ *   of an h x w crop; the figure of the uncropped frame is enough for every crop.  8-byte aligned; need not be initialised.
+ * Bad arguments (null pointer, sizes that differ, unknown format / channel / depth, a domain mismatch, RGB on a Y plane, a crop
+ * that leaves nothing, a stride shorter than a row, a pixel stride the format does not have, a misaligned fp32 frame, an odd
+ * address or stride of a 16-bit plane, a misaligned out) return DVSR_ERR_INVALID, a short workspace DVSR_ERR_WORKSPACE, before
+ * any launch. */
+#define DVSR_SCORE_RGB 0
+#define DVSR_SCORE_Y 1
+typedef struct dvsr_score_args {
+  int channel;            /* DVSR_SCORE_RGB | DVSR_SCORE_Y */
+  int crop_border, depth; /* depth 8, 10 or 12 */
+  float lo, hi;           /* range of an F32_CHW side */
+} dvsr_score_args;
+size_t dvsr_frame_score_workspace_bytes(int channels, int h, int w);
+int dvsr_frame_score(const void* a, const dvsr_frame_desc* da, const void* b, const dvsr_frame_desc* db,
+                     const dvsr_score_args* args, double* out /* [2], 8-byte aligned device memory */, void* workspace,
+                     size_t workspace_bytes, dvsr_stream_t stream);
 
 /* ---- synthetic degradation on the device -------------------------------------------
  * Replaces the tensor part of Degradation.apply (codes/data/random_kernel_generator.py:84-130):
