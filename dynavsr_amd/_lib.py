@@ -79,18 +79,26 @@ FRAME_PAD_REFLECT, FRAME_PAD_REPLICATE = 0, 1
 
 
 class YuvDesc(Structure):
-    """dvsr_yuv_desc: a YCbCr 4:2:0 frame, every plane at any address and pitch (include/dynavsr_hip.h)."""
+    """dvsr_yuv_desc: a YCbCr 4:2:0 / 4:2:2 / 4:4:4 frame, every plane at any address and pitch (include/dynavsr_hip.h)."""
     _fields_ = [("format", c_int), ("h", c_int), ("w", c_int), ("matrix", c_int), ("range", c_int),
                 ("plane", c_void_p * 3), ("row_stride", c_longlong * 3)]
 
 
 YUV_NV12, YUV_I420 = 0, 1
+YUV_CHROMA_420, YUV_CHROMA_422, YUV_CHROMA_444 = 0, 1, 2          # format = form | chroma << 4, of both descriptors
+
+
+def yuv_format(form, chroma):
+    """DVSR_YUV_FORMAT: the semi-planar (0) or planar (1) form of a descriptor with a chroma sub-sampling."""
+    return form | (chroma << 4)
+
+
 YUV_BT601, YUV_BT709 = 0, 1
 YUV_LIMITED, YUV_FULL = 0, 1
 
 
 class Yuv16Desc(Structure):
-    """dvsr_yuv16_desc: a 10- / 12-bit YCbCr 4:2:0 frame in 16-bit words, every plane at any even address and pitch."""
+    """dvsr_yuv16_desc: a 10- / 12-bit YCbCr 4:2:0 / 4:2:2 / 4:4:4 frame in 16-bit words, every plane at any even address and pitch."""
     _fields_ = [("format", c_int), ("depth", c_int), ("h", c_int), ("w", c_int), ("matrix", c_int), ("range", c_int),
                 ("plane", c_void_p * 3), ("row_stride", c_longlong * 3)]
 

@@ -879,7 +879,7 @@ def _video_format(frames, layout):
         raise ValueError("super_resolve_frames: no frames")
     first = fio.resolve_layout(frames[0], layout)
     if not torch.is_tensor(frames):
-        def kind(f):        # a tensor's, or those of the planes of a 4:2:0 frame
+        def kind(f):        # a tensor's, or those of the planes of a YCbCr frame
             if torch.is_tensor(f):
                 return f.dtype, tuple(f.shape)
             return [kind(p) for p in f] if isinstance(f, (tuple, list)) else type(f).__name__
@@ -931,6 +931,10 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     counterparts (csrc/frame_yuv.hip too); `out` None then yields packed torch.uint16 frames of the input's layout, quantised
     from the fp32 SR frame to 1024 / 4096 levels, and the four names force such an output for any input -- an 8-bit source can
     leave with 10 bits.
+    Footage that is not 4:2:0 (frames.py): `layout` and `out` also take the 4:2:2 names 'i422' / 'nv16' / 'i422p10' /
+    'i422p12' / 'p210' / 'p212' (packed [T, 2H, W] or planes; a packed output needs an even sW or `out_size` width alone) and the
+    4:4:4 names 'i444' / 'i444p10' / 'i444p12' (packed [T, 3H, W]; any size), the 16-bit ones as the output of any input;
+    everything said of the 4:2:0 layouts holds for them.
     A video of several scenes: `cuts` (None: one scene, the calls of before) lists the first frame of every new scene, or is
     'auto' for frames.detect_cuts(frames, layout, threshold=cut_threshold); no window then crosses a cut (video_windows), so
     every scene comes out as if it had been passed alone, and the frame cache has stream_slots' capacity.
@@ -988,7 +992,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         lay, h, w = _video_format(frames, layout)
         if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') and not fio.is_yuv(out):
             raise ValueError("super_resolve_frames: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (
-                out, ', '.join(fio.YUV_LAYOUTS + fio.YUV16_LAYOUTS)))
+                out, ', '.join(fio.ALL_YUV_LAYOUTS)))
         fio.check_yuv_names(matrix, yuv_range)
         out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
         if out_size == (sr_scale * h, sr_scale * w):
@@ -997,9 +1001,9 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
             fio.check_resize(sr_scale * h, sr_scale * w, out_size, "super_resolve_frames: out_size")
         if fio.is_yuv(out_fmt):
             oh, ow = out_size if out_size is not None else (sr_scale * h, sr_scale * w)
-            if oh % 2 or ow % 2:
-                raise ValueError("super_resolve_frames: a packed %s output of %d x %d needs an even size%s" % (
-                    out_fmt, oh, ow, " (out_size)" if out_size is not None else ""))
+            if fio.packed_needs(out_fmt, oh, ow):
+                raise ValueError("super_resolve_frames: a packed %s output of %d x %d needs %s%s" % (
+                    out_fmt, oh, ow, fio.packed_needs(out_fmt, oh, ow), " (out_size)" if out_size is not None else ""))
         if h < 4 or w < 4:
             raise ValueError("super_resolve_frames: frames of %d x %d (at least 4 x 4)" % (h, w))
         mult = int(multiple) if multiple is not None else (4 if is_edvr else 1)

@@ -1598,12 +1598,12 @@ static int stream_extract_frame(const char* what, const dvsr_edvr_stream* s, con
   return stream_extract_tape(s, params, raw, dst, ws, packed, st);
 }
 
-// the ingest step of a YCbCr 4:2:0 frame of either descriptor (frame_yuv.hip)
+// the ingest step of a YCbCr frame of either descriptor, of any sub-sampling (frame_yuv.hip)
 template <class Desc>
 static auto yuv_ingest_step(const Desc* fd, int pad_mode) {
   return [=](const char* what, float* raw, int H, int W, hipStream_t st) {
-    Yuv420 f;
-    int rc = yuv420_from(what, fd, &f);
+    YuvFrame f;
+    int rc = yuv_frame_from(what, fd, &f);
     if (rc == DVSR_OK) rc = frame_ingest_yuv_check(what, f, raw, H, W, pad_mode);
     return rc != DVSR_OK ? rc : frame_ingest_yuv_launch(f, raw, H, W, pad_mode, st);
   };

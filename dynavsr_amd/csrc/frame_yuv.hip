@@ -1,9 +1,12 @@
-// YCbCr 4:2:0 frames of 8, 10 and 12 bits in and out of the video path (dvsr_frame_ingest_yuv / dvsr_frame_emit_yuv and their
-// _yuv16 counterparts, engine.hip: dvsr_edvr_stream_extract_frame_yuv / _yuv16), beside the RGB / BGR frames of frame_io.hip.
+// YCbCr 4:2:0, 4:2:2 and 4:4:4 frames of 8, 10 and 12 bits in and out of the video path (dvsr_frame_ingest_yuv /
+// dvsr_frame_emit_yuv and their _yuv16 counterparts, engine.hip: dvsr_edvr_stream_extract_frame_yuv / _yuv16), beside the RGB /
+// BGR frames of frame_io.hip.
 //
 // What a video decoder delivers and an encoder takes: a Y plane [h][w] and either one plane of interleaved Cb, Cr pairs
 // [Hc][Wc][2] (semi-planar) or a Cb and a Cr plane [Hc][Wc] (planar), Hc x Wc = ceil(h/2) x ceil(w/2), every plane at any
-// sample-aligned address and row pitch.  A sample holds a level of d bits:
+// sample-aligned address and row pitch.  The chroma field of the descriptor's format (format = base | chroma << 4) names the
+// other two sub-samplings: 4:2:2, Hc x Wc = h x ceil(w/2), and 4:4:4, h x w (planar alone); what they change is listed under
+// "4:2:2 and 4:4:4" below, everything else is 4:2:0's.  A sample holds a level of d bits:
 //   descriptor        format                         sample          level <-> sample
 //   dvsr_yuv_desc     NV12 (semi) | I420 (planar)    a byte, d = 8   level = byte
 //   dvsr_yuv16_desc   SEMI_MSB (P010 / P012)         a 16-bit word   word = level << (16 - d); the low bits: ignored in, 0 out
@@ -34,6 +37,11 @@
 //   device) and multiplications by reciprocals formed on the host in double and rounded once to fp32 for 16-bit words: one more
 //   rounding of 2^-24 relative per quotient, inside the tests' bars.  They differ in the last bit and in emitted
 //   samples near ties, so they stay apart (Sample8::quot / Sample16::quot).
+//   4:2:2 and 4:4:4: no vertical step either way.
+//     siting  4:2:2: chroma sample (y, k) sits on luma row y, column 2k.  4:4:4: on its pixel.
+//     ingest  4:2:2: C' = Ch(y, x), the horizontal line above on chroma row y.  4:4:4: C' = C[y][x].
+//     emit    4:2:2: chroma sample (y, k) = taps [1,2,1]/4 on columns 2k-1, 2k, 2k+1 of row y, indices clamped to the crop.
+//             4:4:4: the pixel's own cb, cr.
 //
 // One thread = a 4 x 2 luma block (two rows, four columns): one chroma row, two chroma columns, and the neighbours the filters
 // need.  A workgroup is 64 x 4 threads, so a wave owns whole rows and whatever depends on a row's address is wave-uniform.
@@ -44,6 +52,10 @@
 // merged into wider, possibly misaligned ones), no access is narrower than a sample, and nothing outside the rows of a plane is
 // read or written.  Blocks that hold padded rows / columns or the ragged end of the frame work sample by sample.  Pure
 // streaming: all of a lane's loads come ahead of its first store, no grid-stride loop (frame_io.hip).
+// The sub-sampling is a compile-time axis CS of the one kernel pair, beside S and SEMI; the lane's 4 x 2 luma block stays.  Its
+// chroma group is two rows of 2 samples (4:2:2 planar), two rows of two CbCr pairs (4:2:2 semi-planar) or two rows of 4 samples
+// (4:4:4), each at the same multiple of its size inside its row as the 4:2:0 group, so the choice of pieces is still the row's.
+// Every CS_420 line is the line it was: those instantiations compile to what they compiled to before the axis.
 #include <cstdint>
 
 #include "frame_common.h"
@@ -51,6 +63,8 @@
 namespace dvsr {
 
 constexpr int YUV_X = 64, YUV_Y = 4;   // threads of a workgroup along a row (one wave) / block rows of a workgroup
+// the chroma sub-sampling CS of a kernel: the chroma field of a descriptor's format
+constexpr int CS_420 = DVSR_YUV_CHROMA_420, CS_422 = DVSR_YUV_CHROMA_422, CS_444 = DVSR_YUV_CHROMA_444;
 
 // (what the 8-bit kernels read comes first and together: their scalar loads of it stay few)
 struct YuvCoef {
@@ -234,14 +248,91 @@ __device__ __forceinline__ void chroma3(const YuvIngestArgs& a, int j, int k0, i
 
 __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
-template <class S, bool SEMI>
+// 4:2:2 and 4:4:4: the chroma of a 4 x 2 block inside the frame, on the luma grid -- each luma row has its own chroma row
+template <class S, bool SEMI, int CS>
+__device__ __forceinline__ void chroma_rows(const YuvIngestArgs& a, int x0, int y0, float Cb[2][4], float Cr[2][4]) {
+  if constexpr (CS == CS_422) {
+    // columns x0 .. x0 + 3 lie on chroma columns k0, k0 + 1 and reach to k0 + 2 for the last (odd) one
+    const int Wc = (a.w + 1) >> 1, k0 = x0 >> 1, k2 = min(k0 + 2, Wc - 1);
+    float cb[2][3], cr[2][3];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) chroma3<S, SEMI>(a, y0 + r, k0, k2, cb[r], cr[r]);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      Cb[r][0] = cb[r][0];
+      Cb[r][1] = (cb[r][0] + cb[r][1]) * 0.5f;
+      Cb[r][2] = cb[r][1];
+      Cb[r][3] = (cb[r][1] + cb[r][2]) * 0.5f;
+      Cr[r][0] = cr[r][0];
+      Cr[r][1] = (cr[r][0] + cr[r][1]) * 0.5f;
+      Cr[r][2] = cr[r][1];
+      Cr[r][3] = (cr[r][1] + cr[r][2]) * 0.5f;
+    }
+  } else {
+    static_assert(CS == CS_444 && !SEMI, "4:4:4 is planar");
+    typename S::G4 gb[2], gr[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      gb[r] = S::ld4(a.p[1] + (long long)(y0 + r) * a.rs[1] + S::B * x0);
+      gr[r] = S::ld4(a.p[2] + (long long)(y0 + r) * a.rs[2] + S::B * x0);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        Cb[r][i] = S::lev(a, gb[r], i);
+        Cr[r][i] = S::lev(a, gr[r], i);
+      }
+  }
+}
+
+template <class S, bool SEMI, int CS>
 __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvIngestArgs a) {
   const int x0 = (blockIdx.x * YUV_X + threadIdx.x) * 4;
   const int y0 = (blockIdx.y * YUV_Y + threadIdx.y) * 2;
   if (x0 >= a.Wp || y0 >= a.Hp) return;
-  const int Hc = (a.h + 1) >> 1, Wc = (a.w + 1) >> 1;
+  const int Hc = (a.h + 1) >> 1, Wc = (a.w + 1) >> 1;   // (Hc: of 4:2:0; Wc: of 4:2:0 and 4:2:2)
   float Y[2][4], Cb[2][4], Cr[2][4];   // levels: luma as stored, chroma upsampled to the luma grid
-  if (x0 + 3 < a.w && y0 + 1 < a.h) {
+  if constexpr (CS != CS_420) {
+    if (x0 + 3 < a.w && y0 + 1 < a.h) {
+      typename S::G4 yl[2];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) yl[r] = S::ld4(a.p[0] + (long long)(y0 + r) * a.rs[0] + S::B * x0);
+      chroma_rows<S, SEMI, CS>(a, x0, y0, Cb, Cr);
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Y[r][i] = S::lev(a, yl[r], i);
+    } else {
+      // padded rows / columns, the ragged end of a row, the last row of an odd height: sample by sample, every index clamped
+      float cbv[2][4][2], crv[2][4][2];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int sy = pad_index(min(y0 + r, a.Hp - 1), a.h, a.pad);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int sx = pad_index(x0 + i, a.w, a.pad);
+          Y[r][i] = S::lev(a, S::ld1(a.p[0] + (long long)sy * a.rs[0] + S::B * sx), 0);
+          // 4:2:2: the two chroma columns of Ch(sy, sx); 4:4:4: the pixel's own sample, as both
+          const int ka = CS == CS_422 ? sx >> 1 : sx;
+          chroma1<S, SEMI>(a, sy, ka, cbv[r][i][0], crv[r][i][0]);
+          if constexpr (CS == CS_422) {
+            chroma1<S, SEMI>(a, sy, (sx & 1) ? min(ka + 1, Wc - 1) : ka, cbv[r][i][1], crv[r][i][1]);
+          } else {
+            cbv[r][i][1] = cbv[r][i][0];
+            crv[r][i][1] = crv[r][i][0];
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          Cb[r][i] = (cbv[r][i][0] + cbv[r][i][1]) * 0.5f;   // (4:4:4: (c + c) / 2 = c, exactly)
+          Cr[r][i] = (crv[r][i][0] + crv[r][i][1]) * 0.5f;
+        }
+    }
+  } else if (x0 + 3 < a.w && y0 + 1 < a.h) {
     // a block inside the frame: luma rows y0, y0 + 1 share chroma row j; its columns x0 .. x0 + 3 lie on chroma columns
     // k0, k0 + 1 and reach to k0 + 2 for the last (odd) one
     const int j = y0 >> 1, k0 = x0 >> 1, k2 = min(k0 + 2, Wc - 1);
@@ -308,9 +399,17 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
     for (int i = 0; i < 4; ++i) {
       const float yn = S::quot(Y[r][i] - a.k.y0, a.k.ys, a.k.inv_ys), cb = S::quot(Cb[r][i] - S::cm(a.k), a.k.cs, a.k.inv_cs),
                   cr = S::quot(Cr[r][i] - S::cm(a.k), a.k.cs, a.k.inv_cs);
-      o[r][0][i] = clamp01(yn + a.k.r_cr * cr);
-      o[r][1][i] = clamp01(yn - a.k.g_cb * cb - a.k.g_cr * cr);
-      o[r][2][i] = clamp01(yn + a.k.b_cb * cb);
+      if constexpr (CS == CS_420) {
+        o[r][0][i] = clamp01(yn + a.k.r_cr * cr);
+        o[r][1][i] = clamp01(yn - a.k.g_cb * cb - a.k.g_cr * cr);
+        o[r][2][i] = clamp01(yn + a.k.b_cb * cb);
+      } else {
+        // the same lines with every product fused by name: which products the compiler fuses on its own differs between
+        // instantiations (packed math), and a planar and a semi-planar frame of the same levels give the same bits
+        o[r][0][i] = clamp01(fmaf(a.k.r_cr, cr, yn));
+        o[r][1][i] = clamp01(fmaf(-a.k.g_cr, cr, fmaf(-a.k.g_cb, cb, yn)));
+        o[r][2][i] = clamp01(fmaf(a.k.b_cb, cb, yn));
+      }
     }
   const long long plane = (long long)a.Hp * a.Wp;
   float* d = a.dst + (long long)y0 * a.Wp + x0;
@@ -324,8 +423,31 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
 
 __device__ __forceinline__ unsigned quant_level(float v, float top) { return (unsigned)(int)fminf(fmaxf(rintf(v), 0.0f), top); }
 
+// this lane's two chroma columns of chroma row j, as they are stored (4:2:0 and 4:2:2)
 template <class S, bool SEMI>
+__device__ __forceinline__ void store_chroma2(const YuvEmitArgs& a, int j, int x0, const unsigned (&cbw)[2], const unsigned (&crw)[2]) {
+  const bool two = x0 + 2 < a.w;        // this lane's second chroma column exists
+  if (SEMI) {
+    unsigned char* q = a.p[1] + (long long)j * a.rs[1] + S::B * x0;   // pair k0 = x0 / 2 is 2 k0 samples into the row
+    const unsigned s[4] = {cbw[0], crw[0], cbw[1], crw[1]};
+    if (two) S::st4(q, s);
+    else S::st2(q, s);
+  } else {
+    unsigned char* qb = a.p[1] + (long long)j * a.rs[1] + S::B * (x0 >> 1);
+    unsigned char* qr = a.p[2] + (long long)j * a.rs[2] + S::B * (x0 >> 1);
+    if (two) {
+      S::st2(qb, cbw);
+      S::st2(qr, crw);
+    } else {
+      S::st1(qb, cbw[0]);
+      S::st1(qr, crw[0]);
+    }
+  }
+}
+
+template <class S, bool SEMI, int CS>
 __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitArgs a) {
+  static_assert(CS != CS_444 || !SEMI, "4:4:4 is planar");
   const int x0 = (blockIdx.x * YUV_X + threadIdx.x) * 4;
   const int y0 = (blockIdx.y * YUV_Y + threadIdx.y) * 2;
   if (x0 >= a.w || y0 >= a.h) return;
@@ -340,7 +462,8 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitAr
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       v[r][c] = *reinterpret_cast<const f32x4*>(row + c * plane + x0);
-      l[r][c] = row[c * plane + xl];
+      if constexpr (CS == CS_444) l[r][c] = 0.0f;   // (no filter, no left neighbour: what comes of it below is dropped)
+      else l[r][c] = row[c * plane + xl];
     }
   }
   const float scale = a.hi - a.lo;
@@ -365,20 +488,34 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitAr
       crv[r][i] = S::quot(t[0] - y, a.k.r_cr, a.k.inv_r_cr);
       if (i > 0) yv[r][i - 1] = y;
     }
-  unsigned yw[2][4], cbw[2], crw[2];      // samples as they are stored
+  constexpr int CR = CS == CS_420 ? 1 : 2, CK = CS == CS_444 ? 4 : 2;   // this lane's chroma rows, samples of one
+  unsigned yw[2][4], cbw[CR][CK], crw[CR][CK];   // samples as they are stored
 #pragma unroll
   for (int r = 0; r < 2; ++r)
 #pragma unroll
     for (int i = 0; i < 4; ++i) yw[r][i] = S::word(a, quant_level(a.k.y0 + a.k.ys * yv[r][i], a.k.top));
+  if constexpr (CS == CS_420) {
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int i = 2 * k;               // columns 2k - 1, 2k, 2k + 1 of this lane's chroma column k
-    const float fb = 0.5f * (0.25f * (cbv[0][i] + 2.0f * cbv[0][i + 1] + cbv[0][i + 2]) +
-                             0.25f * (cbv[1][i] + 2.0f * cbv[1][i + 1] + cbv[1][i + 2]));
-    const float fr = 0.5f * (0.25f * (crv[0][i] + 2.0f * crv[0][i + 1] + crv[0][i + 2]) +
-                             0.25f * (crv[1][i] + 2.0f * crv[1][i + 1] + crv[1][i + 2]));
-    cbw[k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fb, a.k.top));
-    crw[k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fr, a.k.top));
+    for (int k = 0; k < 2; ++k) {
+      const int i = 2 * k;               // columns 2k - 1, 2k, 2k + 1 of this lane's chroma column k
+      const float fb = 0.5f * (0.25f * (cbv[0][i] + 2.0f * cbv[0][i + 1] + cbv[0][i + 2]) +
+                               0.25f * (cbv[1][i] + 2.0f * cbv[1][i + 1] + cbv[1][i + 2]));
+      const float fr = 0.5f * (0.25f * (crv[0][i] + 2.0f * crv[0][i + 1] + crv[0][i + 2]) +
+                               0.25f * (crv[1][i] + 2.0f * crv[1][i + 1] + crv[1][i + 2]));
+      cbw[0][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fb, a.k.top));
+      crw[0][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fr, a.k.top));
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int k = 0; k < CK; ++k) {
+        // 4:2:2: the same columns, of row r alone; 4:4:4: the pixel's own
+        const float fb = CS == CS_444 ? cbv[r][k + 1] : 0.25f * (cbv[r][2 * k] + 2.0f * cbv[r][2 * k + 1] + cbv[r][2 * k + 2]);
+        const float fr = CS == CS_444 ? crv[r][k + 1] : 0.25f * (crv[r][2 * k] + 2.0f * crv[r][2 * k + 1] + crv[r][2 * k + 2]);
+        cbw[r][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fb, a.k.top));
+        crw[r][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fr, a.k.top));
+      }
   }
   // ---- stores
 #pragma unroll
@@ -393,49 +530,64 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitAr
           if (x0 + i < a.w) S::st1(q + S::B * i, yw[r][i]);
       }
     }
-  const int j = y0 >> 1;
-  const bool two = x0 + 2 < a.w;        // this lane's second chroma column exists
-  if (SEMI) {
-    unsigned char* q = a.p[1] + (long long)j * a.rs[1] + S::B * x0;   // pair k0 = x0 / 2 is 2 k0 samples into the row
-    const unsigned s[4] = {cbw[0], crw[0], cbw[1], crw[1]};
-    if (two) S::st4(q, s);
-    else S::st2(q, s);
+  if constexpr (CS == CS_444) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      if (y0 + r < a.h) {                 // a chroma row is stored like the luma row it belongs to
+        unsigned char* qb = a.p[1] + (long long)(y0 + r) * a.rs[1] + S::B * x0;
+        unsigned char* qr = a.p[2] + (long long)(y0 + r) * a.rs[2] + S::B * x0;
+        if (x0 + 3 < a.w) {
+          S::st4(qb, cbw[r]);
+          S::st4(qr, crw[r]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 3; ++i)
+            if (x0 + i < a.w) {
+              S::st1(qb + S::B * i, cbw[r][i]);
+              S::st1(qr + S::B * i, crw[r][i]);
+            }
+        }
+      }
+  } else if constexpr (CS == CS_422) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      if (y0 + r < a.h) store_chroma2<S, SEMI>(a, y0 + r, x0, cbw[r], crw[r]);   // the chroma row of luma row y0 + r
   } else {
-    unsigned char* qb = a.p[1] + (long long)j * a.rs[1] + S::B * (x0 >> 1);
-    unsigned char* qr = a.p[2] + (long long)j * a.rs[2] + S::B * (x0 >> 1);
-    if (two) {
-      S::st2(qb, cbw);
-      S::st2(qr, crw);
-    } else {
-      S::st1(qb, cbw[0]);
-      S::st1(qr, crw[0]);
-    }
+    store_chroma2<S, SEMI>(a, y0 >> 1, x0, cbw[0], crw[0]);
   }
 }
 
-// ---- the host side, on the one internal frame (kernels.h: Yuv420)
+// ---- the host side, on the one internal frame (kernels.h: YuvFrame)
 
-int yuv420_from(const char* what, const dvsr_yuv_desc* d, Yuv420* f) {
+// format = base | chroma << 4: a known pair (base 0 is the semi-planar form of either descriptor, 1 the planar one)?
+static bool yuv_format_known(int format) {
+  const int base = format & 15, chroma = format >> 4;
+  return format >= 0 && base <= 1 && chroma <= DVSR_YUV_CHROMA_444;
+}
+
+int yuv_frame_from(const char* what, const dvsr_yuv_desc* d, YuvFrame* f) {
   DVSR_REQUIRE(d, DVSR_ERR_INVALID, "%s: null descriptor", what);
-  DVSR_REQUIRE(d->format == DVSR_YUV_NV12 || d->format == DVSR_YUV_I420, DVSR_ERR_INVALID, "%s: unknown YUV format %d", what,
-               d->format);
-  *f = Yuv420{{d->plane[0], d->plane[1], d->plane[2]}, {d->row_stride[0], d->row_stride[1], d->row_stride[2]},
-              d->h, d->w, d->matrix, d->range, d->format == DVSR_YUV_NV12, 1, 8};
+  DVSR_REQUIRE(yuv_format_known(d->format), DVSR_ERR_INVALID, "%s: unknown YUV format %d", what, d->format);
+  DVSR_REQUIRE(d->format != DVSR_YUV_FORMAT(DVSR_YUV_NV12, DVSR_YUV_CHROMA_444), DVSR_ERR_INVALID,
+               "%s: YUV format %d, semi-planar 4:4:4, is not provided", what, d->format);
+  *f = YuvFrame{{d->plane[0], d->plane[1], d->plane[2]}, {d->row_stride[0], d->row_stride[1], d->row_stride[2]},
+                d->h, d->w, d->matrix, d->range, (d->format & 15) == DVSR_YUV_NV12, 1, 8, d->format >> 4};
   return DVSR_OK;
 }
 
-int yuv420_from(const char* what, const dvsr_yuv16_desc* d, Yuv420* f) {
+int yuv_frame_from(const char* what, const dvsr_yuv16_desc* d, YuvFrame* f) {
   DVSR_REQUIRE(d, DVSR_ERR_INVALID, "%s: null descriptor", what);
-  DVSR_REQUIRE(d->format == DVSR_YUV16_SEMI_MSB || d->format == DVSR_YUV16_PLANAR_LSB, DVSR_ERR_INVALID,
-               "%s: unknown 16-bit YUV format %d", what, d->format);
+  DVSR_REQUIRE(yuv_format_known(d->format), DVSR_ERR_INVALID, "%s: unknown 16-bit YUV format %d", what, d->format);
+  DVSR_REQUIRE(d->format != DVSR_YUV_FORMAT(DVSR_YUV16_SEMI_MSB, DVSR_YUV_CHROMA_444), DVSR_ERR_INVALID,
+               "%s: 16-bit YUV format %d, semi-planar 4:4:4, is not provided", what, d->format);
   DVSR_REQUIRE(d->depth == 10 || d->depth == 12, DVSR_ERR_INVALID, "%s: unknown depth %d (10 or 12)", what, d->depth);
-  *f = Yuv420{{d->plane[0], d->plane[1], d->plane[2]}, {d->row_stride[0], d->row_stride[1], d->row_stride[2]},
-              d->h, d->w, d->matrix, d->range, d->format == DVSR_YUV16_SEMI_MSB, 2, d->depth};
+  *f = YuvFrame{{d->plane[0], d->plane[1], d->plane[2]}, {d->row_stride[0], d->row_stride[1], d->row_stride[2]},
+                d->h, d->w, d->matrix, d->range, (d->format & 15) == DVSR_YUV16_SEMI_MSB, 2, d->depth, d->format >> 4};
   return DVSR_OK;
 }
 
 // (arguments checked by yuv_frame_check)
-static YuvCoef yuv_coef(const Yuv420& f) {
+static YuvCoef yuv_coef(const YuvFrame& f) {
   const bool bt709 = f.matrix == DVSR_YUV_BT709, full = f.range == DVSR_YUV_FULL;
   const double kr = bt709 ? 0.2126 : 0.299, kb = bt709 ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
   const double s = (double)(1 << (f.depth - 8)), top = (double)((1 << f.depth) - 1);
@@ -447,14 +599,14 @@ static YuvCoef yuv_coef(const Yuv420& f) {
 }
 
 // the frame on the "any address, any pitch" side, against the h x w it may have at most
-static int yuv_frame_check(const char* what, const Yuv420& f, int Ht, int Wt) {
+static int yuv_frame_check(const char* what, const YuvFrame& f, int Ht, int Wt) {
   DVSR_REQUIRE(f.matrix == DVSR_YUV_BT601 || f.matrix == DVSR_YUV_BT709, DVSR_ERR_INVALID, "%s: unknown YUV matrix %d", what,
                f.matrix);
   DVSR_REQUIRE(f.range == DVSR_YUV_LIMITED || f.range == DVSR_YUV_FULL, DVSR_ERR_INVALID, "%s: unknown YUV range %d", what,
                f.range);
   DVSR_REQUIRE(f.h >= 1 && f.w >= 1 && f.h <= Ht && f.w <= Wt, DVSR_ERR_INVALID,
                "%s: frame size h=%d w=%d outside [1, %d] x [1, %d]", what, f.h, f.w, Ht, Wt);
-  const long long Wc = (f.w + 1) / 2;
+  const long long Wc = f.chroma == DVSR_YUV_CHROMA_444 ? f.w : (f.w + 1) / 2;   // samples of a chroma row, per plane
   for (int i = 0; i < (f.semi ? 2 : 3); ++i) {   // (the two "16-bit samples" checks cannot fail for bytes: % 1)
     DVSR_REQUIRE(f.plane[i], DVSR_ERR_INVALID, "%s: null plane %d", what, i);
     DVSR_REQUIRE(reinterpret_cast<uintptr_t>(f.plane[i]) % f.bytes == 0, DVSR_ERR_INVALID,
@@ -471,16 +623,28 @@ static int yuv_frame_check(const char* what, const Yuv420& f, int Ht, int Wt) {
 static dim3 yuv_grid(int h, int w) { return dim3(ceil_div(ceil_div(w, 4), YUV_X), ceil_div(ceil_div(h, 2), YUV_Y)); }
 
 // the instantiation that takes a frame
-static auto ingest_kernel(const Yuv420& f) {
-  if (f.bytes == 2) return f.semi ? frame_ingest_yuv_kernel<Sample16, true> : frame_ingest_yuv_kernel<Sample16, false>;
-  return f.semi ? frame_ingest_yuv_kernel<Sample8, true> : frame_ingest_yuv_kernel<Sample8, false>;
+template <int CS>
+static auto ingest_kernel_of(const YuvFrame& f) {
+  if (f.bytes == 2) return f.semi ? frame_ingest_yuv_kernel<Sample16, true, CS> : frame_ingest_yuv_kernel<Sample16, false, CS>;
+  return f.semi ? frame_ingest_yuv_kernel<Sample8, true, CS> : frame_ingest_yuv_kernel<Sample8, false, CS>;
 }
-static auto emit_kernel(const Yuv420& f) {
-  if (f.bytes == 2) return f.semi ? frame_emit_yuv_kernel<Sample16, true> : frame_emit_yuv_kernel<Sample16, false>;
-  return f.semi ? frame_emit_yuv_kernel<Sample8, true> : frame_emit_yuv_kernel<Sample8, false>;
+template <int CS>
+static auto emit_kernel_of(const YuvFrame& f) {
+  if (f.bytes == 2) return f.semi ? frame_emit_yuv_kernel<Sample16, true, CS> : frame_emit_yuv_kernel<Sample16, false, CS>;
+  return f.semi ? frame_emit_yuv_kernel<Sample8, true, CS> : frame_emit_yuv_kernel<Sample8, false, CS>;
+}
+static auto ingest_kernel(const YuvFrame& f) {
+  if (f.chroma == CS_444)   // (planar alone: yuv_frame_from)
+    return f.bytes == 2 ? frame_ingest_yuv_kernel<Sample16, false, CS_444> : frame_ingest_yuv_kernel<Sample8, false, CS_444>;
+  return f.chroma == CS_422 ? ingest_kernel_of<CS_422>(f) : ingest_kernel_of<CS_420>(f);
+}
+static auto emit_kernel(const YuvFrame& f) {
+  if (f.chroma == CS_444)
+    return f.bytes == 2 ? frame_emit_yuv_kernel<Sample16, false, CS_444> : frame_emit_yuv_kernel<Sample8, false, CS_444>;
+  return f.chroma == CS_422 ? emit_kernel_of<CS_422>(f) : emit_kernel_of<CS_420>(f);
 }
 
-int frame_ingest_yuv_check(const char* what, const Yuv420& f, const float* dst, int Hp, int Wp, int pad_mode) {
+int frame_ingest_yuv_check(const char* what, const YuvFrame& f, const float* dst, int Hp, int Wp, int pad_mode) {
   int rc = frame_planar_check(what, dst, Hp, Wp, 2 * YUV_Y);
   if (rc != DVSR_OK) return rc;
   rc = yuv_frame_check(what, f, Hp, Wp);
@@ -489,7 +653,7 @@ int frame_ingest_yuv_check(const char* what, const Yuv420& f, const float* dst, 
 }
 
 // (arguments checked by frame_ingest_yuv_check)
-int frame_ingest_yuv_launch(const Yuv420& f, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st) {
+int frame_ingest_yuv_launch(const YuvFrame& f, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st) {
   YuvIngestArgs a{};
   for (int i = 0; i < 3; ++i) {
     a.p[i] = static_cast<const unsigned char*>(f.plane[i]);
@@ -504,13 +668,13 @@ int frame_ingest_yuv_launch(const Yuv420& f, float* dst, int Hp, int Wp, int pad
   return check_launch(f.bytes == 2 ? "frame_ingest_yuv16_kernel" : "frame_ingest_yuv_kernel");
 }
 
-static int frame_ingest_yuv(const char* what, const Yuv420& f, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st) {
+static int frame_ingest_yuv(const char* what, const YuvFrame& f, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st) {
   int rc = frame_ingest_yuv_check(what, f, dst, Hp, Wp, pad_mode);
   if (rc != DVSR_OK) return rc;
   return frame_ingest_yuv_launch(f, dst, Hp, Wp, pad_mode, st);
 }
 
-static int frame_emit_yuv(const char* what, const Yuv420& f, const float* src, int Hs, int Ws, float lo, float hi, hipStream_t st) {
+static int frame_emit_yuv(const char* what, const YuvFrame& f, const float* src, int Hs, int Ws, float lo, float hi, hipStream_t st) {
   int rc = frame_planar_check(what, src, Hs, Ws, 2 * YUV_Y);
   if (rc != DVSR_OK) return rc;
   rc = yuv_frame_check(what, f, Hs, Ws);
@@ -535,27 +699,27 @@ static int frame_emit_yuv(const char* what, const Yuv420& f, const float* src, i
 using namespace dvsr;
 
 extern "C" int dvsr_frame_ingest_yuv(const dvsr_yuv_desc* sd, float* dst, int Hp, int Wp, int pad_mode, dvsr_stream_t stream) {
-  Yuv420 f;
-  int rc = yuv420_from("frame_ingest_yuv", sd, &f);
+  YuvFrame f;
+  int rc = yuv_frame_from("frame_ingest_yuv", sd, &f);
   return rc != DVSR_OK ? rc : frame_ingest_yuv("frame_ingest_yuv", f, dst, Hp, Wp, pad_mode, (hipStream_t)stream);
 }
 
 extern "C" int dvsr_frame_ingest_yuv16(const dvsr_yuv16_desc* sd, float* dst, int Hp, int Wp, int pad_mode, dvsr_stream_t stream) {
-  Yuv420 f;
-  int rc = yuv420_from("frame_ingest_yuv16", sd, &f);
+  YuvFrame f;
+  int rc = yuv_frame_from("frame_ingest_yuv16", sd, &f);
   return rc != DVSR_OK ? rc : frame_ingest_yuv("frame_ingest_yuv16", f, dst, Hp, Wp, pad_mode, (hipStream_t)stream);
 }
 
 extern "C" int dvsr_frame_emit_yuv(const float* src, int Hs, int Ws, const dvsr_yuv_desc* dd, float lo, float hi,
                                    dvsr_stream_t stream) {
-  Yuv420 f;
-  int rc = yuv420_from("frame_emit_yuv", dd, &f);
+  YuvFrame f;
+  int rc = yuv_frame_from("frame_emit_yuv", dd, &f);
   return rc != DVSR_OK ? rc : frame_emit_yuv("frame_emit_yuv", f, src, Hs, Ws, lo, hi, (hipStream_t)stream);
 }
 
 extern "C" int dvsr_frame_emit_yuv16(const float* src, int Hs, int Ws, const dvsr_yuv16_desc* dd, float lo, float hi,
                                      dvsr_stream_t stream) {
-  Yuv420 f;
-  int rc = yuv420_from("frame_emit_yuv16", dd, &f);
+  YuvFrame f;
+  int rc = yuv_frame_from("frame_emit_yuv16", dd, &f);
   return rc != DVSR_OK ? rc : frame_emit_yuv("frame_emit_yuv16", f, src, Hs, Ws, lo, hi, (hipStream_t)stream);
 }

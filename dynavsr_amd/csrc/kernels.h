@@ -241,20 +241,21 @@ int frame_ingest_check(const char* what, const void* src, const dvsr_frame_desc*
                        int pad_mode);
 int frame_ingest_launch(const void* src, const dvsr_frame_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
 
-// frame_yuv.hip: the same pair for a YCbCr 4:2:0 frame of 8, 10 or 12 bits (planes at any address / pitch), on the one form
-// that both public descriptors take inside.  yuv420_from checks the descriptor's own part -- null, format, depth -- and fills
-// it; _check does the rest.
-struct Yuv420 {
+// frame_yuv.hip: the same pair for a YCbCr 4:2:0, 4:2:2 or 4:4:4 frame of 8, 10 or 12 bits (planes at any address / pitch), on
+// the one form that both public descriptors take inside.  yuv_frame_from checks the descriptor's own part -- null, format,
+// depth -- and fills it; _check does the rest.
+struct YuvFrame {
   void* plane[3];
   long long rs[3];          // row strides, bytes
   int h, w, matrix, range;
-  bool semi;                // interleaved CbCr (NV12, P010 / P012); otherwise planar
+  bool semi;                // interleaved CbCr (NV12 / NV16, P010 / P012 / P210 / P212); otherwise planar
   int bytes, depth;         // per sample: 1 or 2; bits of a level: 8, 10 or 12
+  int chroma;               // DVSR_YUV_CHROMA_420 / _422 / _444 (never semi-planar)
 };
-int yuv420_from(const char* what, const dvsr_yuv_desc* d, Yuv420* f);
-int yuv420_from(const char* what, const dvsr_yuv16_desc* d, Yuv420* f);
-int frame_ingest_yuv_check(const char* what, const Yuv420& f, const float* dst, int Hp, int Wp, int pad_mode);
-int frame_ingest_yuv_launch(const Yuv420& f, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
+int yuv_frame_from(const char* what, const dvsr_yuv_desc* d, YuvFrame* f);
+int yuv_frame_from(const char* what, const dvsr_yuv16_desc* d, YuvFrame* f);
+int frame_ingest_yuv_check(const char* what, const YuvFrame& f, const float* dst, int Hp, int Wp, int pad_mode);
+int frame_ingest_yuv_launch(const YuvFrame& f, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
 
 // pad.hip: explicit padding / layout changes of the MFDN estimator and their adjoints
 enum : int { PAD_REFLECT = 0, PAD_REFLECT_S2D = 1, PAD_REPL_T3 = 2 };

@@ -33,6 +33,17 @@ word that carry no level are ignored on the way in and written as 0, and emit re
 siting and filters apply with H.273's level scale at that depth, nothing is rounded to 8 bits on the way, and an 8-bit or RGB
 source may leave with 10 bits (the same kernels of csrc/frame_yuv.hip on 16-bit samples).
 
+Footage that is not 4:2:0 (the chroma axis of the same kernel pair), never inferred either.  4:2:2 -- ProRes, DNxHR,
+XAVC intermediates, capture cards -- has chroma planes Hc x Wc = H x ceil(W/2): 'i422' (yuv422p) and 'nv16', 'i422p10' /
+'i422p12' (yuv422p10le / 12le, the level in the low bits) and 'p210' / 'p212' (the level in the top bits); a packed frame is
+[2H, W] with W even and any H, the planar form contiguous, the semi-planar one at any pitch.  4:4:4 -- screen recordings, Hi444 /
+RExt, animation masters -- has full-size chroma planes: 'i444' (yuv444p), 'i444p10' / 'i444p12' (yuv444p10le / 12le); a packed
+frame is [3H, W] at any size and pitch.  Plane tuples are as above with those plane sizes.  Matrices, ranges, level scales and
+word conventions are those of the 4:2:0 layout of the same sample kind; 4:2:2 keeps the horizontal chroma filters and has no
+vertical one, 4:4:4 has none.  YUV_LAYOUTS / YUV16_LAYOUTS name the 4:2:0 layouts, YUV422_LAYOUTS / YUV444_LAYOUTS these,
+ALL_YUV_LAYOUTS all of them.  Not provided: semi-planar 4:4:4 (nv24 / p410), packed 4:2:2 (YUY2 / UYVY / v210), 4:1:1 / 4:4:0,
+planar GBR, a 'bt2020' matrix, 16-bit depth, chroma siting other than "left".
+
 Scene cuts (csrc/frame_cut.hip: dvsr_frame_luma_sad), for any of the layouts above:
 
     luma_sad(frames, layout)             -> int64 [T-1]: sum over the frame of |Y8_t - Y8_(t-1)|, exact, in one pass on the device
@@ -67,13 +78,28 @@ from . import _lib as L
 
 LAYOUTS = ('chw', 'hwc_rgb', 'hwc_bgr')
 _BYTES, _WORDS = (torch.uint8,), (torch.uint16, torch.int16)
-# 4:2:0 layout -> (semi-planar, depth, the format of its descriptor, the format of its Y plane for luma_sad, its dtypes)
+# YCbCr layout -> (semi-planar, depth, the format of its descriptor, the format of its Y plane for luma_sad, its dtypes, its
+# chroma sub-sampling)
 _YUV = {'nv12': (True, 8, L.YUV_NV12, L.FRAME_U8_Y, _BYTES), 'i420': (False, 8, L.YUV_I420, L.FRAME_U8_Y, _BYTES),
         'p010': (True, 10, L.YUV16_SEMI_MSB, L.FRAME_U16_Y_MSB, _WORDS), 'p012': (True, 12, L.YUV16_SEMI_MSB, L.FRAME_U16_Y_MSB, _WORDS),
         'i420p10': (False, 10, L.YUV16_PLANAR_LSB, L.FRAME_U16_Y_10, _WORDS),
         'i420p12': (False, 12, L.YUV16_PLANAR_LSB, L.FRAME_U16_Y_12, _WORDS)}
+_YUV = {k: v + (L.YUV_CHROMA_420,) for k, v in _YUV.items()}
 YUV_LAYOUTS = tuple(k for k, v in _YUV.items() if v[1] == 8)
 YUV16_LAYOUTS = tuple(k for k, v in _YUV.items() if v[1] > 8)
+# 4:2:2 and 4:4:4: the 4:2:0 layout of the same sample kind with the chroma field of the format set (4:4:4: planar alone)
+for _name, _like, _chroma in (('i422', 'i420', L.YUV_CHROMA_422), ('nv16', 'nv12', L.YUV_CHROMA_422),
+                              ('i422p10', 'i420p10', L.YUV_CHROMA_422), ('i422p12', 'i420p12', L.YUV_CHROMA_422),
+                              ('p210', 'p010', L.YUV_CHROMA_422), ('p212', 'p012', L.YUV_CHROMA_422),
+                              ('i444', 'i420', L.YUV_CHROMA_444), ('i444p10', 'i420p10', L.YUV_CHROMA_444),
+                              ('i444p12', 'i420p12', L.YUV_CHROMA_444)):
+    _v = _YUV[_like]
+    _YUV[_name] = _v[:2] + (L.yuv_format(_v[2], _chroma),) + _v[3:5] + (_chroma,)
+YUV422_LAYOUTS = tuple(k for k, v in _YUV.items() if v[5] == L.YUV_CHROMA_422)
+YUV444_LAYOUTS = tuple(k for k, v in _YUV.items() if v[5] == L.YUV_CHROMA_444)
+ALL_YUV_LAYOUTS = YUV_LAYOUTS + YUV16_LAYOUTS + YUV422_LAYOUTS + YUV444_LAYOUTS
+# sub-sampling -> the shape of a packed frame, as the messages write it
+_PACKED = {L.YUV_CHROMA_420: '[H*3/2, W]', L.YUV_CHROMA_422: '[2H, W]', L.YUV_CHROMA_444: '[3H, W]'}
 _YUV_MATRIX = {'bt601': L.YUV_BT601, 'bt709': L.YUV_BT709}
 _YUV_RANGE = {'limited': L.YUV_LIMITED, 'full': L.YUV_FULL}
 _FORMAT = {'chw': L.FRAME_F32_CHW, 'hwc_rgb': L.FRAME_U8_HWC_RGB, 'hwc_bgr': L.FRAME_U8_HWC_BGR}
@@ -89,12 +115,12 @@ def padded_size(h, w, multiple):
 
 
 def is_yuv(layout):
-    """`layout` is one of the 4:2:0 layouts, of any depth."""
-    return layout in YUV_LAYOUTS + YUV16_LAYOUTS
+    """`layout` is one of the YCbCr layouts, of any sub-sampling and depth."""
+    return layout in ALL_YUV_LAYOUTS
 
 
 def resolve_layout(frame, layout=None):
-    """Checks one frame against `layout` (None: by dtype; the 4:2:0 layouts are never inferred) and returns
+    """Checks one frame against `layout` (None: by dtype; the YCbCr layouts are never inferred) and returns
     (layout, h, w).  No GPU call."""
     if is_yuv(layout):
         return (layout,) + yuv_planes(frame, layout)[1:]
@@ -103,7 +129,7 @@ def resolve_layout(frame, layout=None):
     if layout is None:
         layout = 'hwc_rgb' if frame.dtype == torch.uint8 else 'chw'
     if layout not in LAYOUTS:
-        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + YUV_LAYOUTS + YUV16_LAYOUTS)))
+        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + ALL_YUV_LAYOUTS)))
     if frame.dtype == torch.uint8:
         if layout == 'chw':
             raise ValueError("a uint8 frame is interleaved ('hwc_rgb' / 'hwc_bgr'), not 'chw'")
@@ -158,28 +184,61 @@ def check_yuv_names(matrix, yuv_range):
         raise ValueError("unknown YCbCr range %r ('limited' or 'full')" % (yuv_range,))
 
 
+def chroma_size(layout, h, w):
+    """(Hc, Wc) of a chroma plane of an h x w frame: ceil(h/2) x ceil(w/2) (4:2:0), h x ceil(w/2) (4:2:2), h x w (4:4:4)."""
+    chroma = _YUV[layout][5]
+    return ((h + 1) // 2 if chroma == L.YUV_CHROMA_420 else h), (w if chroma == L.YUV_CHROMA_444 else (w + 1) // 2)
+
+
+def packed_rows(layout, h):
+    """The rows of a packed frame of luma height h: h*3/2 (4:2:0), 2h (4:2:2), 3h (4:4:4)."""
+    return {L.YUV_CHROMA_420: h * 3 // 2, L.YUV_CHROMA_422: 2 * h, L.YUV_CHROMA_444: 3 * h}[_YUV[layout][5]]
+
+
+def packed_needs(layout, h, w):
+    """What a packed frame of `layout` asks of h x w and does not get: 'an even size' (4:2:0), 'an even width' (4:2:2), or None
+    (4:4:4 packs at any size)."""
+    chroma = _YUV[layout][5]
+    if chroma == L.YUV_CHROMA_420:
+        return 'an even size' if h % 2 or w % 2 else None
+    return 'an even width' if chroma == L.YUV_CHROMA_422 and w % 2 else None
+
+
 def yuv_planes(frame, layout):
-    """(planes, h, w) of a 4:2:0 frame -- a packed [H*3/2, W] tensor or a tuple of plane tensors, uint8 for 'nv12' / 'i420',
-    uint16 or int16 for the 10- / 12-bit layouts: the planes as views (y, uv) / (y, u, v), nothing copied.  ValueError for
-    anything else.  No GPU call."""
+    """(planes, h, w) of a YCbCr frame -- a packed tensor ([H*3/2, W] for 4:2:0, [2H, W] for 4:2:2, [3H, W] for 4:4:4) or a tuple
+    of plane tensors, uint8 for the 8-bit layouts, uint16 or int16 for the 10- / 12-bit ones: the planes as views (y, uv) /
+    (y, u, v), nothing copied.  ValueError for anything else.  No GPU call."""
     if not is_yuv(layout):
-        raise ValueError("unknown YCbCr layout %r (one of %s)" % (layout, ', '.join(YUV_LAYOUTS + YUV16_LAYOUTS)))
-    semi, depth, _, _, dtypes = _YUV[layout]
+        raise ValueError("unknown YCbCr layout %r (one of %s)" % (layout, ', '.join(ALL_YUV_LAYOUTS)))
+    semi, depth, _, _, dtypes, chroma = _YUV[layout]
     n, kind = (2 if semi else 3), ('uint8' if depth == 8 else 'uint16 / int16')
     if torch.is_tensor(frame):
         if frame.dtype not in dtypes or frame.dim() != 2:
-            raise ValueError("a packed %s frame must be %s [H*3/2, W], got %s %s" % (layout, kind, frame.dtype, tuple(frame.shape)))
+            raise ValueError("a packed %s frame must be %s %s, got %s %s" % (layout, kind, _PACKED[chroma], frame.dtype,
+                                                                             tuple(frame.shape)))
         rows, w = int(frame.shape[0]), int(frame.shape[1])
-        h = rows * 2 // 3
-        if rows < 3 or rows % 3 or h % 2 or w < 2 or w % 2:
-            raise ValueError("a packed %s frame is [H*3/2, W] with H and W even, got %s (pass planes for odd sizes)"
-                             % (layout, tuple(frame.shape)))
+        if chroma == L.YUV_CHROMA_420:
+            h = rows * 2 // 3
+            if rows < 3 or rows % 3 or h % 2 or w < 2 or w % 2:
+                raise ValueError("a packed %s frame is [H*3/2, W] with H and W even, got %s (pass planes for odd sizes)"
+                                 % (layout, tuple(frame.shape)))
+        elif chroma == L.YUV_CHROMA_422:
+            h = rows // 2
+            if rows < 2 or rows % 2 or w < 2 or w % 2:
+                raise ValueError("a packed %s frame is [2H, W] with W even, got %s (pass planes for an odd width)"
+                                 % (layout, tuple(frame.shape)))
+        else:
+            h = rows // 3
+            if rows < 3 or rows % 3 or w < 1:
+                raise ValueError("a packed %s frame is [3H, W], got %s" % (layout, tuple(frame.shape)))
+            return (frame[:h], frame[h:2 * h], frame[2 * h:]), h, w         # (three planes of full rows: any pitch)
+        hc, wc = chroma_size(layout, h, w)
         if semi:
-            return (frame[:h], frame[h:].unflatten(1, (w // 2, 2))), h, w
+            return (frame[:h], frame[h:].unflatten(1, (wc, 2))), h, w
         if not frame.is_contiguous():
             raise ValueError("a packed %s frame must be contiguous (its chroma rows are half as long); pass planes" % layout)
-        flat, n_c = frame.view(-1), (h // 2) * (w // 2)
-        return (frame[:h], flat[h * w:h * w + n_c].view(h // 2, w // 2), flat[h * w + n_c:].view(h // 2, w // 2)), h, w
+        flat, n_c = frame.view(-1), hc * wc
+        return (frame[:h], flat[h * w:h * w + n_c].view(hc, wc), flat[h * w + n_c:].view(hc, wc)), h, w
     if not isinstance(frame, (tuple, list)) or len(frame) != n or not all(torch.is_tensor(p) for p in frame):
         raise ValueError("a %s frame is a packed %s tensor or %d plane tensors, got %s" % (
             layout, kind, n, type(frame).__name__ if not isinstance(frame, (tuple, list)) else "%d items" % len(frame)))
@@ -190,7 +249,7 @@ def yuv_planes(frame, layout):
     if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
         raise ValueError("the Y plane must be [H,W], got %s" % (tuple(y.shape),))
     h, w = int(y.shape[0]), int(y.shape[1])
-    want = ((h + 1) // 2, (w + 1) // 2) + ((2,) if semi else ())
+    want = chroma_size(layout, h, w) + ((2,) if semi else ())
     for p in planes[1:]:
         if tuple(p.shape) != want:
             raise ValueError("a chroma plane of a %d x %d %s frame must be %s, got %s" % (h, w, layout, list(want), tuple(p.shape)))
@@ -198,11 +257,12 @@ def yuv_planes(frame, layout):
 
 
 def describe_yuv(planes, layout, h, w, matrix='bt601', yuv_range='limited', copy=True):
-    """(planes', dvsr_yuv_desc) of what yuv_planes returned (a dvsr_yuv16_desc for the 10- / 12-bit layouts).  A plane that the
+    """(planes', dvsr_yuv_desc) of what yuv_planes returned (a dvsr_yuv16_desc for the 10- / 12-bit layouts; the layout's chroma
+    sub-sampling is in the descriptor's format).  A plane that the
     descriptor can express -- any offset, any row pitch -- is passed by stride; any other is copied first (copy = False:
     ValueError, for a destination)."""
     check_yuv_names(matrix, yuv_range)
-    (_, depth, fmt, _, _), rest = _YUV[layout], (h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
+    (_, depth, fmt, _, _, _), rest = _YUV[layout], (h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
     desc = L.Yuv16Desc(fmt, depth, *rest) if depth > 8 else L.YuvDesc(fmt, *rest)
     kept = []
     for i, p in enumerate(planes):
@@ -222,7 +282,7 @@ def describe_yuv(planes, layout, h, w, matrix='bt601', yuv_range='limited', copy
 
 
 def _yuv_entry(layout, name):
-    """The C entry point `name` ('frame_ingest' / 'frame_emit' / 'edvr_stream_extract_frame') of a 4:2:0 layout."""
+    """The C entry point `name` ('frame_ingest' / 'frame_emit' / 'edvr_stream_extract_frame') of a YCbCr layout."""
     name = "dvsr_%s_%s" % (name, 'yuv16' if _YUV[layout][1] > 8 else 'yuv')
     return getattr(L.lib(), name), name
 
@@ -248,7 +308,8 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix=
     [3,Hp,Wp] view of a buffer whose rows are.
     'nv12' / 'i420': frame is a packed uint8 [H*3/2, W] tensor or a tuple of planes (module docstring), converted with
     `matrix` / `yuv_range` to un-rounded RGB in [0,1] -- one launch, like the other layouts.  'p010' / 'p012' / 'i420p10' /
-    'i420p12': the same for uint16 / int16 words of 10 or 12 bits."""
+    'i420p12': the same for uint16 / int16 words of 10 or 12 bits.  The 4:2:2 and 4:4:4 layouts (module docstring): the same,
+    packed [2H, W] / [3H, W] or as planes."""
     check_yuv_names(matrix, yuv_range)
     layout, h, w = resolve_layout(frame, layout)
     Hp, Wp = padded_size(h, w, multiple)
@@ -455,15 +516,17 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     tuple of planes (module docstring; needed for an odd h or w) and is returned; bytes outside the planes' rows are not
     touched.  'p010' / 'p012' / 'i420p10' / 'i420p12': the same as 10- / 12-bit words, a packed torch.uint16 [h*3/2, w] tensor
     (`out`: uint16 or int16); the bits of a word that carry no level are written as 0.
+    The 4:2:2 layouts: packed [2h, w], which needs an even w alone; the 4:4:4 layouts: packed [3h, w] at any size.
     size = (oh, ow): the crop is first resampled to oh x ow (resize(): one more launch into a buffer of its own), and
     everything above holds for the oh x ow image -- emit(resize(sr, h, w, size), oh, ow, layout, ...), bit for bit."""
     if layout not in LAYOUTS and not is_yuv(layout):
-        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + YUV_LAYOUTS + YUV16_LAYOUTS)))
+        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + ALL_YUV_LAYOUTS)))
     check_yuv_names(matrix, yuv_range)
     if size is not None:
         oh, ow = check_resize(h, w, size)
-        if is_yuv(layout) and out is None and (oh % 2 or ow % 2):
-            raise ValueError("emit: a packed %s frame needs an even size, got %d x %d: pass `out` as planes" % (layout, oh, ow))
+        if is_yuv(layout) and out is None and packed_needs(layout, oh, ow):
+            raise ValueError("emit: a packed %s frame needs %s, got %d x %d: pass `out` as planes"
+                             % (layout, packed_needs(layout, oh, ow), oh, ow))
         # (the whole buffer goes on: its rows are 16-byte aligned, those of resize()'s view are not when ow % 4)
         return emit(_resize(sr, h, w, (oh, ow))[0], oh, ow, layout, min_max, out, matrix, yuv_range)
     if sr.dim() == 4 and sr.shape[0] == 1:
@@ -475,8 +538,9 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     if not (1 <= h <= Hs and 1 <= w <= Ws):
         raise ValueError("emit: crop %d x %d outside the frame %d x %d" % (h, w, Hs, Ws))
     if is_yuv(layout):
-        if out is None and (h % 2 or w % 2):
-            raise ValueError("emit: a packed %s frame needs an even size, got %d x %d: pass `out` as planes" % (layout, h, w))
+        if out is None and packed_needs(layout, h, w):
+            raise ValueError("emit: a packed %s frame needs %s, got %d x %d: pass `out` as planes"
+                             % (layout, packed_needs(layout, h, w), h, w))
         if out is not None:
             planes, ho, wo = yuv_planes(out, layout)
             if (ho, wo) != (h, w):
@@ -493,7 +557,7 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     if is_yuv(layout):
         with torch.cuda.device(sr.device):
             if out is None:
-                out = torch.empty((h * 3 // 2, w), dtype=_YUV[layout][4][0], device=sr.device)
+                out = torch.empty((packed_rows(layout, h), w), dtype=_YUV[layout][4][0], device=sr.device)
                 planes = yuv_planes(out, layout)[0]
             _, desc = describe_yuv(planes, layout, h, w, matrix, yuv_range, copy=False)
             fn, name = _yuv_entry(layout, 'frame_emit')
@@ -611,7 +675,7 @@ SCORE_MAX_SIDE = 32768
 
 
 def layout_depth(layout):
-    """The bits of a sample of `layout`: 10 or 12 for the 16-bit 4:2:0 layouts, 8 for everything else (a float frame is scored
+    """The bits of a sample of `layout`: 10 or 12 for the 16-bit YCbCr layouts, 8 for everything else (a float frame is scored
     as the 8-bit image emit() would write)."""
     return _YUV[layout][1] if is_yuv(layout) else 8
 

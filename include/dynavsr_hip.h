@@ -410,15 +410,32 @@ int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_frame_desc* des
  * dvsr_edvr_stream_extract_frame_yuv: dvsr_edvr_stream_extract_frame for such a frame (no temporary, no device copy).
  * Bad arguments (null descriptor / plane, unknown format / matrix / range / pad mode, h or w < 1 or beyond the target, a row
  * stride shorter than a row, a reflect pad not smaller than the dimension, a misaligned fp32 side) return DVSR_ERR_INVALID
- * before any launch. */
+ * before any launch.
+ *
+ * 4:2:2 and 4:4:4 (ProRes / DNxHR / XAVC intermediates and capture surfaces; screen recordings, Hi444 / RExt, animation
+ * masters): new values of `format` for the same functions and for those of the 16-bit section below -- the form (semi-planar
+ * 0 | planar 1) in the low four bits, the sub-sampling above them: format = DVSR_YUV_FORMAT(form, chroma).  Chroma planes:
+ *   DVSR_YUV_CHROMA_420  Hc x Wc = ceil(h/2) x ceil(w/2)   (0: the two forms alone are NV12 / I420, as they always were)
+ *   DVSR_YUV_CHROMA_422  Hc x Wc = h x ceil(w/2)           nv16 / yuv422p; p210le / p212le / yuv422p10le / yuv422p12le
+ *   DVSR_YUV_CHROMA_444  Hc x Wc = h x w, planar alone     yuv444p; yuv444p10le / yuv444p12le
+ * Matrices, ranges, level scales, word conventions, clamps and roundings are those of 4:2:0; only the resampling differs.
+ * 4:2:2: chroma sample (y, k) sits on luma row y, column 2k; ingest takes the [1,1]/2 step between two chroma columns and no
+ * vertical step; emit takes the taps [1,2,1]/4 on columns 2k-1 .. 2k+1 of row y, clamped to the crop, and no vertical mean.
+ * 4:4:4: a pixel's chroma is its own sample both ways.  A row stride must hold Wc samples (planar) or 2 Wc (semi-planar).
+ * Not provided: semi-planar 4:4:4 (nv24 / p410: refused as an unknown format), packed 4:2:2 (YUY2 / UYVY / v210), 4:1:1 /
+ * 4:4:0, planar GBR, a BT.2020 matrix, depth 16, chroma siting other than "left". */
 #define DVSR_YUV_NV12 0      /* plane[0] = Y [h][w], plane[1] = CbCr interleaved [Hc][Wc][2]; plane[2] ignored */
 #define DVSR_YUV_I420 1      /* plane[0] = Y, plane[1] = Cb [Hc][Wc], plane[2] = Cr [Hc][Wc] */
+#define DVSR_YUV_CHROMA_420 0
+#define DVSR_YUV_CHROMA_422 1
+#define DVSR_YUV_CHROMA_444 2
+#define DVSR_YUV_FORMAT(form, chroma) ((form) | ((chroma) << 4))   /* e.g. nv16 = DVSR_YUV_FORMAT(DVSR_YUV_NV12, DVSR_YUV_CHROMA_422) */
 #define DVSR_YUV_BT601 0
 #define DVSR_YUV_BT709 1
 #define DVSR_YUV_LIMITED 0
 #define DVSR_YUV_FULL 1
 typedef struct dvsr_yuv_desc {
-  int format;   /* DVSR_YUV_NV12 / _I420 */
+  int format;   /* DVSR_YUV_NV12 / _I420, or DVSR_YUV_FORMAT(one of them, DVSR_YUV_CHROMA_*) */
   int h, w;     /* the frame's own (luma) size */
   int matrix, range;
   void* plane[3];
@@ -449,7 +466,7 @@ int dvsr_edvr_stream_extract_frame_yuv(const dvsr_edvr_stream* stream_plan, cons
 #define DVSR_YUV16_SEMI_MSB 0     /* plane[0] = Y [h][w], plane[1] = CbCr interleaved [Hc][Wc][2]; plane[2] ignored */
 #define DVSR_YUV16_PLANAR_LSB 1   /* plane[0] = Y, plane[1] = Cb [Hc][Wc], plane[2] = Cr [Hc][Wc] */
 typedef struct dvsr_yuv16_desc {
-  int format, depth;         /* DVSR_YUV16_*; depth 10 or 12 */
+  int format, depth;         /* DVSR_YUV16_*, or DVSR_YUV_FORMAT(one of them, DVSR_YUV_CHROMA_*); depth 10 or 12 */
   int h, w;                  /* the frame's own (luma) size */
   int matrix, range;         /* DVSR_YUV_BT601 / _BT709, DVSR_YUV_LIMITED / _FULL */
   void* plane[3];

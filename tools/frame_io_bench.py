@@ -26,8 +26,20 @@
    more than that yardstick's own max - min spread.  Then frames/s of a pinned P010 video -> P010 frames on the host against
    the same video through the HWC uint8 path of 2, which moves the same 3 bytes per output pixel back to the host.
 
+5. the chroma axis of that kernel pair (4:2:2 and 4:4:4), by the method of 3:
+   a. with `--parent-lib PATH` (a libdynavsr_hip.so built from the commit before the axis): the four 4:2:0 kernels of part 3 / 4
+      -- ingest 180x320 and emit 720x1280, NV12 and P010 -- of this build and of that library, alternated in this process.
+      Expected: the difference of the medians inside the parent's own max - min spread.
+   b. every new layout's ingest and emit against the 4:2:0 kernel of the same sample kind in this build (NV12 for bytes, P010
+      for words), PER BYTE MOVED: per pixel, ingest reads 1.5 / 2 / 3 samples (4:2:0 / 4:2:2 / 4:4:4) and writes 12 B, emit the
+      reverse.  Expectation, not a gate: us per MB not above the yardstick's by more than its spread.
+   c. frames/s of a pinned p210 video -> p210 frames on the host against the same levels as a p010 video -> p010 frames.  A p210
+      frame is 4 bytes per pixel against 3 both ways; what comes back dominates (16 x the pixels), so the expected cost is the
+      copy time of a third more bytes, where the copy is not hidden behind the network.
+
 usage (GPU box): python tools/frame_io_bench.py [--h 180 --w 320 --frames 100 --repeats 5 --calls 200 --yuv-repeats 10]
-                 > profiles/r12_yuv16_io.txt   (profiles/r10_yuv_io.txt: parts 1 to 3; profiles/r08_frame_io.txt: 1 and 2)"""
+                 [--parent-lib PATH] > profiles/r16_chroma_io.txt   (profiles/r12_yuv16_io.txt: parts 1 to 4;
+                 profiles/r10_yuv_io.txt: 1 to 3; profiles/r08_frame_io.txt: 1 and 2)"""
 import argparse
 import ctypes
 import os
@@ -52,6 +64,7 @@ ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--calls", type=int, default=200)
 ap.add_argument("--in-flight", type=int, default=2)
 ap.add_argument("--yuv-repeats", type=int, default=10)
+ap.add_argument("--parent-lib", default=None, help="part 5a: a libdynavsr_hip.so built from the parent commit")
 args = ap.parse_args()
 H, W, T = args.h, args.w, args.frames
 OPT = {'scale': 4, 'network_G': {'which_model_G': 'EDVR', 'nframes': 5}}
@@ -324,3 +337,88 @@ print("  HWC RGB in, HWC RGB out (%.2f MB back)        median %7.1f frames/s  sp
     12 * H * 4 * W / 1e6, mh, sh, " ".join("%.1f" % v for v in fh)))
 print("  P010 - HWC = %+.1f frames/s (%+.1f %%); HWC spread %.1f -> expectation %s" % (
     mp - mh, 100 * (mp - mh) / mh, sh, "MET (not below the HWC path by more than its spread)" if mp >= mh - sh else "MISSED"))
+
+
+# ---- 5. the chroma axis: 4:2:2 and 4:4:4 next to 4:2:0
+def yuv_launches(lb, lay, h, w, buf, plane, ingest):
+    """One launch of `lay`'s ingest (packed frame `buf` -> `plane`) or emit (`plane` -> `buf`) through library `lb`."""
+    planes, d = frames.describe_yuv(frames.yuv_planes(buf, lay)[0], lay, h, w, copy=ingest)
+    keep.append((planes, d))
+    suffix = "yuv16" if frames.layout_depth(lay) > 8 else "yuv"
+    if ingest:
+        return c_launch(getattr(lb, "dvsr_frame_ingest_" + suffix), ctypes.byref(d), plane.data_ptr(), h, w, L.FRAME_PAD_REFLECT)
+    return c_launch(getattr(lb, "dvsr_frame_emit_" + suffix), plane.data_ptr(), h, w, ctypes.byref(d), ctypes.c_float(0.0),
+                    ctypes.c_float(1.0))
+
+
+def packed_frame(lay, h, w):
+    """A packed frame of random levels in `lay` on the device."""
+    depth, rows = frames.layout_depth(lay), frames.packed_rows(lay, h)
+    if depth == 8:
+        return torch.from_numpy(r.randint(0, 256, (rows, w)).astype(np.uint8)).cuda()
+    shift = 16 - depth if lay.startswith('p') else 0
+    return torch.from_numpy((r.randint(0, 2 ** depth, (rows, w)) << shift).astype(np.uint16)).cuda()
+
+
+def frame_bytes(lay, h, w):
+    """The algorithmic bytes of one ingest or emit: the packed frame once and the fp32 planes once."""
+    return frames.packed_rows(lay, h) * w * (1 if frames.layout_depth(lay) == 8 else 2) + 12 * h * w
+
+
+keep = []
+planes_in, planes_out = torch.empty((3, 180, 320), device='cuda'), torch.rand((3, 720, 1280), device='cuda')
+if args.parent_lib:
+    parent = ctypes.CDLL(args.parent_lib)
+    for name in ("dvsr_frame_ingest_yuv", "dvsr_frame_emit_yuv", "dvsr_frame_ingest_yuv16", "dvsr_frame_emit_yuv16"):
+        getattr(parent, name).argtypes, getattr(parent, name).restype = getattr(lib, name).argtypes, getattr(lib, name).restype
+    print("5a. the 4:2:0 kernels of this build against those of %s (the yardstick of every pair)" % os.path.basename(args.parent_lib))
+    for lay in ('nv12', 'p010'):
+        for ingest, (h, w), plane in ((True, (180, 320), planes_in), (False, (720, 1280), planes_out)):
+            buf = packed_frame(lay, h, w)
+            what = "%s %s %dx%d" % ("ingest" if ingest else "emit", lay, h, w)
+            compare("%s, %d launches per replay, %d repetitions alternated" % (what, args.calls, args.yuv_repeats),
+                    [("parent " + what, yuv_launches(parent, lay, h, w, buf, plane, ingest), frame_bytes(lay, h, w)),
+                     ("this build " + what, yuv_launches(lib, lay, h, w, buf, plane, ingest), frame_bytes(lay, h, w))],
+                    args.yuv_repeats)
+else:
+    print("5a. NOT measured: no --parent-lib")
+print("5b. every new layout against the 4:2:0 kernel of its sample kind, per byte moved")
+for group in (('nv12', 'nv16', 'i422', 'i444'), ('p010', 'p210', 'i422p10', 'i444p10')):
+    for ingest, (h, w), plane in ((True, (180, 320), planes_in), (False, (720, 1280), planes_out)):
+        entries = [("%s %s" % ("ingest" if ingest else "emit", lay),
+                    yuv_launches(lib, lay, h, w, packed_frame(lay, h, w), plane, ingest), frame_bytes(lay, h, w)) for lay in group]
+        compare("%s %dx%d, %d launches per replay, %d repetitions alternated" % ("ingest" if ingest else "emit", h, w, args.calls,
+                                                                                args.yuv_repeats), entries, args.yuv_repeats, per_byte=True)
+del keep, planes_in, planes_out
+
+levels = r.randint(64, 941, (T, 2 * H, W))                                   # Y | CbCr rows of a 4:2:2 frame; 4:2:0 takes 3/4 of them
+p210_video = torch.from_numpy((levels << 6).astype(np.uint16)).pin_memory()                          # [T,2H,W] pinned
+p010_video = torch.from_numpy((levels[:, :H * 3 // 2] << 6).astype(np.uint16)).pin_memory()          # [T,H*3/2,W] pinned
+p210_out = torch.empty((T, 8 * H, 4 * W), dtype=torch.uint16).pin_memory()
+
+
+def p2x0_path(video, layout, out):
+    def go():
+        for i, y in enumerate(adapt.super_resolve_frames(OPT, net, video, in_flight=args.in_flight, layout=layout)):
+            out[i].copy_(y, non_blocking=True)
+        torch.cuda.synchronize()
+    return go
+
+
+p210_path, p010_path = p2x0_path(p210_video, 'p210', p210_out), p2x0_path(p010_video, 'p010', p010_out)
+p210_path()
+p010_path()
+f2, f0 = [], []
+for _ in range(args.yuv_repeats):
+    f2.append(timed(p210_path))
+    f0.append(timed(p010_path))
+m2, m0 = statistics.median(f2), statistics.median(f0)
+s0 = max(f0) - min(f0)
+print("5c. video %d frames %dx%d pinned host -> %dx%d host, in_flight %d, %d repetitions alternated" % (
+    T, H, W, 4 * H, 4 * W, args.in_flight, args.yuv_repeats))
+print("  p210 in, p210 out (%.2f MB in, %.2f MB back per frame)   median %7.1f frames/s  spread %5.1f  (%s)" % (
+    4 * H * W / 1e6, 16 * H * 4 * W / 1e6, m2, max(f2) - min(f2), " ".join("%.1f" % v for v in f2)))
+print("  p010 in, p010 out (%.2f MB in, %.2f MB back per frame)   median %7.1f frames/s  spread %5.1f  (%s)" % (
+    3 * H * W / 1e6, 12 * H * 4 * W / 1e6, m0, s0, " ".join("%.1f" % v for v in f0)))
+print("  p210 - p010 = %+.1f frames/s (%+.1f %%); p010 spread %.1f; 4 bytes per pixel against 3 travel both ways -> %s" % (
+    m2 - m0, 100 * (m2 - m0) / m0, s0, "inside the p010 spread" if m2 >= m0 - s0 else "below the p010 path by more than its spread"))
