@@ -111,6 +111,11 @@ class ResizeAxis(Structure):
     _fields_ = [("first", c_void_p), ("weights", c_void_p), ("taps", c_int)]
 
 
+class StitchAxis(Structure):
+    """dvsr_stitch_axis: the table of one axis of dvsr_frame_stitch, in device memory (include/dynavsr_hip.h)."""
+    _fields_ = [("first", c_void_p), ("weights", c_void_p), ("origins", c_void_p), ("cover", c_int)]
+
+
 FLIP_W, FLIP_H = 1, 2                                             # dvsr_frame_flip's flags
 
 
@@ -249,6 +254,12 @@ def _declare(lib):
         "dvsr_frame_resize": (I, [P, I, I, I, I, P, I, I, I, I, POINTER(ResizeAxis), POINTER(ResizeAxis), P]),
         "dvsr_frame_flip": (I, [P, P, LL, I, I, I, P]),
         "dvsr_frame_flip_mean": (I, [P, P, P, P, P, LL, I, I, P]),
+        "dvsr_frame_stitch_origins": (I, [I, I, I, POINTER(c_int), I]),
+        "dvsr_frame_stitch_cover": (I, [I, I, I]),
+        "dvsr_frame_stitch_table": (I, [I, I, I, I, I, P, P]),
+        "dvsr_frame_stitch": (I, [P, I, I, I, I, I, P, I, I, POINTER(StitchAxis), POINTER(StitchAxis), POINTER(c_int),
+                                  POINTER(c_int), P]),
+        "dvsr_edvr_stream_max_image_bytes": (ctypes.c_ulonglong, [P]),
         "dvsr_frame_score_workspace_bytes": (c_size_t, [I, I, I]),
         "dvsr_frame_score": (I, [P, POINTER(FrameDesc), P, POINTER(FrameDesc), POINTER(ScoreArgs), P, P, c_size_t, P]),
     }

@@ -890,9 +890,131 @@ def _video_format(frames, layout):
     return first
 
 
+MAX_IMAGE_BYTES = 1 << 32     # the conv and DCN kernels address one image of a tensor with 32-bit offsets (csrc/common.h)
+
+
+def tile_origins(n, tile, overlap):
+    """The origins of the tiles of one axis of padded length n (a multiple of 4), in LR pixels: tile a multiple of 4, overlap a
+    multiple of 4 with 0 <= overlap <= tile / 2.  tile >= n: [0], one tile of length n.  Otherwise step = tile - overlap and
+    the origins are k * step for every k * step < n - tile, then n - tile: every tile has the same size, the last one is anchored
+    at the edge, every origin is a multiple of 4 and a position is covered by at most 3 tiles (dvsr_frame_stitch_origins; host
+    code)."""
+    import ctypes
+    from . import _lib as L
+    n, tile, overlap = int(n), int(tile), int(overlap)
+    count = L.lib().dvsr_frame_stitch_origins(n, tile, overlap, None, 0)
+    if count < 1:
+        raise ValueError("tile_origins: " + L.lib().dvsr_last_error().decode("utf-8", "replace"))
+    arr = (ctypes.c_int * count)()
+    L.lib().dvsr_frame_stitch_origins(n, tile, overlap, arr, count)
+    return list(arr)
+
+
+def _check_tile(tile, overlap, budget=None, who="super_resolve_frames"):
+    """(tile, overlap) of the tile arguments: tile is None, 'auto' or (th, tw); ValueError for anything else.  No GPU call."""
+    import numbers
+
+    def integral(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if not integral(overlap) or overlap < 0 or overlap % 4:
+        raise ValueError("%s: tile_overlap=%r must be a multiple of 4, >= 0" % (who, overlap))
+    if budget is not None and not (isinstance(tile, str) and tile == 'auto'):
+        raise ValueError("%s: tile_budget is the budget of tile='auto', got tile=%r" % (who, tile))
+    if budget is not None and (isinstance(budget, bool) or not isinstance(budget, numbers.Real) or not budget > 0):
+        raise ValueError("%s: tile_budget=%r must be a positive number of bytes" % (who, budget))
+    if tile is None:
+        return None, int(overlap)
+    if isinstance(tile, str):
+        if tile != 'auto':
+            raise ValueError("%s: tile=%r (None, 'auto', an int or (th, tw))" % (who, tile))
+        return 'auto', int(overlap)
+    if integral(tile):
+        tile = (tile, tile)
+    if not isinstance(tile, (tuple, list)) or len(tile) != 2 or not all(integral(v) for v in tile):
+        raise ValueError("%s: tile=%r (None, 'auto', an int or (th, tw))" % (who, tile))
+    for v in tile:
+        if v % 4 or v < 16 or v < 2 * overlap:
+            raise ValueError("%s: tile=%r with tile_overlap=%d: a tile side is a multiple of 4, at least 16 and at least twice the "
+                             "overlap" % (who, tuple(tile), overlap))
+    return (int(tile[0]), int(tile[1])), int(overlap)
+
+
+def _tile_parts(net, h, w, tile, overlap, in_flight, scenes=1, flip_test=False, multiple=4):
+    """tile_footprint's terms as a dict, 'plan' (a StreamPlan built for the query alone, never run), 'tile' and 'grid' beside
+    them."""
+    from . import frames as fio
+    from .models.archs.EDVR_arch import EDVR
+    if not isinstance(net, EDVR):
+        raise ValueError("tile_footprint: the footprint comes from an EDVR stream plan's queries; got %s" % type(net).__name__)
+    tile, overlap = _check_tile(tile, overlap, who="tile_footprint")
+    if tile == 'auto':
+        raise ValueError("tile_footprint: tile='auto' is choose_tile's answer, pass it")
+    in_flight, scenes, mult = max(1, int(in_flight)), max(1, int(scenes)), int(multiple)
+    mult *= 4 // math.gcd(mult, 4)
+    Hp, Wp = fio.padded_size(h, w, mult)
+    th, tw = (Hp, Wp) if tile is None else (min(tile[0], Hp), min(tile[1], Wp))
+    ny, nx = len(tile_origins(Hp, th, overlap)), len(tile_origins(Wp, tw, overlap))
+    n_tiles, nv, s = ny * nx, (4 if flip_test else 1), int(net.scale)
+    plan = engine.StreamPlan(net._cfg(), th, tw, n_tiles * nv * stream_slots(int(net.nframes), in_flight, scenes))
+    tile_out = 3 * s * th * s * tw * 4                       # one fuse tape's output
+    return {'plan': plan, 'tile': (th, tw), 'grid': (ny, nx),
+            'cache': plan.cache_bytes,
+            'workspaces': in_flight * plan.workspace_bytes,
+            'tile_buffers': in_flight * n_tiles * tile_out if n_tiles > 1 else 0,
+            'staging': in_flight * 3 * s * Hp * s * Wp * 4,
+            'flip': in_flight * (2 * 3 * th * tw * 4 + 4 * tile_out) if flip_test else 0}
+
+
+_FOOTPRINT_TERMS = ('cache', 'workspaces', 'tile_buffers', 'staging', 'flip')
+
+
+def tile_footprint(net, h, w, tile, overlap=16, in_flight=2, scenes=1, flip_test=False, multiple=4):
+    """The bytes of every allocation that super_resolve_frames(net, h x w frames, tile=tile, tile_overlap=overlap, ...) makes for
+    an EDVR network itself, from the stream plan's queries and without a GPU (the network may be on the CPU): the frame cache
+    (n_tiles * nv * stream_slots slots of the tile's plan), one workspace per window in flight, and per window in flight the
+    [n_tiles,3,s th,s tw] buffer of the fuse tapes' outputs (more than one tile), the stitched / fuse tape's [1,3,s Hp,s Wp]
+    frame (the staging buffer, or the yielded tensor itself), and under flip_test the two [3,th,tw] mirror buffers and the
+    four fuse outputs.  Not counted: the frames the caller holds, a frame's bytes on their way in, the yielded frames of
+    `out` / `out_size` (a resampled frame and the encoder's bytes: a few times oh x ow), `scores`' workspace, and what the
+    caching allocator rounds up.  tile=None: the whole frame as one tile.  `scenes`: 1, or any larger number for a video with
+    cuts (stream_slots)."""
+    parts = _tile_parts(net, h, w, tile, overlap, in_flight, scenes, flip_test, multiple)
+    return sum(parts[k] for k in _FOOTPRINT_TERMS)
+
+
+def choose_tile(net, h, w, budget, overlap=16, in_flight=2, scenes=1, flip_test=False, multiple=4):
+    """(th, tw): the tile of the grid with the fewest tiles whose tile_footprint is at most `budget` bytes and whose plan passes
+    the size check (StreamPlan.max_image_bytes < 2^32); among grids of one tile count the tile closest to square.  For a grid of
+    ky x kx tiles the tile is the smallest that gives it: per axis the padded length itself (k = 1), or the smallest multiple of
+    `multiple` (raised to a multiple of 4) >= (n + (k - 1) overlap) / k, at least 16 and 2 * overlap.  At most 16 tiles per axis
+    are tried.  ValueError when no grid fits.  Host code."""
+    from . import frames as fio
+    _, overlap = _check_tile(None, overlap, who="choose_tile")
+    mult = int(multiple) * (4 // math.gcd(int(multiple), 4))
+    Hp, Wp = fio.padded_size(h, w, mult)
+
+    def axis(n):
+        found = {}
+        for k in range(1, 17):
+            t = n if k == 1 else max(-(-(n + (k - 1) * overlap) // (k * mult)) * mult, -(-16 // mult) * mult,
+                                     -(-2 * overlap // mult) * mult)
+            if t <= n and (k == 1 or t < n) and len(tile_origins(n, t, overlap)) == k:
+                found.setdefault(k, t)
+        return found
+    ys, xs = axis(Hp), axis(Wp)
+    grids = sorted(((ky * kx, abs(ys[ky] - xs[kx]), ys[ky], xs[kx]) for ky in ys for kx in xs))
+    for _, _, th, tw in grids:
+        parts = _tile_parts(net, h, w, (th, tw) if (th, tw) != (Hp, Wp) else None, overlap, in_flight, scenes, flip_test, mult)
+        if parts['plan'].max_image_bytes < MAX_IMAGE_BYTES and sum(parts[k] for k in _FOOTPRINT_TERMS) <= budget:
+            return th, tw
+    raise ValueError("choose_tile: no grid of at most 16 x 16 tiles of a %d x %d frame fits %d bytes (overlap %d, in_flight %d)"
+                     % (h, w, int(budget), overlap, max(1, int(in_flight))))
+
+
 def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, layout=None, out=None, pad_mode='reflect',
                          multiple=None, matrix='bt601', yuv_range='limited', cuts=None, cut_threshold=10.0, out_size=None,
-                         flip_test=False, gt=None, gt_layout=None, score='rgb', crop_border=0, scores=None):
+                         flip_test=False, gt=None, gt_layout=None, score='rgb', crop_border=0, scores=None,
+                         tile=None, tile_overlap=16, tile_budget=None):
     """Super-resolves a VIDEO: `frames` is a [T,3,H,W] tensor or a list of [3,H,W] frames (CPU or GPU); yields the SR frame
     [1,3,sH,sW] of every frame, in order -- what `net(frames[index_generation(i, T, nframes, padding)][None])` gives, the
     sliding-window test of the reference's video datasets (video_test_dataset_int.py:219, `padding: new_info` in the
@@ -965,6 +1087,23 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     against an RGB GT needs matrix='bt601', yuv_range='limited': the only pair for which the Y plane is the Y8 of the GT.
     score_summary turns `scores` into the reference's per-scene PSNR / SSIM means.  The yielded frames are what they are
     without `gt`; None takes exactly the calls described above.
+    Frames too large for one plan: the kernels address one image of a tensor with 32-bit offsets, so an EDVR plan whose largest
+    per-image tensor (engine.StreamPlan.max_image_bytes: 4096 h w bytes for nf = 64 at scale 4) reaches 2^32 -- 1080 x 1920 does
+    -- is refused with a ValueError that names `tile`, and the workspace of a plan grows with its pixels.  `tile` = (th, tw), an
+    int for both, or 'auto' (None: the whole frame, exactly the calls described above) cuts the padded frame into overlapping
+    tiles of ONE size, th x tw LR pixels (multiples of 4 and of `multiple`, at least 16 and 2 * tile_overlap), tile_origins
+    per axis with `tile_overlap` LR pixels (a multiple of 4; 16 is a policy default, not tuned on real footage) shared by
+    neighbours; a tile >= the frame on both axes is the whole frame again.  The frame that goes into the crop / `out_size` /
+    `out` / `gt` chain above is then frames.stitch (csrc/frame_stitch.hip) of, for every tile, what
+    super_resolve_frames(..., out='float') gives for the video of that tile's view [y : min(y + th, h), x : min(x + tw, w)] of
+    every frame (frames.tile_view; only a tile at the bottom or right edge is padded, from itself) -- a linear cross-fade over
+    the overlaps.  It is NOT the whole-frame output: EDVR's receptive field is larger than any overlap.  EDVR: one plan of
+    th x tw with n_tiles * nv * slots cache slots, tile t's variant v of frame f in slot (t * nv + v) * slots + f % slots; a CPU
+    frame crosses the bus once and every tile view is extracted from it; a window runs the tiles' fuse tapes (and flip_mean per
+    tile under flip_test) into a per-stream [n_tiles,3,s th,s tw] buffer and one stitch launch writes the tensor the single fuse
+    tape writes otherwise, all on the window's stream.  Other networks: the tiles run as clips through super_resolve_video and
+    are stitched on the caller's stream; with `tile` set `multiple` is raised to a multiple of 4.  'auto' is
+    choose_tile(net, h, w, tile_budget, ...) (EDVR), `tile_budget` bytes or, None, 0.8 x the free device memory -- a policy value.
     Arguments are checked before the first GPU call (ValueError)."""
     from . import frames as fio
     from .models.archs.EDVR_arch import EDVR
@@ -985,7 +1124,10 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     sr_scale = int(net.scale) if is_edvr else int(opt.get('scale') or 1)
     if out_size is not None:
         out_size = fio.check_size(out_size, "super_resolve_frames: out_size")
-    plain = plain and out_size is None
+    tile, tile_overlap = _check_tile(tile, tile_overlap, tile_budget)
+    if tile == 'auto' and not is_edvr:
+        raise ValueError("super_resolve_frames: tile='auto' sizes an EDVR stream plan; pass (th, tw) for %s" % type(net).__name__)
+    plain = plain and out_size is None and tile is None
     if plain:
         h, w, lay, out_fmt, Hp, Wp = int(frames[0].shape[-2]), int(frames[0].shape[-1]), 'chw', 'float', None, None
     else:
@@ -1009,12 +1151,10 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         mult = int(multiple) if multiple is not None else (4 if is_edvr else 1)
         if mult < 1:
             raise ValueError("super_resolve_frames: multiple=%r must be positive" % (multiple,))
-        if is_edvr and mult % 4:
-            mult *= 4 // math.gcd(mult, 4)            # the EDVR plans take multiples of 4 only
+        if (is_edvr or tile is not None) and mult % 4:
+            mult *= 4 // math.gcd(mult, 4)            # the EDVR plans and the tile grid take multiples of 4 only
         Hp, Wp = fio.padded_size(h, w, mult)
         fio.check_pad(h, w, Hp, -(-Wp // 4) * 4, pad_mode)
-        if lay == 'chw' and out_fmt == 'float' and (Hp, Wp) == (h, w) and out_size is None:
-            Hp = Wp = None                            # nothing to convert, pad or crop: today's calls
     score_into = None
     if gt is None:
         if scores is not None:
@@ -1044,6 +1184,21 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
         cuts = fio.detect_cuts(frames, lay, threshold=cut_threshold)
     elif cuts is not None:
         cuts = [a for a, _ in scene_bounds(T, cuts)][1:]
+    grid = None                                       # (th, tw, the tiles' origins per axis): more than one tile
+    if tile is not None:
+        if tile == 'auto':
+            video_windows(T, n, padding, cuts)        # (the last check, in front of a query of the device's free memory)
+            budget = tile_budget if tile_budget is not None else 0.8 * torch.cuda.mem_get_info(next(net.parameters()).device)[0]
+            tile = choose_tile(net, h, w, budget, tile_overlap, in_flight, 1 if cuts is None else len(cuts) + 1, flip_test, mult)
+        th, tw = min(tile[0], Hp), min(tile[1], Wp)
+        if (th < Hp and th % mult) or (tw < Wp and tw % mult):
+            raise ValueError("super_resolve_frames: tile=%r must be a multiple of multiple=%d" % (tuple(tile), mult))
+        ys, xs = tile_origins(Hp, th, tile_overlap), tile_origins(Wp, tw, tile_overlap)
+        if len(ys) * len(xs) > 1:
+            grid = (th, tw, ys, xs)
+            fio.check_pad(h - ys[-1], w - xs[-1], th, tw, pad_mode)     # the tile at the bottom right is padded from itself
+    if not plain and grid is None and lay == 'chw' and out_fmt == 'float' and (Hp, Wp) == (h, w) and out_size is None:
+        Hp = Wp = None                                # nothing to convert, pad or crop: today's calls
     if not is_edvr:
         windows, _ = video_windows(T, n, padding, cuts)            # (validates T, the mode and the cuts)
         if flip_test and (w if Hp is None else Wp) % 4:
@@ -1060,20 +1215,8 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                 score_into(i, sr)                      # (on the caller's stream, which the frame is ordered against)
                 yield sr
             return
-        kept = {}                                      # frame -> its ingested tensor; the last 2n are kept
-
-        def ingested(j):
-            x = kept.get(j)
-            if x is None:
-                x = kept[j] = fio.ingest(frames[j], lay, mult, pad_mode, matrix=matrix, yuv_range=yuv_range)
-                while len(kept) > 2 * n:
-                    kept.pop(next(iter(kept)))
-            return x
-
-        def padded_clips():
-            for win in windows:
-                yield torch.stack([ingested(j) for j in win])[None]
-        for i, sr in enumerate(super_resolve_video(opt, net, padded_clips(), in_flight, flip_test)):
+        def finished(i, sr):
+            """Frame i as it is yielded: the crop / resampling / conversion and the score, on the caller's stream."""
             s = sr.shape[-2] // Hp
             if out_size is not None:
                 if s != sr_scale:
@@ -1088,20 +1231,87 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                 sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
             if score_into is not None:
                 score_into(i, sr)                      # (behind the conversion, on the caller's stream like it)
-            yield sr
+            return sr
+        if grid is not None:
+            # every window as n_tiles clips, tile by tile, through super_resolve_video; their outputs are copied into one
+            # buffer and stitched on the caller's stream, which the clips' outputs are ordered against
+            th, tw, ys, xs = grid
+            origins = [(y, x) for y in ys for x in xs]
+            first = frames[0] if torch.is_tensor(frames[0]) else frames[0][0]
+            dev = first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device())
+            on_device, kept = {}, {}                   # frame -> the frame on the device; (frame, tile) -> the ingested tile
+
+            def ingested_tile(j, t):
+                x = kept.get((j, t))
+                if x is None:
+                    if j not in on_device:
+                        on_device[j] = fio.to_device(frames[j], dev)   # (a CPU frame crosses the bus once)
+                        while len(on_device) > 2 * n:
+                            on_device.pop(next(iter(on_device)))
+                    x = kept[(j, t)] = fio.ingest(fio.tile_view(on_device[j], lay, origins[t][0], origins[t][1], th, tw), lay,
+                                                  mult, pad_mode, matrix=matrix, yuv_range=yuv_range)
+                    while len(kept) > 2 * n * len(origins):
+                        kept.pop(next(iter(kept)))
+                return x
+
+            def tile_clips():
+                for win in windows:
+                    for t in range(len(origins)):
+                        yield torch.stack([ingested_tile(j, t) for j in win])[None]
+            tiles_sr = super_resolve_video(opt, net, tile_clips(), in_flight, flip_test)
+            tables = None
+            for i in range(T):
+                buf = None
+                for t in range(len(origins)):
+                    sr = next(tiles_sr)
+                    if buf is None:
+                        s = sr.shape[-2] // th
+                        if tuple(sr.shape) != (1, 3, s * th, s * tw) or s < 1:
+                            raise RuntimeError("super_resolve_frames: a %d x %d tile came back as %s" % (th, tw, tuple(sr.shape)))
+                        buf = torch.empty((len(origins), 3, s * th, s * tw), dtype=torch.float32, device=sr.device)
+                        if tables is None:
+                            tables = (fio.stitch_table(Hp, th, tile_overlap, s), fio.stitch_table(Wp, tw, tile_overlap, s))
+                    buf[t].copy_(sr[0])
+                yield finished(i, fio.stitch(buf, len(ys), len(xs), tables[0], tables[1])[None])
+            return
+        kept = {}                                      # frame -> its ingested tensor; the last 2n are kept
+
+        def ingested(j):
+            x = kept.get(j)
+            if x is None:
+                x = kept[j] = fio.ingest(frames[j], lay, mult, pad_mode, matrix=matrix, yuv_range=yuv_range)
+                while len(kept) > 2 * n:
+                    kept.pop(next(iter(kept)))
+            return x
+
+        def padded_clips():
+            for win in windows:
+                yield torch.stack([ingested(j) for j in win])[None]
+        for i, sr in enumerate(super_resolve_video(opt, net, padded_clips(), in_flight, flip_test)):
+            yield finished(i, sr)
         return
     leaves = net.ordered_parameters()
     dev = leaves[0].device
-    if dev.type != 'cuda':
-        raise RuntimeError("dynavsr_amd EDVR runs on the MI355X only (the network is on %s); there is no CPU fallback" % dev)
     sched = list(stream_schedule(T, net.nframes, padding, in_flight, cuts))
-    if Hp is None and tuple(frames[0].shape[-3:-2]) != (3,):
-        raise RuntimeError("super_resolve_frames expects frames [3,H,W], got %s" % (tuple(frames[0].shape),))
     direct = Hp is None                               # fp32 planar frames of the plan's size in, the fuse tape's tensor out
     ph, pw = (h, w) if direct else (Hp, Wp)
     slots = stream_slots(net.nframes, in_flight, 1 if cuts is None else len(cuts) + 1)
     nv = 4 if flip_test else 1                        # variants of a frame in the cache: slot v * slots + f % slots
-    plan = engine.get_stream_plan(net._cfg(), ph, pw, nv * slots, dev)
+    # the tiles: one plan of the tile's size, tile t's variant v of frame f in slot (t * nv + v) * slots + f % slots
+    pth, ptw, origins = (ph, pw, [(0, 0)]) if grid is None else (grid[0], grid[1], [(y, x) for y in grid[2] for x in grid[3]])
+    n_t = len(origins)
+    plan = engine.get_stream_plan(net._cfg(), pth, ptw, n_t * nv * slots, dev)
+    if plan.max_image_bytes >= MAX_IMAGE_BYTES:       # (a host query: before the device check and the first GPU call)
+        raise ValueError("super_resolve_frames: a %d x %d %s needs a tensor of %d bytes per image, and the kernels address an image "
+                         "with 32-bit offsets (< 2^32 bytes): pass tile= (a smaller tile, or 'auto') to run it in tiles"
+                         % (pth, ptw, "frame" if grid is None else "tile", plan.max_image_bytes))
+    if dev.type != 'cuda':
+        raise RuntimeError("dynavsr_amd EDVR runs on the MI355X only (the network is on %s); there is no CPU fallback" % dev)
+    if Hp is None and tuple(frames[0].shape[-3:-2]) != (3,):
+        raise RuntimeError("super_resolve_frames expects frames [3,H,W], got %s" % (tuple(frames[0].shape),))
+
+    def sid(t, v, slot):
+        return (t * nv + v) * slots + slot
     main = torch.cuda.current_stream(dev)
     streams = _clip_streams(dev, in_flight)
     with torch.cuda.device(dev):
@@ -1113,18 +1323,35 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     resized = {}                               # stream index -> the resampled frame when a conversion follows it
     flipped = {}                               # flip_test: stream index -> [the padded frame, one mirror image of it]
     fused = {}                                 # flip_test: stream index -> the four fuse tapes' outputs
+    tiled = {}                                 # tiles: stream index -> the tiles' fuse outputs [n_t,3,s pth,s ptw]
+    if grid is not None:
+        with torch.cuda.device(dev):               # the blend tables of the two axes, on the device once per video
+            axes = [fio._stitch_axis(fio.stitch_table(nn, tt, tile_overlap, int(net.scale)), dev)
+                    for nn, tt in ((ph, pth), (pw, ptw))]
 
-    def fuse(k, wslots, dst):
-        """The window in `wslots` -> dst [1,3,s ph,s pw] on the current stream (of index k): the fuse tape, or, with
+    def fuse_tile(k, t, wslots, dst):
+        """Tile t of the window in `wslots` -> dst [1,3,s pth,s ptw] on the current stream (of index k): the fuse tape, or, with
         flip_test, the four variants' fuse tapes and the launch that un-flips and averages them."""
         if not flip_test:
-            plan.fuse(leaves, wslots, cache, dst)
+            plan.fuse(leaves, [sid(t, 0, slot) for slot in wslots], cache, dst)
             return
         if k not in fused:
             fused[k] = [torch.empty_like(dst) for _ in range(nv)]
         for v in range(nv):
-            plan.fuse(leaves, [v * slots + slot for slot in wslots], cache, fused[k][v])
+            plan.fuse(leaves, [sid(t, v, slot) for slot in wslots], cache, fused[k][v])
         fio.flip_mean(*fused[k], out=dst)
+
+    def fuse(k, wslots, dst):
+        """The window in `wslots` -> dst [1,3,s ph,s pw] on the current stream (of index k): fuse_tile, or every tile's into
+        the stream's tile buffer and the launch that stitches them."""
+        if grid is None:
+            fuse_tile(k, 0, wslots, dst)
+            return
+        if k not in tiled:
+            tiled[k] = torch.empty((n_t, 3, net.scale * pth, net.scale * ptw), dtype=torch.float32, device=dev)
+        for t in range(n_t):
+            fuse_tile(k, t, wslots, tiled[k][t:t + 1])
+        fio._stitch_run(tiled[k], len(grid[2]), len(grid[3]), axes[0], axes[1], dst[0])
     was_training = net.training
     net.eval()
     try:
@@ -1144,31 +1371,37 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                         x = engine._prep(x if x.is_cuda else x.to(dev))
                     else:
                         x = fio.to_device(x, dev)                    # (8-bit frames travel as bytes)
-                    for v in range(nv):
-                        for ev in readers.pop(v * slots + slot, ()):
-                            s.wait_event(ev)
-                    if flip_test:                     # the padded fp32 frame, then its mirror images one at a time
-                        k = step % len(streams)
-                        if k not in flipped:
-                            flipped[k] = [torch.empty((3, ph, pw), dtype=torch.float32, device=dev) for _ in range(2)]
+                    for t in range(n_t):
+                        for v in range(nv):
+                            for ev in readers.pop(sid(t, v, slot), ()):
+                                s.wait_event(ev)
+                    read = []                         # the tensors the extraction launches read
+                    for t, (ty, tx) in enumerate(origins):
+                        xt = x if grid is None else fio.tile_view(x, lay, ty, tx, pth, ptw)
+                        if flip_test:                 # the padded fp32 frame, then its mirror images one at a time
+                            k = step % len(streams)
+                            if k not in flipped:
+                                flipped[k] = [torch.empty((3, pth, ptw), dtype=torch.float32, device=dev) for _ in range(2)]
+                            if direct:
+                                padded = xt if xt.data_ptr() % 16 == 0 else flipped[k][0].copy_(xt)
+                            else:
+                                padded = fio.ingest(xt, lay, mult, pad_mode, out=flipped[k][0], matrix=matrix, yuv_range=yuv_range)
                         if direct:
-                            padded = x if x.data_ptr() % 16 == 0 else flipped[k][0].copy_(x)
+                            plan.extract(leaves, xt, sid(t, 0, slot), cache)
                         else:
-                            padded = fio.ingest(x, lay, mult, pad_mode, out=flipped[k][0], matrix=matrix, yuv_range=yuv_range)
-                    if direct:
-                        plan.extract(leaves, x, slot, cache)
-                    else:
-                        x = plan.extract_frame(leaves, x, slot, cache, lay, pad_mode, matrix, yuv_range)
-                    for v in range(1, nv):
-                        plan.extract(leaves, fio.flip(padded, v, out=flipped[k][1]), v * slots + slot, cache)
+                            xt = plan.extract_frame(leaves, xt, sid(t, 0, slot), cache, lay, pad_mode, matrix, yuv_range)
+                        read += [xt] if torch.is_tensor(xt) else list(xt)
+                        for v in range(1, nv):
+                            plan.extract(leaves, fio.flip(padded, v, out=flipped[k][1]), sid(t, v, slot), cache)
                     ev = torch.cuda.Event()
                     ev.record(s)
-                    for v in range(nv):
-                        extracted[v * slots + slot] = ev
+                    for t in range(n_t):
+                        for v in range(nv):
+                            extracted[sid(t, v, slot)] = ev
                     if s != main:
-                        for t in (x,) if torch.is_tensor(x) else x:
+                        for t in read:
                             t.record_stream(s)
-                for ev in set(extracted[v * slots + slot] for v in range(nv) for slot in set(wslots)):
+                for ev in set(extracted[sid(t, v, slot)] for t in range(n_t) for v in range(nv) for slot in set(wslots)):
                     s.wait_event(ev)
                 if direct or (out_fmt == 'float' and (ph, pw) == (h, w) and out_size is None):
                     sr = torch.empty((1, 3, net.scale * ph, net.scale * pw), dtype=torch.float32, device=dev)
@@ -1194,8 +1427,9 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                 ev = torch.cuda.Event()
                 ev.record(s)
             for slot in set(wslots):
-                for v in range(nv):
-                    readers.setdefault(v * slots + slot, []).append(ev)
+                for t in range(n_t):
+                    for v in range(nv):
+                        readers.setdefault(sid(t, v, slot), []).append(ev)
             pending.append((sr, ev))
         while pending:
             sr, ev = pending.pop(0)

@@ -1545,6 +1545,22 @@ extern "C" size_t dvsr_edvr_stream_workspace_bytes(const dvsr_edvr_stream* s) {
   return s ? (s->fuse.arena_floats + s->extract.arena_floats) * sizeof(float) : 0;
 }
 
+// numel / N of every tensor an op names; an op without a batch dimension (N == 0: the streaming ops) counts as one image, and a
+// view without an extent of its own (numel == 0) lies inside a tensor that another op names whole
+extern "C" unsigned long long dvsr_edvr_stream_max_image_bytes(const dvsr_edvr_stream* s) {
+  if (!s) return 0;
+  size_t most = 0;
+  for (const dvsr_edvr_plan* p : {&s->extract, &s->fuse})
+    for (const dvsr::Op& o : p->ops) {
+      const size_t images = o.N > 0 ? (size_t)o.N : 1;
+      for (const dvsr::T* t : {&o.x0, &o.x1, &o.res, &o.y, &o.y2, &o.ypad, &o.pre})
+        if (t->valid()) most = std::max(most, t->numel / images);
+      if (o.type == dvsr::OP_CONV || o.type == dvsr::OP_DCN)   // (inputs given as views: from the geometry)
+        most = std::max(most, (size_t)std::max(o.c0, o.c1) * o.H * o.W);
+    }
+  return (unsigned long long)most * sizeof(float);
+}
+
 // what both calls require of their buffers (16-byte accesses in the gather and the packed kernels)
 static int stream_check(const dvsr_edvr_stream* s, const void* params, const void* cache, size_t cache_bytes, const void* ws,
                         size_t ws_bytes, const char* what) {

@@ -504,6 +504,8 @@ class StreamPlan:
         self.n_launches = (L.lib().dvsr_edvr_stream_num_launches(self._h, 0), L.lib().dvsr_edvr_stream_num_launches(self._h, 1))
         self.cache_bytes = int(L.lib().dvsr_edvr_stream_cache_bytes(self._h))
         self.workspace_bytes = int(L.lib().dvsr_edvr_stream_workspace_bytes(self._h))
+        # the largest tensor one image occupies over both tapes: the kernels address an image with 32-bit offsets (< 2^32)
+        self.max_image_bytes = int(L.lib().dvsr_edvr_stream_max_image_bytes(self._h))
         self.stats = {'extracted': 0, 'fused': 0, 'gathers': 0, 'packs': 0}
         self._ws = {}      # (device index, stream handle) -> [workspace, {'extract': sig, 'fuse': sig}]
 

@@ -64,6 +64,12 @@ The flip-test x4 self-ensemble (csrc/frame_flip.hip: dvsr_frame_flip / dvsr_fram
     flip(x, flags)                       -> fp32 [..., H, W] mirrored in W (flags & 1) and / or H (flags & 2), one launch
     flip_mean(y0, yw, yh, yhw)           -> (((y0 + yw.flip(-1)) + yh.flip(-2)) + yhw.flip((-2, -1))) * 0.25, one launch
 
+Frames in overlapping tiles (csrc/frame_stitch.hip: dvsr_frame_stitch_origins / _cover / _table / dvsr_frame_stitch):
+
+    tile_view(frame, layout, y, x, th, tw) -> the tile's strided view (plane views for YCbCr) that ingest / extract_frame take
+    stitch_table(n, tile, overlap, scale) -> (origins [tiles] in SR pixels, first int32 [s n], weights fp32 [s n, K]): one axis
+    stitch(tiles, ny, nx, rows, cols)    -> fp32 [..., H, W] from [ny * nx, ..., Ht, Wt]: the seams cross-faded, one launch
+
 PSNR / SSIM against ground truth, RGB or Y (csrc/frame_score.hip: dvsr_frame_score), for any two of the layouts:
 
     score(a, b, layout_a, layout_b, channel='rgb' | 'y', crop_border=k) -> float64 [mse, ssim] on the device, no host sync
@@ -504,6 +510,130 @@ def flip_mean(y0, yw, yh, yhw, out=None):
         L.check(L.lib().dvsr_frame_flip_mean(y0.data_ptr(), yw.data_ptr(), yh.data_ptr(), yhw.data_ptr(), out.data_ptr(),
                                              y0.numel() // (H * W), H, W, L.stream()), "dvsr_frame_flip_mean")
     return out
+
+
+def tile_view(frame, layout, y, x, th, tw):
+    """The tile [y : min(y + th, h), x : min(x + tw, w)] of a frame that resolve_layout accepts, as a strided view -- or, for a
+    YCbCr layout, as the tuple of plane views (packed frames included) -- that ingest / StreamPlan.extract_frame take: nothing
+    is copied.  y and x must be even where the layout sub-samples that axis (a tile then starts on a chroma sample; the
+    multiples of 4 of adapt.tile_origins are).  No GPU call."""
+    layout, h, w = resolve_layout(frame, layout)
+    y, x, th, tw = int(y), int(x), int(th), int(tw)
+    if not (0 <= y < h and 0 <= x < w and th >= 1 and tw >= 1):
+        raise ValueError("tile_view: a tile of %d x %d at (%d, %d) lies outside the %d x %d frame" % (th, tw, y, x, h, w))
+    y1, x1 = min(y + th, h), min(x + tw, w)
+    if layout == 'chw':
+        return frame[:, y:y1, x:x1]
+    if not is_yuv(layout):
+        return frame[y:y1, x:x1]
+    chroma = _YUV[layout][5]
+    sy, sx = (2 if chroma == L.YUV_CHROMA_420 else 1), (1 if chroma == L.YUV_CHROMA_444 else 2)
+    if y % sy or x % sx:
+        raise ValueError("tile_view: a %s tile must start on a chroma sample, got (%d, %d)" % (layout, y, x))
+    planes = yuv_planes(frame, layout)[0]
+    cy0, cy1, cx0, cx1 = y // sy, -(-y1 // sy), x // sx, -(-x1 // sx)
+    return (planes[0][y:y1, x:x1],) + tuple(p[cy0:cy1, cx0:cx1] for p in planes[1:])
+
+
+def stitch_table(n, tile, overlap, scale):
+    """One axis of the tile grid and its blend weights: (origins int32 [tiles] in SR pixels, first int32 [scale * n], weights fp32
+    [scale * n, K]) CPU tensors from dvsr_frame_stitch_origins / _cover / _table -- n the padded length in LR pixels, tile and
+    overlap as adapt.tile_origins takes them; SR position r is sum_a weights[r, a] * tile(first[r] + a) at r - origins[first[r]
+    + a]; rows with fewer covering tiles than K are zero-padded.  No GPU call."""
+    n, tile, overlap, scale = int(n), int(tile), int(overlap), int(scale)
+    lib = L.lib()
+    count = lib.dvsr_frame_stitch_origins(n, tile, overlap, None, 0)
+    if count < 1:
+        raise ValueError("stitch_table: " + lib.dvsr_last_error().decode("utf-8", "replace"))
+    if not 1 <= scale <= 16:
+        raise ValueError("stitch_table: scale=%d outside [1, 16]" % scale)
+    arr = (ctypes.c_int * count)()
+    lib.dvsr_frame_stitch_origins(n, tile, overlap, arr, count)
+    cover = lib.dvsr_frame_stitch_cover(n, tile, overlap)
+    origins = torch.tensor([scale * o for o in arr], dtype=torch.int32)
+    first = torch.empty((scale * n,), dtype=torch.int32)
+    weights = torch.empty((scale * n, cover), dtype=torch.float32)
+    L.check(lib.dvsr_frame_stitch_table(n, tile, overlap, scale, cover, first.data_ptr(), weights.data_ptr()),
+            "dvsr_frame_stitch_table")
+    return origins, first, weights
+
+
+_stitch_axes = {}      # (device, the table's bytes) -> the table on the device + the dvsr_stitch_axis that points at it
+
+
+def _stitch_axis(table, device):
+    origins, first, weights = table
+    if not (all(torch.is_tensor(t) for t in table) and origins.dtype == torch.int32 and first.dtype == torch.int32 and
+            weights.dtype == torch.float32 and origins.dim() == 1 and first.dim() == 1 and weights.dim() == 2 and
+            origins.numel() >= 1 and weights.shape[0] == first.shape[0] and 1 <= weights.shape[1] <= 3):
+        raise ValueError("stitch: an axis is stitch_table's (origins int32 [tiles], first int32 [N], weights fp32 [N, K <= 3])")
+    host = tuple(t.cpu().contiguous() for t in table)
+    key = (str(device),) + tuple(t.numpy().tobytes() for t in host)
+    hit = _stitch_axes.get(key)
+    if hit is None:
+        dev = tuple(t.to(device) for t in host)                     # (blocking copies: usable from any stream afterwards)
+        hit = _stitch_axes[key] = (dev, L.StitchAxis(dev[1].data_ptr(), dev[2].data_ptr(), dev[0].data_ptr(), int(weights.shape[1])),
+                                   (ctypes.c_int * origins.numel())(*host[0].tolist()))
+    return hit
+
+
+def stitch(tiles, ny, nx, rows, cols, out=None):
+    """SR tiles -> the SR frame, the seams blended (dvsr_frame_stitch, one launch with 16-byte accesses only).
+
+    tiles: fp32 [ny * nx, ..., Ht, Wt] on the GPU, contiguous, 16-byte aligned, tile (iy, ix) at index iy * nx + ix; rows, cols:
+    stitch_table's result for the two axes (their tables are copied to the device once per content and kept).  Returns fp32
+    [..., H, W], H = len(rows' first), W = len(cols' first):
+        out[..., r, c] = sum_a sum_b (wy[r, a] * wx[c, b]) * tiles[(first_y[r] + a) * nx + first_x[c] + b][..., r - O_y, c - O_x]
+    a outer, b inner, in fp32, never contracted, the accumulator starting as the first term; a zero weight is neither read nor
+    added.  out: the tensor to fill -- it must not overlap tiles.  Arguments are checked before the GPU call (ValueError)."""
+    ny, nx = int(ny), int(nx)
+    if not torch.is_tensor(tiles) or tiles.dtype != torch.float32 or tiles.dim() < 3:
+        raise ValueError("stitch: tiles must be an fp32 [ny * nx, ..., Ht, Wt] tensor, got %s" % (
+            "%s %s" % (tiles.dtype, tuple(tiles.shape)) if torch.is_tensor(tiles) else type(tiles).__name__))
+    if ny < 1 or nx < 1 or tiles.shape[0] != ny * nx or tiles.numel() < 1:
+        raise ValueError("stitch: %s is not %d x %d tiles" % (tuple(tiles.shape), ny, nx))
+    Ht, Wt = int(tiles.shape[-2]), int(tiles.shape[-1])
+    if not tiles.is_contiguous() or tiles.data_ptr() % 16:
+        raise ValueError("stitch: tiles must be contiguous and 16-byte aligned")
+    for name, table, tl, cnt in (("rows", rows, Ht, ny), ("cols", cols, Wt, nx)):
+        if not isinstance(table, (tuple, list)) or len(table) != 3:
+            raise ValueError("stitch: %s must be stitch_table's (origins, first, weights)" % name)
+    H, W = int(rows[1].shape[0]), int(cols[1].shape[0])
+    shape = tuple(tiles.shape[1:-2]) + (H, W)
+    planes = tiles.numel() // (ny * nx * Ht * Wt)
+    if Ht % 4 or Wt % 4 or H % 4 or W % 4 or Ht > H or Wt > W or H > 65535 or planes > 65535:
+        raise ValueError("stitch: tiles of %d x %d into %d x %d (multiples of 4, a tile no larger than the frame, at most 65535 "
+                         "rows and planes)" % (Ht, Wt, H, W))
+    for name, table, tl, cnt, N in (("rows", rows, Ht, ny, H), ("cols", cols, Wt, nx, W)):
+        o = [int(v) for v in table[0].tolist()]
+        ok = len(o) == cnt and o[0] == 0 and o[-1] == N - tl and all(v % 4 == 0 for v in o) and \
+            all(0 < b - a <= tl for a, b in zip(o[:-1], o[1:]))
+        if not ok:
+            raise ValueError("stitch: the origins %s of %s do not tile %d with %d tiles of %d" % (o, name, N, cnt, tl))
+    if out is not None:
+        if not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and out.device == tiles.device):
+            raise ValueError("stitch: out must be an fp32 %s tensor on %s" % (list(shape), tiles.device))
+        if not out.is_contiguous() or out.data_ptr() % 16:
+            raise ValueError("stitch: out must be contiguous and 16-byte aligned")
+        a0, b0 = tiles.data_ptr(), out.data_ptr()
+        if a0 < b0 + out.numel() * 4 and b0 < a0 + tiles.numel() * 4:
+            raise ValueError("stitch: out overlaps tiles (stitching in place is not provided)")
+    if not tiles.is_cuda:
+        raise RuntimeError("stitch runs on the GPU (libdynavsr_hip); there is no CPU path")
+    with torch.cuda.device(tiles.device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=tiles.device)
+        _stitch_run(tiles, ny, nx, _stitch_axis(rows, tiles.device), _stitch_axis(cols, tiles.device), out)
+    return out
+
+
+def _stitch_run(tiles, ny, nx, rows, cols, out):
+    """stitch() behind its checks, on the current device and stream; rows, cols: what _stitch_axis returned (adapt.
+    super_resolve_frames prepares them once per video)."""
+    Ht, Wt, H, W = int(tiles.shape[-2]), int(tiles.shape[-1]), int(out.shape[-2]), int(out.shape[-1])
+    L.check(L.lib().dvsr_frame_stitch(tiles.data_ptr(), ny, nx, tiles.numel() // (ny * nx * Ht * Wt), Ht, Wt, out.data_ptr(), H, W,
+                                      ctypes.byref(rows[1]), ctypes.byref(cols[1]), rows[2], cols[2], L.stream()),
+            "dvsr_frame_stitch")
 
 
 def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='limited', size=None):

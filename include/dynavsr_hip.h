@@ -312,6 +312,10 @@ int dvsr_edvr_stream_num_params(const dvsr_edvr_stream* stream_plan);
 int dvsr_edvr_stream_num_launches(const dvsr_edvr_stream* stream_plan, int which);
 size_t dvsr_edvr_stream_cache_bytes(const dvsr_edvr_stream* stream_plan);
 size_t dvsr_edvr_stream_workspace_bytes(const dvsr_edvr_stream* stream_plan);
+/* The largest tensor that one image of a batch occupies, in bytes, over the ops of both tapes (numel / N * 4; an op without a
+ * batch dimension counts as one image).  The conv and DCN kernels address one image of an NCHW tensor through a raw buffer
+ * resource with 32-bit offsets: a plan for which this reaches 2^32 must not be run.  Host code, no device call. */
+unsigned long long dvsr_edvr_stream_max_image_bytes(const dvsr_edvr_stream* stream_plan);
 int dvsr_edvr_stream_extract(const dvsr_edvr_stream* stream_plan, const float* const* params, const float* frame, int slot,
                              void* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, int packed,
                              dvsr_stream_t stream);
@@ -528,6 +532,45 @@ int dvsr_frame_resize(const float* src, int Hs, int Ws, int h, int w, float* dst
 int dvsr_frame_flip(const float* src, float* dst, long long planes, int H, int W, int flags, dvsr_stream_t stream);
 int dvsr_frame_flip_mean(const float* y0, const float* yw, const float* yh, const float* yhw, float* dst,
                          long long planes, int H, int W, dvsr_stream_t stream);
+
+/* ---- Frames in overlapping tiles: the tile grid, the blend weights, and the launch that stitches the SR tiles ----------
+ * A frame too large for one plan is cut into tiles of ONE size, super-resolved tile by tile and blended at the seams.
+ * Per axis, on the padded length n (LR pixels): n, tile multiples of 4 and >= 4, overlap a multiple of 4 with
+ * 0 <= overlap <= tile / 2.  tile >= n: one tile of length n at 0.  Otherwise step = tile - overlap and the origins are
+ * k step for every k step < n - tile, then n - tile (the last tile is anchored at the edge); a position is covered by at
+ * most 3 tiles.  In SR pixels at scale s (L = s min(tile, n), O_k = s origin_k) tile k has at O_k <= r < O_k + L the raw
+ * weight u_k(r) = min(dl, dr), dl = r - O_k + 0.5 (L for the first tile), dr = O_k + L - r - 0.5 (L for the last one), and
+ * the weight w_k(r) = u_k(r) / sum_j u_j(r): a linear cross-fade in a pairwise overlap, exactly 1.0f where one tile covers.
+ * dvsr_frame_stitch_origins: the number of tiles; origins[0 .. count) (HOST, LR pixels) when origins != NULL (capacity >=
+ *   count).  dvsr_frame_stitch_cover: K, the largest number of tiles over one position (1 .. 3).  dvsr_frame_stitch_table:
+ *   first[s n] (the first tile covering each SR position) and weights[s n][cover] (HOST memory; cover >= K and <= 3), computed
+ *   in double, rounded to fp32, zero-padded; 1 <= s <= 16.  Host code, no device call.
+ * dvsr_frame_stitch: tiles fp32 contiguous [ny nx][planes][Ht][Wt], tile (iy, ix) at index iy nx + ix  ->  dst fp32
+ *   [planes][H][W]; Ht, Wt, H, W multiples of 4, H and planes <= 65535, every pointer 16-byte aligned.
+ *     dst[p][r][c] = sum_a sum_b (wy[r][a] wx[c][b]) tile(first_y[r] + a, first_x[c] + b)[p][r - O_y][c - O_x],
+ *   a outer, b inner, the product of the two weights first, then the product with the value, the accumulator starting as the
+ *   first term, in fp32 and never contracted: the bits of the same loop in torch.  An entry whose row or column weight is
+ *   exactly 0 is neither read nor added.  Columns go in 16-byte chunks: first_x is read at a chunk's first column and a column
+ *   index is clamped chunk-wise (origins are multiples of 4, so the four columns of a chunk share their tiles).  rows / cols: the tables of the axis as dvsr_frame_stitch_table fills them and the
+ *   origins in SR pixels, copied to DEVICE memory (weights 16-byte aligned); origins_y[ny] / origins_x[nx]: the same origins
+ *   in HOST memory, which the call checks (0 first, H - Ht resp. W - Wt last, ascending multiples of 4, no gap).  The kernel
+ *   clamps every index into `tiles` and dst: a table with other contents gives a wrong picture, never an access outside
+ *   either tensor.  One launch, 16-byte loads and stores only, no atomics, deterministic; every element of dst is written once
+ *   and nothing else is.  dst must not overlap tiles.
+ * Bad arguments (null or misaligned pointer, ny / nx / planes < 1, a size that is no multiple of 4, cover outside 1 .. 3,
+ * origins inconsistent with H, W, Ht, Wt, dst overlapping tiles) return DVSR_ERR_INVALID before any launch. */
+typedef struct dvsr_stitch_axis {
+  const int* first;       /* [N]         device memory; N = H (rows) or W (columns) */
+  const float* weights;   /* [N][cover]  device memory */
+  const int* origins;     /* [tiles]     device memory, SR pixels */
+  int cover;
+} dvsr_stitch_axis;
+int dvsr_frame_stitch_origins(int n, int tile, int overlap, int* origins, int capacity);
+int dvsr_frame_stitch_cover(int n, int tile, int overlap);
+int dvsr_frame_stitch_table(int n, int tile, int overlap, int scale, int cover, int* first, float* weights);
+int dvsr_frame_stitch(const float* tiles, int ny, int nx, int planes, int Ht, int Wt, float* dst, int H, int W,
+                      const dvsr_stitch_axis* rows, const dvsr_stitch_axis* cols, const int* origins_y, const int* origins_x,
+                      dvsr_stream_t stream);
 
 /* ---- Down-scaling estimators MFDN / SFDN as one launch tape ------------------------------------
  * Replaces DirectKernelEstimatorVideo.forward (models/archs/LRimg_estimator.py:92-117, "MFDN":
