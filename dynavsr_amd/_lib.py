@@ -217,6 +217,10 @@ def _declare(lib):
         "dvsr_charbonnier_backward_grouped": (I, [P, P, P, P, LL, I, F, P]),
         "dvsr_l1_tail_forward_grouped": (I, [P, P, P, F, P, LL, I, P, c_size_t, P]),
         "dvsr_l1_tail_backward_grouped": (I, [P, P, P, F, P, LL, I, P]),
+        "dvsr_charbonnier_region_forward": (I, [P, P, P, I, LL, I, I, I, I, F, P, c_size_t, P]),
+        "dvsr_charbonnier_region_backward": (I, [P, P, P, P, I, LL, I, I, I, I, F, P]),
+        "dvsr_l1_tail_region_forward": (I, [P, P, P, F, P, I, LL, I, I, I, I, P, c_size_t, P]),
+        "dvsr_l1_tail_region_backward": (I, [P, P, P, F, P, I, LL, I, I, I, I, P]),
         "dvsr_edvr_op_info": (I, [P, I, c_char_p, I, c_char_p, I, POINTER(ctypes.c_double),
                                   POINTER(ctypes.c_double)]),
         "dvsr_edvr_forward_timed": (I, [P, POINTER(c_void_p), P, P, P, c_size_t, P, POINTER(c_float)]),

@@ -66,19 +66,63 @@ def draw_patch_positions(min_h, min_w, ps, n):
     return py, px
 
 
-def crop(LR_seq, HR, num_patches_for_batch=4, patch_size=44):
+def slr_region(region, scale):
+    """The SLR cells that hold at least one real pixel of a clip whose valid LR size is region = (h, w):
+    (ceil(h / scale), ceil(w / scale)) -- the region of the SLR term."""
+    s = int(scale)
+    return -(-int(region[0]) // s), -(-int(region[1]) // s)
+
+
+def patch_region(region, scale):
+    """The SLR cells that hold real pixels alone: (floor(h / scale), floor(w / scale)) -- where use_patch draws its patches."""
+    s = int(scale)
+    return int(region[0]) // s, int(region[1]) // s
+
+
+def check_adapt_region(opt, lqs_shape, region):
+    """The `region` argument of the adaptation loops for a clip [..., H, W]: None, or (h, w) with 1 <= h <= H, 1 <= w <= W, the
+    clip's valid LR size (the rest is padding).  Returns None for None and for the whole clip -- the calls of before -- and
+    (h, w) otherwise; with train.maml.use_patch the region must hold one patch (ValueError).  Host code."""
+    if region is None:
+        return None
+    h, w = hipops.check_region(lqs_shape, region, "region")
+    if (h, w) == (int(lqs_shape[-2]), int(lqs_shape[-1])):
+        return None
+    m = opt['train']['maml']
+    if m['use_patch']:
+        # (TOFlow sees the SLR clip at the clip's own size, backbone_input: its patches are cut there, one cell per pixel)
+        k = 1 if (opt['network_G'] or {}).get('which_model_G') == 'TOF' else opt['scale']
+        ps, (ph, pw) = int(m['patch_size']) // 2, patch_region((h, w), k)
+        if (opt['network_G'] or {}).get('which_model_G') == 'EDVR' and ps % 4:
+            raise ValueError("train.maml.patch_size=%d cuts patches of %d x %d (patch_size // 2), and EDVR takes multiples of 4"
+                             % (m['patch_size'], ps, ps))
+        if ph < ps or pw < ps:
+            raise ValueError("region=%r holds %d x %d whole cells of the backbone's input (1 / %d the size), fewer than a patch "
+                             "of %d x %d (train.maml.patch_size=%d: the crop's edge is patch_size // 2)" % (
+                                 (h, w), ph, pw, k, ps, ps, m['patch_size']))
+    return h, w
+
+
+def crop(LR_seq, HR, num_patches_for_batch=4, patch_size=44, region=None):
     """The `crop` of test_dynavsr.py:118-145 / train_dynavsr.py:208-243: `num_patches_for_batch` random patches of the
     SLR clip LR_seq [1,T,C,h,w] and, at the same places, of its target HR [1,C,s*h,s*w], stacked into batches
     [P,T,C,ps,ps] / [P,C,s*ps,s*ps] with ps = patch_size // 2.  Positions come from python's `random` in the
     reference's order (common_crop, preprocessing.py:76-77: py then px per patch), so a seeded run draws the same
-    patches; the crops themselves are one gather launch each (hipops.patch_gather), differentiable w.r.t. the clip."""
+    patches; the crops themselves are one gather launch each (hipops.patch_gather), differentiable w.r.t. the clip.
+    region = (h, w): only the top-left h x w of HR is real (the rest is padding), and the patches are drawn where they cover
+    real pixels alone -- positions below (floor(h / k), floor(w / k)) for HR k times the size of the smaller tensor."""
     assert HR.size(0) == 1
     seq, hr = LR_seq[0], HR[0]
     min_h, min_w = min(seq.shape[-2], hr.shape[-2]), min(seq.shape[-1], hr.shape[-1])
     ps = patch_size // 2
+    s_seq, s_hr = int(seq.shape[-2] // min_h), int(hr.shape[-2] // min_h)
+    if region is not None:
+        min_h, min_w = min(min_h, int(region[0]) // s_hr), min(min_w, int(region[1]) // s_hr)
+        if min_h < ps or min_w < ps:
+            raise ValueError("crop: region=%r leaves %d x %d positions, fewer than a patch of %d x %d" % (
+                tuple(region), min_h, min_w, ps, ps))
     py, px = draw_patch_positions(min_h, min_w, ps, num_patches_for_batch)
-    return (hipops.patch_gather(seq, py, px, ps, int(seq.shape[-2] // min_h)),
-            hipops.patch_gather(hr, py, px, ps, int(hr.shape[-2] // min_h)))
+    return (hipops.patch_gather(seq, py, px, ps, s_seq), hipops.patch_gather(hr, py, px, ps, s_hr))
 
 
 def _fresh_copy(dst, src):
@@ -101,14 +145,22 @@ def _fresh_copy(dst, src):
 
 
 def adapt_frame(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, val_data, slr_weight=10.0,
-                final_test=True):
+                final_test=True, region=None):
     """Adapt copies of (model.netG, est_model.netE) on one LR clip and super-resolve it.
 
     val_data: {'LQs': [1,N,3,H,W] (+ 'SuperLQs' when train.use_real)}.  Returns a dict with the
     adapted output ``sr`` [1,3,sH,sW] (on device), the per-step ``losses`` and the updated wrappers
-    (modelcp.netG / est_modelcp.netE hold the adapted weights)."""
+    (modelcp.netG / est_modelcp.netE hold the adapted weights).
+
+    region = (h, w): the clip's valid LR size -- a frame of h x w that was padded at the bottom and right to H x W.  The
+    objective then counts the frame's own pixels: the pixel loss is the mean over [:h, :w] of netG(SLR) and the LR centre
+    frame (hipops.charbonnier_region; any other criterion on the two slices), the SLR term the mean over the
+    slr_region(region, scale) cells that hold a real pixel (hipops.inner_loss_region), and use_patch draws its patches inside
+    patch_region(region, scale), where the pixel loss needs no mask (the SLR term keeps its region).  The networks still run
+    on the whole padded clip, and ``sr`` is the whole [1,3,sH,sW].  None, or the whole clip, is every call of before."""
     lqs = val_data['LQs']
     assert lqs.size(0) == 1
+    region = check_adapt_region(opt, lqs.shape, region)
     center = lqs.size(1) // 2
     steps = opt['train']['maml']['adapt_iter']
     prev = (modelcp.netG, est_modelcp.netE)
@@ -142,12 +194,18 @@ def adapt_frame(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, va
         inner.zero_grad()
         g_in = backbone_input(opt, slr)                         # TOF: bicubic x scale (test_dynavsr.py:245-250)
         if m['use_patch']:                                      # test_dynavsr.py:255-260
-            p_lq, p_gt = crop(g_in, target, m['num_patch'], m['patch_size'])
+            p_lq, p_gt = crop(g_in, target, m['num_patch'], m['patch_size'], region)
             modelcp.feed_data({'LQs': p_lq, 'GT': p_gt})
         else:
             modelcp.feed_data({'LQs': g_in, 'GT': target})
-        loss = modelcp.calculate_loss()
-        if slr.is_cuda and loss.is_cuda:       # one native reduction for the L1 tail (hipops.inner_loss)
+        loss = modelcp.calculate_loss() if region is None or m['use_patch'] else modelcp.calculate_loss(region=region)
+        if region is not None:
+            sh, sw = slr_region(region, opt['scale'])
+            if slr.is_cuda and loss.is_cuda:
+                loss = hipops.inner_loss_region(loss, slr, slr_fixed, (sh, sw), slr_weight)
+            else:
+                loss = loss + slr_weight * F.l1_loss(slr.to(slr_fixed.device)[..., :sh, :sw], slr_fixed[..., :sh, :sw])
+        elif slr.is_cuda and loss.is_cuda:     # one native reduction for the L1 tail (hipops.inner_loss)
             loss = hipops.inner_loss(loss, slr, slr_fixed, slr_weight)
         else:
             loss = loss + slr_weight * F.l1_loss(slr.to(slr_fixed.device), slr_fixed)
@@ -385,6 +443,7 @@ class FrameBatch:
     def __init__(self, opt, netG, netE, k):
         self.k = k
         m = opt['train']['maml']
+        self.scale = opt['scale']
         self.sig = self.signature(opt, netG, netE)
         with torch.no_grad():
             self.g_stack = [torch.empty((k,) + tuple(p.shape), dtype=torch.float32, device=p.device).requires_grad_()
@@ -458,12 +517,17 @@ class FrameBatch:
             if e.training != netE.training:
                 e.train(netE.training)
 
-    def adapt(self, model, est_model, est_model_fixed, lqs, slr_weight=10.0, steps=1, slr_ref=None):
+    def adapt(self, model, est_model, est_model_fixed, lqs, slr_weight=10.0, steps=1, slr_ref=None, region=None):
         """lqs [K,N,3,H,W] -> (per-step list of per-frame losses [K], SLR clips [K,N,3,h,w]); afterwards slice k holds
         frame k's adapted weights.  Same statements as adapt_frame's step loop, on the batch.  The SLR term's reference is
         the frozen estimator's output (test time, test_dynavsr.py:264-274) or, with ``slr_ref``, a given clip (meta-training:
-        the dataset's SuperLQs with weight 1, train_dynavsr.py:393)."""
+        the dataset's SuperLQs with weight 1, train_dynavsr.py:393).  region = (h, w): the clips' valid LR size, as in
+        adapt_frame (the per-frame region losses of hipops); None, or the whole clip, is every call of before."""
         assert lqs.size(0) == self.k
+        if region is not None:
+            region = hipops.check_region(lqs.shape, region, "region")
+            if region == (int(lqs.shape[-2]), int(lqs.shape[-1])):
+                region = None
         self.refresh(model.netG, est_model.netE)
         center = lqs.size(1) // 2
         if slr_ref is None:
@@ -485,8 +549,13 @@ class FrameBatch:
                 b, t, c = lqs.shape[:3]
                 slr = y.reshape(b, t, c, y.shape[-2], y.shape[-1])
             sr = model.netG.forward_stacked(slr, self.g_stack, per_slice=diverged)
-            l_pix = model.l_pix_w * hipops.charbonnier_per_sample(sr, lqs[:, center], model.cri_pix.eps)
-            loss = hipops.inner_loss_per_sample(l_pix, slr, slr_fixed, slr_weight)
+            if region is None:
+                l_pix = model.l_pix_w * hipops.charbonnier_per_sample(sr, lqs[:, center], model.cri_pix.eps)
+                loss = hipops.inner_loss_per_sample(l_pix, slr, slr_fixed, slr_weight)
+            else:
+                l_pix = model.l_pix_w * hipops.charbonnier_region(sr, lqs[:, center], region, model.cri_pix.eps, per_sample=True)
+                loss = hipops.inner_loss_region(l_pix, slr, slr_fixed, slr_region(region, self.scale), slr_weight,
+                                                per_sample=True)
             self.inner.zero_grad()
             loss.sum().backward()                          # d loss_k / d (slice k) only: the losses share no weights
             self.inner.step()
@@ -606,7 +675,8 @@ def super_resolve_video(opt, net, clips, in_flight=2, flip_test=False):
         net.train(was_training)
 
 
-def adapt_video(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, clips, overlap=True, frames_per_batch=1):
+def adapt_video(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, clips, overlap=True, frames_per_batch=1,
+                region=None, baseline=True):
     """The frame loop of test_dynavsr.py:197-283 as a generator: for every clip {'LQs': [1,N,3,H,W]} yields
     (baseline SR, adapt_frame's result dict with the adapted 'sr').
 
@@ -621,10 +691,14 @@ def adapt_video(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, cl
     and the current clip's adapted forward run on a further HIP stream underneath the following adaptation
     (two alternating sets of copies, so a forward never reads weights that are being refreshed).  Results are
     those of the sequential loop (same kernels, same inputs).  A yielded result stays valid until the generator
-    is advanced twice."""
+    is advanced twice (frames_per_batch = K > 1: until it is advanced 2 K times).
+
+    region = (h, w): every clip's valid LR size (adapt_frame / FrameBatch.adapt); None, or the whole clip, is every call of
+    before.  baseline=False skips the un-adapted forward, which only reports and is a third of a frame's device
+    time: the generator then yields (None, result).  True is every call of before."""
     if frames_per_batch > 1 and FrameBatch.supported(opt, model, est_model):
         yield from _adapt_video_batched(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, clips, overlap,
-                                        frames_per_batch)
+                                        frames_per_batch, region, baseline)
         return
     clips = iter(clips)
     cur = next(clips, None)
@@ -634,9 +708,11 @@ def adapt_video(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, cl
     if not overlap:
         while cur is not None:
             lqs = cur['LQs'] if cur['LQs'].is_cuda else cur['LQs'].cuda()
-            model.feed_data({'LQs': backbone_input(opt, lqs)}, need_GT=False)
-            model.test()
-            yield model.fake_H, adapt_frame(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, cur)
+            if baseline:
+                model.feed_data({'LQs': backbone_input(opt, lqs)}, need_GT=False)
+                model.test()
+            yield (model.fake_H if baseline else None,
+                   adapt_frame(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, cur, region=region))
             cur = next(clips, None)
         return
     s_base, s_test = _side_streams(lqs_device=cur['LQs'].device if cur['LQs'].is_cuda else torch.device('cuda'))
@@ -661,37 +737,41 @@ def adapt_video(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, cl
     def on_gpu(data):
         return data['LQs'] if data['LQs'].is_cuda else data['LQs'].cuda()
 
-    pending, i, prev_out = forward_on(s_base, model.netG, on_gpu(cur)), 0, None
+    def hand_out(out):
+        (p0, pe0), (p1, pe1), pr = out
+        if p0 is not None:
+            main.wait_event(pe0)
+            p0.record_stream(main)
+        main.wait_event(pe1)
+        p1.record_stream(main)
+        pr['sr'] = p1
+        return p0, pr
+
+    pending, i, prev_out = (forward_on(s_base, model.netG, on_gpu(cur)) if baseline else (None, None)), 0, None
     while cur is not None:
         nxt = next(clips, None)
         lqs = on_gpu(cur)
         sr0, ev0 = pending
-        if nxt is not None:
+        if nxt is not None and baseline:
             pending = forward_on(s_base, model.netG, on_gpu(nxt))   # enqueued first: runs underneath the adaptation
         st = sets[i & 1]
         if st[3] is not None:
             main.wait_event(st[3])                   # this set's previous adapted forward has read its weights
         modelcp.netG, est_modelcp.netE, modelcp._inner_opt = st[0], st[1], st[2]
-        r = adapt_frame(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, {'LQs': lqs}, final_test=False)
+        r = adapt_frame(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, {'LQs': lqs}, final_test=False,
+                        region=region)
         st[0], st[1], st[2] = modelcp.netG, est_modelcp.netE, getattr(modelcp, '_inner_opt', None)
         sr1, ev1 = forward_on(s_test, modelcp.netG, lqs)
         st[3] = ev1
         if prev_out is not None:                     # hand out clip i-1 now that clip i's work is enqueued
-            (p0, pe0), (p1, pe1), pr = prev_out
-            main.wait_event(pe0); main.wait_event(pe1)
-            p0.record_stream(main); p1.record_stream(main)
-            pr['sr'] = p1
-            yield p0, pr
+            yield hand_out(prev_out)
         prev_out = ((sr0, ev0), (sr1, ev1), r)
         cur, i = nxt, i + 1
-    (p0, pe0), (p1, pe1), pr = prev_out
-    main.wait_event(pe0); main.wait_event(pe1)
-    p0.record_stream(main); p1.record_stream(main)
-    pr['sr'] = p1
-    yield p0, pr
+    yield hand_out(prev_out)
 
 
-def _adapt_video_batched(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, clips, overlap, K):
+def _adapt_video_batched(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, clips, overlap, K, region=None,
+                         baseline=True):
     """adapt_video with the inner steps of K consecutive frames as one batch.  With ``overlap`` the 2K full-size forwards
     of a chunk (un-adapted baselines, adapted outputs) run on the side stream underneath the NEXT chunk's batched inner
     step; two alternating FrameBatch sets, so a forward never reads weights that are being refreshed."""
@@ -747,10 +827,14 @@ def _adapt_video_batched(opt, model, est_model, modelcp, est_modelcp, est_model_
     def hand_out(out):
         base, adapted, losses, slr, fb = out
         for k_, ((b_sr, b_ev), (a_sr, a_ev)) in enumerate(zip(base, adapted)):
-            if b_ev is not None:
+            if a_ev is not None:
                 if k_ == 0:
-                    main.wait_event(b_ev); main.wait_event(a_ev)
-                b_sr.record_stream(main); a_sr.record_stream(main)
+                    if b_ev is not None:
+                        main.wait_event(b_ev)
+                    main.wait_event(a_ev)
+                if b_sr is not None:
+                    b_sr.record_stream(main)
+                a_sr.record_stream(main)
             modelcp.netG, est_modelcp.netE = fb.netG[k_], fb.netE[k_]     # the frame's adapted copies, like the reference's modelcp
             yield b_sr, {'sr': a_sr, 'losses': [l_[k_] for l_ in losses], 'slr': slr[k_:k_ + 1]}
 
@@ -763,12 +847,12 @@ def _adapt_video_batched(opt, model, est_model, modelcp, est_modelcp, est_model_
         # the un-adapted baselines of the chunk share their weights too: ONE forward over the K clips (N = K through the
         # trunk instead of 450 tiles on 256 CUs; the small pyramid levels K times fatter); enqueued first, it runs
         # underneath the adaptation
-        b_sr, b_ev = forward_on(model.netG, lqs)
-        base = [(b_sr[k_:k_ + 1], b_ev) for k_ in range(len(chunk))]
+        b_sr, b_ev = forward_on(model.netG, lqs) if baseline else (None, None)
+        base = [(b_sr[k_:k_ + 1] if baseline else None, b_ev) for k_ in range(len(chunk))]
         fb = batch_for(ci & 1, len(chunk))
         if fb.last_use is not None:
             main.wait_event(fb.last_use)                                 # this set's previous adapted forwards are done
-        losses, slr = fb.adapt(model, est_model, est_model_fixed, lqs, steps=opt['train']['maml']['adapt_iter'])
+        losses, slr = fb.adapt(model, est_model, est_model_fixed, lqs, steps=opt['train']['maml']['adapt_iter'], region=region)
         # the K adapted forwards as ONE forward with per-frame weights (backbone_input: identity for EDVR, the only
         # backbone FrameBatch takes)
         a_sr, a_ev = forward_on(fb, lqs)
@@ -872,11 +956,11 @@ def stream_schedule(T, nframes, padding='new_info', in_flight=2, cuts=None):
         yield c, new, [(f, f % slots) for f in new], [f % slots for f in win]
 
 
-def _video_format(frames, layout):
+def _video_format(frames, layout, who="super_resolve_frames"):
     """(layout, h, w) of a video -- a [T,...] tensor or a list of frames of one kind and size.  No GPU call."""
     from . import frames as fio
     if len(frames) < 1:
-        raise ValueError("super_resolve_frames: no frames")
+        raise ValueError("%s: no frames" % who)
     first = fio.resolve_layout(frames[0], layout)
     if not torch.is_tensor(frames):
         def kind(f):        # a tensor's, or those of the planes of a YCbCr frame
@@ -885,7 +969,7 @@ def _video_format(frames, layout):
             return [kind(p) for p in f] if isinstance(f, (tuple, list)) else type(f).__name__
         for i, f in enumerate(frames):
             if kind(f) != kind(frames[0]):
-                raise ValueError("super_resolve_frames: frame %d is %s, frame 0 is %s" % (i, kind(f), kind(frames[0])))
+                raise ValueError("%s: frame %d is %s, frame 0 is %s" % (who, i, kind(f), kind(frames[0])))
             fio.resolve_layout(f, layout)
     return first
 
@@ -1011,6 +1095,96 @@ def choose_tile(net, h, w, budget, overlap=16, in_flight=2, scenes=1, flip_test=
                      % (h, w, int(budget), overlap, max(1, int(in_flight))))
 
 
+def _frame_format(who, frames, layout, out, multiple, pad_mode, matrix, yuv_range, out_size, sr_scale, default_multiple,
+                  multiple_of):
+    """The front end's checks of a video that is taken as a decoder delivers it, shared by super_resolve_frames and
+    adapt_frames: (lay, h, w, out_fmt, Hp, Wp, out_size, mult) -- the frames' layout and size, the format of the yielded frames,
+    the padded size, `out_size` (None where it is the SR frame's own size) and the multiple the frames are padded to
+    (`multiple`, None: default_multiple; raised to a multiple of `multiple_of`).  ValueError for anything else; no GPU call."""
+    from . import frames as fio
+    lay, h, w = _video_format(frames, layout, who)
+    if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') and not fio.is_yuv(out):
+        raise ValueError("%s: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (
+            who, out, ', '.join(fio.ALL_YUV_LAYOUTS)))
+    fio.check_yuv_names(matrix, yuv_range)
+    out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
+    if out_size == (sr_scale * h, sr_scale * w):
+        out_size = None                           # the SR frame's own size: today's calls
+    if out_size is not None:
+        fio.check_resize(sr_scale * h, sr_scale * w, out_size, "%s: out_size" % who)
+    if fio.is_yuv(out_fmt):
+        oh, ow = out_size if out_size is not None else (sr_scale * h, sr_scale * w)
+        if fio.packed_needs(out_fmt, oh, ow):
+            raise ValueError("%s: a packed %s output of %d x %d needs %s%s" % (
+                who, out_fmt, oh, ow, fio.packed_needs(out_fmt, oh, ow), " (out_size)" if out_size is not None else ""))
+    if h < 4 or w < 4:
+        raise ValueError("%s: frames of %d x %d (at least 4 x 4)" % (who, h, w))
+    mult = int(multiple) if multiple is not None else int(default_multiple)
+    if mult < 1:
+        raise ValueError("%s: multiple=%r must be positive" % (who, multiple))
+    if mult % multiple_of:
+        mult *= multiple_of // math.gcd(mult, multiple_of)   # the EDVR plans and the tile grid take multiples of 4 only
+    Hp, Wp = fio.padded_size(h, w, mult)
+    fio.check_pad(h, w, Hp, -(-Wp // 4) * 4, pad_mode)
+    return lay, h, w, out_fmt, Hp, Wp, out_size, mult
+
+
+def _check_scores(who, scores, T, name="scores"):
+    if not (torch.is_tensor(scores) and scores.dtype == torch.float64 and tuple(scores.shape) == (T, 2)
+            and scores.is_cuda and scores.is_contiguous()):
+        raise ValueError("%s: gt needs %s, a contiguous float64 [%d, 2] tensor on the GPU" % (who, name, T))
+
+
+def _frame_scoring(who, T, gt, gt_layout, scores, score, crop_border, out_fmt, out_size, sr_scale, h, w, matrix, yuv_range):
+    """The checks of the `gt` arguments of the two frame generators, and score_into(i, sr, into=scores): row i of `into` from
+    the frame about to be yielded, on the current stream.  None without `gt`.  ValueError for anything else; no GPU call."""
+    from . import frames as fio
+    if gt is None:
+        if scores is not None:
+            raise ValueError("%s: scores without gt" % who)
+        return None
+    if len(gt) != T:
+        raise ValueError("%s: gt has %d frames, the video %d" % (who, len(gt), T))
+    glay, gh, gw = _video_format(gt, gt_layout, who)
+    olay = 'chw' if out_fmt == 'float' else out_fmt
+    oh, ow = out_size if out_size is not None else (sr_scale * h, sr_scale * w)
+    fio.check_score((olay, oh, ow), (glay, gh, gw), score, crop_border, (0, 1), "%s: gt" % who)
+    if fio.is_yuv(olay) and not fio.is_yuv(glay) and (matrix, yuv_range) != ('bt601', 'limited'):
+        raise ValueError("%s: the Y plane of a %s output is the Y8 of an RGB gt for matrix='bt601', "
+                         "yuv_range='limited' alone, not for %r, %r" % (who, olay, matrix, yuv_range))
+    _check_scores(who, scores, T)
+
+    def score_into(i, sr, into=scores):
+        fio.score(sr[0] if olay == 'chw' else sr, gt[i], olay, glay, channel=score, crop_border=crop_border, out=into[i])
+    return score_into
+
+
+def _finish_frame(who, sr, geometry, out_fmt, out_size, sr_scale, matrix, yuv_range, i=None, score_into=None, into=None):
+    """The back end of the two frame generators for a network output sr [1,3,s Hp,s Wp] of a frame that was padded from
+    h x w to Hp x Wp (geometry): frame i as it is yielded -- the s h x s w crop, resampled to `out_size` and converted to
+    `out_fmt` -- and its score, on the current stream."""
+    from . import frames as fio
+    h, w, Hp, Wp = geometry
+    s = sr.shape[-2] // Hp
+    if out_size is not None:
+        if s != sr_scale:
+            raise RuntimeError("%s: the network scales by %d, opt['scale'] says %d" % (who, s, sr_scale))
+        if out_fmt == 'float':
+            sr = fio.resize(sr, s * h, s * w, out_size)[None]
+        else:
+            sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range, size=out_size)
+    elif out_fmt == 'float':
+        sr = sr if (Hp, Wp) == (h, w) else fio.emit(sr, s * h, s * w, 'chw')[None]
+    else:
+        sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
+    if score_into is not None:
+        if into is None:
+            score_into(i, sr)                      # (behind the conversion, on the caller's stream like it)
+        else:
+            score_into(i, sr, into)
+    return sr
+
+
 def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, layout=None, out=None, pad_mode='reflect',
                          multiple=None, matrix='bt601', yuv_range='limited', cuts=None, cut_threshold=10.0, out_size=None,
                          flip_test=False, gt=None, gt_layout=None, score='rgb', crop_border=0, scores=None,
@@ -1131,51 +1305,11 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     if plain:
         h, w, lay, out_fmt, Hp, Wp = int(frames[0].shape[-2]), int(frames[0].shape[-1]), 'chw', 'float', None, None
     else:
-        lay, h, w = _video_format(frames, layout)
-        if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') and not fio.is_yuv(out):
-            raise ValueError("super_resolve_frames: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (
-                out, ', '.join(fio.ALL_YUV_LAYOUTS)))
-        fio.check_yuv_names(matrix, yuv_range)
-        out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
-        if out_size == (sr_scale * h, sr_scale * w):
-            out_size = None                           # the SR frame's own size: today's calls
-        if out_size is not None:
-            fio.check_resize(sr_scale * h, sr_scale * w, out_size, "super_resolve_frames: out_size")
-        if fio.is_yuv(out_fmt):
-            oh, ow = out_size if out_size is not None else (sr_scale * h, sr_scale * w)
-            if fio.packed_needs(out_fmt, oh, ow):
-                raise ValueError("super_resolve_frames: a packed %s output of %d x %d needs %s%s" % (
-                    out_fmt, oh, ow, fio.packed_needs(out_fmt, oh, ow), " (out_size)" if out_size is not None else ""))
-        if h < 4 or w < 4:
-            raise ValueError("super_resolve_frames: frames of %d x %d (at least 4 x 4)" % (h, w))
-        mult = int(multiple) if multiple is not None else (4 if is_edvr else 1)
-        if mult < 1:
-            raise ValueError("super_resolve_frames: multiple=%r must be positive" % (multiple,))
-        if (is_edvr or tile is not None) and mult % 4:
-            mult *= 4 // math.gcd(mult, 4)            # the EDVR plans and the tile grid take multiples of 4 only
-        Hp, Wp = fio.padded_size(h, w, mult)
-        fio.check_pad(h, w, Hp, -(-Wp // 4) * 4, pad_mode)
-    score_into = None
-    if gt is None:
-        if scores is not None:
-            raise ValueError("super_resolve_frames: scores without gt")
-    else:
-        if len(gt) != T:
-            raise ValueError("super_resolve_frames: gt has %d frames, the video %d" % (len(gt), T))
-        glay, gh, gw = _video_format(gt, gt_layout)
-        olay = 'chw' if out_fmt == 'float' else out_fmt
-        oh, ow = out_size if out_size is not None else (sr_scale * h, sr_scale * w)
-        fio.check_score((olay, oh, ow), (glay, gh, gw), score, crop_border, (0, 1), "super_resolve_frames: gt")
-        if fio.is_yuv(olay) and not fio.is_yuv(glay) and (matrix, yuv_range) != ('bt601', 'limited'):
-            raise ValueError("super_resolve_frames: the Y plane of a %s output is the Y8 of an RGB gt for matrix='bt601', "
-                             "yuv_range='limited' alone, not for %r, %r" % (olay, matrix, yuv_range))
-        if not (torch.is_tensor(scores) and scores.dtype == torch.float64 and tuple(scores.shape) == (T, 2)
-                and scores.is_cuda and scores.is_contiguous()):
-            raise ValueError("super_resolve_frames: gt needs scores, a contiguous float64 [%d, 2] tensor on the GPU" % T)
-
-        def score_into(i, sr):
-            """Row i of `scores` from the frame about to be yielded, on the current stream."""
-            fio.score(sr[0] if olay == 'chw' else sr, gt[i], olay, glay, channel=score, crop_border=crop_border, out=scores[i])
+        lay, h, w, out_fmt, Hp, Wp, out_size, mult = _frame_format(
+            "super_resolve_frames", frames, layout, out, multiple, pad_mode, matrix, yuv_range, out_size, sr_scale,
+            4 if is_edvr else 1, 4 if is_edvr or tile is not None else 1)
+    score_into = _frame_scoring("super_resolve_frames", T, gt, gt_layout, scores, score, crop_border, out_fmt, out_size,
+                                sr_scale, h, w, matrix, yuv_range)
     n = int(net.nframes) if is_edvr or not (opt.get('network_G') or {}).get('nframes') else int(opt['network_G']['nframes'])
     if isinstance(cuts, str):
         if cuts != 'auto':
@@ -1216,22 +1350,8 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
                 yield sr
             return
         def finished(i, sr):
-            """Frame i as it is yielded: the crop / resampling / conversion and the score, on the caller's stream."""
-            s = sr.shape[-2] // Hp
-            if out_size is not None:
-                if s != sr_scale:
-                    raise RuntimeError("super_resolve_frames: the network scales by %d, opt['scale'] says %d" % (s, sr_scale))
-                if out_fmt == 'float':
-                    sr = fio.resize(sr, s * h, s * w, out_size)[None]
-                else:
-                    sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range, size=out_size)
-            elif out_fmt == 'float':
-                sr = sr if (Hp, Wp) == (h, w) else fio.emit(sr, s * h, s * w, 'chw')[None]
-            else:
-                sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
-            if score_into is not None:
-                score_into(i, sr)                      # (behind the conversion, on the caller's stream like it)
-            return sr
+            return _finish_frame("super_resolve_frames", sr, (h, w, Hp, Wp), out_fmt, out_size, sr_scale, matrix, yuv_range,
+                                 i, score_into)
         if grid is not None:
             # every window as n_tiles clips, tile by tile, through super_resolve_video; their outputs are copied into one
             # buffer and stitched on the caller's stream, which the clips' outputs are ordered against
@@ -1443,6 +1563,129 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
             main.wait_event(ev)
             sr.record_stream(main)
         net.train(was_training)
+
+
+def adapt_multiple(opt):
+    """The multiple of its sides at which a clip can be adapted: the backbone runs on the clip and on its SLR version, 1 / scale
+    the size.  EDVR takes multiples of 4, so 4 * scale; TOFlow multiples of 16 at the clip's size, where it also sees the SLR
+    clip (backbone_input), so lcm(scale, 16); DUF any size, so scale.  Host code."""
+    which = (opt['network_G'] or {}).get('which_model_G')
+    s = int(opt['scale'])
+    if which == 'EDVR':
+        return 4 * s
+    if which == 'TOF':
+        return s * 16 // math.gcd(s, 16)
+    if which == 'DUF':
+        return s
+    raise ValueError("adapt_multiple: network_G.which_model_G=%r (EDVR, TOF or DUF)" % (which,))
+
+
+def adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, frames, padding='new_info', *, layout=None,
+                 out=None, pad_mode='reflect', multiple=None, matrix='bt601', yuv_range='limited', cuts=None,
+                 cut_threshold=10.0, out_size=None, gt=None, gt_layout=None, score='rgb', crop_border=0, scores=None,
+                 baseline_scores=None, losses=None, baseline=True, overlap=True, frames_per_batch=1):
+    """Test-time adaptation of a decoded VIDEO (test_dynavsr.py:197-283 without the caller cutting, cropping or converting
+    clips): for every frame, in order, yields (baseline frame | None, adapted frame) -- the un-adapted network's output and the
+    output of the copies adapted on that frame's window, both in the format super_resolve_frames would yield for the same
+    `layout` / `out` / `out_size`.
+
+    Front end: `frames`, `layout`, `matrix`, `yuv_range` as in super_resolve_frames -- uint8 RGB / BGR, every YCbCr layout at
+    8 / 10 / 12 bits, float planar, CPU or GPU, of any size.  Every frame goes through frames.ingest once, on the device, padded
+    at the bottom and right (`pad_mode`) to a multiple of `multiple` (None: M = adapt_multiple(opt); a caller's value must be
+    a multiple of M); the last 2 * nframes ingested frames are kept.  The windows are video_windows(T, nframes, padding, cuts)
+    (`cuts` = 'auto': frames.detect_cuts), the clips torch.stack of the ingested frames.
+    Middle: adapt_video(clips, overlap, frames_per_batch, region=(h, w), baseline=baseline), unchanged otherwise.  The padded
+    band holds copies of real pixels, so the objective counts the frame's own h x w alone (adapt_frame's `region`; left out
+    when the frame needed no padding).  baseline=False skips the un-adapted forward -- a third of a frame's device time -- and
+    yields None in its place.
+    Back end: the SR frame's s h x s w crop through frames.resize (`out_size`) and frames.emit, on the caller's stream.  With
+    `gt` (a video of T frames of the output's size) row i of `scores` becomes [mse, ssim] of frames.score(adapted frame i,
+    gt[i]) and row i of `baseline_scores` (optional; needs baseline=True) that of the baseline frame, with the argument rules of
+    super_resolve_frames (float64 [T, 2] GPU tensors; score_summary reads them).  `losses`: an optional float32
+    [T, train.maml.adapt_iter] GPU tensor; row i receives frame i's per-step losses without a host synchronisation.
+
+    A yielded pair stays valid until the generator is advanced 2 * max(1, frames_per_batch) times: where nothing is cropped,
+    resampled or converted (float output of an unpadded frame) the pair is adapt_video's own, which holds its rule; every other
+    pair is a tensor of its own.  Frames and results are ordered against the caller's current stream.
+    Not provided: train.use_real (the reference reads ready-made SLR images from disk there); `tile` and `flip_test`; frames
+    whose EDVR plan reaches the 4 GiB image limit (ValueError); adapting once per scene; chroma-only adaptation.
+    Arguments are checked before the first GPU call (ValueError)."""
+    from . import frames as fio
+    who = "adapt_frames"
+    if opt['train']['use_real']:
+        raise ValueError("adapt_frames: train.use_real reads ready-made SLR clips ('SuperLQs'), which a decoded video does not "
+                         "have; pass clips to adapt_video")
+    T = len(frames)
+    if T < 1:
+        raise ValueError("adapt_frames: no frames")
+    if pad_mode not in ('reflect', 'replicate'):
+        raise ValueError("adapt_frames: pad_mode=%r ('reflect' or 'replicate')" % (pad_mode,))
+    M = adapt_multiple(opt)
+    if multiple is not None and (isinstance(multiple, bool) or int(multiple) < 1 or int(multiple) % M):
+        raise ValueError("adapt_frames: multiple=%r must be a multiple of %d (adapt_multiple)" % (multiple, M))
+    sr_scale = int(opt['scale'])
+    if out_size is not None:
+        out_size = fio.check_size(out_size, "adapt_frames: out_size")
+    lay, h, w, out_fmt, Hp, Wp, out_size, mult = _frame_format(who, frames, layout, out, multiple, pad_mode, matrix, yuv_range,
+                                                               out_size, sr_scale, M, 1)
+    score_into = _frame_scoring(who, T, gt, gt_layout, scores, score, crop_border, out_fmt, out_size, sr_scale, h, w, matrix,
+                                yuv_range)
+    if baseline_scores is not None:
+        if not baseline:
+            raise ValueError("adapt_frames: baseline_scores needs the baseline frames (baseline=True)")
+        if gt is None:
+            raise ValueError("adapt_frames: baseline_scores without gt")
+        _check_scores(who, baseline_scores, T, "baseline_scores")
+    steps = int(opt['train']['maml']['adapt_iter'])
+    if losses is not None:
+        if not (torch.is_tensor(losses) and losses.dtype == torch.float32 and tuple(losses.shape) == (T, steps)):
+            raise ValueError("adapt_frames: losses must be a float32 [%d, %d] tensor (frames x train.maml.adapt_iter)" % (T, steps))
+        if not (losses.is_cuda and losses.is_contiguous()):
+            raise ValueError("adapt_frames: losses must be contiguous and on the GPU")
+    n = (opt['network_G'] or {}).get('nframes')
+    if not n:
+        raise ValueError("adapt_frames: network_G.nframes, the length of a window, is not set")
+    n = int(n)
+    region = check_adapt_region(opt, (3, Hp, Wp), (h, w))         # (None where the frame needs no padding)
+    from .models.archs.EDVR_arch import EDVR
+    if isinstance(getattr(model, 'netG', None), EDVR):
+        # (a host query of a stream plan that is never run: the tapes of the loops hold the same per-image tensors)
+        need = engine.StreamPlan(model.netG._cfg(), Hp, Wp, int(model.netG.nframes)).max_image_bytes
+        if need >= MAX_IMAGE_BYTES:
+            raise ValueError("adapt_frames: a %d x %d frame needs a tensor of %d bytes per image, and the kernels address an "
+                             "image with 32-bit offsets (< 2^32 bytes); adaptation in tiles is not provided" % (Hp, Wp, need))
+    if isinstance(cuts, str):
+        if cuts != 'auto':
+            raise ValueError("adapt_frames: cuts=%r (None, 'auto' or a sequence of frame numbers)" % (cuts,))
+        video_windows(T, n, padding, [])                           # (the mode, before the first GPU call)
+        cuts = fio.detect_cuts(frames, lay, threshold=cut_threshold)
+    elif cuts is not None:
+        cuts = [a for a, _ in scene_bounds(T, cuts)][1:]
+    windows, _ = video_windows(T, n, padding, cuts)
+    kept = {}                                          # frame -> its ingested tensor; the last 2n are kept
+
+    def ingested(j):
+        x = kept.get(j)
+        if x is None:
+            x = kept[j] = fio.ingest(frames[j], lay, mult, pad_mode, matrix=matrix, yuv_range=yuv_range)
+            while len(kept) > 2 * n:
+                kept.pop(next(iter(kept)))
+        return x
+
+    def clips():
+        for win in windows:
+            yield {'LQs': torch.stack([ingested(j) for j in win])[None]}
+
+    def finished(i, sr, into):
+        return _finish_frame(who, sr, (h, w, Hp, Wp), out_fmt, out_size, sr_scale, matrix, yuv_range, i,
+                             score_into if into is not None else None, into)
+    results = adapt_video(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, clips(), overlap=overlap,
+                          frames_per_batch=frames_per_batch, region=region, baseline=baseline)
+    for i, (base, r) in enumerate(results):
+        if losses is not None:
+            losses[i].copy_(torch.stack([l_.reshape(()) for l_ in r['losses']]))
+        yield (finished(i, base, baseline_scores) if base is not None else None,
+               finished(i, r['sr'], scores if score_into is not None else None))
 
 
 def score_summary(scores, nframes, cuts=None, peak=255):

@@ -587,6 +587,144 @@ __global__ void l1_bwd_kernel(const float* __restrict__ x, const float* __restri
   }
 }
 
+// ---- region forms of the two losses: operands [groups][planes][H][W], the loss taken over the top-left h x w of every
+// plane (the frame's own pixels of a clip that was padded at the bottom and right).  The forward kernels walk the region's
+// planes * h * w elements in the row-major order of the cropped tensor with the grid, the per-thread stride and the
+// reduction of the kernels above, so a value is bit-identical to theirs on a contiguous copy of the crop.  The position
+// of an element is kept as (plane, row, col) and advanced by the stride in that form: no division inside the loop.
+// an element count as planes, rows and columns of a rows x cols plane; o: what it adds to an offset into planes of H x W
+struct RegionStep { unsigned long long p, o; int r, c; };
+static inline RegionStep region_step(size_t count, int rows, int cols, int H = 0, int W = 0) {
+  RegionStep s;
+  s.c = (int)(count % (size_t)cols);
+  const size_t q = count / (size_t)cols;
+  s.r = (int)(q % (size_t)rows);
+  s.p = q / (size_t)rows;
+  s.o = ((size_t)s.p * H + s.r) * W + s.c;
+  return s;
+}
+struct RegionWalk {
+  size_t p; int r, c;
+  // (a thread's first element: below gridDim.x * 256 <= 2^20 by the grid caps of the launches, so 32-bit divisions do)
+  __device__ RegionWalk(unsigned i, int rows, int cols) {
+    c = (int)(i % (unsigned)cols);
+    const unsigned q = i / (unsigned)cols;
+    r = (int)(q % (unsigned)rows);
+    p = q / (unsigned)rows;
+  }
+  __device__ void advance(const RegionStep& s, int rows, int cols) {
+    c += s.c; if (c >= cols) { c -= cols; ++r; }
+    r += s.r; if (r >= rows) { r -= rows; ++p; }
+    p += s.p;
+  }
+  // The same step inside an h x w region of H x W planes, for the element's offset o = (p * H + r) * W + c in the whole tensor:
+  // s.o is the step's own offset, a row carried adds W - w, a plane carried (H - h) * W; no multiplication per element.
+  __device__ size_t advance_offset(size_t o, const RegionStep& s, int H, int W, int h, int w) {
+    o += s.o;
+    c += s.c; if (c >= w) { c -= w; ++r; o += (size_t)(W - w); }
+    r += s.r; if (r >= h) { r -= h; o += (size_t)(H - h) * W; }
+    return o;
+  }
+};
+// (n = planes * h * w region elements per group, full = planes * H * W elements per group)
+__global__ void charbonnier_region_partial_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                  float* __restrict__ partial, size_t n, size_t full, int H, int W, int h,
+                                                  int w, RegionStep step, float eps) {
+  __shared__ float red[256];
+  x += blockIdx.y * full; y += blockIdx.y * full; partial += blockIdx.y * (size_t)CHARB_BLOCKS;
+  float s = 0.f;
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  RegionWalk at((unsigned)i, h, w);
+  size_t o = (at.p * H + at.r) * W + at.c;
+  for (; i < n; i += (size_t)gridDim.x * blockDim.x, o = at.advance_offset(o, step, H, W, h, w)) {
+    const float d = x[o] - y[o];
+    s += sqrtf(d * d + eps);
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int k = 128; k > 0; k >>= 1) {
+    if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+__global__ void l1_region_partial_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                         float* __restrict__ partial, size_t n, size_t full, int H, int W, int h, int w,
+                                         RegionStep step) {
+  __shared__ float red[256];
+  x += blockIdx.y * full; y += blockIdx.y * full; partial += blockIdx.y * (size_t)CHARB_BLOCKS;
+  float s = 0.f;
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  RegionWalk at((unsigned)i, h, w);
+  size_t o = (at.p * H + at.r) * W + at.c;
+  for (; i < n; i += (size_t)gridDim.x * blockDim.x, o = at.advance_offset(o, step, H, W, h, w))
+    s += fabsf(x[o] - y[o]);
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int k = 128; k > 0; k >>= 1) {
+    if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+// The gradients walk the WHOLE tensor (every element of gx is written): the formulas above inside the region, 0 outside.
+// L1: the L1 tail's gradient (mul = weight / n), otherwise the Charbonnier loss's (mul = 1 / n).
+template <bool L1>
+__device__ inline float region_grad(float d, float g, float eps) {
+  if (L1) return d > 0.f ? g : (d < 0.f ? -g : 0.f);
+  return g * d / sqrtf(d * d + eps);
+}
+template <bool L1>
+__global__ void region_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                  const float* __restrict__ gscale, float* __restrict__ gx, size_t full, int H, int W, int h,
+                                  int w, RegionStep step, float eps, float mul) {
+  const float g = gscale[blockIdx.y] * mul;
+  x += blockIdx.y * full; y += blockIdx.y * full; gx += blockIdx.y * full;
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  RegionWalk at((unsigned)i, H, W);
+  for (; i < full; i += (size_t)gridDim.x * blockDim.x, at.advance(step, H, W))
+    gx[i] = at.r < h && at.c < w ? region_grad<L1>(x[i] - y[i], g, eps) : 0.f;
+}
+// Four columns per thread, for W a multiple of 4 and 16-byte aligned operands: the same walk over the H x W/4 quads of a plane
+// (a quarter of the threads, each with the same set-up), 16-byte loads and stores; a quad that straddles the region's right edge is masked
+// per element.
+template <bool L1>
+__global__ void region_bwd4_kernel(const float4* __restrict__ x, const float4* __restrict__ y,
+                                   const float* __restrict__ gscale, float4* __restrict__ gx, size_t full4, int H, int W4,
+                                   int h, int w, RegionStep step, float eps, float mul) {
+  const float g = gscale[blockIdx.y] * mul;
+  x += blockIdx.y * full4; y += blockIdx.y * full4; gx += blockIdx.y * full4;
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  RegionWalk at((unsigned)i, H, W4);
+  for (; i < full4; i += (size_t)gridDim.x * blockDim.x, at.advance(step, H, W4)) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int c = 4 * at.c;
+    if (at.r < h && c < w) {
+      const float4 a = x[i], b = y[i];
+      v.x = region_grad<L1>(a.x - b.x, g, eps);
+      if (c + 1 < w) v.y = region_grad<L1>(a.y - b.y, g, eps);
+      if (c + 2 < w) v.z = region_grad<L1>(a.z - b.z, g, eps);
+      if (c + 3 < w) v.w = region_grad<L1>(a.w - b.w, g, eps);
+    }
+    gx[i] = v;
+  }
+}
+// One launch site for the two losses: four columns per thread where the operands allow it, one otherwise.
+template <bool L1>
+static int region_backward(const float* x, const float* y, const float* grad_loss, float* gx, int groups, size_t full, int H,
+                           int W, int h, int w, float eps, float mul, hipStream_t st) {
+  if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gx) & 15) == 0) {
+    const int nq = stream_grid(full / 4);
+    hipLaunchKernelGGL(region_bwd4_kernel<L1>, dim3(nq, groups), dim3(256), 0, st, (const float4*)x, (const float4*)y, grad_loss,
+                       (float4*)gx, full / 4, H, W / 4, h, w, region_step((size_t)nq * 256, H, W / 4), eps, mul);
+    return check_launch("region_bwd4_kernel");
+  }
+  const int nb = stream_grid(full);
+  hipLaunchKernelGGL(region_bwd_kernel<L1>, dim3(nb, groups), dim3(256), 0, st, x, y, grad_loss, gx, full, H, W, h, w,
+                     region_step((size_t)nb * 256, H, W), eps, mul);
+  return check_launch("region_bwd_kernel");
+}
+
 #define LAUNCH(kern, n, st, ...) \
   hipLaunchKernelGGL(kern, dim3(stream_grid(n)), dim3(256), 0, st, __VA_ARGS__)
 
@@ -844,6 +982,66 @@ extern "C" int dvsr_l1_tail_backward(const float* x, const float* y, const float
                                      long long n, dvsr_stream_t stream) {
   return dvsr_l1_tail_backward_grouped(x, y, grad_loss, weight, gx, n, 1, stream);
 }
+
+// The region forms: [groups][planes][H][W] operands, the top-left h x w of every plane.
+#define REGION_REQUIRE(what)                                                                                               \
+  DVSR_REQUIRE(groups > 0 && planes > 0 && H > 0 && W > 0 && H <= (1 << 30) && W <= (1 << 30), DVSR_ERR_INVALID,           \
+               what ": groups=%d, planes=%lld, H=%d, W=%d must be positive (H, W <= 2^30)", groups, planes, H, W);         \
+  DVSR_REQUIRE(h >= 1 && h <= H && w >= 1 && w <= W, DVSR_ERR_INVALID, what ": the region %d x %d is not inside %d x %d", \
+               h, w, H, W)
+
+extern "C" int dvsr_charbonnier_region_forward(const float* x, const float* y, float* loss, int groups, long long planes,
+                                               int H, int W, int h, int w, float eps, void* workspace,
+                                               size_t workspace_bytes, dvsr_stream_t stream) {
+  DVSR_REQUIRE(x && y && loss && workspace, DVSR_ERR_INVALID, "charbonnier_region_forward: null argument");
+  REGION_REQUIRE("charbonnier_region_forward");
+  DVSR_REQUIRE(workspace_bytes >= (size_t)groups * CHARB_BLOCKS * sizeof(float), DVSR_ERR_WORKSPACE,
+               "charbonnier_region_forward: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)planes * h * w, full = (size_t)planes * H * W;
+  int nb = (int)((n + 255) / 256 < (size_t)CHARB_BLOCKS ? (n + 255) / 256 : (size_t)CHARB_BLOCKS);
+  hipLaunchKernelGGL(charbonnier_region_partial_kernel, dim3(nb, groups), dim3(256), 0, st, x, y, (float*)workspace, n, full,
+                     H, W, h, w, region_step((size_t)nb * 256, h, w, H, W), eps);
+  hipLaunchKernelGGL(charbonnier_final_kernel, dim3(groups), dim3(256), 0, st, (const float*)workspace, loss, nb,
+                     1.f / (float)n);
+  return check_launch("charbonnier_region_forward");
+}
+
+extern "C" int dvsr_charbonnier_region_backward(const float* x, const float* y, const float* grad_loss, float* gx, int groups,
+                                                long long planes, int H, int W, int h, int w, float eps,
+                                                dvsr_stream_t stream) {
+  DVSR_REQUIRE(x && y && grad_loss && gx, DVSR_ERR_INVALID, "charbonnier_region_backward: null argument");
+  REGION_REQUIRE("charbonnier_region_backward");
+  const size_t n = (size_t)planes * h * w, full = (size_t)planes * H * W;
+  return region_backward<false>(x, y, grad_loss, gx, groups, full, H, W, h, w, eps, 1.f / (float)n, (hipStream_t)stream);
+}
+
+extern "C" int dvsr_l1_tail_region_forward(const float* x, const float* y, const float* base, float weight, float* loss,
+                                           int groups, long long planes, int H, int W, int h, int w, void* workspace,
+                                           size_t workspace_bytes, dvsr_stream_t stream) {
+  DVSR_REQUIRE(x && y && loss && workspace, DVSR_ERR_INVALID, "l1_tail_region_forward: null argument");
+  REGION_REQUIRE("l1_tail_region_forward");
+  DVSR_REQUIRE(workspace_bytes >= (size_t)groups * CHARB_BLOCKS * sizeof(float), DVSR_ERR_WORKSPACE,
+               "l1_tail_region_forward: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)planes * h * w, full = (size_t)planes * H * W;
+  int nb = (int)((n + 255) / 256 < (size_t)CHARB_BLOCKS ? (n + 255) / 256 : (size_t)CHARB_BLOCKS);
+  hipLaunchKernelGGL(l1_region_partial_kernel, dim3(nb, groups), dim3(256), 0, st, x, y, (float*)workspace, n, full, H, W, h,
+                     w, region_step((size_t)nb * 256, h, w, H, W));
+  hipLaunchKernelGGL(l1_final_kernel, dim3(groups), dim3(256), 0, st, (const float*)workspace, base, loss, nb,
+                     weight / (float)n);
+  return check_launch("l1_tail_region_forward");
+}
+
+extern "C" int dvsr_l1_tail_region_backward(const float* x, const float* y, const float* grad_loss, float weight, float* gx,
+                                            int groups, long long planes, int H, int W, int h, int w,
+                                            dvsr_stream_t stream) {
+  DVSR_REQUIRE(x && y && grad_loss && gx, DVSR_ERR_INVALID, "l1_tail_region_backward: null argument");
+  REGION_REQUIRE("l1_tail_region_backward");
+  const size_t n = (size_t)planes * h * w, full = (size_t)planes * H * W;
+  return region_backward<true>(x, y, grad_loss, gx, groups, full, H, W, h, w, 0.f, weight / (float)n, (hipStream_t)stream);
+}
+#undef REGION_REQUIRE
 
 extern "C" int dvsr_upsample_bilinear_forward(const float* x, float* y, long long planes, int H,
                                               int W, int scale, float mul, dvsr_stream_t stream) {

@@ -304,6 +304,110 @@ def inner_loss(loss_pix, slr, slr_fixed, weight=10.0):
     return _InnerLoss.apply(loss_pix, slr, slr_fixed, weight)
 
 
+def check_region(shape, region, who="region"):
+    """(h, w) of a region = (h, w), the top-left h x w of the [..., H, W] planes of `shape`: ints with 1 <= h <= H and
+    1 <= w <= W, ValueError otherwise.  Host code."""
+    import numbers
+    if isinstance(region, (str, bytes)) or not isinstance(region, (tuple, list, torch.Size)) or len(region) != 2 or \
+            any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in region):
+        raise ValueError("%s=%r must be a pair of ints (h, w)" % (who, region))
+    if len(shape) < 2:
+        raise ValueError("%s: a tensor of shape %s has no [H, W] planes" % (who, tuple(shape)))
+    h, w, H, W = int(region[0]), int(region[1]), int(shape[-2]), int(shape[-1])
+    if not (1 <= h <= H and 1 <= w <= W):
+        raise ValueError("%s=%r is not inside the %d x %d planes" % (who, (h, w), H, W))
+    return h, w
+
+
+def _region_geometry(x, per_sample):
+    """(groups, planes, H, W) of a contiguous [..., H, W] operand: the leading dimension is the group with per_sample."""
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    k = int(x.shape[0]) if per_sample else 1
+    return k, x.numel() // (k * H * W), H, W
+
+
+class _CharbonnierRegion(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, h, w, eps, per_sample):
+        if x.shape != y.shape:
+            raise RuntimeError("charbonnier: prediction %s and target %s differ in shape" % (tuple(x.shape), tuple(y.shape)))
+        x, y = x.contiguous(), y.contiguous()
+        k, planes, H, W = _region_geometry(x, per_sample)
+        ws = torch.empty(k * int(L.lib().dvsr_charbonnier_workspace_bytes()), dtype=torch.uint8, device=x.device)
+        loss = x.new_empty((k,) if per_sample else ())
+        L.check(L.lib().dvsr_charbonnier_region_forward(L.ptr(x), L.ptr(y), loss.data_ptr(), k, planes, H, W, h, w, eps,
+                                                        ws.data_ptr(), ws.numel(), L.stream()),
+                "dvsr_charbonnier_region_forward")
+        ctx.save_for_backward(x, y)
+        ctx.geo = (k, planes, H, W, h, w, eps)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        k, planes, H, W, h, w, eps = ctx.geo
+        gx = torch.empty_like(x)
+        g = g.contiguous().float()
+        L.check(L.lib().dvsr_charbonnier_region_backward(L.ptr(x), L.ptr(y), g.data_ptr(), L.ptr(gx), k, planes, H, W, h, w,
+                                                         eps, L.stream()), "dvsr_charbonnier_region_backward")
+        return (gx if ctx.needs_input_grad[0] else None, -gx if ctx.needs_input_grad[1] else None, None, None, None, None)
+
+
+def charbonnier_region(x, y, region, eps=1e-6, per_sample=False):
+    """`charbonnier` (per_sample: `charbonnier_per_sample`, one loss per x[k]) over the top-left region = (h, w) of the
+    [..., H, W] planes: mean(sqrt((x-y)^2 + eps)) of x[..., :h, :w] and y[..., :h, :w], bit-identical to those functions on
+    contiguous copies of the two crops, without the copies; the gradient is 0 outside the region.  A region that is the whole
+    plane calls them."""
+    h, w = check_region(x.shape, region, "charbonnier_region: region")
+    if (h, w) == (int(x.shape[-2]), int(x.shape[-1])):
+        return charbonnier_per_sample(x, y, eps) if per_sample else charbonnier(x, y, eps)
+    return _CharbonnierRegion.apply(x, y, h, w, eps, bool(per_sample))
+
+
+class _InnerLossRegion(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, base, x, y, h, w, weight, per_sample):
+        if x.shape != y.shape or (per_sample and base.shape != (x.shape[0],)):
+            raise RuntimeError("inner_loss: %s vs %s, base %s" % (tuple(x.shape), tuple(y.shape), tuple(base.shape)))
+        x, y = x.contiguous(), y.contiguous()
+        k, planes, H, W = _region_geometry(x, per_sample)
+        b = base.detach().contiguous().float() if per_sample else base.detach().reshape(()).float()
+        ws = torch.empty(k * int(L.lib().dvsr_charbonnier_workspace_bytes()), dtype=torch.uint8, device=x.device)
+        loss = x.new_empty((k,) if per_sample else ())
+        L.check(L.lib().dvsr_l1_tail_region_forward(L.ptr(x), L.ptr(y), b.data_ptr(), float(weight), loss.data_ptr(), k, planes,
+                                                    H, W, h, w, ws.data_ptr(), ws.numel(), L.stream()),
+                "dvsr_l1_tail_region_forward")
+        ctx.save_for_backward(x, y)
+        ctx.geo = (k, planes, H, W, h, w, float(weight))
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        k, planes, H, W, h, w, weight = ctx.geo
+        g = g.contiguous().float()
+        gx = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gx = torch.empty_like(x)
+            L.check(L.lib().dvsr_l1_tail_region_backward(L.ptr(x), L.ptr(y), g.data_ptr(), weight, L.ptr(gx), k, planes, H, W,
+                                                         h, w, L.stream()), "dvsr_l1_tail_region_backward")
+        return (g if ctx.needs_input_grad[0] else None, gx if ctx.needs_input_grad[1] else None,
+                -gx if ctx.needs_input_grad[2] else None, None, None, None, None)
+
+
+def inner_loss_region(loss_pix, slr, slr_fixed, region, weight=10.0, per_sample=False):
+    """`inner_loss` (per_sample: `inner_loss_per_sample`) with the L1 term over the top-left region = (h, w) of the
+    [..., H, W] planes of the two SLR clips: loss_pix + weight * F.l1_loss(slr[..., :h, :w], slr_fixed[..., :h, :w]),
+    bit-identical to those functions on contiguous copies of the crops; the gradient is 0 outside the region.  A region that
+    is the whole plane calls them."""
+    h, w = check_region(slr.shape, region, "inner_loss_region: region")
+    if (h, w) == (int(slr.shape[-2]), int(slr.shape[-1])):
+        return (inner_loss_per_sample if per_sample else inner_loss)(loss_pix, slr, slr_fixed, weight)
+    return _InnerLossRegion.apply(loss_pix, slr, slr_fixed, h, w, weight, bool(per_sample))
+
+
 class _PatchGather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, src, py, px, edge, scale):

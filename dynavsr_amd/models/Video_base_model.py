@@ -78,8 +78,19 @@ class VideoBaseModel(BaseModel):
         self.fake_H = self.netG(self.var_L)
         return self.l_pix_w * self.cri_pix(self.fake_H, self.real_H)
 
-    def calculate_loss(self):
-        l_pix = self._pixel_loss()
+    def _region_pixel_loss(self, region):
+        """_pixel_loss with the criterion over the top-left region = (h, w) of output and target (a frame padded at the bottom
+        and right: adapt.adapt_frame) -- one native reduction for the Charbonnier loss on the GPU (hipops.charbonnier_region),
+        the criterion on the two slices otherwise."""
+        h, w = region
+        self.fake_H = self.netG(self.var_L)
+        if isinstance(self.cri_pix, CharbonnierLoss) and self.fake_H.is_cuda:
+            from dynavsr_amd import hipops
+            return self.l_pix_w * hipops.charbonnier_region(self.fake_H.float(), self.real_H.float(), (h, w), self.cri_pix.eps)
+        return self.l_pix_w * self.cri_pix(self.fake_H[..., :h, :w], self.real_H[..., :h, :w])
+
+    def calculate_loss(self, region=None):
+        l_pix = self._pixel_loss() if region is None else self._region_pixel_loss(region)
         self.log_dict['l_pix'] = l_pix.detach().clone()   # own storage: the drivers add to the returned loss IN PLACE (test_dynavsr.py:264-274)
         return l_pix
 

@@ -645,6 +645,25 @@ int dvsr_l1_tail_forward_grouped(const float* x, const float* y, const float* ba
 int dvsr_l1_tail_backward_grouped(const float* x, const float* y, const float* grad_loss, float weight, float* gx,
                                   long long n, int groups, dvsr_stream_t stream);
 
+/* ---- region forms of the two losses (a clip padded at the bottom and right: the objective counts the frame's own pixels)
+ * x, y (and gx) = [groups][planes][H][W] contiguous fp32; the region is the top-left h x w of every plane, 1 <= h <= H,
+ * 1 <= w <= W; n = planes * h * w.  Grouped like *_grouped (groups = 1: the scalar loss).
+ * forward:  loss[g] = mean over the region of sqrt((x-y)^2 + eps)  /  (base ? base[g] : 0) + weight * mean over it of |x-y|.
+ *           The region is walked in the row-major order of the cropped tensor with the grid, stride and reduction of the
+ *           functions above: the value is bit-identical to theirs on a contiguous copy of the crop.
+ * backward: writes EVERY element of gx -- inside the region the formulas above with 1/n (bit-identical to them on the
+ *           crop), outside exactly 0.f -- so gx may be uninitialised memory.
+ * Workspace (forward): groups * dvsr_charbonnier_workspace_bytes(). */
+int dvsr_charbonnier_region_forward(const float* x, const float* y, float* loss, int groups, long long planes, int H, int W,
+                                    int h, int w, float eps, void* workspace, size_t workspace_bytes, dvsr_stream_t stream);
+int dvsr_charbonnier_region_backward(const float* x, const float* y, const float* grad_loss, float* gx, int groups,
+                                     long long planes, int H, int W, int h, int w, float eps, dvsr_stream_t stream);
+int dvsr_l1_tail_region_forward(const float* x, const float* y, const float* base, float weight, float* loss, int groups,
+                                long long planes, int H, int W, int h, int w, void* workspace, size_t workspace_bytes,
+                                dvsr_stream_t stream);
+int dvsr_l1_tail_region_backward(const float* x, const float* y, const float* grad_loss, float weight, float* gx, int groups,
+                                 long long planes, int H, int W, int h, int w, dvsr_stream_t stream);
+
 /* ---- op-level entries to the pipelined / small-grid conv kernels ---------------------------------------------------
  * dvsr_conv2d_forward needs no workspace and runs the un-packed kernel.  These pack the weights into a caller
  * workspace on the stream and run the geometry the whole-network plan would pick for the shape (pipelined 4-row tiles,
