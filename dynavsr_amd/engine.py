@@ -483,7 +483,7 @@ _splans = {}
 class StreamPlan:
     """Owns one dvsr_edvr_stream: the B = 1 no-grad EDVR tape split at L3_fea around a frame cache of `slots` slots
     (include/dynavsr_hip.h).  `extract` writes one frame's features into a slot, `fuse` turns a window of slots into the
-    SR frame; adapt.super_resolve_frames drives the two over a video.
+    SR frame; video.super_resolve_frames drives the two over a video.
 
     The plan keeps one workspace per (device, HIP stream) -- and with it the packed weights of both tapes -- for as long
     as it lives, so a second video through the same frozen network packs nothing (`release()` frees them).  Packs are

@@ -13,7 +13,7 @@ interleaved back.  The reference does both on the host (`img.astype(np.float32) 
                                      or fp32 [3,h,w]
 
 `layout` is 'chw' (fp32 planar), 'hwc_rgb' or 'hwc_bgr' (uint8 interleaved); None means 'chw' for a float tensor and
-'hwc_rgb' for a uint8 one.  adapt.super_resolve_frames uses these (and engine.StreamPlan.extract_frame, which ingests
+'hwc_rgb' for a uint8 one.  video.super_resolve_frames uses these (and engine.StreamPlan.extract_frame, which ingests
 straight into the frame cache); they are also the building blocks for feeding padded clips to the adaptation loops by hand.
 
 What a video decoder delivers (ffmpeg rawvideo pipes, PyAV) and an encoder takes is 8-bit YCbCr 4:2:0: the layouts 'nv12'
@@ -516,7 +516,7 @@ def tile_view(frame, layout, y, x, th, tw):
     """The tile [y : min(y + th, h), x : min(x + tw, w)] of a frame that resolve_layout accepts, as a strided view -- or, for a
     YCbCr layout, as the tuple of plane views (packed frames included) -- that ingest / StreamPlan.extract_frame take: nothing
     is copied.  y and x must be even where the layout sub-samples that axis (a tile then starts on a chroma sample; the
-    multiples of 4 of adapt.tile_origins are).  No GPU call."""
+    multiples of 4 of video.tile_origins are).  No GPU call."""
     layout, h, w = resolve_layout(frame, layout)
     y, x, th, tw = int(y), int(x), int(th), int(tw)
     if not (0 <= y < h and 0 <= x < w and th >= 1 and tw >= 1):
@@ -538,7 +538,7 @@ def tile_view(frame, layout, y, x, th, tw):
 def stitch_table(n, tile, overlap, scale):
     """One axis of the tile grid and its blend weights: (origins int32 [tiles] in SR pixels, first int32 [scale * n], weights fp32
     [scale * n, K]) CPU tensors from dvsr_frame_stitch_origins / _cover / _table -- n the padded length in LR pixels, tile and
-    overlap as adapt.tile_origins takes them; SR position r is sum_a weights[r, a] * tile(first[r] + a) at r - origins[first[r]
+    overlap as video.tile_origins takes them; SR position r is sum_a weights[r, a] * tile(first[r] + a) at r - origins[first[r]
     + a]; rows with fewer covering tiles than K are zero-padded.  No GPU call."""
     n, tile, overlap, scale = int(n), int(tile), int(overlap), int(scale)
     lib = L.lib()
@@ -740,7 +740,7 @@ def _luma_sad_launch(a, b, fields, frame_stride, pairs, sad):
 def luma_sad(frames, layout=None):
     """SAD_t = sum over the h x w frame of |Y8_t(p) - Y8_(t-1)(p)| for t = 1 .. T - 1, as an int64 CPU tensor [T - 1].
 
-    `frames` is what adapt.super_resolve_frames accepts: a [T,...] tensor or a list of frames of one kind and size, on the CPU
+    `frames` is what video.super_resolve_frames accepts: a [T,...] tensor or a list of frames of one kind and size, on the CPU
     or the GPU, in any `layout` (None: by dtype).  Y8, the luma of a pixel, is an 8-bit integer: the Y-plane byte of an
     'nv12' / 'i420' frame as it is (`matrix` and `yuv_range` play no part), the top 8 bits of the level of a 10- / 12-bit
     Y-plane word (so that scores and thresholds mean what they mean for 8-bit video), (77 R + 150 G + 29 B + 128) >> 8 of an
@@ -913,7 +913,7 @@ def scene_scores(sad, h, w):
 
 def detect_cuts(frames, layout=None, threshold=10.0):
     """The hard cuts of a video: the list of t with scene_scores(luma_sad(frames, layout))[t] >= threshold, frame t being
-    the first of a new scene -- the `cuts` of adapt.super_resolve_frames.  The default threshold is a policy default that
+    the first of a new scene -- the `cuts` of video.super_resolve_frames.  The default threshold is a policy default that
     callers override; it has not been tuned on real footage.  Fades and dissolves are not found."""
     threshold = float(threshold)
     if not threshold > 0:
