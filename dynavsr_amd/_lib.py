@@ -5,6 +5,7 @@ carrying dvsr_last_error() is raised.  The product path never routes through tor
 the oracle.
 """
 import ctypes
+import functools
 import os
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
@@ -266,6 +267,10 @@ def _declare(lib):
         "dvsr_edvr_stream_max_image_bytes": (ctypes.c_ulonglong, [P]),
         "dvsr_frame_score_workspace_bytes": (c_size_t, [I, I, I]),
         "dvsr_frame_score": (I, [P, POINTER(FrameDesc), P, POINTER(FrameDesc), POINTER(ScoreArgs), P, P, c_size_t, P]),
+        "dvsr_switch_count": (I, []),
+        "dvsr_switch_info": (I, [I, POINTER(c_char_p), POINTER(c_int), POINTER(c_int), POINTER(c_char_p)]),
+        "dvsr_switch_parse": (I, [I, c_char_p, POINTER(c_int)]),
+        "dvsr_switch_value": (I, [I, POINTER(c_int)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -285,6 +290,34 @@ def lib():
         _lib = ctypes.CDLL(os.environ.get("DVSR_HIP_LIB", SO_PATH))
         _lib._signatures = _declare(_lib)
     return _lib
+
+
+SW_BUILD, SW_PROCESS, SW_CALL, SW_DEBUG = 0, 1, 2, 3             # DVSR_SW_*: when the library reads a switch
+
+
+@functools.lru_cache(maxsize=None)
+def switches():
+    """The library's table of DVSR_* environment switches (csrc/switches.h), in its order: [(name, scope, default, doc)].
+    A switch's index in this list is its index in dvsr_switch_parse / dvsr_switch_value.  No device needed."""
+    rows = []
+    for i in range(lib().dvsr_switch_count()):
+        name, doc, scope, dflt = c_char_p(), c_char_p(), c_int(), c_int()
+        check(lib().dvsr_switch_info(i, ctypes.byref(name), ctypes.byref(scope), ctypes.byref(dflt), ctypes.byref(doc)), "dvsr_switch_info")
+        rows.append((name.value.decode(), scope.value, dflt.value, doc.value.decode()))
+    return tuple(rows)
+
+
+@functools.lru_cache(maxsize=None)
+def switch_names(scope):
+    """The names of one scope: SW_BUILD makes the engine's plan-cache key, SW_PROCESS its warn-on-change list."""
+    return tuple(name for name, s, _dflt, _doc in switches() if s == scope)
+
+
+def switch_value(name):
+    """What the library takes the switch for now, under its scope (dvsr_switch_value)."""
+    v = c_int()
+    check(lib().dvsr_switch_value([r[0] for r in switches()].index(name), ctypes.byref(v)), "dvsr_switch_value")
+    return v.value
 
 
 def check(rc, what=""):

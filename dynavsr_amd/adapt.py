@@ -480,10 +480,10 @@ class FrameBatch:
         # what the per-sample weight sets of the native tapes need (dvsr_edvr_plan_create_ex: whole 8-channel deformable
         # groups; the fused DCN backward: whole 64-cout blocks; no DVSR_CONV_V1 A/B kernel) -- anything else would raise
         # DVSR_ERR_UNSUPPORTED in the middle of a batch instead of taking the per-frame loop
-        import os
+        from . import _lib as L
         nf, groups = int(model.netG.nf), int(model.netG.groups)
         return (nf % 64 == 0 and groups > 0 and nf % groups == 0 and (nf // groups) % 8 == 0
-                and os.environ.get("DVSR_CONV_V1", "0") in ("", "0"))
+                and not L.switch_value("DVSR_CONV_V1"))
 
     def refresh(self, netG, netE):
         """Every slice = the un-adapted weights (the per-frame deepcopy), fresh optimiser state."""

@@ -509,7 +509,7 @@ static int launch_conv2(ConvK2 k, hipStream_t st) {
   size_t lds = Sh::LDS_BYTES;
 #ifdef DVSR_CONV_TRACE
   // debug: DVSR_CONV_LDS=<bytes> inflates the LDS request to force fewer workgroups per CU
-  if (const char* e = getenv("DVSR_CONV_LDS")) lds = std::max(lds, (size_t)atol(e));
+  lds = std::max(lds, (size_t)sw(Sw::CONV_LDS));
 #endif
   set_dyn_lds_once(attr_once, (const void*)kern, lds);
   k.tiles_x = ceil_div(k.Wo, 32); k.tiles_y = ceil_div(k.Ho, TH); k.ntiles = k.tiles_x * k.tiles_y * k.N;
@@ -905,7 +905,6 @@ static int launch_ksplit(ConvK2 k, hipStream_t st) {
 // One function per decision; conv2_choose below lists them in priority order.
 namespace {
 struct ConvShape { int ks, stride, N, Ho, Wo, Cout, Ctot; };
-int int_or(const char* v, int dflt) { return v ? atoi(v) : dflt; }   // of a getenv() result
 
 // Calibrated on MI355X per-layer timings of all five candidate geometries
 // (profiles/r01_conv_geometry_sweep.txt): the 4x32-pixel tile beats 8x32 on every EDVR layer, 16-channel
@@ -1035,9 +1034,9 @@ ConvGeo conv2_choose(int ks, int stride, int N, int Ho, int Wo, int Cout, int Ct
   // F(2x2) on the bf16 pipe with the exact 3-way operand split, 0: on the fp32 pipe and no F(4x4); DVSR_CONV_WINO5: 0 no F(4x4),
   // 1 where the model says it is faster (default), 2 wherever it is eligible, 3 eligible and 16x32-pixel workgroup tiles (A/B aids).
   // ALLOW_ONLY_F4 is the 2 of one launch: it does not override a switch that turns the kernel off.
-  const int wino_on = int_or(getenv("DVSR_CONV_WINO"), 1);
+  const int wino_on = sw(Sw::CONV_WINO);
   if (!(wino_on && g.kernel == ConvKernel::DMA_HALO && (allow & ALLOW_WINO) && Cout >= 32 && Ctot >= 16)) return g;
-  const int wino3_on = int_or(getenv("DVSR_CONV_WINO3"), 1), wino5_on = int_or(getenv("DVSR_CONV_WINO5"), 1);
+  const int wino3_on = sw(Sw::CONV_WINO3), wino5_on = sw(Sw::CONV_WINO5);
   const double direct = direct_cost(s), cus = (double)device_cus();
   const WinoPick f2 = wino_f2_cost(s, cus, wino3_on != 0);
   // (both Winograd kernels hold a workgroup's whole working set in ~150 KB of LDS: gfx950's 160 KB, checked, not assumed)
@@ -1122,11 +1121,7 @@ int conv2d_packed_prepare(const dvsr_conv2d_desc& d, const float* wp, const Conv
   {
     // measurement aid of the debug build, results are WRONG when set (profiles/r02_z_conv_dma_ablation.txt): bit 0 no
     // stores, bit 1 no halo DMA, bit 2 no weight DMA, bit 3 no chunk barriers (conv2d_dma_kernel only)
-    static int ablate = -1;
-    if (ablate < 0) {
-      const char* v = getenv("DVSR_CONV_ABLATE");
-      ablate = v ? atoi(v) : 0;
-    }
+    static const int ablate = sw(Sw::CONV_ABLATE);
     k.ablate = ablate;
   }
 #endif

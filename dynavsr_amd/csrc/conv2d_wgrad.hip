@@ -209,19 +209,8 @@ int wgrad_reduce_batch(const WgradReduceEntry* entries, int n, hipStream_t st, i
 // ---- launch geometry ----------------------------------------------------------------------------------------
 // One function per decision; conv2d_wgrad_choose below lists them in priority order.
 
-// A/B switches, read once per process.  Every other figure of the rule is a named constant beside its decision.
-static bool env_off(const char* v) { return v && v[0] == '0'; }
-struct WgradSwitches {
-  bool wide = !env_off(getenv("DVSR_WGRAD_WIDE"));   // =0: scalar loads in the fp32 and the split kernels
-  bool s3v = !env_off(getenv("DVSR_WGRAD_S3V"));     // =0: the split stays on its scalar-staging (round-4) kernel
-  bool s3w = !env_off(getenv("DVSR_WGRAD_S3W"));     // =0: no eight-wave form
-  // =<tiles x cout blocks x cin blocks>: moves split_row_split's threshold (0 = never)
-  int s3_kys_below = getenv("DVSR_WGRAD_S3_KYS_BELOW") ? atoi(getenv("DVSR_WGRAD_S3_KYS_BELOW")) : 4000;
-  int s3_wgs = getenv("DVSR_WGRAD_S3_WGS") ? atoi(getenv("DVSR_WGRAD_S3_WGS")) : 0;   // =<workgroups per row-split launch of the split kernel>
-  bool split3 = !env_off(getenv("DVSR_WGRAD_SPLIT3"));   // =0: the plans' 3x3 stride-1 weight gradients stay on the fp32 MFMA kernel
-};
-static const WgradSwitches& wgrad_switches() { static const WgradSwitches s; return s; }
-bool wgrad_split3_default() { return wgrad_switches().split3; }
+// The rule's A/B switches are the DVSR_WGRAD_* rows of switches.h; every other figure is a named constant beside its decision.
+bool wgrad_split3_default() { return sw(Sw::WGRAD_SPLIT3); }
 
 // The kernel argument without the rule's answers and the slot pointers: the descriptor's defaults resolved, and the tiling every
 // kernel shares (2 x 32-pixel tiles, 64 x 64 (cout, cin) blocks)
@@ -292,7 +281,7 @@ static int pipe_row_splits(const WgradDesc& d, const WgradK& k) {
 // and the pointers allow it.  The fp32 pipelined kernel and the split kernel have the same two vector forms; plain bf16 has none.
 static int vector_width(const WgradDesc& d, const WgradK& k, int bf) {
   const bool gy_ok = !k.gy_ps && k.Wo % 4 == 0 && ((uintptr_t)k.gy & 15) == 0;
-  if (!wgrad_switches().wide || !gy_ok || d.stride != 1 || d.ks > 3 || bf == 1) return 0;
+  if (!sw(Sw::WGRAD_WIDE) || !gy_ok || d.stride != 1 || d.ks > 3 || bf == 1) return 0;
   if (k.W % 4 == 0 && k.x_bs % 4 == 0 && ((uintptr_t)k.x & 15) == 0) return 4;
   if (k.W % 2 == 0 && k.x_bs % 2 == 0 && ((uintptr_t)k.x & 7) == 0) return 2;
   return 0;
@@ -303,23 +292,23 @@ static int vector_width(const WgradDesc& d, const WgradK& k, int bf) {
 static bool split_vector_staging(const WgradDesc& d, const WgradK& k, int vx) {
   const bool vec_form = (d.ks == 3 && (k.pad == 0 || k.pad == 1)) || (d.ks == 2 && k.pad == 0);
   const bool fits = (unsigned long long)k.Cin * k.H * k.W < (1ull << 30) && (unsigned long long)k.Cout * k.Ho * k.Wo < (1ull << 30);
-  return wgrad_switches().s3v && vx != 0 && vec_form && fits;
+  return sw(Sw::WGRAD_S3V) && vx != 0 && vec_form && fits;
 }
 // The vector-staging form can run one kernel ROW per workgroup, two workgroups per CU (conv2d_wgrad_bf16.hip:
 // conv2d_wgrad_split3v_kernel<.., KYS>).  It stages gy three times and x one and a half times, so it pays where a workgroup has
 // few tiles and the fixed costs (first loads, flush, the tail of the last round) weigh most -- measured (tools/wgrad_bench.py,
 // us with / without): 40 x 44x80 93 / 102, 8 x 44x80 40 / 51, 40 x 22x40 47 / 61, 1 x 176x320 52 / 63, but 40 x 176x320
 // 1046 / 941, 64 -> 216 at 40 x 44x80 290 / 264.
-static bool split_row_split(const WgradK& k) { return work(k) < wgrad_switches().s3_kys_below; }
+static bool split_row_split(const WgradK& k) { return work(k) < sw(Sw::WGRAD_S3_KYS_BELOW); }
 // two workgroups per CU from ~1000 tiles, one below; rounded DOWN (one workgroup more than the CUs hold at once is a second
 // round with one workgroup in it)
 static int split_row_splits(const WgradDesc& d, const WgradK& k) {
-  const int wgs = wgrad_switches().s3_wgs > 0 ? wgrad_switches().s3_wgs : (work(k) >= 1000 ? 512 : 256);
+  const int wgs = sw(Sw::WGRAD_S3_WGS) > 0 ? sw(Sw::WGRAD_S3_WGS) : (work(k) >= 1000 ? 512 : 256);
   return per_group(k, wgs / (d.ks * k.nob * k.ncb));
 }
 // The eight-wave form (two waves per SIMD, 16x16x32 MFMAs) for the float4-staged launches that are not row-split: 7 - 14 % per
 // launch over the four-wave form (profiles/r05_wgrad_s3w.txt); the float2 forms spill there and stay on four waves.
-static bool split_eight_waves(int vx) { return wgrad_switches().s3w && vx == 4; }
+static bool split_eight_waves(int vx) { return sw(Sw::WGRAD_S3W) && vx == 4; }
 
 static WgradGeo choose(const WgradDesc& d, const WgradK& k) {
   WgradGeo g;
@@ -381,7 +370,7 @@ int conv2d_wgrad_prepare(const WgradDesc& d, void* ws, size_t ws_bytes, hipStrea
   k.nsplit = g.nsplit; k.nslot = g.nslot; k.vx = g.vx;
   out->geo = g; out->ks = d.ks;
 #ifdef DVSR_CONV_TRACE
-  { static const int nf = getenv("DVSR_WGRAD_NOFLUSH") ? atoi(getenv("DVSR_WGRAD_NOFLUSH")) : 0; k.noflush = nf; }
+  { static const int nf = sw(Sw::WGRAD_NOFLUSH); k.noflush = nf; }
   k.trace = g_wgrad_trace;
 #endif
   k.partial = (float*)ws;

@@ -294,9 +294,8 @@ int conv3x3_small_cout_run(const float* x, const float* w, const float* bias, co
   k.x = x; k.w = w; k.bias = bias; k.res = res; k.y = y; k.N = N; k.C = C; k.H = H; k.W = W; k.Cout = Cout; k.act = act;
   k.wdiv = wdiv > 0 ? wdiv : 1; k.w_gs = w_gs; k.b_gs = b_gs;
   // the matrix-pipe form: 64 input channels, up to 3 outputs, rows of whole 16-byte groups, one sample below 2 GB
-  // (DVSR_CONV_LAST_MFMA=1 takes it: measured no faster than the VALU kernel, see above; read once per process)
-  static const bool mfma_on = [] { const char* v = getenv("DVSR_CONV_LAST_MFMA"); return v && v[0] == '1'; }();
-  if (mfma_on && C == 64 && Cout <= 3 && W % 4 == 0 && (unsigned long long)C * H * W * 4 < 0x7fffffffull &&
+  // (DVSR_CONV_LAST_MFMA=1 takes it: measured no faster than the VALU kernel, see above)
+  if (sw(Sw::CONV_LAST_MFMA) && C == 64 && Cout <= 3 && W % 4 == 0 && (unsigned long long)C * H * W * 4 < 0x7fffffffull &&
       ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) == 0) && w_gs % 4 == 0) {
     if (Cout == 1) return launch_small_mfma<1>(k, st);
     if (Cout == 2) return launch_small_mfma<2>(k, st);

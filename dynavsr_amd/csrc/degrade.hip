@@ -216,7 +216,7 @@ extern "C" int dvsr_degrade_apply(const float* img, const float* kernels, float*
                K / 2, K / 2, H, W);
   const int pad = K / 2;
   const int Ho = (H + 2 * pad - K) / scale + 1, Wo = (W + 2 * pad - K) / scale + 1;
-  if (N * C <= 65535 && !getenv("DVSR_DEGRADE_GENERIC")) {
+  if (N * C <= 65535 && !sw(Sw::DEGRADE_GENERIC)) {
     const int J = ceil_div(K, scale);
     hipStream_t st = (hipStream_t)stream;
 #define DVSR_DG_CASE(S_, J_) \

@@ -190,8 +190,7 @@ static WgradDesc wgrad_shape(const dvsr_edvr_plan& p, const Op& o, int which) {
 // whole.  The two packs share whole's slot: main [0, c0), then reference [c0, c0 + c1) of the parameter.
 static Op::LaunchList plan_hoist(const Op& o, const dvsr_edvr_plan& p, ConvAllow fwd_ok, const Op::Launch& whole) {
   Op::LaunchList pair;
-  const char* hv = getenv("DVSR_PCD_HOIST");
-  if ((hv && hv[0] == '0') || p.use_v1 || p.wsets != 1 || whole.pack.geo.kernel != ConvKernel::WINO_F4 || o.x1_bdiv <= 1 || o.c1 <= 0 ||
+  if (!sw(Sw::PCD_HOIST) || p.use_v1 || p.wsets != 1 || whole.pack.geo.kernel != ConvKernel::WINO_F4 || o.x1_bdiv <= 1 || o.c1 <= 0 ||
       o.N % o.x1_bdiv != 0 || o.res.valid() || o.ps)
     return pair;
   const int Ho = conv_out(o, o.H), Wo = conv_out(o, o.W), bd = o.x1_bdiv;
@@ -217,12 +216,11 @@ static void plan_conv_launches(Op& o, dvsr_edvr_plan& p) {
   const int ks = o.ks, N = o.N, c0 = o.c0, c1 = o.c1, Cout = o.Cout, Ho = conv_out(o, o.H), Wo = conv_out(o, o.W);
   // (estimator plans: also the 2x2 space-to-depth form of the 4x4 stride-2 convolutions, DVSR_EST_SPLIT2=0 keeps those
   // on the fp32 MFMA)
-  const char* s2 = getenv("DVSR_EST_SPLIT2");
-  const int split2 = s2 ? atoi(s2) : 1;   // (read per plan build, as DVSR_EST_SPLIT is; 2: forward launches only)
+  const int split2 = sw(Sw::EST_SPLIT2);   // (2: forward launches only)
   const bool bf = p.cfg.bf16_mfma && (ks == 3 || (ks == 2 && p.split_any_pad && p.cfg.bf16_mfma == 2 && split2 && c0 % 16 == 0)) &&
                   o.stride == 1 && (o.pad < 0 || p.split_any_pad) && (c1 == 0 || c0 % 16 == 0);
   // bf16_mfma = 2: 8-row tiles (two 32-pixel rows per wave) once they still give ~a workgroup per CU
-  static const int split_th8_from = getenv("DVSR_SPLIT_TH8_FROM") ? atoi(getenv("DVSR_SPLIT_TH8_FROM")) : 200;
+  const int split_th8_from = sw(Sw::SPLIT_TH8_FROM);
   auto as_bf = [&](ConvGeo g, int ho, int wo, int cout, bool dgrad = false) {
     if (!bf || (ks == 2 && split2 == 2 && dgrad)) return g;
     // the 2x2 form only where it pays (launches of at least a workgroup per CU): small launches stay on the fp32 kernel
@@ -466,9 +464,8 @@ static int build_plan(dvsr_edvr_plan& p, PlanPart part = PART_WHOLE) {
   T fea = b.conv("tsa_fea", ffu, gated, Nf * C, none, 0, B, H, W, C, 1, 1, L);
   T att = b.conv("tsa_att1", s1, gated, Nf * C, none, 0, B, H, W, C, 1, 1, L);
   {  // fea_fusion and sAtt_1 read the same 5 x 64-channel tensor (EDVR_arch.py:183-202): one pass over it
-    static const bool dual_on = [] { const char* v = getenv("DVSR_TSA_DUAL"); return !(v && v[0] == '0'); }();
     const int ia = (int)p.ops.size() - 2, ib = ia + 1;
-    if (dual_on && C == 64 && !p.cfg.bf16_mfma) { p.ops[ia].dual = ib; p.ops[ib].fused_into = ia; }
+    if (sw(Sw::TSA_DUAL) && C == 64 && !p.cfg.bf16_mfma) { p.ops[ia].dual = ib; p.ops[ib].fused_into = ia; }
   }
   T pmx, pav;
   b.pool("tsa_pool1", att, (size_t)B * C, H, W, pmx, pav);
@@ -599,8 +596,7 @@ struct BackBuilder {
   void copyadd(const T& dst, const Ref& src, size_t n, int fwd) {
     if (dst.space == SP_ARENA) {   // first, whole-slot contribution: keep the copy pending
       const int ai = alloc_index(dst.off);
-      static const bool defer = [] { const char* v = getenv("DVSR_FUSE_RES_BWD"); return !(v && v[0] == '0'); }();
-      if (defer && !written[ai] && dst.off == p.allocs[ai].first && dst.numel == p.allocs[ai].second && n == dst.numel) {
+      if (sw(Sw::FUSE_RES_BWD) && !written[ai] && dst.off == p.allocs[ai].first && dst.numel == p.allocs[ai].second && n == dst.numel) {
         written[ai] = 2;
         pending[ai] = Pending{src, n, fwd};
         return;
@@ -642,7 +638,7 @@ static void build_backward(dvsr_edvr_plan& p) {
   std::vector<char> act_fused(p.ops.size(), 0);  // the producer's B_ACT is done by its consumer's launch
   // DVSR_FUSE_ACT_BWD=0 keeps every activation backward a separate launch (A/B aid); the un-pipelined conv
   // kernel (DVSR_CONV_V1) has no mask input
-  const bool fuse_act = !p.use_v1 && [] { const char* v = getenv("DVSR_FUSE_ACT_BWD"); return !(v && v[0] == '0'); }();
+  const bool fuse_act = !p.use_v1 && sw(Sw::FUSE_ACT_BWD);
   for (int i = (int)p.ops.size() - 1; i >= 0; --i) {
     const Op& o = p.ops[i];
     const Ref gy = BackBuilder::grad(o.y);
@@ -1097,13 +1093,13 @@ extern "C" int dvsr_edvr_plan_create_ex(const dvsr_edvr_config* cfg, int B, int 
                "edvr_plan_create: nf/groups=%d (supported: 4, 8, 16)", cpg);
   dvsr_edvr_plan* p = new dvsr_edvr_plan();
   p->cfg = *cfg; p->B = B; p->H = H; p->W = W; p->wgroups = grad_groups; p->wsets = weight_sets;
-  { const char* v = getenv("DVSR_CONV_V1"); p->use_v1 = v && v[0] == '1'; }
+  p->use_v1 = sw(Sw::CONV_V1);
   if (weight_sets > 1 && (p->use_v1 || cpg % 8 != 0)) {
     delete p;
     DVSR_REQUIRE(false, DVSR_ERR_UNSUPPORTED, "edvr_plan_create: per-sample weight sets need the packed kernels (no "
                  "DVSR_CONV_V1) and nf/groups a multiple of 8");
   }
-  { const char* v = getenv("DVSR_BWD_STREAMS"); p->side_streams = (v && v[0] == '0') ? 0 : 1; }
+  p->side_streams = sw(Sw::BWD_STREAMS);
   int rc = build_plan(*p);
   if (rc != DVSR_OK) { delete p; return rc; }
   build_backward(*p);
@@ -1193,8 +1189,7 @@ extern "C" int dvsr_edvr_backward(const dvsr_edvr_plan* p, const float* const* p
   // which on the small inner-step clips is a third of a layer: the weight gradients of `fork_every` consecutive
   // layers therefore share one fork (a gradient buffer is never rewritten once its layer's turn has come, so
   // launching a weight gradient a few layers late is safe).  DVSR_BWD_FORK_EVERY=<layers> (1 = a fork per layer).
-  static const int fork_env = [] { const char* v = getenv("DVSR_BWD_FORK_EVERY"); return v ? atoi(v) : 0; }();
-  const int fork_every = fork_env > 0 ? fork_env : p->fork_every;
+  const int fork_every = sw(Sw::BWD_FORK_EVERY) > 0 ? sw(Sw::BWD_FORK_EVERY) : p->fork_every;
   std::vector<WgradLaunch> waiting;
   int waiting_layers = 0;
   auto flush_waiting = [&]() -> int {
@@ -1510,11 +1505,10 @@ extern "C" int dvsr_edvr_stream_create(const dvsr_edvr_config* cfg, int H, int W
   const int cpg = cfg->nf / cfg->groups;
   DVSR_REQUIRE(cpg == 4 || cpg == 8 || cpg == 16, DVSR_ERR_UNSUPPORTED, "edvr_stream_create: nf/groups=%d (supported: 4, 8, 16)", cpg);
   dvsr_edvr_stream* s = new dvsr_edvr_stream();
-  const char* v1 = getenv("DVSR_CONV_V1");
   int k = 0;
   for (dvsr_edvr_plan* p : {&s->extract, &s->fuse}) {
     p->cfg = *cfg; p->B = 1; p->H = H; p->W = W;
-    p->use_v1 = v1 && v1[0] == '1';
+    p->use_v1 = sw(Sw::CONV_V1);
     int rc = build_plan(*p, k++ == 0 ? PART_EXTRACT : PART_FUSE);   // (no backward tape: these plans never take a gradient)
     if (rc != DVSR_OK) { delete s; return rc; }
   }
@@ -1710,7 +1704,7 @@ static int build_estimator(dvsr_estimator_plan& ep) {
   // DVSR_EST_FUSE_PAD=0 keeps every padding a separate launch (A/B aid).  Fused: the conv that produces x stores it
   // straight into the reflect-padded (space-to-depth) tensor this conv reads -- the pad op stays on the tape for the
   // backward (its fold + the producer's activation backward) but launches nothing in the forward.
-  static const bool fuse_pad = [] { const char* v = getenv("DVSR_EST_FUSE_PAD"); return !(v && v[0] == '0'); }();
+  const bool fuse_pad = sw(Sw::EST_FUSE_PAD);
   auto fuse = [&](int mode) {
     // the op before the pad op just pushed must be the conv that produced its input, with this pad as its only reader
     const int pi = (int)p.ops.size() - 1;
@@ -1809,11 +1803,10 @@ extern "C" int dvsr_estimator_plan_create_ex(const dvsr_estimator_config* cfg, i
     // off the DMA-halo and Winograd kernels; the register-staged kernel with the exact 3-way bf16 operand split
     // (cfg.bf16_mfma = 2: fp32-accurate, six bf16 products per fp32 product) is 1.3x the fp32 MFMA on them: MFDN x4 forward
     // at 5x3x176x320 0.72 -> 0.62 ms, the batched inner step 4.55 -> 4.36 ms per frame.  DVSR_EST_SPLIT=0: fp32 MFMA.
-    const char* v = getenv("DVSR_EST_SPLIT");
-    if (!v || atoi(v)) { p.cfg.bf16_mfma = 2; p.split_any_pad = true; }
+    if (sw(Sw::EST_SPLIT)) { p.cfg.bf16_mfma = 2; p.split_any_pad = true; }
   }
   p.B = B; p.H = H; p.W = W; p.wgroups = grad_groups; p.wsets = weight_sets;
-  { const char* v = getenv("DVSR_BWD_STREAMS"); p.side_streams = (v && v[0] == '0') ? 0 : 1; }
+  p.side_streams = sw(Sw::BWD_STREAMS);
   p.fork_every = 1;   // seven layers whose weight gradients outlast the data-gradient chain: every fork at once
   int rc = build_estimator(*ep);
   if (rc != DVSR_OK) { delete ep; return rc; }

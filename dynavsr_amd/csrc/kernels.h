@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/dynavsr_hip.h"
 #include "common.h"
+#include "switches.h"
 
 namespace dvsr {
 
@@ -165,7 +166,7 @@ struct WgradGeo {
 // THE rule: which kernel a weight gradient runs on and how it is launched (conv2d_wgrad.hip).  Host arithmetic only: no
 // HIP call, and of the pointers it reads the alignment alone.
 WgradGeo conv2d_wgrad_choose(const WgradDesc& d);
-bool wgrad_split3_default();   // DVSR_WGRAD_SPLIT3 (read once with the rule's other switches): plans ask for mode 2
+bool wgrad_split3_default();   // DVSR_WGRAD_SPLIT3: plans ask for mode 2
 size_t conv2d_wgrad_workspace_bytes(const WgradDesc& d);   // the slot regions at the most slots the rule gives this shape
 // scratch_is_zero: the slot regions hold zeros (a reduce leaves them so); defer: the caller reduces a batch of layers later
 // (wgrad_reduce_batch) and `ws` stays untouched until then
@@ -185,7 +186,7 @@ int mdcn_forward_packed_run(const float* x, const float* off, long long off_bs, 
                             long long msk_bs, int mask_logit, const float* wp, const float* b, float* out,
                             int N, int C, int H, int W, int Cout, int dg, int act, hipStream_t st, int wdiv = 1,
                             long long w_gs = 0, int b_gs = 0, PackLayout layout = PackLayout::INTERLEAVED);
-int mdcn_fwd_variant();      // DVSR_DCN_FWD, read once: 3 split (default), 0 dma, 2 reg
+int mdcn_fwd_variant();      // DVSR_DCN_FWD: 3 split (default), 0 dma, 2 reg
 int mdcn_pack_floats();      // fp32-sized slots per (64-cout block, 8-channel chunk) of a PackLayout::DCN_SPLIT pack
 PackLayout mdcn_pack_layout(int W);   // PackEntry::layout of a DCN weight pack for images of width W
 int pack_weights_dcn3_run(const PackTable& t, hipStream_t st);   // mdcn_split.hip: PackLayout::DCN_SPLIT entries

@@ -1012,12 +1012,8 @@ int mdcn_backward_run(const float* x, const float* off, long long off_bs, const 
   float* col = (float*)ws;
   void* ws2 = (char*)ws + (size_t)N * C * 9 * P * sizeof(float);
   const size_t ws2_bytes = ws_bytes - (size_t)N * C * 9 * P * sizeof(float);
-  static int use_fused = -1;  // DVSR_DCN_BWD=unfused: the three-kernel path for every shape (A/B aid)
-  if (use_fused < 0) {
-    const char* v = getenv("DVSR_DCN_BWD");
-    use_fused = (v && v[0] == 'u') ? 0 : 1;
-  }
-  if (use_fused && a.cpg % 8 == 0 && stride == 1 && pad == 1 && dil == 1 && Cout % 64 == 0 && Cout <= 128) {
+  const int ab_path = sw(Sw::DCN_BWD);   // A/B aid: 1 (unfused) the three-kernel path, 2 (fp32) the fp32-MFMA contractions, for every shape
+  if (ab_path != 1 && a.cpg % 8 == 0 && stride == 1 && pad == 1 && dil == 1 && Cout % 64 == 0 && Cout <= 128) {
     constexpr int HALO = 4, XPX = (8 + 2 + 2 * HALO) * (32 + 2 + 2 * HALO);
     DcnF f;
     f.x = x; f.off = off; f.msk = msk; f.w = w; f.gout = gout; f.gx = gx; f.goff = goff; f.gmsk = gmsk;
@@ -1037,9 +1033,7 @@ int mdcn_backward_run(const float* x, const float* off, long long off_bs, const 
       const int nsets = w_gs ? ceil_div(N, f.wdiv) : 1;
       DVSR_REQUIRE(nsets <= std::max(groups, 1), DVSR_ERR_INVALID, "mdcn_backward: %d weight sets for %d groups", nsets, groups);
       f.vec = (W % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)gout & 15) == 0) ? 1 : 0;
-      // DVSR_DCN_BWD=fp32: the fp32-MFMA contractions for every shape (A/B aid; read once per process)
-      static const bool split_on = [] { const char* v = getenv("DVSR_DCN_BWD"); return !(v && v[0] == 'f'); }();
-      split = split_on && f.vec && Cout == 64;
+      split = ab_path != 2 && f.vec && Cout == 64;
       if (split) {
         const size_t total = (size_t)nsets * (C / 8) * (3 * 4 * 64 * 8);
         hipLaunchKernelGGL(mdcn_bwd_wt3_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, st, w, w_gs,

@@ -49,14 +49,7 @@
 
 namespace dvsr {
 
-int mdcn_fwd_variant() {
-  static const int variant = [] {
-    const char* v = getenv("DVSR_DCN_FWD");
-    if (!v || !v[0] || v[0] == 's') return 3;
-    return v[0] == 'r' ? 2 : 0;   // (the LDS-column-tile kernel, 'lds', was retired in round 6)
-  }();
-  return variant;
-}
+int mdcn_fwd_variant() { return sw(Sw::DCN_FWD); }
 int mdcn_pack_floats() { return 6912; }   // 9 taps x 3 pieces x 64 couts x 8 channels bf16 (the fp32 pack needs 4608)
 PackLayout mdcn_pack_layout(int W) { return (mdcn_fwd_variant() == 3 && W % 4 == 0) ? PackLayout::DCN_SPLIT : PackLayout::INTERLEAVED; }
 

@@ -734,9 +734,7 @@ int upsample_bilinear_fwd(const float* x, float* y, size_t planes, int H, int W,
                "upsample_bilinear_fwd: bad argument");
   const size_t nout = planes * H * W * S * S;
   if (S == 2 && W % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)x & 15) == 0 && nout < (1ull << 32)) {
-    // DVSR_UP2=4: four input columns per thread (the round-1 kernel; A/B aid, read once per process)
-    static const bool four = [] { const char* v = getenv("DVSR_UP2"); return v && v[0] == '4'; }();
-    if (!four) {
+    if (!sw(Sw::UP2)) {   // (=4: four input columns per thread, the round-1 kernel)
       LAUNCH(upsample2x_fwd2_kernel, planes * H * (W / 2), st, x, y, (unsigned)planes, H, W, mul);
       return check_launch("upsample2x_fwd2_kernel");
     }
@@ -819,8 +817,7 @@ int tsa_gate_fwd(const float* emb, const float* emb_ref, const float* aligned, f
   DVSR_REQUIRE(emb && emb_ref && aligned && cor && gated && B > 0 && N > 0 && C > 0 && HW > 0,
                DVSR_ERR_INVALID, "tsa_gate_fwd: bad argument");
   const bool al16 = (((uintptr_t)emb | (uintptr_t)emb_ref | (uintptr_t)aligned | (uintptr_t)cor | (uintptr_t)gated) & 15) == 0;
-  static int vsel = -1;
-  if (vsel < 0) { const char* v = getenv("DVSR_TSA_V"); vsel = v ? atoi(v) : 2; }  // 2 measured best: 54.9 (scalar) / 45.1 (x2) / 47.5 us (x4)
+  const int vsel = sw(Sw::TSA_V);  // 2 measured best: 54.9 (scalar) / 45.1 (x2) / 47.5 us (x4)
   if (HW % 4 == 0 && al16 && vsel == 4) {
     LAUNCH(tsa_gate_fwd_vec_kernel<4>, (size_t)B * N * HW / 4, st, emb, emb_ref, aligned, cor, gated, B, N, C, HW);
     return check_launch("tsa_gate_fwd_vec_kernel");

@@ -77,7 +77,7 @@ static int probe_side_overlap(hipStream_t st, hipStream_t side) {
 // launch stream's queue unless everything is on one), cached per (device, launch stream).  nullptr: none overlaps -- the
 // caller keeps its weight gradients on `st`.  *known = false: the probe could not run (stream capture): candidate 0, unprobed.
 hipStream_t side_stream_for(hipStream_t st, bool* known) {
-  static const bool probe_on = [] { const char* v = getenv("DVSR_BWD_PROBE"); return !(v && v[0] == '0'); }();
+  const bool probe_on = sw(Sw::BWD_PROBE);
   if (known) *known = probe_on;
   if (!probe_on) return shared_side_stream();
   // (a NEGATIVE answer is not kept for ever: the stream -> hardware-queue mapping moves as the process creates streams, and a

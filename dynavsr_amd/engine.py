@@ -14,16 +14,11 @@ import torch
 from . import _lib as L
 
 _plans = {}
-# Environment switches the native plan builder reads EVERY TIME it builds a plan (conv2_choose, Builder::conv, build_backward,
-# dvsr_*_plan_create): they are part of the plan-cache key, so a plan built under one setting is never handed out under another.
-_GEOMETRY_ENV = ("DVSR_CONV_WINO", "DVSR_CONV_WINO3", "DVSR_CONV_WINO5", "DVSR_CONV_V1", "DVSR_EST_SPLIT", "DVSR_EST_SPLIT2", "DVSR_FUSE_ACT_BWD",
-                 "DVSR_BWD_STREAMS", "DVSR_PCD_HOIST")
-# ... and the ones the native side reads ONCE PER PROCESS (function-local statics): changing them after the first plan has no
-# effect, so they are deliberately NOT in the key -- set them before the first call (the A/B tools run one process per value).
-_PROCESS_ENV = ("DVSR_CONV_LDS", "DVSR_CONV_LAST_MFMA", "DVSR_SPLIT_TH8_FROM", "DVSR_WGRAD_SPLIT3",
-                "DVSR_WGRAD_WIDE", "DVSR_WGRAD_S3V", "DVSR_WGRAD_S3_KYS_BELOW", "DVSR_WGRAD_S3_WGS", "DVSR_WGRAD_S3W", "DVSR_DCN_FWD", "DVSR_DCN_BWD",
-                "DVSR_EST_FUSE_PAD", "DVSR_FUSE_RES_BWD", "DVSR_BWD_FORK_EVERY", "DVSR_BWD_PROBE", "DVSR_TSA_DUAL", "DVSR_TSA_V",
-                "DVSR_DEGRADE_GENERIC", "DVSR_UP2")
+# The native library's own table (csrc/switches.h, L.switch_names) says which DVSR_* switches it reads when; it is asked at the
+# first plan build, never at import.  BUILD switches are read EVERY TIME a plan is built: they are part of the plan-cache key, so a
+# plan built under one setting is never handed out under another.  PROCESS switches are read once and kept: changing them after
+# the first plan has no effect, so they are deliberately NOT in the key -- set them before the first call (the A/B tools run one
+# process per value).
 _process_env_seen = None   # their values when the first plan of the process was built
 
 
@@ -33,11 +28,12 @@ def _check_process_env():
     import os
     import warnings
     global _process_env_seen
-    now = tuple(os.environ.get(k) for k in _PROCESS_ENV)
+    names = L.switch_names(L.SW_PROCESS)
+    now = tuple(os.environ.get(k) for k in names)
     if _process_env_seen is None:
         _process_env_seen = now
         return
-    for k, a, b in zip(_PROCESS_ENV, _process_env_seen, now):
+    for k, a, b in zip(names, _process_env_seen, now):
         if a != b:
             warnings.warn("dynavsr_amd: %s=%r now, but the native library read %r when the first plan of this process was built "
                           "and keeps that value (switches of this kind are read once per process: set them before the first "
@@ -53,7 +49,7 @@ _WORK_KEYS = ("fwd_algorithmic", "fwd_executed", "bwd_algorithmic", "bwd_execute
 
 def _env_key():
     import os
-    return tuple(os.environ.get(k) for k in _GEOMETRY_ENV)
+    return tuple(os.environ.get(k) for k in L.switch_names(L.SW_BUILD))
 
 
 class Plan:

@@ -706,6 +706,22 @@ int dvsr_conv2d_wgrad_split3(const dvsr_conv2d_desc* d, const float* gy, float* 
 int dvsr_conv2d_wgrad_geometry(const dvsr_conv2d_desc* d, int mode, int groups, int geo[8]);
 size_t dvsr_conv2d_wgrad_workspace_bytes(const dvsr_conv2d_desc* d, int groups);
 
+/* ---- The DVSR_* environment switches (A/B aids and kill-switches; INTEGRATION.md lists them) ----------------
+ * One table in the library states every switch's name, scope, parser and default; these queries read it and need no device.
+ * Scope = when the library reads the variable: */
+#define DVSR_SW_BUILD 0   /* every time a plan is built or an op-level entry chooses a geometry: part of a plan's identity */
+#define DVSR_SW_PROCESS 1 /* at the switch's own first use, then kept: set it before the first call, one process per value */
+#define DVSR_SW_CALL 2    /* on every call */
+#define DVSR_SW_DEBUG 3   /* on every call, and consumed by the -DDVSR_CONV_TRACE build only */
+int dvsr_switch_count(void);
+/* Row i in [0, count): the variable's name, its scope, its value when unset and one line of documentation (static strings;
+ * any pointer may be NULL). */
+int dvsr_switch_info(int i, const char** name, int* scope, int* dflt, const char** doc);
+/* What row i's parser makes of `text` (NULL: the variable is unset).  Does not touch the environment. */
+int dvsr_switch_parse(int i, const char* text, int* value);
+/* What the library itself takes switch i for now, under its scope (a PROCESS switch: this is a first use like any other). */
+int dvsr_switch_value(int i, int* value);
+
 /* ---- TOFlow backbone ops (codes/models/archs/TOF_arch.py:25-140, arch_util.py:55-79) --------
  * The convolutions of SpyNet (7x7) and of the TOFlow head (9x9, 1x1) go through dvsr_conv2d_forward / _backward
  * (ks = 7, 9, 1); the ops below are the rest of the graph.  All fp32 NCHW, HBM-bound streaming kernels.
