@@ -179,6 +179,7 @@ def _declare(lib):
         "dvsr_sgd_step": (I, [POINTER(c_void_p)] * 2 + [POINTER(LL), I, F, F, P]),
         "dvsr_replicate_tensors": (I, [POINTER(c_void_p)] * 2 + [POINTER(LL), I, I, P]),
         "dvsr_degrade_apply": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),
+        "dvsr_frame_degrade": (I, [P, POINTER(FrameDesc), P, I, I, P, LL, LL, I, P]),
         "dvsr_frame_metrics_workspace_bytes": (c_size_t, [I, I, I]),
         "dvsr_frame_metrics": (I, [P, P, I, I, I, F, F, P, P, P, c_size_t, P]),
         "dvsr_charbonnier_workspace_bytes": (c_size_t, []),

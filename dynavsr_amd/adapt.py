@@ -23,9 +23,9 @@ import torch.nn.functional as F
 from . import engine, hipops, optim
 # the video front and back end (video.py): what the loops below use, and every public name that used to live here
 from .video import (MAX_IMAGE_BYTES, backbone_input, choose_tile, evaluate_frames, scene_bounds, score_summary,  # noqa: F401
-                    stream_schedule, stream_slots, super_resolve_frames, super_resolve_video, tile_footprint, tile_origins,
+                    degrade_frames, stream_schedule, stream_slots, super_resolve_frames, super_resolve_video, tile_footprint, tile_origins,
                     video_windows, _check_scores, _finish_frame, _frame_format, _frame_scoring, _ingest_cache, _resolve_cuts,
-                    _side_streams)
+                    _side_streams, _SCORES_LATER, _degraded_evaluation, _without_device_queries)
 
 
 def make_inner_optimizer(opt, netG, netE):
@@ -766,36 +766,11 @@ def adapt_multiple(opt):
     raise ValueError("adapt_multiple: network_G.which_model_G=%r (EDVR, TOF or DUF)" % (which,))
 
 
-def adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, frames, padding='new_info', *, layout=None,
-                 out=None, pad_mode='reflect', multiple=None, matrix='bt601', yuv_range='limited', cuts=None,
-                 cut_threshold=10.0, out_size=None, gt=None, gt_layout=None, score='rgb', crop_border=0, scores=None,
-                 baseline_scores=None, losses=None, baseline=True, overlap=True, frames_per_batch=1):
-    """Test-time adaptation of a decoded VIDEO (test_dynavsr.py:197-283 without the caller cutting, cropping or converting
-    clips): for every frame, in order, yields (baseline frame | None, adapted frame) -- the un-adapted network's output and the
-    output of the copies adapted on that frame's window, both in the format super_resolve_frames would yield for the same
-    `layout` / `out` / `out_size`.
-
-    Front end: `frames`, `layout`, `matrix`, `yuv_range` as in super_resolve_frames -- uint8 RGB / BGR, every YCbCr layout at
-    8 / 10 / 12 bits, float planar, CPU or GPU, of any size.  Every frame goes through frames.ingest once, on the device, padded
-    at the bottom and right (`pad_mode`) to a multiple of `multiple` (None: M = adapt_multiple(opt); a caller's value must be
-    a multiple of M); the last 2 * nframes ingested frames are kept.  The windows are video_windows(T, nframes, padding, cuts)
-    (`cuts` = 'auto': frames.detect_cuts), the clips torch.stack of the ingested frames.
-    Middle: adapt_video(clips, overlap, frames_per_batch, region=(h, w), baseline=baseline), unchanged otherwise.  The padded
-    band holds copies of real pixels, so the objective counts the frame's own h x w alone (adapt_frame's `region`; left out
-    when the frame needed no padding).  baseline=False skips the un-adapted forward -- a third of a frame's device time -- and
-    yields None in its place.
-    Back end: the SR frame's s h x s w crop through frames.resize (`out_size`) and frames.emit, on the caller's stream.  With
-    `gt` (a video of T frames of the output's size) row i of `scores` becomes [mse, ssim] of frames.score(adapted frame i,
-    gt[i]) and row i of `baseline_scores` (optional; needs baseline=True) that of the baseline frame, with the argument rules of
-    super_resolve_frames (float64 [T, 2] GPU tensors; score_summary reads them).  `losses`: an optional float32
-    [T, train.maml.adapt_iter] GPU tensor; row i receives frame i's per-step losses without a host synchronisation.
-
-    A yielded pair stays valid until the generator is advanced 2 * max(1, frames_per_batch) times: where nothing is cropped,
-    resampled or converted (float output of an unpadded frame) the pair is adapt_video's own, which holds its rule; every other
-    pair is a tensor of its own.  Frames and results are ordered against the caller's current stream.
-    Not provided: train.use_real (the reference reads ready-made SLR images from disk there); `tile` and `flip_test`; frames
-    whose EDVR plan reaches the 4 GiB image limit (ValueError); adapting once per scene; chroma-only adaptation.
-    Arguments are checked before the first GPU call (ValueError)."""
+def _adapt_arguments(opt, model, frames, padding, layout, out, pad_mode, multiple, matrix, yuv_range, cuts, cut_threshold, out_size,
+                     gt, gt_layout, score, crop_border, scores, baseline_scores, losses, baseline):
+    """The first stage of adapt_frames: its arguments checked and resolved into one record.  No GPU call, except for what
+    cuts='auto' (frames.detect_cuts) asks for, behind every other check."""
+    from types import SimpleNamespace
     from . import frames as fio
     who = "adapt_frames"
     if opt['train']['use_real']:
@@ -842,6 +817,46 @@ def adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, f
                              "image with 32-bit offsets (< 2^32 bytes); adaptation in tiles is not provided" % (Hp, Wp, need))
     cuts = _resolve_cuts(who, cuts, T, n, padding, frames, lay, cut_threshold)
     windows, _ = video_windows(T, n, padding, cuts)
+    return SimpleNamespace(lay=lay, h=h, w=w, out_fmt=out_fmt, Hp=Hp, Wp=Wp, out_size=out_size, mult=mult, sr_scale=sr_scale,
+                           score_into=score_into, region=region, windows=windows, cuts=cuts, n=n)
+
+
+def adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, frames, padding='new_info', *, layout=None,
+                 out=None, pad_mode='reflect', multiple=None, matrix='bt601', yuv_range='limited', cuts=None,
+                 cut_threshold=10.0, out_size=None, gt=None, gt_layout=None, score='rgb', crop_border=0, scores=None,
+                 baseline_scores=None, losses=None, baseline=True, overlap=True, frames_per_batch=1):
+    """Test-time adaptation of a decoded VIDEO (test_dynavsr.py:197-283 without the caller cutting, cropping or converting
+    clips): for every frame, in order, yields (baseline frame | None, adapted frame) -- the un-adapted network's output and the
+    output of the copies adapted on that frame's window, both in the format super_resolve_frames would yield for the same
+    `layout` / `out` / `out_size`.
+
+    Front end: `frames`, `layout`, `matrix`, `yuv_range` as in super_resolve_frames -- uint8 RGB / BGR, every YCbCr layout at
+    8 / 10 / 12 bits, float planar, CPU or GPU, of any size.  Every frame goes through frames.ingest once, on the device, padded
+    at the bottom and right (`pad_mode`) to a multiple of `multiple` (None: M = adapt_multiple(opt); a caller's value must be
+    a multiple of M); the last 2 * nframes ingested frames are kept.  The windows are video_windows(T, nframes, padding, cuts)
+    (`cuts` = 'auto': frames.detect_cuts), the clips torch.stack of the ingested frames.
+    Middle: adapt_video(clips, overlap, frames_per_batch, region=(h, w), baseline=baseline), unchanged otherwise.  The padded
+    band holds copies of real pixels, so the objective counts the frame's own h x w alone (adapt_frame's `region`; left out
+    when the frame needed no padding).  baseline=False skips the un-adapted forward -- a third of a frame's device time -- and
+    yields None in its place.
+    Back end: the SR frame's s h x s w crop through frames.resize (`out_size`) and frames.emit, on the caller's stream.  With
+    `gt` (a video of T frames of the output's size) row i of `scores` becomes [mse, ssim] of frames.score(adapted frame i,
+    gt[i]) and row i of `baseline_scores` (optional; needs baseline=True) that of the baseline frame, with the argument rules of
+    super_resolve_frames (float64 [T, 2] GPU tensors; score_summary reads them).  `losses`: an optional float32
+    [T, train.maml.adapt_iter] GPU tensor; row i receives frame i's per-step losses without a host synchronisation.
+
+    A yielded pair stays valid until the generator is advanced 2 * max(1, frames_per_batch) times: where nothing is cropped,
+    resampled or converted (float output of an unpadded frame) the pair is adapt_video's own, which holds its rule; every other
+    pair is a tensor of its own.  Frames and results are ordered against the caller's current stream.
+    Not provided: train.use_real (the reference reads ready-made SLR images from disk there); `tile` and `flip_test`; frames
+    whose EDVR plan reaches the 4 GiB image limit (ValueError); adapting once per scene; chroma-only adaptation.
+    Arguments are checked before the first GPU call (ValueError)."""
+    from . import frames as fio
+    who = "adapt_frames"
+    a = _adapt_arguments(opt, model, frames, padding, layout, out, pad_mode, multiple, matrix, yuv_range, cuts, cut_threshold,
+                         out_size, gt, gt_layout, score, crop_border, scores, baseline_scores, losses, baseline)
+    lay, h, w, out_fmt, Hp, Wp, out_size, mult = a.lay, a.h, a.w, a.out_fmt, a.Hp, a.Wp, a.out_size, a.mult
+    sr_scale, score_into, region, windows, n = a.sr_scale, a.score_into, a.region, a.windows, a.n
     ingested = _ingest_cache(lambda j: fio.ingest(frames[j], lay, mult, pad_mode, matrix=matrix, yuv_range=yuv_range), 2 * n)
 
     def clips():
@@ -858,3 +873,62 @@ def adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, f
             losses[i].copy_(torch.stack([l_.reshape(()) for l_ in r['losses']]))
         yield (finished(i, base, baseline_scores) if base is not None else None,
                finished(i, r['sr'], scores if score_into is not None else None))
+
+
+def _defaults_of(f):
+    import inspect
+    return {k: p.default for k, p in inspect.signature(f).parameters.items() if p.default is not inspect.Parameter.empty}
+
+
+_ADAPT_FRAMES_DEFAULTS = _defaults_of(adapt_frames)       # what evaluate_degraded checks ahead of the call, beside its own arguments
+
+
+def evaluate_degraded(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, hr, degradation, *, hr_layout=None,
+                      quantise=True, **kw):
+    """"This ground-truth video, this blur: what does adaptation buy?" in one call -- the table test_dynavsr.py prints with
+    `degradation_mode: set`.  The LR video is degrade_frames(hr, degradation, layout=hr_layout, quantise=quantise, matrix=,
+    yuv_range=), the ground truth the top-left Hc x Wc view of every HR frame (frames.tile_view, nothing copied); the generator
+    adapt_frames(opt, <the five wrappers>, lr, gt=gt, gt_layout=hr_layout, scores=, baseline_scores=, **kw) is drained and
+    {'baseline': score_summary(baseline_scores, nframes, cuts, peak), 'adapted': score_summary(scores, ...), 'gain_db': the
+    adapted mean PSNR minus the baseline's (the 'mean' entries of the two summaries), 'scores', 'baseline_scores'} returned, the
+    two float64 [T, 2] GPU tensors allocated here unless passed.  `kw` is adapt_frames' (padding, out, cuts, score, crop_border,
+    overlap, frames_per_batch, ...) and `peak` (None: 255, or 2^d - 1 for a 10- / 12-bit output); cuts='auto' is resolved on the
+    LR video, the way evaluate_frames does it, so that the summaries have the scenes the windows had.
+    ValueError before the first GPU call: degradation.scale != opt['scale']; scale * h_lr != Hc (an even shifted kernel); per-frame
+    kernels of another count than the video; an HR frame not larger than the kernel's pad; `gt`, `gt_layout`, `layout` or
+    baseline=False in kw; and what adapt_frames refuses for these arguments."""
+    from . import frames as fio
+    who = "evaluate_degraded"
+    kw = dict(kw)
+    peak = kw.pop('peak', None)
+    lay, shape, gt = _degraded_evaluation(who, opt, hr, degradation, hr_layout, kw)
+    if not kw.get('baseline', True):
+        raise ValueError("evaluate_degraded: the gain is measured against the baseline frames (baseline=True)")
+    T = shape[0]
+    stand_in = torch.empty(shape, dtype=torch.float32, device='meta')       # the LR video's size and kind, for the checks alone
+    check = _without_device_queries(kw)
+    for name in ('scores', 'baseline_scores'):
+        check[name] = check[name] if check.get(name) is not None else _SCORES_LATER
+    unknown = sorted(set(check) - set(_ADAPT_FRAMES_DEFAULTS))
+    if unknown:
+        raise TypeError("evaluate_degraded: adapt_frames takes no %s" % ', '.join(unknown))
+    b = dict(_ADAPT_FRAMES_DEFAULTS, gt=gt, gt_layout=lay, **check)
+    _adapt_arguments(opt, model, stand_in, *[b[k] for k in (
+        'padding', 'layout', 'out', 'pad_mode', 'multiple', 'matrix', 'yuv_range', 'cuts', 'cut_threshold', 'out_size', 'gt',
+        'gt_layout', 'score', 'crop_border', 'scores', 'baseline_scores', 'losses', 'baseline')])
+    lr = degrade_frames(hr, degradation, layout=lay, quantise=quantise, matrix=kw.get('matrix', 'bt601'),
+                        yuv_range=kw.get('yuv_range', 'limited'))
+    if isinstance(kw.get('cuts'), str) and kw['cuts'] == 'auto':
+        kw['cuts'] = fio.detect_cuts(lr, 'chw', threshold=kw.get('cut_threshold', 10.0))
+    for name in ('scores', 'baseline_scores'):
+        if kw.get(name) is None:
+            kw[name] = torch.zeros((T, 2), dtype=torch.float64, device=lr.device)
+    for _ in adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, lr, gt=gt, gt_layout=lay, **kw):
+        pass
+    if peak is None:
+        o = kw.get('out')
+        peak = 2 ** fio.layout_depth(o) - 1 if fio.is_yuv(o) else 255
+    n = int(opt['network_G']['nframes'])
+    base, adapted = (score_summary(kw[name], n, kw.get('cuts'), peak) for name in ('baseline_scores', 'scores'))
+    return {'baseline': base, 'adapted': adapted, 'gain_db': adapted['mean']['psnr'] - base['mean']['psnr'],
+            'scores': kw['scores'], 'baseline_scores': kw['baseline_scores']}

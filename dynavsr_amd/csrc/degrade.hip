@@ -9,6 +9,13 @@
 // gathered into LDS through the reflection index map (no padded copy in HBM), the K x K weights next to it;
 // each thread then walks the taps in row-major order with fp32 FMAs.  HBM-bound by construction: every input
 // sample is read ~once (plus the tile halo), every output written once.
+//
+// dvsr_frame_degrade is the same pair of kernels on ONE ground-truth frame in the form a decoder delivers it (fp32 planes or
+// interleaved bytes at any address and pitch, cropped to a multiple of the stride) into a destination given by stride: the
+// kernels are templates over a source policy and differ in their staging loads alone, so the bits are dvsr_degrade_apply's on
+// the ingested frame without that fp32 frame ever being written.
+#include <climits>
+#include <cstdint>
 #include <cstdlib>
 
 #include "common.h"
@@ -25,22 +32,67 @@ __device__ __forceinline__ int reflect_index(int i, int n) {  // ReflectionPad2d
   return i >= n ? 2 * n - 2 - i : i;
 }
 
-__global__ __launch_bounds__(256) void degrade_kernel(const float* __restrict__ x, const float* __restrict__ kern,
-                                                      float* __restrict__ y, int N, int C, int H, int W, int K, int S,
-                                                      int Ho, int Wo, int kern_per_frame, int kern_frames,
+// Where the staging loops of the two kernels read from.  A policy gives row(plane, y, lut), the row y of plane `plane`
+// (blockIdx.z), col(x), the offset of column x inside a row, and Row::operator[](offset), the sample as fp32; LUT is the number
+// of floats of LDS it wants behind the kernel's own, filled by fill(lut, tid, threads) ahead of a barrier.  Everything behind
+// the staging -- the tap loops, the quantiser -- sees fp32 in LDS and is the same code for every source.
+struct SrcPlanarF32 {  // fp32 planes by stride: the [N,C,H,W] clip of dvsr_degrade_apply, a DVSR_FRAME_F32_CHW frame
+  static constexpr int LUT = 0;
+  const float* base;
+  long long row_stride, plane_stride;  // floats
+  struct Row {
+    const float* p;
+    __device__ __forceinline__ float operator[](int off) const { return p[off]; }
+  };
+  __device__ __forceinline__ void fill(float*, int, int) const {}
+  __device__ __forceinline__ Row row(int plane, int y, const float*) const {
+    return Row{base + plane * plane_stride + y * row_stride};
+  }
+  __device__ __forceinline__ int col(int x) const { return x; }
+};
+
+// 8-bit interleaved RGB / BGR by stride and channel: v / 255.0f, dvsr_frame_ingest's true division -- made once per value and
+// workgroup into a 256-entry table in LDS.  With a division per staged sample a uint8 720 x 1280 frame at scale 4, K = 27 took
+// 34.8 us against 30.9 us with the table, a 2160 x 3840 frame 194.4 against 175.7 (profiles/r19_frame_degrade.txt).  The three
+// workgroups of a tile (one per channel) each fetch its bytes: the second and third find them in the caches.
+struct SrcBytesHWC {
+  static constexpr int LUT = 256;
+  const unsigned char* base;
+  long long row_stride;  // bytes
+  int pixel_stride, swap;
+  struct Row {
+    const unsigned char* p;
+    const float* lut;
+    __device__ __forceinline__ float operator[](int off) const { return lut[p[off]]; }
+  };
+  __device__ __forceinline__ void fill(float* lut, int tid, int threads) const {
+    for (int i = tid; i < LUT; i += threads) lut[i] = (float)i / 255.0f;
+  }
+  __device__ __forceinline__ Row row(int plane, int y, const float* lut) const {
+    return Row{base + y * row_stride + (swap ? 2 - plane : plane), lut};
+  }
+  __device__ __forceinline__ int col(int x) const { return x * pixel_stride; }
+};
+
+template <class Src>
+__global__ __launch_bounds__(256) void degrade_kernel(Src src, const float* __restrict__ kern, float* __restrict__ y,
+                                                      long long y_row, long long y_plane, int N, int C, int H, int W, int K,
+                                                      int S, int Ho, int Wo, int kern_per_frame, int kern_frames,
                                                       int kern_offset, int quantise) {
   extern __shared__ float smem[];
   const int P = (DG_T - 1) * S + K;  // input patch edge
   float* s_in = smem;                // [P][P + 1]
   float* s_k = smem + P * (P + 1);   // [K][K]
+  float* s_lut = s_k + K * K;        // [Src::LUT]
   const int plane = blockIdx.z, n = plane / C;
   const int oy0 = blockIdx.y * DG_T, ox0 = blockIdx.x * DG_T;
   const int pad = K / 2;
-  const float* xp = x + (size_t)plane * H * W;
   // frame n uses kernel (n + kern_offset) mod kern_frames when there is one kernel per frame
   // (random_kernel_generator.py:105-113: offset -1 for DUF's two extra frames), else kernel 0
   const float* kp = kern + (size_t)(kern_per_frame ? ((n + kern_offset) % kern_frames + kern_frames) % kern_frames : 0) * K * K;
   for (int i = threadIdx.x; i < K * K; i += 256) s_k[i] = kp[i];
+  src.fill(s_lut, threadIdx.x, 256);
+  if (Src::LUT) __syncthreads();
   const int iy0 = oy0 * S - pad, ix0 = ox0 * S - pad;
   {  // a wave per patch row, two passes of 64 columns (P <= 93); four rows = 8 loads in flight per lane
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -49,16 +101,16 @@ __global__ __launch_bounds__(256) void degrade_kernel(const float* __restrict__ 
     for (int p = 0; p < 2; ++p) {
       const int gx = reflect_index(ix0 + lane + 64 * p, W);
       // rows / columns only needed by outputs beyond the image edge may reflect out of range: clamp (never used)
-      cx[p] = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+      cx[p] = src.col(gx < 0 ? 0 : (gx >= W ? W - 1 : gx));
     }
     for (int r0 = wave * 4; r0 < P; r0 += 16) {
       float v[4][2];
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int gy = reflect_index(iy0 + r0 + rr, H);
-        const int cy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy);
+        const typename Src::Row xr = src.row(plane, gy < 0 ? 0 : (gy >= H ? H - 1 : gy), s_lut);
 #pragma unroll
-        for (int p = 0; p < 2; ++p) v[rr][p] = xp[(size_t)cy * W + cx[p]];
+        for (int p = 0; p < 2; ++p) v[rr][p] = xr[cx[p]];
       }
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
@@ -80,7 +132,7 @@ __global__ __launch_bounds__(256) void degrade_kernel(const float* __restrict__ 
     row += P + 1;
   }
   if (quantise) acc = rintf(fminf(fmaxf(acc * 255.f, 0.f), 255.f)) / 255.f;  // mul(255).clamp(0,255).round().div(255)
-  y[((size_t)plane * Ho + oy) * Wo + ox] = acc;
+  y[plane * y_plane + oy * y_row + ox] = acc;
 }
 
 // Register-tiled variant for the (stride, taps-per-phase) pairs the datasets produce (21-tap Gaussian: K = 27 at
@@ -90,10 +142,10 @@ __global__ __launch_bounds__(256) void degrade_kernel(const float* __restrict__ 
 // inside a plane the operation is a dense J x J correlation with unit stride and a thread can own FOUR
 // consecutive outputs of a row: per (phase, jy) it reads 4 + J - 1 inputs as aligned 16-byte vectors and the J
 // weights of that row as broadcast vectors -- 5 LDS instructions for 4 J FMAs at J = 7.
-template <int S, int J>
-__global__ __launch_bounds__(128) void degrade_tiled_kernel(const float* __restrict__ x, const float* __restrict__ kern,
-                                                            float* __restrict__ y, int N, int C, int H, int W, int K,
-                                                            int Ho, int Wo, int kern_per_frame, int kern_frames,
+template <int S, int J, class Src>
+__global__ __launch_bounds__(128) void degrade_tiled_kernel(Src src, const float* __restrict__ kern, float* __restrict__ y,
+                                                            long long y_row, long long y_plane, int N, int C, int H, int W,
+                                                            int K, int Ho, int Wo, int kern_per_frame, int kern_frames,
                                                             int kern_offset, int quantise) {
   constexpr int TW = 32, TH = 16;
   constexpr int NV = (4 + J - 1 + 3) / 4;            // float4 input vectors per thread and row
@@ -101,11 +153,11 @@ __global__ __launch_bounds__(128) void degrade_tiled_kernel(const float* __restr
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* s_in = smem;                   // [S*S][QH][QW], zero outside the patch
   float* s_k = smem + S * S * QH * QW;  // [S*S][J][JP], zero where the tap does not exist
+  float* s_lut = s_k + S * S * J * JP;  // [Src::LUT]
   const int PH = (TH - 1) * S + K, PW = (TW - 1) * S + K;
   const int plane = blockIdx.z, n = plane / C;
   const int oy0 = blockIdx.y * TH, ox0 = blockIdx.x * TW;
   const int pad = K / 2;
-  const float* xp = x + (size_t)plane * H * W;
   const float* kp = kern + (size_t)(kern_per_frame ? ((n + kern_offset) % kern_frames + kern_frames) % kern_frames : 0) * K * K;
   for (int i = threadIdx.x; i < S * S * J * JP; i += 128) {
     const int jx = i % JP, jy = (i / JP) % J, ph = i / (JP * J);
@@ -113,6 +165,7 @@ __global__ __launch_bounds__(128) void degrade_tiled_kernel(const float* __restr
     s_k[i] = (jx < J && ky < K && kx < K) ? kp[ky * K + kx] : 0.f;
   }
   for (int i = threadIdx.x; i < S * S * QH * QW / 4; i += 128) reinterpret_cast<float4*>(s_in)[i] = float4{0.f, 0.f, 0.f, 0.f};
+  src.fill(s_lut, threadIdx.x, 128);
   __syncthreads();
   const int iy0 = oy0 * S - pad, ix0 = ox0 * S - pad;
   // a wave per patch row, 64 consecutive columns per pass (PW <= 157: three passes); sixteen rows = 48 loads are in
@@ -124,7 +177,7 @@ __global__ __launch_bounds__(128) void degrade_tiled_kernel(const float* __restr
     for (int p = 0; p < 3; ++p) {
       const int gx = reflect_index(ix0 + lane + 64 * p, W);
       // rows / columns only needed by outputs beyond the image edge may reflect out of range: clamp (never used)
-      cx[p] = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+      cx[p] = src.col(gx < 0 ? 0 : (gx >= W ? W - 1 : gx));
     }
     constexpr int RB = 16;  // rows per batch: 48 loads in flight per lane
     for (int r0 = wave * RB; r0 < PH; r0 += 2 * RB) {
@@ -132,8 +185,7 @@ __global__ __launch_bounds__(128) void degrade_tiled_kernel(const float* __restr
 #pragma unroll
       for (int rr = 0; rr < RB; ++rr) {
         const int gy = reflect_index(iy0 + r0 + rr, H);
-        const int cy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy);
-        const float* xr = xp + (size_t)cy * W;
+        const typename Src::Row xr = src.row(plane, gy < 0 ? 0 : (gy >= H ? H - 1 : gy), s_lut);
 #pragma unroll
         for (int p = 0; p < 3; ++p) v[rr][p] = xr[cx[p]];
       }
@@ -183,20 +235,57 @@ __global__ __launch_bounds__(128) void degrade_tiled_kernel(const float* __restr
     if (ox >= Wo) continue;
     float v = acc[o];
     if (quantise) v = rintf(fminf(fmaxf(v * 255.f, 0.f), 255.f)) / 255.f;
-    y[((size_t)plane * Ho + oy) * Wo + ox] = v;
+    y[plane * y_plane + oy * y_row + ox] = v;
   }
 }
 
-template <int S, int J>
-static int launch_degrade_tiled(const float* img, const float* kernels, float* out, int N, int C, int H, int W, int K,
-                                int Ho, int Wo, int n_kernels, int kernel_offset, int quantise, hipStream_t st) {
+// what a launch reads and writes, behind the checks: planes of H x W from `src`, [Ho][Wo] planes of `out` by stride
+struct DegradeJob {
+  const float* kernels;
+  float* out;
+  long long out_row, out_plane;  // floats
+  int N, C, H, W, K, scale, Ho, Wo, n_kernels, kernel_offset, quantise;
+};
+
+template <int S, int J, class Src>
+static int launch_degrade_tiled(const Src& src, const DegradeJob& d, hipStream_t st) {
   constexpr int NV = (4 + J - 1 + 3) / 4, QW = 28 + 4 * NV, QH = 16 + J - 1, JP = (J + 3) / 4 * 4;
-  constexpr size_t lds = ((size_t)S * S * QH * QW + (size_t)S * S * J * JP) * sizeof(float);
+  constexpr size_t lds = ((size_t)S * S * QH * QW + (size_t)S * S * J * JP + Src::LUT) * sizeof(float);
   static_assert(lds <= 64 * 1024, "phase planes must fit the default dynamic LDS limit");
-  const dim3 grid(ceil_div(Wo, 32), ceil_div(Ho, 16), N * C);
-  hipLaunchKernelGGL((degrade_tiled_kernel<S, J>), grid, dim3(128), lds, st, img, kernels, out, N, C, H, W, K, Ho, Wo,
-                     n_kernels > 1 ? 1 : 0, n_kernels, kernel_offset, quantise);
+  const dim3 grid(ceil_div(d.Wo, 32), ceil_div(d.Ho, 16), d.N * d.C);
+  hipLaunchKernelGGL((degrade_tiled_kernel<S, J, Src>), grid, dim3(128), lds, st, src, d.kernels, d.out, d.out_row, d.out_plane,
+                     d.N, d.C, d.H, d.W, d.K, d.Ho, d.Wo, d.n_kernels > 1 ? 1 : 0, d.n_kernels, d.kernel_offset, d.quantise);
   return check_launch("degrade_tiled_kernel");
+}
+
+// the one selection rule of dvsr_degrade_apply and dvsr_frame_degrade: the phase-plane kernel for the (stride, taps per phase)
+// pairs it is built for, the generic kernel otherwise and under DVSR_DEGRADE_GENERIC
+template <class Src>
+static int degrade_launch(const char* what, const Src& src, const DegradeJob& d, hipStream_t st) {
+  if (d.N * d.C <= 65535 && !sw(Sw::DEGRADE_GENERIC)) {
+    const int J = ceil_div(d.K, d.scale);
+#define DVSR_DG_CASE(S_, J_) \
+    if (d.scale == S_ && J == J_) return launch_degrade_tiled<S_, J_>(src, d, st);
+    DVSR_DG_CASE(4, 7) DVSR_DG_CASE(2, 13) DVSR_DG_CASE(2, 8) DVSR_DG_CASE(3, 9)
+#undef DVSR_DG_CASE
+  }
+  const int P = (DG_T - 1) * d.scale + d.K;
+  const size_t lds = ((size_t)P * (P + 1) + (size_t)d.K * d.K + Src::LUT) * sizeof(float);
+  const dim3 grid(ceil_div(d.Wo, DG_T), ceil_div(d.Ho, DG_T), d.N * d.C);
+  DVSR_REQUIRE(grid.z <= 65535, DVSR_ERR_UNSUPPORTED, "%s: N*C = %d planes", what, d.N * d.C);
+  hipLaunchKernelGGL(degrade_kernel<Src>, grid, dim3(256), lds, st, src, d.kernels, d.out, d.out_row, d.out_plane, d.N, d.C, d.H,
+                     d.W, d.K, d.scale, d.Ho, d.Wo, d.n_kernels > 1 ? 1 : 0, d.n_kernels, d.kernel_offset, d.quantise);
+  return check_launch("degrade_kernel");
+}
+
+// the limits of the two kernels on an H x W plane, shared by the two entries
+static int degrade_shape_check(const char* what, int H, int W, int K, int scale) {
+  DVSR_REQUIRE(K >= 1 && K <= DG_MAXK && scale >= 1 && scale <= DG_MAXS, DVSR_ERR_UNSUPPORTED,
+               "%s: kernel edge %d (<= %d) / scale %d (<= %d)", what, K, DG_MAXK, scale, DG_MAXS);
+  // ReflectionPad2d's own contract: padding must be smaller than the input
+  DVSR_REQUIRE(K / 2 < H && K / 2 < W, DVSR_ERR_INVALID, "%s: reflection pad %d needs H, W > %d (got %dx%d)", what, K / 2, K / 2,
+               H, W);
+  return DVSR_OK;
 }
 
 }  // namespace dvsr
@@ -209,27 +298,40 @@ extern "C" int dvsr_degrade_apply(const float* img, const float* kernels, float*
   DVSR_REQUIRE(img && kernels && out, DVSR_ERR_INVALID, "degrade_apply: null img/kernels/out");
   DVSR_REQUIRE(N >= 1 && C >= 1 && H >= 1 && W >= 1 && n_kernels >= 1, DVSR_ERR_INVALID,
                "degrade_apply: N=%d C=%d H=%d W=%d n_kernels=%d", N, C, H, W, n_kernels);
-  DVSR_REQUIRE(K >= 1 && K <= DG_MAXK && scale >= 1 && scale <= DG_MAXS, DVSR_ERR_UNSUPPORTED,
-               "degrade_apply: kernel edge %d (<= %d) / scale %d (<= %d)", K, DG_MAXK, scale, DG_MAXS);
-  // ReflectionPad2d's own contract: padding must be smaller than the input
-  DVSR_REQUIRE(K / 2 < H && K / 2 < W, DVSR_ERR_INVALID, "degrade_apply: reflection pad %d needs H, W > %d (got %dx%d)",
-               K / 2, K / 2, H, W);
+  int rc = degrade_shape_check("degrade_apply", H, W, K, scale);
+  if (rc != DVSR_OK) return rc;
   const int pad = K / 2;
   const int Ho = (H + 2 * pad - K) / scale + 1, Wo = (W + 2 * pad - K) / scale + 1;
-  if (N * C <= 65535 && !sw(Sw::DEGRADE_GENERIC)) {
-    const int J = ceil_div(K, scale);
-    hipStream_t st = (hipStream_t)stream;
-#define DVSR_DG_CASE(S_, J_) \
-    if (scale == S_ && J == J_) \
-      return launch_degrade_tiled<S_, J_>(img, kernels, out, N, C, H, W, K, Ho, Wo, n_kernels, kernel_offset, quantise, st);
-    DVSR_DG_CASE(4, 7) DVSR_DG_CASE(2, 13) DVSR_DG_CASE(2, 8) DVSR_DG_CASE(3, 9)
-#undef DVSR_DG_CASE
-  }
-  const int P = (DG_T - 1) * scale + K;
-  const size_t lds = ((size_t)P * (P + 1) + (size_t)K * K) * sizeof(float);
-  const dim3 grid(ceil_div(Wo, DG_T), ceil_div(Ho, DG_T), N * C);
-  DVSR_REQUIRE(grid.z <= 65535, DVSR_ERR_UNSUPPORTED, "degrade_apply: N*C = %d planes", N * C);
-  hipLaunchKernelGGL(degrade_kernel, grid, dim3(256), lds, (hipStream_t)stream, img, kernels, out, N, C, H, W, K, scale,
-                     Ho, Wo, n_kernels > 1 ? 1 : 0, n_kernels, kernel_offset, quantise);
-  return check_launch("degrade_kernel");
+  const DegradeJob d{kernels, out, Wo, (long long)Ho * Wo, N, C, H, W, K, scale, Ho, Wo, n_kernels, kernel_offset, quantise};
+  return degrade_launch("degrade_apply", SrcPlanarF32{img, W, (long long)H * W}, d, (hipStream_t)stream);
+}
+
+extern "C" int dvsr_frame_degrade(const void* src, const dvsr_frame_desc* sd, const float* kernel, int K, int scale,
+                                  float* dst, long long dst_row_stride, long long dst_plane_stride, int quantise,
+                                  dvsr_stream_t stream) {
+  DVSR_REQUIRE(kernel && dst, DVSR_ERR_INVALID, "frame_degrade: null kernel / dst");
+  int rc = frame_desc_check("frame_degrade", src, sd, INT_MAX, INT_MAX, false);
+  if (rc != DVSR_OK) return rc;
+  DVSR_REQUIRE(K >= 1 && K <= DG_MAXK && scale >= 1 && scale <= DG_MAXS, DVSR_ERR_UNSUPPORTED,
+               "frame_degrade: kernel edge %d (<= %d) / scale %d (<= %d)", K, DG_MAXK, scale, DG_MAXS);
+  const int Hc = sd->h - sd->h % scale, Wc = sd->w - sd->w % scale;  // modcrop (data/util.py:302)
+  DVSR_REQUIRE(Hc >= 1 && Wc >= 1, DVSR_ERR_INVALID, "frame_degrade: a %d x %d frame has no multiple of scale %d inside", sd->h,
+               sd->w, scale);
+  rc = degrade_shape_check("frame_degrade", Hc, Wc, K, scale);
+  if (rc != DVSR_OK) return rc;
+  const int pad = K / 2;
+  const int Ho = (Hc + 2 * pad - K) / scale + 1, Wo = (Wc + 2 * pad - K) / scale + 1;
+  DVSR_REQUIRE(dst_row_stride >= Wo && dst_plane_stride >= (long long)(Ho - 1) * dst_row_stride + Wo, DVSR_ERR_INVALID,
+               "frame_degrade: destination row stride %lld / plane stride %lld shorter than a row of %d / a plane of %d rows",
+               dst_row_stride, dst_plane_stride, Wo, Ho);
+  DVSR_REQUIRE(reinterpret_cast<uintptr_t>(dst) % 4 == 0 && reinterpret_cast<uintptr_t>(kernel) % 4 == 0, DVSR_ERR_INVALID,
+               "frame_degrade: misaligned fp32 destination / kernel (4 bytes)");
+  const DegradeJob d{kernel, dst, dst_row_stride, dst_plane_stride, 1, 3, Hc, Wc, K, scale, Ho, Wo, 1, 0, quantise};
+  if (sd->format == DVSR_FRAME_F32_CHW)
+    return degrade_launch("frame_degrade", SrcPlanarF32{static_cast<const float*>(src), sd->row_stride, sd->plane_stride}, d,
+                          (hipStream_t)stream);
+  return degrade_launch("frame_degrade",
+                        SrcBytesHWC{static_cast<const unsigned char*>(src), sd->row_stride, sd->pixel_stride,
+                                    sd->format == DVSR_FRAME_U8_HWC_BGR},
+                        d, (hipStream_t)stream);
 }

@@ -208,7 +208,7 @@ __global__ __launch_bounds__(FIO_X * FIO_Y) void frame_emit_kernel(EmitArgs a) {
 static bool is_u8(int format) { return format == DVSR_FRAME_U8_HWC_RGB || format == DVSR_FRAME_U8_HWC_BGR; }
 
 // the frame on the "any address, any pitch" side, against the h x w it may have at most
-static int frame_desc_check(const char* what, const void* ptr, const dvsr_frame_desc* d, int Ht, int Wt, bool emit) {
+int frame_desc_check(const char* what, const void* ptr, const dvsr_frame_desc* d, int Ht, int Wt, bool emit) {
   DVSR_REQUIRE(ptr && d, DVSR_ERR_INVALID, "%s: null frame / descriptor", what);
   DVSR_REQUIRE(d->format == DVSR_FRAME_F32_CHW || is_u8(d->format), DVSR_ERR_INVALID, "%s: unknown frame format %d", what,
                d->format);

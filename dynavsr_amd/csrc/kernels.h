@@ -241,6 +241,9 @@ hipStream_t side_stream_for(hipStream_t st, bool* known = nullptr);
 int frame_ingest_check(const char* what, const void* src, const dvsr_frame_desc* sd, const float* dst, int Hp, int Wp,
                        int pad_mode);
 int frame_ingest_launch(const void* src, const dvsr_frame_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
+// the descriptor's own part of that check (null, format, 1 <= h <= Ht, 1 <= w <= Wt, strides, fp32 alignment); dvsr_frame_degrade
+// (degrade.hip) reads a source frame through it too
+int frame_desc_check(const char* what, const void* ptr, const dvsr_frame_desc* d, int Ht, int Wt, bool emit);
 
 // frame_yuv.hip: the same pair for a YCbCr 4:2:0, 4:2:2 or 4:4:4 frame of 8, 10 or 12 bits (planes at any address / pitch), on
 // the one form that both public descriptors take inside.  yuv_frame_from checks the descriptor's own part -- null, format,

@@ -49,11 +49,22 @@ class Degradation:
     def kernel_shift(self, kernel):
         """Centre of mass -> kernel centre + half a (scale - parity) pixel, so that the down-sampled image stays
         aligned with the ground truth; zero-padded first so the cubic-spline shift loses nothing."""
+        shift, pad = self._shift_of(kernel)
+        kernel = np.pad(kernel, pad, 'constant')
+        return ndimage.shift(kernel, shift)
+
+    def _shift_of(self, kernel):
+        """(the shift of kernel_shift, the zero padding on every side that goes with it)."""
         com = np.array(ndimage.center_of_mass(kernel))
         want = np.array(kernel.shape) // 2 + 0.5 * (self.scale - (kernel.shape[0] % 2))
         shift = want - com
-        kernel = np.pad(kernel, int(np.ceil(np.max(shift))) + 1, 'constant')
-        return ndimage.shift(kernel, shift)
+        return shift, int(np.ceil(np.max(shift))) + 1
+
+    def shifted_edge(self, index=0):
+        """K, the edge of the shifted kernel (kernel `index` of a [T,K0,K0] set) -- what apply() convolves with and what
+        decides the size of its output -- from kernel_shift's arithmetic, without the spline shift.  Host code."""
+        k = self.kernel if self.kernel.ndim == 2 else self.kernel[index]
+        return int(k.shape[0]) + 2 * self._shift_of(k)[1]
 
     def _shifted_on(self, device):
         """The shifted kernel(s) as a [T,K,K] fp32 device tensor.  The reference redoes the spline shift in every

@@ -74,6 +74,12 @@ PSNR / SSIM against ground truth, RGB or Y (csrc/frame_score.hip: dvsr_frame_sco
 
     score(a, b, layout_a, layout_b, channel='rgb' | 'y', crop_border=k) -> float64 [mse, ssim] on the device, no host sync
     psnr(mse, peak=255)                  -> 20 log10(peak / sqrt(mse)) on the host, inf at 0
+
+A ground-truth frame degraded as it arrives (csrc/degrade.hip: dvsr_frame_degrade):
+
+    degraded_size(h, w, K, scale)        -> (Hc, Wc, h_lr, w_lr): the crop to a multiple of the scale and the LR size; host code
+    degrade(frame, degradation, layout)  -> fp32 [3,h_lr,w_lr] on the GPU: Degradation.apply(.., quantise) of the frame's Hc x Wc
+                                            crop, from the frame's own bytes, one launch
 """
 import ctypes
 import numbers
@@ -345,6 +351,83 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix=
             L.check(L.lib().dvsr_frame_ingest(frame.data_ptr(), ctypes.byref(desc), buf.data_ptr(), Hp, Wb, _PAD[pad_mode],
                                               L.stream()), "dvsr_frame_ingest")
     return buf if Wb == Wp else buf[:, :, :Wp]
+
+
+DEGRADE_MAX_K, DEGRADE_MAX_SCALE = 33, 4      # the limits of dvsr_degrade_apply / dvsr_frame_degrade (csrc/degrade.hip)
+
+
+def degraded_size(h, w, K, scale):
+    """(Hc, Wc, h_lr, w_lr) of an h x w frame degraded with a shifted kernel of edge K at stride `scale`: the frame is cropped
+    to Hc x Wc = (h - h % scale) x (w - w % scale), the reference's modcrop (data/util.py:302), reflection-padded by K // 2 and
+    correlated at that stride, so h_lr = (Hc + 2 (K // 2) - K) // scale + 1 and w_lr likewise -- Hc / scale for an odd K, one more
+    for an even one.  ValueError for what dvsr_frame_degrade refuses: K outside [1, 33], scale outside [1, 4], a frame with no
+    multiple of the scale inside, a pad K // 2 that is not smaller than the crop.  Host code."""
+    h, w, K, scale = int(h), int(w), int(K), int(scale)
+    if not (1 <= K <= DEGRADE_MAX_K and 1 <= scale <= DEGRADE_MAX_SCALE):
+        raise ValueError("degraded_size: kernel edge %d (1 .. %d) / scale %d (1 .. %d)" % (K, DEGRADE_MAX_K, scale, DEGRADE_MAX_SCALE))
+    Hc, Wc = h - h % scale, w - w % scale
+    if Hc < 1 or Wc < 1:
+        raise ValueError("degraded_size: a %d x %d frame has no multiple of scale %d inside" % (h, w, scale))
+    pad = K // 2
+    if pad >= Hc or pad >= Wc:
+        raise ValueError("degraded_size: the reflection pad %d of a %d x %d kernel is not smaller than the %d x %d crop of a "
+                         "%d x %d frame" % (pad, K, K, Hc, Wc, h, w))
+    return Hc, Wc, (Hc + 2 * pad - K) // scale + 1, (Wc + 2 * pad - K) // scale + 1
+
+
+def degradation_edge(degradation, kernel_index=0, who="degrade"):
+    """(K, scale) of a data.random_kernel_generator.Degradation for kernel `kernel_index` of its set (0 for a single [K0,K0]
+    kernel): the edge of the shifted kernel and the stride.  ValueError for an index outside the set.  Host code."""
+    kernel = degradation.kernel
+    n = 1 if kernel.ndim == 2 else int(kernel.shape[0])
+    if isinstance(kernel_index, bool) or not isinstance(kernel_index, numbers.Integral) or not 0 <= kernel_index < n:
+        raise ValueError("%s: kernel_index=%r outside the degradation's %d kernel%s" % (who, kernel_index, n, "" if n == 1 else "s"))
+    return degradation.shifted_edge(int(kernel_index)), int(degradation.scale)
+
+
+def degrade(frame, degradation, layout=None, *, kernel_index=0, quantise=True, out=None, matrix='bt601', yuv_range='limited'):
+    """One ground-truth frame -> its LR frame, fp32 [3,h_lr,w_lr] on the GPU ((Hc, Wc, h_lr, w_lr) = degraded_size(h, w, K,
+    degradation.scale)): Degradation.apply(ingest(frame, multiple=1)[:, :Hc, :Wc].contiguous()[None], quantise)[0] bit for bit,
+    in one launch that reads the frame as it is (dvsr_frame_degrade) -- no fp32 copy of the HR frame, no crop.
+
+    frame: anything ingest() takes, on the CPU or the GPU (a CPU frame is copied to the device as it is: 8-bit frames travel as
+    bytes).  degradation: a data.random_kernel_generator.Degradation; its shifted kernel (cached per device) is the kernel and
+    its `scale` the stride; `kernel_index` picks one of a [T,K0,K0] set.  quantise: the 8-bit round trip of vsrbase.py:185,
+    mul(255).clamp(0, 255).round().div(255), in the same launch -- what an LR video stored as 8-bit images holds.
+    RGB / BGR bytes and float planar frames go to the kernel directly, views by stride (nothing is copied); every YCbCr layout
+    goes through ingest(.., multiple=1) first -- one extra fp32 HR frame -- and gives the bits of that float frame.
+    out: the fp32 [3,h_lr,w_lr] GPU tensor to fill, possibly a view with contiguous columns and rows and planes that do not
+    overlap.  Arguments are checked before the first GPU call (ValueError)."""
+    check_yuv_names(matrix, yuv_range)
+    layout, h, w = resolve_layout(frame, layout)
+    K, scale = degradation_edge(degradation, kernel_index)
+    Hc, Wc, hl, wl = degraded_size(h, w, K, scale)
+    if out is not None:
+        if not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (3, hl, wl)):
+            raise ValueError("degrade: out must be an fp32 [3,%d,%d] tensor" % (hl, wl))
+        st = out.stride()
+        if not ((st[2] == 1 or wl == 1) and (st[1] >= wl or hl == 1) and st[0] >= (hl - 1) * st[1] + wl):
+            raise ValueError("degrade: out must have contiguous columns and rows and planes that do not overlap")
+        if not out.is_cuda:
+            raise RuntimeError("degrade: out must be on the GPU (libdynavsr_hip); there is no CPU path")
+    first = frame if torch.is_tensor(frame) else frame[0]
+    dev = out.device if out is not None else (first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+    frame = to_device(frame, dev)
+    with torch.cuda.device(dev):
+        if is_yuv(layout):
+            # (multiple=1 pads nothing but the buffer's rows to 4 floats, which are never read here)
+            frame, layout = ingest(frame, layout, 1, 'replicate', matrix=matrix, yuv_range=yuv_range), 'chw'
+        frame, desc = describe(frame, layout)
+        kernel = degradation._shifted_on(dev)[int(kernel_index)]
+        if tuple(kernel.shape) != (K, K):
+            raise RuntimeError("degrade: the shifted kernel is %s, shifted_edge() says %d" % (tuple(kernel.shape), K))
+        if out is None:
+            out = torch.empty((3, hl, wl), dtype=torch.float32, device=dev)
+        st = out.stride()
+        L.check(L.lib().dvsr_frame_degrade(frame.data_ptr(), ctypes.byref(desc), kernel.data_ptr(), K, scale, out.data_ptr(),
+                                           max(int(st[1]), wl), int(st[0]), 1 if quantise else 0, L.stream()),
+                "dvsr_frame_degrade")
+    return out
 
 
 def check_size(size, what="size"):

@@ -7,6 +7,8 @@
     the schedules          scene_bounds, video_windows, stream_slots, stream_schedule (pure Python)
     the tile geometry      tile_origins, tile_footprint, choose_tile
     the scores             score_summary, evaluate_frames
+    a degraded video       degrade_frames, evaluate_degraded: a ground-truth video blurred, sub-sampled and quantised on the device,
+                           super-resolved and scored against the frames it came from
 
 This module imports nothing from adapt.py; adapt.py re-exports its public names."""
 import math
@@ -400,7 +402,12 @@ def _frame_format(who, frames, layout, out, multiple, pad_mode, matrix, yuv_rang
     return lay, h, w, out_fmt, Hp, Wp, out_size, mult
 
 
+_SCORES_LATER = object()      # `scores` of a check that runs ahead of the call that allocates them (evaluate_degraded)
+
+
 def _check_scores(who, scores, T, name="scores"):
+    if scores is _SCORES_LATER:
+        return
     if not (torch.is_tensor(scores) and scores.dtype == torch.float64 and tuple(scores.shape) == (T, 2)
             and scores.is_cuda and scores.is_contiguous()):
         raise ValueError("%s: gt needs %s, a contiguous float64 [%d, 2] tensor on the GPU" % (who, name, T))
@@ -968,3 +975,115 @@ def evaluate_frames(opt, net, frames, gt, **kw):
         o = kw.get('out') if kw.get('out') is not None else kw.get('layout')
         peak = 2 ** fio.layout_depth(o) - 1 if fio.is_yuv(o) else 255
     return score_summary(scores, _window_length(opt, net), kw.get('cuts'), peak), scores
+
+
+def _degraded_geometry(who, hr, degradation, layout):
+    """The host checks of degrade_frames: (lay, h, w, per_frame, K, scale, (Hc, Wc, h_lr, w_lr)).  ValueError for a video that
+    _video_format refuses, a kernel set whose length is not the video's or whose shifted kernels differ in size, and everything
+    frames.degraded_size refuses.  No GPU call."""
+    lay, h, w = _video_format(hr, layout, who)
+    kernel = getattr(degradation, 'kernel', None)
+    if kernel is None or getattr(kernel, 'ndim', 0) not in (2, 3):
+        raise ValueError("%s: degradation must be a data.random_kernel_generator.Degradation with a [K0,K0] or [T,K0,K0] kernel" % who)
+    per_frame = kernel.ndim == 3
+    if per_frame and kernel.shape[0] != len(hr):
+        raise ValueError("%s: %d per-frame kernels for a video of %d frames (frame j takes kernel j)" % (who, kernel.shape[0], len(hr)))
+    edges = sorted(set(fio.degradation_edge(degradation, j, who)[0] for j in range(kernel.shape[0] if per_frame else 1)))
+    if len(edges) != 1:
+        raise ValueError("%s: the shifted per-frame kernels have edges %s; one LR size needs one edge" % (who, edges))
+    K, scale = edges[0], int(degradation.scale)
+    try:
+        sizes = fio.degraded_size(h, w, K, scale)
+    except ValueError as e:
+        raise ValueError("%s: %s" % (who, e))
+    return lay, h, w, per_frame, K, scale, sizes
+
+
+def degrade_frames(hr, degradation, *, layout=None, quantise=True, matrix='bt601', yuv_range='limited', out=None):
+    """A ground-truth video -> its LR video, fp32 [T,3,h_lr,w_lr] on the GPU: what super_resolve_frames / adapt_frames take.
+
+    hr: a [T,...] tensor or a list of frames of one kind and size, in any `layout` frames.ingest takes (None: by dtype; the
+    YCbCr layouts are never inferred), on the CPU or the GPU.  Frame j becomes frames.degrade(hr[j], degradation, layout,
+    quantise=quantise): its top-left (h - h % scale) x (w - w % scale) crop blurred and sub-sampled with the degradation's
+    shifted kernel and, with `quantise`, rounded to the 8-bit grid -- test_dynavsr.py's `degradation_mode: set` on a video that is
+    never held as fp32 at HR size.  One launch per frame on the caller's stream; a CPU frame crosses the bus once, as bytes.
+    A [T,K0,K0] degradation.kernel needs T == len(hr), and frame j is degraded with kernel j.  That is NOT the reference's
+    `preset` mode, which degrades a whole window of frames with the centre frame's kernel, so that one frame appears with up to
+    nframes different blurs: here a frame is degraded once.
+    out: the fp32 [T,3,h_lr,w_lr] GPU tensor to fill.  Arguments are checked before the first GPU call (ValueError)."""
+    who = "degrade_frames"
+    fio.check_yuv_names(matrix, yuv_range)
+    lay, h, w, per_frame, K, scale, (Hc, Wc, hl, wl) = _degraded_geometry(who, hr, degradation, layout)
+    T = len(hr)
+    if out is not None:
+        if not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (T, 3, hl, wl)):
+            raise ValueError("%s: out must be an fp32 [%d,3,%d,%d] tensor" % (who, T, hl, wl))
+        if not out.is_cuda:
+            raise RuntimeError("%s: out must be on the GPU (libdynavsr_hip); there is no CPU path" % who)
+    first = hr[0] if torch.is_tensor(hr[0]) else hr[0][0]
+    dev = out.device if out is not None else (first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+    with torch.cuda.device(dev):
+        lr = out if out is not None else torch.empty((T, 3, hl, wl), dtype=torch.float32, device=dev)
+        for j in range(T):
+            fio.degrade(hr[j], degradation, lay, kernel_index=j if per_frame else 0, quantise=quantise, out=lr[j], matrix=matrix,
+                        yuv_range=yuv_range)
+    return lr
+
+
+def _degraded_evaluation(who, opt, hr, degradation, hr_layout, kw):
+    """The checks that the two evaluate_degraded functions share, and the ground truth: (lay, (T, 3, h_lr, w_lr), gt) -- gt the
+    top-left Hc x Wc view of every HR frame (frames.tile_view: plane views for YCbCr, nothing copied).  ValueError when the SR
+    frames would not have the ground truth's size (an even shifted kernel: scale * h_lr != Hc), when the degradation's scale is
+    not the network's, and for arguments that belong to the functions' own part.  No GPU call."""
+    lay, h, w, _, K, scale, (Hc, Wc, hl, wl) = _degraded_geometry(who, hr, degradation, hr_layout)
+    for name in ('gt', 'gt_layout', 'layout'):
+        if name in kw:
+            raise ValueError("%s: %s is the function's own (the LR video is fp32 planar, the ground truth the HR video)" % (who, name))
+    if scale != int(opt['scale']):
+        raise ValueError("%s: the degradation's scale %d is not opt['scale'] = %r" % (who, scale, opt['scale']))
+    if scale * hl != Hc or scale * wl != Wc:
+        raise ValueError("%s: an even shifted kernel (edge %d) gives LR frames of %d x %d, whose SR frames %d x %d are not the "
+                         "%d x %d of the ground truth; use an odd kernel_size" % (who, K, hl, wl, scale * hl, scale * wl, Hc, Wc))
+    gt = [fio.tile_view(f, lay, 0, 0, Hc, Wc) for f in hr]
+    return lay, (len(hr), 3, hl, wl), gt
+
+
+def _without_device_queries(kw):
+    """`kw` of a frame generator for a check ahead of its call: cuts='auto' and tile='auto' ask the device, so the check takes one
+    scene and no tile in their place (what the generators check in front of those queries)."""
+    kw = dict(kw)
+    if isinstance(kw.get('cuts'), str) and kw['cuts'] == 'auto':
+        kw['cuts'] = []
+    if isinstance(kw.get('tile'), str) and kw['tile'] == 'auto':
+        kw.pop('tile')
+        kw.pop('tile_budget', None)
+    return kw
+
+
+def evaluate_degraded(opt, net, hr, degradation, *, hr_layout=None, quantise=True, **kw):
+    """"This ground-truth video, this blur: how good is the network?" in one call -- the un-adapted half of test_dynavsr.py with
+    `degradation_mode: set`.  The LR video is degrade_frames(hr, degradation, layout=hr_layout, quantise=quantise, matrix=,
+    yuv_range=), the ground truth the top-left Hc x Wc view of every HR frame (what the LR frames were made from; frames.tile_view,
+    nothing copied), and the result is evaluate_frames(opt, net, lr, gt, gt_layout=hr_layout, **kw): (summary, scores).
+    `kw` is evaluate_frames' (out, cuts -- 'auto' is resolved on the LR video --, score, crop_border, scores, peak, tile, ...;
+    `matrix` / `yuv_range` name the conversion of a YCbCr `hr` and of a YCbCr `out` alike).
+    ValueError before the first GPU call: degradation.scale != opt['scale']; scale * h_lr != Hc (an even shifted kernel: the SR
+    frames would not have the ground truth's size); per-frame kernels of another count than the video; an HR frame not larger
+    than the kernel's pad; `gt`, `gt_layout` or `layout` in kw; and what super_resolve_frames refuses for these arguments."""
+    import inspect
+    who = "evaluate_degraded"
+    lay, shape, gt = _degraded_evaluation(who, opt, hr, degradation, hr_layout, kw)
+    stand_in = torch.empty(shape, dtype=torch.float32, device='meta')       # the LR video's size and kind, for the checks alone
+    check = {k: v for k, v in _without_device_queries(kw).items() if k != 'peak'}
+    check['scores'] = check['scores'] if check.get('scores') is not None else _SCORES_LATER
+    defaults = {k: p.default for k, p in inspect.signature(super_resolve_frames).parameters.items()
+                if p.default is not inspect.Parameter.empty}
+    unknown = sorted(set(check) - set(defaults))
+    if unknown:
+        raise TypeError("evaluate_degraded: super_resolve_frames takes no %s" % ', '.join(unknown))
+    b = dict(defaults, gt=gt, gt_layout=lay, **check)
+    a = _frame_arguments(opt, net, stand_in, *[b[k] for k in list(inspect.signature(_frame_arguments).parameters)[3:]])
+    video_windows(a.T, a.n, a.padding, a.cuts)              # (the padding mode and the window length, which the paths check later)
+    lr = degrade_frames(hr, degradation, layout=lay, quantise=quantise, matrix=kw.get('matrix', 'bt601'),
+                        yuv_range=kw.get('yuv_range', 'limited'))
+    return evaluate_frames(opt, net, lr, gt, gt_layout=lay, **kw)

@@ -908,6 +908,27 @@ int dvsr_frame_score(const void* a, const dvsr_frame_desc* da, const void* b, co
 int dvsr_degrade_apply(const float* img, const float* kernels, float* out, int N, int C, int H, int W, int K,
                        int scale, int n_kernels, int kernel_offset, int quantise, dvsr_stream_t stream);
 
+/* ---- a ground-truth frame degraded as it arrives --------------------------------------------------
+ * What test_dynavsr.py does with `degradation_mode: set | preset` to every frame of a ground-truth video -- read it, modcrop
+ * it to a multiple of the scale (data/util.py:302), blur and sub-sample it, quantise the result to 8 bits -- for a frame in
+ * the form a decoder delivers it, in one launch and without an fp32 copy of the HR frame:
+ *   src / sd   one HR frame as dvsr_frame_ingest takes it: DVSR_FRAME_F32_CHW, DVSR_FRAME_U8_HWC_RGB or _BGR, at any address,
+ *              pitch and pixel stride 3 or 4.  Only its top-left Hc x Wc is read, Hc = h - h % scale, Wc = w - w % scale.
+ *   kernel     ONE centre-of-mass-shifted K x K fp32 kernel on the device; K <= 33, scale <= 4 and a reflection pad
+ *              K / 2 < Hc, Wc: the limits of dvsr_degrade_apply.
+ *   dst        fp32 planar RGB [3][h_lr][w_lr], row and plane strides in FLOATS, 4-byte aligned;
+ *              h_lr = (Hc + 2 (K / 2) - K) / scale + 1, w_lr likewise.
+ * The values are bit-identical to dvsr_degrade_apply(.., quantise) on the contiguous [1,3,Hc,Wc] crop of dvsr_frame_ingest's
+ * output for the same frame: the two kernels of dvsr_degrade_apply read their input patch through a source policy (fp32 planes
+ * by stride, or interleaved bytes by stride and channel as v / 255.0f, a true division) and everything behind it -- the choice
+ * of the kernel by (scale, ceil(K / scale)) and DVSR_DEGRADE_GENERIC, the order of the taps, fmaf from an accumulator of 0, the
+ * quantiser rintf(fminf(fmaxf(acc * 255, 0), 255)) / 255 -- is the same code.
+ * Bad arguments return before any launch: a null pointer, an unknown format, a pixel stride outside {3,4}, a row stride shorter
+ * than a row, Hc or Wc < 1, a pad not smaller than the crop, a destination stride shorter than w_lr (or planes that overlap), a
+ * misaligned fp32 side: DVSR_ERR_INVALID; K or scale out of range: DVSR_ERR_UNSUPPORTED. */
+int dvsr_frame_degrade(const void* src, const dvsr_frame_desc* sd, const float* kernel, int K, int scale, float* dst,
+                       long long dst_row_stride, long long dst_plane_stride, int quantise, dvsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
