@@ -258,6 +258,10 @@ def _declare(lib):
         "dvsr_frame_resize_taps": (I, [I, I]),
         "dvsr_frame_resize_table": (I, [I, I, I, P, P]),
         "dvsr_frame_resize": (I, [P, I, I, I, I, P, I, I, I, I, POINTER(ResizeAxis), POINTER(ResizeAxis), P]),
+        "dvsr_frame_imresize_taps": (I, [I, I, I, I, POINTER(c_int)]),
+        "dvsr_frame_imresize_table": (I, [I, I, I, I, I, P, P]),
+        "dvsr_frame_imresize": (I, [P, POINTER(FrameDesc), I, I, I, I, I, P, LL, LL, I, I, POINTER(ResizeAxis), POINTER(ResizeAxis),
+                                    I, P]),
         "dvsr_frame_flip": (I, [P, P, LL, I, I, I, P]),
         "dvsr_frame_flip_mean": (I, [P, P, P, P, P, LL, I, I, P]),
         "dvsr_frame_stitch_origins": (I, [I, I, I, POINTER(c_int), I]),

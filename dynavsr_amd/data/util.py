@@ -8,6 +8,9 @@ taken as they are; a position that falls off either end is replaced according to
     reflection  [2, 1, 0, 1, 2]   mirrored about the border frame
     new_info    [4, 3, 0, 1, 2]   frames from beyond the window's far end: every entry is a different frame
     circle      [3, 4, 0, 1, 2]   shifted by N (a missing position p takes p + N at the start, p - N at the end)
+
+Also here, with the reference's signatures: the YCbCr conversions (rgb2ycbcr, bgr2ycbcr, ycbcr2rgb) and MATLAB's imresize
+(modcrop, imresize, imresize_np; the arithmetic of the latter two runs on the GPU).
 """
 
 PADDING_MODES = ('replicate', 'reflection', 'new_info', 'circle')
@@ -76,3 +79,42 @@ def ycbcr2rgb(img):
     x, is_u8, dtype = _colour_levels(img)
     levels = np.matmul(x, [list(r) for r in _RGB_FROM_YCBCR]) * 255.0 + [-222.921, 135.576, -276.836]
     return _colour_result(levels, is_u8, dtype)
+
+
+# ---- MATLAB's imresize, as the reference's data/util.py offers it (:302-524) ---------------------------------------------------
+# The arithmetic runs on the GPU (dynavsr_amd.frames.imresize, csrc/frame_imresize.hip): as with Degradation.apply there is no
+# CPU arithmetic path, and a CPU input is copied to the current device and the result back.
+def modcrop(img_in, scale):
+    """img_in: numpy, HWC or HW -> a copy of its top-left (H - H % scale) x (W - W % scale)."""
+    import numpy as np
+    img = np.copy(img_in)
+    if img.ndim not in (2, 3):
+        raise ValueError('Wrong img ndim: [{:d}].'.format(img.ndim))
+    H, W = img.shape[:2]
+    return np.copy(img[:H - H % scale, :W - W % scale])
+
+
+def imresize(img, scale, antialiasing=True):
+    """MATLAB's imresize(img, scale, 'bicubic').  img: a [3,H,W] tensor (RGB or BGR alike) in [0,1]; scale: 1/2, 1/3, 1/4, 2, 3 or 4
+    within 1e-9 (ValueError otherwise).  -> fp32 [3, ceil(H scale), ceil(W scale)], not rounded, on the device img lives on."""
+    import torch
+    from dynavsr_amd import frames
+    ratio = frames.imresize_ratio(scale, "imresize")
+    if not torch.is_tensor(img) or img.dim() != 3 or img.shape[0] != 3 or not img.is_floating_point():
+        raise ValueError("imresize: img must be a float [3,H,W] tensor, got %s" % (
+            "%s %s" % (img.dtype, tuple(img.shape)) if torch.is_tensor(img) else type(img).__name__))
+    out = frames.imresize(img, ratio, 'chw', antialiasing=antialiasing)
+    return out if img.is_cuda else out.cpu()
+
+
+def imresize_np(img, scale, antialiasing=True):
+    """imresize for a numpy image [H,W,3] in [0,1] (any channel order) -> float32 [ceil(H scale), ceil(W scale), 3]."""
+    import numpy as np
+    import torch
+    from dynavsr_amd import frames
+    ratio = frames.imresize_ratio(scale, "imresize_np")
+    img = np.asarray(img)
+    if img.ndim != 3 or img.shape[2] != 3 or img.dtype.kind != 'f':
+        raise ValueError("imresize_np: img must be a float [H,W,3] array, got %s %s" % (img.dtype, img.shape))
+    chw = torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1), dtype=np.float32))
+    return np.ascontiguousarray(frames.imresize(chw, ratio, 'chw', antialiasing=antialiasing).cpu().numpy().transpose(1, 2, 0))

@@ -80,6 +80,16 @@ A ground-truth frame degraded as it arrives (csrc/degrade.hip: dvsr_frame_degrad
     degraded_size(h, w, K, scale)        -> (Hc, Wc, h_lr, w_lr): the crop to a multiple of the scale and the LR size; host code
     degrade(frame, degradation, layout)  -> fp32 [3,h_lr,w_lr] on the GPU: Degradation.apply(.., quantise) of the frame's Hc x Wc
                                             crop, from the frame's own bytes, one launch
+
+MATLAB's imresize(img, scale, 'bicubic') (csrc/frame_imresize.hip: dvsr_frame_imresize_taps / _table / dvsr_frame_imresize;
+DESIGN 3.2u) -- the BI degradation imresize(hr, 1 / s) and the "Bicubic" baseline imresize(lr, s); scale is one of 1/2, 1/3,
+1/4, 2, 3, 4:
+
+    imresize_size(h, w, scale)           -> (oh, ow) = (ceil(h scale), ceil(w scale)); host code
+    imresize_table(n_in, scale)          -> (first int32 [n_out], weights fp32 [n_out, taps]) on the CPU: one axis, folded
+    imresize(frame, scale, layout)       -> fp32 [3,oh,ow] on the GPU from the frame's own bytes, one launch
+    Imresize(s)                          -> names BI where a degradation is expected: degrade(frame, Imresize(4)) =
+                                            imresize(frame, 1/4, quantise=True, modcrop=4)
 """
 import ctypes
 import numbers
@@ -392,13 +402,20 @@ def degrade(frame, degradation, layout=None, *, kernel_index=0, quantise=True, o
 
     frame: anything ingest() takes, on the CPU or the GPU (a CPU frame is copied to the device as it is: 8-bit frames travel as
     bytes).  degradation: a data.random_kernel_generator.Degradation; its shifted kernel (cached per device) is the kernel and
-    its `scale` the stride; `kernel_index` picks one of a [T,K0,K0] set.  quantise: the 8-bit round trip of vsrbase.py:185,
+    its `scale` the stride; `kernel_index` picks one of a [T,K0,K0] set.  A data.old_kernel_generator.Degradation is taken the
+    same way (its kernel as it is: no shift).  An Imresize(s) is BI instead of a blur: imresize(frame, 1 / s, layout,
+    quantise=quantise, modcrop=s), fp32 [3, Hc / s, Wc / s].  quantise: the 8-bit round trip of vsrbase.py:185,
     mul(255).clamp(0, 255).round().div(255), in the same launch -- what an LR video stored as 8-bit images holds.
     RGB / BGR bytes and float planar frames go to the kernel directly, views by stride (nothing is copied); every YCbCr layout
     goes through ingest(.., multiple=1) first -- one extra fp32 HR frame -- and gives the bits of that float frame.
     out: the fp32 [3,h_lr,w_lr] GPU tensor to fill, possibly a view with contiguous columns and rows and planes that do not
     overlap.  Arguments are checked before the first GPU call (ValueError)."""
     check_yuv_names(matrix, yuv_range)
+    if isinstance(degradation, Imresize):
+        if isinstance(kernel_index, bool) or not isinstance(kernel_index, numbers.Integral) or kernel_index != 0:
+            raise ValueError("degrade: kernel_index=%r of an Imresize, which has no kernel set" % (kernel_index,))
+        return imresize(frame, (1, degradation.scale), layout, antialiasing=degradation.antialiasing, quantise=quantise,
+                        modcrop=degradation.scale, out=out, matrix=matrix, yuv_range=yuv_range)
     layout, h, w = resolve_layout(frame, layout)
     K, scale = degradation_edge(degradation, kernel_index)
     Hc, Wc, hl, wl = degraded_size(h, w, K, scale)
@@ -428,6 +445,133 @@ def degrade(frame, degradation, layout=None, *, kernel_index=0, quantise=True, o
                                            max(int(st[1]), wl), int(st[0]), 1 if quantise else 0, L.stream()),
                 "dvsr_frame_degrade")
     return out
+
+
+IMRESIZE_SCALES = ((1, 2), (1, 3), (1, 4), (2, 1), (3, 1), (4, 1))     # num / den: what dvsr_frame_imresize takes
+
+
+def imresize_ratio(scale, who="imresize"):
+    """(num, den) of a scale: a number within 1e-9 of 1/2, 1/3, 1/4, 2, 3 or 4, or such a pair itself.  ValueError otherwise."""
+    if isinstance(scale, (tuple, list)):
+        if tuple(scale) in IMRESIZE_SCALES:
+            return int(scale[0]), int(scale[1])
+    elif isinstance(scale, numbers.Real) and not isinstance(scale, bool):
+        for num, den in IMRESIZE_SCALES:
+            if abs(float(scale) - num / den) <= 1e-9:
+                return num, den
+    raise ValueError("%s: scale=%r is not one of 1/2, 1/3, 1/4, 2, 3, 4" % (who, scale))
+
+
+def imresize_size(h, w, scale):
+    """(oh, ow) of MATLAB's imresize of an h x w image: ceil(h scale), ceil(w scale) in integers.  Host code."""
+    num, den = imresize_ratio(scale, "imresize_size")
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError("imresize_size: h=%d, w=%d must be positive" % (h, w))
+    return -(-h * num // den), -(-w * num // den)
+
+
+def imresize_table(n_in, scale, antialiasing=True):
+    """One axis of MATLAB's bicubic imresize, n_in -> ceil(n_in scale) samples: (first int32 [n_out], weights fp32 [n_out, taps])
+    CPU tensors from dvsr_frame_imresize_taps / _table -- output i is sum_t weights[i, t] * x[first[i] + t]: the reference's
+    calculate_weights_indices evaluated in double, the taps beyond either edge folded back onto the image (MATLAB's symmetric
+    copy) and added to the taps they land on; taps = the longest window of the axis, shorter rows zero-padded.  No GPU call."""
+    num, den = imresize_ratio(scale, "imresize_table")
+    n_in = int(n_in)
+    if n_in < 1:
+        raise ValueError("imresize_table: n_in=%d must be positive" % n_in)
+    n_out = ctypes.c_int()
+    taps = L.lib().dvsr_frame_imresize_taps(n_in, num, den, 1 if antialiasing else 0, ctypes.byref(n_out))
+    if taps < 1:
+        raise ValueError("imresize_table: " + L.lib().dvsr_last_error().decode("utf-8", "replace"))
+    first = torch.empty((n_out.value,), dtype=torch.int32)
+    weights = torch.empty((n_out.value, taps), dtype=torch.float32)
+    L.check(L.lib().dvsr_frame_imresize_table(n_in, num, den, 1 if antialiasing else 0, taps, first.data_ptr(),
+                                              weights.data_ptr()), "dvsr_frame_imresize_table")
+    return first, weights
+
+
+_imresize_tables = {}    # (n_in, (num, den), antialiasing, device) -> the table on the device + its dvsr_resize_axis
+
+
+def _imresize_axis(n_in, ratio, antialiasing, device):
+    key = (int(n_in), ratio, bool(antialiasing), str(device))
+    hit = _imresize_tables.get(key)
+    if hit is None:
+        first, weights = imresize_table(n_in, ratio, antialiasing)
+        first, weights = first.to(device), weights.to(device)       # (blocking copies: usable from any stream afterwards)
+        hit = _imresize_tables[key] = (first, weights, L.ResizeAxis(first.data_ptr(), weights.data_ptr(), int(weights.shape[1])))
+    return hit[2]
+
+
+def imresize(frame, scale, layout=None, *, antialiasing=True, quantise=False, modcrop=None, out=None, matrix='bt601',
+             yuv_range='limited'):
+    """MATLAB's imresize(frame, scale, 'bicubic') -- the reference's data.util.imresize -- of one frame: fp32 [3,oh,ow] on the
+    GPU, (oh, ow) = imresize_size(h, w, scale), in one launch that reads the frame as it is (dvsr_frame_imresize).
+
+    frame: anything ingest() takes, on the CPU or the GPU (a CPU frame is copied to the device as it is).  scale: 1/2, 1/3, 1/4
+    (with `antialiasing` the kernel is widened by 1 / scale: BI) or 2, 3, 4.  modcrop=m: only the top-left (h - h % m) x
+    (w - w % m) of the frame is read, the reference's modcrop, at no cost.  quantise: the 8-bit round trip
+    mul(255).clamp(0, 255).round().div(255) in the same launch (round half to even).  RGB / BGR bytes and float planar frames go
+    to the kernel directly, views by stride; every YCbCr layout goes through ingest(.., multiple=1) first.  out: the fp32
+    [3,oh,ow] GPU tensor to fill, possibly a view with contiguous columns and rows and planes that do not overlap.
+    Arguments are checked before the first GPU call (ValueError)."""
+    check_yuv_names(matrix, yuv_range)
+    ratio = imresize_ratio(scale)
+    layout, h, w = resolve_layout(frame, layout)
+    if modcrop is not None:
+        if isinstance(modcrop, bool) or not isinstance(modcrop, numbers.Integral) or modcrop < 1:
+            raise ValueError("imresize: modcrop=%r must be a positive int" % (modcrop,))
+        h, w = h - h % modcrop, w - w % modcrop
+        if h < 1 or w < 1:
+            raise ValueError("imresize: the frame has no multiple of modcrop=%d inside" % modcrop)
+    oh, ow = imresize_size(h, w, ratio)
+    if out is not None:
+        if not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (3, oh, ow)):
+            raise ValueError("imresize: out must be an fp32 [3,%d,%d] tensor" % (oh, ow))
+        st = out.stride()
+        if not ((st[2] == 1 or ow == 1) and (st[1] >= ow or oh == 1) and st[0] >= (oh - 1) * st[1] + ow):
+            raise ValueError("imresize: out must have contiguous columns and rows and planes that do not overlap")
+        if not out.is_cuda:
+            raise RuntimeError("imresize: out must be on the GPU (libdynavsr_hip); there is no CPU path")
+    first = frame if torch.is_tensor(frame) else frame[0]
+    dev = out.device if out is not None else (first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+    frame = to_device(frame, dev)
+    with torch.cuda.device(dev):
+        if is_yuv(layout):
+            frame, layout = ingest(frame, layout, 1, 'replicate', matrix=matrix, yuv_range=yuv_range), 'chw'
+        frame, desc = describe(frame, layout)
+        rows, cols = _imresize_axis(h, ratio, antialiasing, dev), _imresize_axis(w, ratio, antialiasing, dev)
+        if out is None:
+            out = torch.empty((3, oh, ow), dtype=torch.float32, device=dev)
+        st = out.stride()
+        L.check(L.lib().dvsr_frame_imresize(frame.data_ptr(), ctypes.byref(desc), h, w, ratio[0], ratio[1], 1 if antialiasing else 0,
+                                            out.data_ptr(), max(int(st[1]), ow), max(int(st[0]), (oh - 1) * max(int(st[1]), ow) + ow),
+                                            oh, ow, ctypes.byref(rows), ctypes.byref(cols), 1 if quantise else 0, L.stream()),
+                "dvsr_frame_imresize")
+    return out
+
+
+class Imresize:
+    """BI -- MATLAB's imresize(img, 1 / scale, 'bicubic') -- where degrade(), video.degrade_frames and the evaluate_degraded
+    functions expect a degradation: `scale` is the integer down-scale factor (2, 3 or 4), `antialiasing` the reference's."""
+
+    def __init__(self, scale, antialiasing=True):
+        if isinstance(scale, bool) or not isinstance(scale, numbers.Integral) or (1, int(scale)) not in IMRESIZE_SCALES:
+            raise ValueError("Imresize: scale=%r is not 2, 3 or 4" % (scale,))
+        self.scale = int(scale)
+        self.antialiasing = bool(antialiasing)
+
+    def __repr__(self):
+        return "Imresize(%d, antialiasing=%r)" % (self.scale, self.antialiasing)
+
+    def lr_size(self, h, w):
+        """(Hc, Wc, h_lr, w_lr) of an h x w frame: the crop to a multiple of the scale and Hc / scale x Wc / scale."""
+        s = self.scale
+        Hc, Wc = int(h) - int(h) % s, int(w) - int(w) % s
+        if Hc < 1 or Wc < 1:
+            raise ValueError("Imresize: a %d x %d frame has no multiple of scale %d inside" % (h, w, s))
+        return Hc, Wc, Hc // s, Wc // s
 
 
 def check_size(size, what="size"):

@@ -982,9 +982,15 @@ def _degraded_geometry(who, hr, degradation, layout):
     _video_format refuses, a kernel set whose length is not the video's or whose shifted kernels differ in size, and everything
     frames.degraded_size refuses.  No GPU call."""
     lay, h, w = _video_format(hr, layout, who)
+    if isinstance(degradation, fio.Imresize):                # BI: no kernel, the LR size is the crop's over the scale
+        try:
+            return lay, h, w, False, 0, degradation.scale, degradation.lr_size(h, w)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (who, e))
     kernel = getattr(degradation, 'kernel', None)
     if kernel is None or getattr(kernel, 'ndim', 0) not in (2, 3):
-        raise ValueError("%s: degradation must be a data.random_kernel_generator.Degradation with a [K0,K0] or [T,K0,K0] kernel" % who)
+        raise ValueError("%s: degradation must be a frames.Imresize or a data.random_kernel_generator.Degradation with a [K0,K0] "
+                         "or [T,K0,K0] kernel" % who)
     per_frame = kernel.ndim == 3
     if per_frame and kernel.shape[0] != len(hr):
         raise ValueError("%s: %d per-frame kernels for a video of %d frames (frame j takes kernel j)" % (who, kernel.shape[0], len(hr)))
@@ -1007,6 +1013,10 @@ def degrade_frames(hr, degradation, *, layout=None, quantise=True, matrix='bt601
     quantise=quantise): its top-left (h - h % scale) x (w - w % scale) crop blurred and sub-sampled with the degradation's
     shifted kernel and, with `quantise`, rounded to the 8-bit grid -- test_dynavsr.py's `degradation_mode: set` on a video that is
     never held as fp32 at HR size.  One launch per frame on the caller's stream; a CPU frame crosses the bus once, as bytes.
+    `degradation` may also be a frames.Imresize(s) -- BI, MATLAB's imresize(hr, 1 / s) of the crop, Hc / s x Wc / s -- or a
+    data.old_kernel_generator.Degradation, the YAMLs' `degradation_type: bicubic` (its kernel is applied as it is).  The
+    reference's scripts build LR folders as a cascade of x2 applications with the 8-bit round trip between them: that is
+    degrade_frames called on its own output.
     A [T,K0,K0] degradation.kernel needs T == len(hr), and frame j is degraded with kernel j.  That is NOT the reference's
     `preset` mode, which degrades a whole window of frames with the centre frame's kernel, so that one frame appears with up to
     nframes different blurs: here a frame is degraded once.
@@ -1087,3 +1097,46 @@ def evaluate_degraded(opt, net, hr, degradation, *, hr_layout=None, quantise=Tru
     lr = degrade_frames(hr, degradation, layout=lay, quantise=quantise, matrix=kw.get('matrix', 'bt601'),
                         yuv_range=kw.get('yuv_range', 'limited'))
     return evaluate_frames(opt, net, lr, gt, gt_layout=lay, **kw)
+
+
+def evaluate_bicubic(opt, net, frames, gt, *, layout=None, out=None, matrix='bt601', yuv_range='limited', cuts=None,
+                     cut_threshold=10.0, gt_layout=None, score='rgb', crop_border=0, scores=None, peak=None):
+    """The "Bicubic" row of an SR table for one video: frame i is frames.imresize(frames[i], opt['scale'], layout) -- MATLAB's
+    imresize(lr, s) on the device -- in place of the network's output, then converted to `out` and scored against gt[i] exactly
+    as evaluate_frames does it, so that the two summaries compare row for row: (score_summary(scores, nframes, cuts, peak),
+    scores).  `net` only supplies the window length, for the border / centre split of the summary.  `frames` is what
+    super_resolve_frames takes (any size: nothing is padded); `out`, `cuts` ('auto' included), `gt_layout`, `score`,
+    `crop_border`, `scores` and `peak` are evaluate_frames'.  Arguments are checked before the first GPU call (ValueError)."""
+    who = "evaluate_bicubic"
+    T = len(frames)
+    if T < 1:
+        raise ValueError("%s: no frames" % who)
+    try:
+        s = fio.imresize_ratio(int(opt['scale']), who)[0]
+    except (TypeError, KeyError):
+        raise ValueError("%s: opt['scale'] must be 2, 3 or 4" % who)
+    lay, h, w = _video_format(frames, layout, who)
+    if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') and not fio.is_yuv(out):
+        raise ValueError("%s: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (who, out, ', '.join(fio.ALL_YUV_LAYOUTS)))
+    fio.check_yuv_names(matrix, yuv_range)
+    out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
+    if fio.is_yuv(out_fmt) and fio.packed_needs(out_fmt, s * h, s * w):
+        raise ValueError("%s: a packed %s output of %d x %d needs %s" % (who, out_fmt, s * h, s * w,
+                                                                       fio.packed_needs(out_fmt, s * h, s * w)))
+    score_into = _frame_scoring(who, T, gt, gt_layout, _SCORES_LATER if scores is None else scores, score, crop_border, out_fmt,
+                                None, s, h, w, matrix, yuv_range)
+    if score_into is None:
+        raise ValueError("%s: gt is what the frames are scored against" % who)
+    n = _window_length(opt, net)
+    cuts = _resolve_cuts(who, cuts, T, n, 'replicate', frames, lay, cut_threshold)
+    first = frames[0] if torch.is_tensor(frames[0]) else frames[0][0]
+    dev = scores.device if scores is not None else (first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+    with torch.cuda.device(dev):
+        if scores is None:
+            scores = torch.zeros((T, 2), dtype=torch.float64, device=dev)
+        for i in range(T):
+            sr = fio.imresize(frames[i], (s, 1), lay, matrix=matrix, yuv_range=yuv_range)[None]
+            _finish_frame(who, sr, (s * h, s * w, s * h, s * w), out_fmt, None, 1, matrix, yuv_range, i, score_into, scores)
+    if peak is None:
+        peak = 2 ** fio.layout_depth(out_fmt) - 1 if fio.is_yuv(out_fmt) else 255
+    return score_summary(scores, n, cuts, peak), scores

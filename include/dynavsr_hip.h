@@ -929,6 +929,42 @@ int dvsr_degrade_apply(const float* img, const float* kernels, float* out, int N
 int dvsr_frame_degrade(const void* src, const dvsr_frame_desc* sd, const float* kernel, int K, int scale, float* dst,
                        long long dst_row_stride, long long dst_plane_stride, int quantise, dvsr_stream_t stream);
 
+/* ---- MATLAB's imresize(img, scale, 'bicubic') of a frame as it arrives ----------------------------------
+ * The BI degradation of the SR literature (imresize(hr, 1 / s), antialiased) and the "Bicubic" row of its tables
+ * (imresize(lr, s)): codes/data/util.py:323-524 of the reference (calculate_weights_indices, imresize, imresize_np).
+ * Per axis, n_in -> n_out = ceil(n_in num / den), scale = num / den out of {1/2, 1/3, 1/4, 2/1, 3/1, 4/1}, in double:
+ * kw = 4, or 4 / scale when scale < 1 and antialias != 0 (the reference's `antialiasing`);  P = ceil(kw) + 2 taps.  Output i:
+ * u = (i + 1) / scale + 0.5 (1 - 1 / scale), left = floor(u - kw / 2); tap t reads the 1-based sample left + t with weight
+ * c(u - left - t), or scale c((u - left - t) scale) when kw was widened, divided by the sum of the P weights;
+ * c(x) = 1.5 |x|^3 - 2.5 |x|^2 + 1 for |x| <= 1, -0.5 |x|^3 + 2.5 |x|^2 - 4 |x| + 2 for 1 < |x| <= 2, 0 otherwise.  A 0-based
+ * index outside [0, n_in) is folded back by MATLAB's periodic symmetric rule (-k -> k - 1, n_in - 1 + k -> n_in - k, period
+ * 2 n_in) and its weight added, in tap order, to the tap it lands on; the taps with a non-zero weight are then one contiguous
+ * window [first, first + len), len <= 16 (1/4), 11 (1/3), 8 (1/2), 4 (up-scaling).  Any n_in >= 1 is accepted (the reference
+ * raises for 2 <= n_in <= 6 at 1/4, 2 .. 5 at 1/3, 2 .. 3 at 1/2, where its symmetric copy is longer than the image).
+ * dvsr_frame_imresize_taps: the longest window of the axis; *n_out (may be null) receives n_out.  Host code, no device call.
+ * dvsr_frame_imresize_table: first[n_out] and weights[n_out][taps] (HOST memory), taps >= dvsr_frame_imresize_taps and <= 18;
+ *   the folded weights rounded to fp32 and zero-padded to taps.  Host code, no device call.
+ * dvsr_frame_imresize: one launch per frame.
+ *   src / sd   one frame as dvsr_frame_degrade takes it: DVSR_FRAME_F32_CHW, DVSR_FRAME_U8_HWC_RGB or _BGR, at any address,
+ *              pitch and pixel stride 3 or 4; bytes become v / 255.0f, dvsr_frame_ingest's bits.  ONLY its top-left h x w crop
+ *              is read (h <= sd->h, w <= sd->w: the reference's modcrop at no cost).
+ *   dst        fp32 planar RGB [3][oh][ow], row and plane strides in FLOATS, 4-byte aligned; oh, ow must be the definition's
+ *              n_out of h and w.  Rows outside oh and columns outside ow are not written.  quantise != 0 stores
+ *              rintf(fminf(fmaxf(255 y, 0), 255)) / 255, the quantiser of dvsr_frame_degrade (round half to even).
+ *   rows / cols  the tables of h and w as dvsr_frame_imresize_table fills them, copied to DEVICE memory.  The kernel clamps
+ *              every index: a table with other contents gives a wrong picture, never an access outside the crop or oh x ow.
+ *   Columns are resampled first, then rows, in fp32 (fmaf in tap order from an accumulator of 0).  No atomics, deterministic.
+ * Bad arguments return before any launch: a null pointer, an unknown format, a pixel stride outside {3,4}, a row stride shorter
+ * than a row, a crop beyond the frame, oh / ow that are not the definition's, taps outside [longest window, 18], a destination
+ * stride shorter than ow (or planes that overlap), a misaligned fp32 side or table: DVSR_ERR_INVALID; a scale outside the six:
+ * DVSR_ERR_UNSUPPORTED.  Not provided: other scales, different scales per axis, MATLAB's round-half-away uint8 output, kernels
+ * other than the cubic, a YCbCr source. */
+int dvsr_frame_imresize_taps(int n_in, int num, int den, int antialias, int* n_out);
+int dvsr_frame_imresize_table(int n_in, int num, int den, int antialias, int taps, int* first, float* weights);
+int dvsr_frame_imresize(const void* src, const dvsr_frame_desc* sd, int h, int w, int num, int den, int antialias, float* dst,
+                        long long dst_row_stride, long long dst_plane_stride, int oh, int ow, const dvsr_resize_axis* rows,
+                        const dvsr_resize_axis* cols, int quantise, dvsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
