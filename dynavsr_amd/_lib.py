@@ -118,6 +118,12 @@ class StitchAxis(Structure):
 
 
 FLIP_W, FLIP_H = 1, 2                                             # dvsr_frame_flip's flags
+TASK_TRANSPOSE = 4                                                # beside them in a dvsr_task_frame's flags
+
+
+class TaskFrame(Structure):
+    """dvsr_task_frame: one frame of one task of dvsr_task_degrade / dvsr_task_gather, 32 bytes (include/dynavsr_hip.h)."""
+    _fields_ = [("src", c_void_p), ("row_stride", c_longlong), ("plane_stride", c_longlong), ("kernel", c_int), ("flags", c_int)]
 
 
 class ScoreArgs(Structure):
@@ -180,6 +186,8 @@ def _declare(lib):
         "dvsr_replicate_tensors": (I, [POINTER(c_void_p)] * 2 + [POINTER(LL), I, I, P]),
         "dvsr_degrade_apply": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),
         "dvsr_frame_degrade": (I, [P, POINTER(FrameDesc), P, I, I, P, LL, LL, I, P]),
+        "dvsr_task_degrade": (I, [P, P, I, I, I, I, I, P, I, I, I, P, I, P]),
+        "dvsr_task_gather": (I, [P, P, I, I, I, I, I, P, P]),
         "dvsr_frame_metrics_workspace_bytes": (c_size_t, [I, I, I]),
         "dvsr_frame_metrics": (I, [P, P, I, I, I, F, F, P, P, P, c_size_t, P]),
         "dvsr_charbonnier_workspace_bytes": (c_size_t, []),

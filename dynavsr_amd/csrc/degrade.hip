@@ -14,6 +14,11 @@
 // interleaved bytes at any address and pitch, cropped to a multiple of the stride) into a destination given by stride: the
 // kernels are templates over a source policy and differ in their staging loads alone, so the bits are dvsr_degrade_apply's on
 // the ingested frame without that fp32 frame ever being written.
+//
+// dvsr_task_degrade is the same pair once more on a BATCH of crops (the table and its check: task.hip): a table
+// source policy finds each item's base, strides and kernel index in a table of dvsr_task_frame on the device, and a destination
+// policy stores each result through its item's flip / transpose flags.  The other two entries store through DstStrided: the
+// addresses they stored to before.
 #include <climits>
 #include <cstdint>
 #include <cstdlib>
@@ -33,11 +38,19 @@ __device__ __forceinline__ int reflect_index(int i, int n) {  // ReflectionPad2d
   return i >= n ? 2 * n - 2 - i : i;
 }
 
-// Where the staging loops of the two kernels read from: the source policies of frame_source.h.
+// frame n uses kernel (n + kern_offset) mod kern_frames when there is one kernel per frame
+// (random_kernel_generator.py:105-113: offset -1 for DUF's two extra frames), else kernel 0; an item of a table names its own
 template <class Src>
-__global__ __launch_bounds__(256) void degrade_kernel(Src src, const float* __restrict__ kern, float* __restrict__ y,
-                                                      long long y_row, long long y_plane, int N, int C, int H, int W, int K,
-                                                      int S, int Ho, int Wo, int kern_per_frame, int kern_frames,
+__device__ __forceinline__ int kernel_of(const Src& src, int n, int kern_per_frame, int kern_frames, int kern_offset) {
+  if constexpr (Src::TABLE) return src.kernel(n);
+  else return kern_per_frame ? ((n + kern_offset) % kern_frames + kern_frames) % kern_frames : 0;
+}
+
+// Where the staging loops of the two kernels read from and where their last statement stores to: the source and destination
+// policies of frame_source.h.
+template <class Src, class Dst>
+__global__ __launch_bounds__(256) void degrade_kernel(Src src, const float* __restrict__ kern, Dst dst, int N, int C, int H,
+                                                      int W, int K, int S, int Ho, int Wo, int kern_per_frame, int kern_frames,
                                                       int kern_offset, int quantise) {
   extern __shared__ float smem[];
   const int P = (DG_T - 1) * S + K;  // input patch edge
@@ -47,9 +60,7 @@ __global__ __launch_bounds__(256) void degrade_kernel(Src src, const float* __re
   const int plane = blockIdx.z, n = plane / C;
   const int oy0 = blockIdx.y * DG_T, ox0 = blockIdx.x * DG_T;
   const int pad = K / 2;
-  // frame n uses kernel (n + kern_offset) mod kern_frames when there is one kernel per frame
-  // (random_kernel_generator.py:105-113: offset -1 for DUF's two extra frames), else kernel 0
-  const float* kp = kern + (size_t)(kern_per_frame ? ((n + kern_offset) % kern_frames + kern_frames) % kern_frames : 0) * K * K;
+  const float* kp = kern + (size_t)kernel_of(src, n, kern_per_frame, kern_frames, kern_offset) * K * K;
   for (int i = threadIdx.x; i < K * K; i += 256) s_k[i] = kp[i];
   src.fill(s_lut, threadIdx.x, 256);
   if (Src::LUT) __syncthreads();
@@ -92,7 +103,7 @@ __global__ __launch_bounds__(256) void degrade_kernel(Src src, const float* __re
     row += P + 1;
   }
   if (quantise) acc = rintf(fminf(fmaxf(acc * 255.f, 0.f), 255.f)) / 255.f;  // mul(255).clamp(0,255).round().div(255)
-  y[plane * y_plane + oy * y_row + ox] = acc;
+  dst.plane(plane, Ho, Wo).store(oy, ox, acc);
 }
 
 // Register-tiled variant for the (stride, taps-per-phase) pairs the datasets produce (21-tap Gaussian: K = 27 at
@@ -102,11 +113,10 @@ __global__ __launch_bounds__(256) void degrade_kernel(Src src, const float* __re
 // inside a plane the operation is a dense J x J correlation with unit stride and a thread can own FOUR
 // consecutive outputs of a row: per (phase, jy) it reads 4 + J - 1 inputs as aligned 16-byte vectors and the J
 // weights of that row as broadcast vectors -- 5 LDS instructions for 4 J FMAs at J = 7.
-template <int S, int J, class Src>
-__global__ __launch_bounds__(128) void degrade_tiled_kernel(Src src, const float* __restrict__ kern, float* __restrict__ y,
-                                                            long long y_row, long long y_plane, int N, int C, int H, int W,
-                                                            int K, int Ho, int Wo, int kern_per_frame, int kern_frames,
-                                                            int kern_offset, int quantise) {
+template <int S, int J, class Src, class Dst>
+__global__ __launch_bounds__(128) void degrade_tiled_kernel(Src src, const float* __restrict__ kern, Dst dst, int N, int C,
+                                                            int H, int W, int K, int Ho, int Wo, int kern_per_frame,
+                                                            int kern_frames, int kern_offset, int quantise) {
   constexpr int TW = 32, TH = 16;
   constexpr int NV = (4 + J - 1 + 3) / 4;            // float4 input vectors per thread and row
   constexpr int QW = (TW - 4) + 4 * NV, QH = TH + J - 1, JP = (J + 3) / 4 * 4;
@@ -118,7 +128,7 @@ __global__ __launch_bounds__(128) void degrade_tiled_kernel(Src src, const float
   const int plane = blockIdx.z, n = plane / C;
   const int oy0 = blockIdx.y * TH, ox0 = blockIdx.x * TW;
   const int pad = K / 2;
-  const float* kp = kern + (size_t)(kern_per_frame ? ((n + kern_offset) % kern_frames + kern_frames) % kern_frames : 0) * K * K;
+  const float* kp = kern + (size_t)kernel_of(src, n, kern_per_frame, kern_frames, kern_offset) * K * K;
   for (int i = threadIdx.x; i < S * S * J * JP; i += 128) {
     const int jx = i % JP, jy = (i / JP) % J, ph = i / (JP * J);
     const int ky = jy * S + ph / S, kx = jx * S + ph % S;
@@ -189,43 +199,42 @@ __global__ __launch_bounds__(128) void degrade_tiled_kernel(Src src, const float
   }
   const int oy = oy0 + row;
   if (oy >= Ho) return;
+  const typename Dst::Plane out = dst.plane(plane, Ho, Wo);
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
     const int ox = ox0 + gx4 + o;
     if (ox >= Wo) continue;
     float v = acc[o];
     if (quantise) v = rintf(fminf(fmaxf(v * 255.f, 0.f), 255.f)) / 255.f;
-    y[plane * y_plane + oy * y_row + ox] = v;
+    out.store(oy, ox, v);
   }
 }
 
-// what a launch reads and writes, behind the checks: planes of H x W from `src`, [Ho][Wo] planes of `out` by stride
+// what a launch computes, behind the checks: planes of H x W from a source policy to [Ho][Wo] planes of a destination policy
 struct DegradeJob {
   const float* kernels;
-  float* out;
-  long long out_row, out_plane;  // floats
   int N, C, H, W, K, scale, Ho, Wo, n_kernels, kernel_offset, quantise;
 };
 
-template <int S, int J, class Src>
-static int launch_degrade_tiled(const Src& src, const DegradeJob& d, hipStream_t st) {
+template <int S, int J, class Src, class Dst>
+static int launch_degrade_tiled(const Src& src, const Dst& dst, const DegradeJob& d, hipStream_t st) {
   constexpr int NV = (4 + J - 1 + 3) / 4, QW = 28 + 4 * NV, QH = 16 + J - 1, JP = (J + 3) / 4 * 4;
   constexpr size_t lds = ((size_t)S * S * QH * QW + (size_t)S * S * J * JP + Src::LUT) * sizeof(float);
   static_assert(lds <= 64 * 1024, "phase planes must fit the default dynamic LDS limit");
   const dim3 grid(ceil_div(d.Wo, 32), ceil_div(d.Ho, 16), d.N * d.C);
-  hipLaunchKernelGGL((degrade_tiled_kernel<S, J, Src>), grid, dim3(128), lds, st, src, d.kernels, d.out, d.out_row, d.out_plane,
-                     d.N, d.C, d.H, d.W, d.K, d.Ho, d.Wo, d.n_kernels > 1 ? 1 : 0, d.n_kernels, d.kernel_offset, d.quantise);
+  hipLaunchKernelGGL((degrade_tiled_kernel<S, J, Src, Dst>), grid, dim3(128), lds, st, src, d.kernels, dst, d.N, d.C, d.H, d.W,
+                     d.K, d.Ho, d.Wo, d.n_kernels > 1 ? 1 : 0, d.n_kernels, d.kernel_offset, d.quantise);
   return check_launch("degrade_tiled_kernel");
 }
 
-// the one selection rule of dvsr_degrade_apply and dvsr_frame_degrade: the phase-plane kernel for the (stride, taps per phase)
-// pairs it is built for, the generic kernel otherwise and under DVSR_DEGRADE_GENERIC
-template <class Src>
-static int degrade_launch(const char* what, const Src& src, const DegradeJob& d, hipStream_t st) {
+// the one selection rule of dvsr_degrade_apply, dvsr_frame_degrade and dvsr_task_degrade: the phase-plane kernel for the
+// (stride, taps per phase) pairs it is built for, the generic kernel otherwise and under DVSR_DEGRADE_GENERIC
+template <class Src, class Dst>
+static int degrade_launch(const char* what, const Src& src, const Dst& dst, const DegradeJob& d, hipStream_t st) {
   if (d.N * d.C <= 65535 && !sw(Sw::DEGRADE_GENERIC)) {
     const int J = ceil_div(d.K, d.scale);
 #define DVSR_DG_CASE(S_, J_) \
-    if (d.scale == S_ && J == J_) return launch_degrade_tiled<S_, J_>(src, d, st);
+    if (d.scale == S_ && J == J_) return launch_degrade_tiled<S_, J_>(src, dst, d, st);
     DVSR_DG_CASE(4, 7) DVSR_DG_CASE(2, 13) DVSR_DG_CASE(2, 8) DVSR_DG_CASE(3, 9)
 #undef DVSR_DG_CASE
   }
@@ -233,8 +242,8 @@ static int degrade_launch(const char* what, const Src& src, const DegradeJob& d,
   const size_t lds = ((size_t)P * (P + 1) + (size_t)d.K * d.K + Src::LUT) * sizeof(float);
   const dim3 grid(ceil_div(d.Wo, DG_T), ceil_div(d.Ho, DG_T), d.N * d.C);
   DVSR_REQUIRE(grid.z <= 65535, DVSR_ERR_UNSUPPORTED, "%s: N*C = %d planes", what, d.N * d.C);
-  hipLaunchKernelGGL(degrade_kernel<Src>, grid, dim3(256), lds, st, src, d.kernels, d.out, d.out_row, d.out_plane, d.N, d.C, d.H,
-                     d.W, d.K, d.scale, d.Ho, d.Wo, d.n_kernels > 1 ? 1 : 0, d.n_kernels, d.kernel_offset, d.quantise);
+  hipLaunchKernelGGL((degrade_kernel<Src, Dst>), grid, dim3(256), lds, st, src, d.kernels, dst, d.N, d.C, d.H, d.W, d.K, d.scale,
+                     d.Ho, d.Wo, d.n_kernels > 1 ? 1 : 0, d.n_kernels, d.kernel_offset, d.quantise);
   return check_launch("degrade_kernel");
 }
 
@@ -262,8 +271,9 @@ extern "C" int dvsr_degrade_apply(const float* img, const float* kernels, float*
   if (rc != DVSR_OK) return rc;
   const int pad = K / 2;
   const int Ho = (H + 2 * pad - K) / scale + 1, Wo = (W + 2 * pad - K) / scale + 1;
-  const DegradeJob d{kernels, out, Wo, (long long)Ho * Wo, N, C, H, W, K, scale, Ho, Wo, n_kernels, kernel_offset, quantise};
-  return degrade_launch("degrade_apply", SrcPlanarF32{img, W, (long long)H * W}, d, (hipStream_t)stream);
+  const DegradeJob d{kernels, N, C, H, W, K, scale, Ho, Wo, n_kernels, kernel_offset, quantise};
+  return degrade_launch("degrade_apply", SrcPlanarF32{img, W, (long long)H * W}, DstStrided{out, Wo, (long long)Ho * Wo}, d,
+                        (hipStream_t)stream);
 }
 
 extern "C" int dvsr_frame_degrade(const void* src, const dvsr_frame_desc* sd, const float* kernel, int K, int scale,
@@ -286,12 +296,33 @@ extern "C" int dvsr_frame_degrade(const void* src, const dvsr_frame_desc* sd, co
                dst_row_stride, dst_plane_stride, Wo, Ho);
   DVSR_REQUIRE(reinterpret_cast<uintptr_t>(dst) % 4 == 0 && reinterpret_cast<uintptr_t>(kernel) % 4 == 0, DVSR_ERR_INVALID,
                "frame_degrade: misaligned fp32 destination / kernel (4 bytes)");
-  const DegradeJob d{kernel, dst, dst_row_stride, dst_plane_stride, 1, 3, Hc, Wc, K, scale, Ho, Wo, 1, 0, quantise};
+  const DegradeJob d{kernel, 1, 3, Hc, Wc, K, scale, Ho, Wo, 1, 0, quantise};
+  const DstStrided to{dst, dst_row_stride, dst_plane_stride};
   if (sd->format == DVSR_FRAME_F32_CHW)
-    return degrade_launch("frame_degrade", SrcPlanarF32{static_cast<const float*>(src), sd->row_stride, sd->plane_stride}, d,
+    return degrade_launch("frame_degrade", SrcPlanarF32{static_cast<const float*>(src), sd->row_stride, sd->plane_stride}, to, d,
                           (hipStream_t)stream);
   return degrade_launch("frame_degrade",
                         SrcBytesHWC{static_cast<const unsigned char*>(src), sd->row_stride, sd->pixel_stride,
                                     sd->format == DVSR_FRAME_U8_HWC_BGR},
-                        d, (hipStream_t)stream);
+                        to, d, (hipStream_t)stream);
+}
+
+extern "C" int dvsr_task_degrade(const dvsr_task_frame* items, const dvsr_task_frame* items_dev, int n, int format,
+                                 int pixel_stride, int H, int W, const float* kernels, int n_kernels, int K, int scale, float* dst,
+                                 int quantise, dvsr_stream_t stream) {
+  DVSR_REQUIRE(kernels && dst, DVSR_ERR_INVALID, "task_degrade: null kernels / dst");
+  DVSR_REQUIRE(H >= 1 && W >= 1 && n_kernels >= 1, DVSR_ERR_INVALID, "task_degrade: H=%d W=%d n_kernels=%d", H, W, n_kernels);
+  int rc = degrade_shape_check("task_degrade", H, W, K, scale);
+  if (rc != DVSR_OK) return rc;
+  const int pad = K / 2;
+  const int Ho = (H + 2 * pad - K) / scale + 1, Wo = (W + 2 * pad - K) / scale + 1;
+  rc = task_table_check("task_degrade", items, items_dev, n, format, pixel_stride, H, W, n_kernels, Ho == Wo);
+  if (rc != DVSR_OK) return rc;
+  DVSR_REQUIRE(reinterpret_cast<uintptr_t>(dst) % 4 == 0 && reinterpret_cast<uintptr_t>(kernels) % 4 == 0, DVSR_ERR_INVALID,
+               "task_degrade: misaligned fp32 destination / kernels (4 bytes)");
+  const DegradeJob d{kernels, n, 3, H, W, K, scale, Ho, Wo, n_kernels, 0, quantise};
+  const DstTask to{dst, items_dev};
+  if (format == DVSR_FRAME_F32_CHW) return degrade_launch("task_degrade", SrcTaskF32{items_dev}, to, d, (hipStream_t)stream);
+  return degrade_launch("task_degrade", SrcTaskBytes{items_dev, pixel_stride, format == DVSR_FRAME_U8_HWC_BGR}, to, d,
+                        (hipStream_t)stream);
 }

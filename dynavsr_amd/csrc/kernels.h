@@ -245,6 +245,12 @@ int frame_ingest_launch(const void* src, const dvsr_frame_desc& sd, float* dst, 
 // (degrade.hip) reads a source frame through it too
 int frame_desc_check(const char* what, const void* ptr, const dvsr_frame_desc* d, int Ht, int Wt, bool emit);
 
+// task.hip: the table of dvsr_task_degrade (degrade.hip) and dvsr_task_gather -- null, n, format, pixel stride, and every row of
+// the HOST copy: source, strides, fp32 alignment, flags (DVSR_TASK_TRANSPOSE only where `square`), kernel index (n_kernels = 0:
+// not looked at).  Launches nothing.
+int task_table_check(const char* what, const dvsr_task_frame* items, const dvsr_task_frame* items_dev, int n, int format,
+                     int pixel_stride, int H, int W, int n_kernels, bool square);
+
 // frame_yuv.hip: the same pair for a YCbCr 4:2:0, 4:2:2 or 4:4:4 frame of 8, 10 or 12 bits (planes at any address / pitch), on
 // the one form that both public descriptors take inside.  yuv_frame_from checks the descriptor's own part -- null, format,
 // depth -- and fills it; _check does the rest.

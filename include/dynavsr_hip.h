@@ -965,6 +965,46 @@ int dvsr_frame_imresize(const void* src, const dvsr_frame_desc* sd, int h, int w
                         long long dst_row_stride, long long dst_plane_stride, int oh, int ow, const dvsr_resize_axis* rows,
                         const dvsr_resize_axis* cols, int quantise, dvsr_stream_t stream);
 
+/* ---- a batch of meta-training tasks cut from frames on the device ----------------------------------------
+ * What VSRBase.__getitem__ (codes/data/meta_learner/vsrbase.py:135-198) does per task on the CPU -- crop N frames, blur and
+ * sub-sample them with one kernel, quantise, blur again, flip all three clips alike -- for a whole batch in a constant number
+ * of launches.  A batch is a table of n items (one per frame of every task):
+ *   src           the crop's top-left sample (channel 0 as stored), on the device, inside a frame as it was decoded
+ *   row_stride    bytes (U8 HWC) or floats (F32 CHW);  plane_stride  floats, F32 CHW only
+ *   kernel        index into kernels[n_kernels][K][K] (dvsr_task_gather ignores it)
+ *   flags         on the STORE side: DVSR_FLIP_W | DVSR_FLIP_H | DVSR_TASK_TRANSPOSE
+ * `items` is the table in host memory: the entry reads it during the call only and validates every row before anything is
+ * launched.  `items_dev` is the caller's copy of the same bytes on the device (8-byte aligned), which the kernel reads; it must
+ * stay as it is until the launch has run.  The library allocates nothing, copies nothing and never synchronises.  format is
+ * DVSR_FRAME_F32_CHW, DVSR_FRAME_U8_HWC_RGB or _BGR and pixel_stride 3 or 4 (bytes only); both hold for the whole launch, as
+ * does the crop H x W.
+ * dvsr_task_degrade: item i, plane c of dst [n,3,Ho,Wo] (contiguous) is what dvsr_degrade_apply gives for that crop with
+ *   kernels[items[i].kernel] -- ReflectionPad2d(K / 2), stride `scale`, no modcrop, Ho = (H + 2 (K / 2) - K) / scale + 1, Wo
+ *   likewise, the same choice of kernel by (scale, ceil(K / scale)) and DVSR_DEGRADE_GENERIC, the same quantiser as an option,
+ *   bit for bit -- stored through the item's flags: with r that result and f[y][x] = r[fy(y)][fx(x)] (fx, fy as in
+ *   dvsr_frame_flip), dst[y][x] = f[y][x], or f[x][y] under DVSR_TASK_TRANSPOSE.  That is the order of the reference's augment
+ *   (hflip, vflip, then the permute: preprocessing.py:209-237), applied where the reference applies it: AFTER the degradation (a
+ *   flipped input through an unflipped, centre-of-mass-shifted kernel is a different image).
+ * dvsr_task_gather: the same store with no blur, dst [n,3,H,W]: bytes as v / 255.0f (dvsr_frame_ingest's bits), fp32 copied.
+ * Bad arguments return before any launch: a null pointer (a null items[i].src among them), n < 1, a format outside the three, a
+ * pixel stride outside {3,4} for bytes, a pad K / 2 not smaller than the crop, a kernel index outside [0, n_kernels), flags
+ * outside 0 .. 7, DVSR_TASK_TRANSPOSE with Ho != Wo (degrade) or H != W (gather), a row stride shorter than a crop row (or a
+ * plane stride shorter than the crop's plane), a misaligned fp32 source, dst, kernels or table: DVSR_ERR_INVALID; 3 n > 65535, K
+ * or scale out of range: DVSR_ERR_UNSUPPORTED. */
+#define DVSR_TASK_TRANSPOSE 4
+typedef struct dvsr_task_frame {
+  const void* src;
+  long long row_stride;
+  long long plane_stride;
+  int kernel;
+  int flags;
+} dvsr_task_frame;
+int dvsr_task_degrade(const dvsr_task_frame* items, const dvsr_task_frame* items_dev, int n, int format, int pixel_stride,
+                      int H, int W, const float* kernels, int n_kernels, int K, int scale, float* dst, int quantise,
+                      dvsr_stream_t stream);
+int dvsr_task_gather(const dvsr_task_frame* items, const dvsr_task_frame* items_dev, int n, int format, int pixel_stride, int H,
+                     int W, float* dst, dvsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
