@@ -76,7 +76,15 @@ class FrameDesc(Structure):
 
 FRAME_F32_CHW, FRAME_U8_HWC_RGB, FRAME_U8_HWC_BGR, FRAME_U8_Y = 0, 1, 2, 3
 FRAME_U16_Y_MSB, FRAME_U16_Y_10, FRAME_U16_Y_12 = 4, 5, 6          # (U8_Y and these: dvsr_frame_luma_sad and dvsr_frame_score)
+FRAME_U16_HWC_RGB, FRAME_U16_HWC_BGR = 16, 17                      # rgb48le / bgr48le (pixel stride 6 or 8 bytes), depth 16
+FRAME_U8_CHW_RGB, FRAME_U8_CHW_GBR = 18, 19                        # planar bytes: torchvision's decoded image / gbrp
+FRAME_U16_CHW_RGB, FRAME_U16_CHW_GBR = 20, 21                      # planar words, the level in the low bits: frame_depth()
 FRAME_PAD_REFLECT, FRAME_PAD_REPLICATE = 0, 1
+
+
+def frame_depth(fmt, depth):
+    """DVSR_FRAME_DEPTH: a 16-bit-word format of dvsr_frame_desc with the bits of a level, 10, 12 or 16 (stored as 0)."""
+    return fmt | ((depth & 15) << 8)
 
 
 class YuvDesc(Structure):

@@ -24,7 +24,7 @@ from . import engine, hipops, optim
 # the video front and back end (video.py): what the loops below use, and every public name that used to live here
 from .video import (MAX_IMAGE_BYTES, backbone_input, choose_tile, evaluate_frames, scene_bounds, score_summary,  # noqa: F401
                     degrade_frames, stream_schedule, stream_slots, super_resolve_frames, super_resolve_video, tile_footprint, tile_origins,
-                    video_windows, _check_scores, _finish_frame, _frame_format, _frame_scoring, _ingest_cache, _resolve_cuts,
+                    video_windows, _check_scores, _finish_frame, _frame_format, _frame_scoring, _ingest_cache, _peak, _resolve_cuts,
                     _side_streams, _SCORES_LATER, _degraded_evaluation, _without_device_queries)
 
 
@@ -926,8 +926,7 @@ def evaluate_degraded(opt, model, est_model, modelcp, est_modelcp, est_model_fix
     for _ in adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, lr, gt=gt, gt_layout=lay, **kw):
         pass
     if peak is None:
-        o = kw.get('out')
-        peak = 2 ** fio.layout_depth(o) - 1 if fio.is_yuv(o) else 255
+        peak = _peak(kw.get('out'), lay)
     n = int(opt['network_G']['nframes'])
     base, adapted = (score_summary(kw[name], n, kw.get('cuts'), peak) for name in ('baseline_scores', 'scores'))
     return {'baseline': base, 'adapted': adapted, 'gain_db': adapted['mean']['psnr'] - base['mean']['psnr'],

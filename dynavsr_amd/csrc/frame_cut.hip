@@ -9,6 +9,8 @@
 //                               (word & 4095) >> 4 (yuv420p12le) -- scores mean what they mean for 8-bit video
 //     8-bit RGB / BGR (3 | 4 B) Y8 = (77 R + 150 G + 29 B + 128) >> 8
 //     fp32 planar               the same formula on quant_u8(v, 0, 1) of each channel (quant.h: the library's one quantiser)
+//     16-bit RGB / BGR words,   the same formula on the top 8 bits of each level: word >> 8 (interleaved, 3 | 4 words a pixel),
+//     integer RGB / GBR planes  (word & (2^d - 1)) >> (d - 8) or the byte itself (planes; frame_rgb.hip's formats)
 //   sad[pair] = sum over the h x w frame of |Y8_b(p) - Y8_a(p)|, an exact unsigned 64-bit integer: integer sums are
 //   associative, so the result does not depend on the order in which lanes, waves and workgroups add.
 // One thread = 4 consecutive pixels (Y plane: 16; 16-bit Y plane: 8) of a row of BOTH frames, in SAD_ROWS rows; a workgroup is 64 x 4 threads, so a
@@ -22,8 +24,10 @@
 // about 12 ns each as measured; with one row per wave a 1080 x 1920 RGB pair ended in 2160 of them, 26 us against 3 us of
 // reading.  Eight rows make it 272.
 #include <cstdint>
+#include <type_traits>
 
 #include "common.h"
+#include "frame_sample.h"
 #include "kernels.h"
 #include "quant.h"
 
@@ -31,7 +35,8 @@ namespace dvsr {
 
 constexpr int SAD_X = 64, SAD_Y = 4;   // threads of a workgroup along a row (one wave) / rows of a workgroup at a time
 constexpr int SAD_ROWS = 8;            // rows of a wave: a workgroup covers SAD_Y * SAD_ROWS rows
-enum : int { SAD_F32 = 0, SAD_YPLANE = 1, SAD_HWC3 = 3, SAD_HWC4 = 4, SAD_Y16_MSB = 5, SAD_Y16_10 = 6, SAD_Y16_12 = 7 };
+enum : int { SAD_F32 = 0, SAD_YPLANE = 1, SAD_HWC3 = 3, SAD_HWC4 = 4, SAD_Y16_MSB = 5, SAD_Y16_10 = 6, SAD_Y16_12 = 7,
+             SAD_HWC16_3 = 8, SAD_HWC16_4 = 9, SAD_CHW8 = 10, SAD_CHW16 = 11 };   // frame_rgb.hip's formats: 4 pixels a thread
 
 struct SadArgs {
   const void* a;
@@ -40,6 +45,9 @@ struct SadArgs {
   int h, w;
   long long row_stride, plane_stride, frame_stride;   // bytes (8-bit formats) / floats (F32_CHW)
   int swap;                                           // BGR
+  long long po[3];                                    // planar integer RGB / GBR: the byte offsets of the R, G and B plane
+  unsigned mask;                                      // ... and of its words: level = word & mask, luma from level >> shift
+  int shift;
 };
 
 __device__ __forceinline__ unsigned luma8(unsigned r, unsigned g, unsigned b) { return (77u * r + 150u * g + 29u * b + 128u) >> 8; }
@@ -144,6 +152,55 @@ __device__ __forceinline__ void luma8_plane16(const unsigned char* row, int x0, 
   e[1] = luma2_w16<KIND>(d4[2]) | (luma2_w16<KIND>(d4[3]) << 16);
 }
 
+// the lumas of pixels x0 .. x0 + 3 of a row of interleaved 16-bit words (PSW = 3 | 4 words a pixel), from the top 8 bits of
+// each level, one per byte (0 for a pixel beyond w); the group moves as in frame_rgb.hip (frame_sample.h: ld_words)
+template <int PSW>
+__device__ __forceinline__ unsigned luma4_hwc16(const unsigned char* row, int x0, int w, int swap) {
+  unsigned px[4][3];
+  if (x0 + 3 < w) {
+    unsigned d[2 * PSW];
+    ld_words<4 * PSW>(row + (long long)x0 * (2 * PSW), d);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) px[i][c] = word_of(d, i * PSW + c) >> 8;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        px[i][c] = x0 + i < w ? Words16::ld1(row + (long long)(x0 + i) * (2 * PSW) + 2 * c) >> 8 : 0u;
+  }
+  unsigned y4 = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y4 |= luma8(swap ? px[i][2] : px[i][0], px[i][1], swap ? px[i][0] : px[i][2]) << (8 * i);
+  return y4;
+}
+
+// the same of three planes of samples S (Bytes8 / Words16) whose rows start at row + po[c]: (level & mask) >> shift
+template <class S>
+__device__ __forceinline__ unsigned luma4_chw(const unsigned char* row, const long long po[3], int x0, int w, unsigned mask, int shift) {
+  unsigned v[3][4];
+  if (x0 + 3 < w) {
+    typename S::G4 g[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) g[c] = S::ld4(row + po[c] + (long long)x0 * S::B);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[c][i] = S::raw(g[c], i);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[c][i] = x0 + i < w ? S::ld1(row + po[c] + (long long)(x0 + i) * S::B) : 0u;
+  }
+  unsigned y4 = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y4 |= luma8((v[0][i] & mask) >> shift, (v[1][i] & mask) >> shift, (v[2][i] & mask) >> shift) << (8 * i);
+  return y4;
+}
+
 // the lumas of pixels x0 .. x0 + 3 of an fp32 planar row, one per byte (0 for a pixel beyond w)
 __device__ __forceinline__ unsigned luma4_f32(const float* row, long long plane, int x0, int w) {
   float v[3][4];
@@ -205,6 +262,16 @@ __global__ __launch_bounds__(SAD_X * SAD_Y) void frame_luma_sad_kernel(SadArgs a
       luma8_plane16<KIND>(static_cast<const unsigned char*>(a.b) + off, x0, a.w, eb);
 #pragma unroll
       for (int k = 0; k < 2; ++k) s = __builtin_amdgcn_sad_u8(ea[k], eb[k], s);
+    } else if constexpr (KIND == SAD_HWC16_3 || KIND == SAD_HWC16_4) {
+      constexpr int PSW = KIND == SAD_HWC16_3 ? 3 : 4;
+      const unsigned ya = luma4_hwc16<PSW>(static_cast<const unsigned char*>(a.a) + off, x0, a.w, a.swap);
+      const unsigned yb = luma4_hwc16<PSW>(static_cast<const unsigned char*>(a.b) + off, x0, a.w, a.swap);
+      s = __builtin_amdgcn_sad_u8(ya, yb, s);
+    } else if constexpr (KIND == SAD_CHW8 || KIND == SAD_CHW16) {
+      using S = typename std::conditional<KIND == SAD_CHW8, Bytes8, Words16>::type;
+      const unsigned ya = luma4_chw<S>(static_cast<const unsigned char*>(a.a) + off, a.po, x0, a.w, a.mask, a.shift);
+      const unsigned yb = luma4_chw<S>(static_cast<const unsigned char*>(a.b) + off, a.po, x0, a.w, a.mask, a.shift);
+      s = __builtin_amdgcn_sad_u8(ya, yb, s);
     } else {
       const unsigned ya = luma4_hwc<KIND>(static_cast<const unsigned char*>(a.a) + off, x0, a.w, a.swap);
       const unsigned yb = luma4_hwc<KIND>(static_cast<const unsigned char*>(a.b) + off, x0, a.w, a.swap);
@@ -233,15 +300,30 @@ extern "C" int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_fram
                                    unsigned long long* sad, dvsr_stream_t stream) {
   DVSR_REQUIRE(a && b && d && sad, DVSR_ERR_INVALID, "frame_luma_sad: null frame / descriptor / result");
   const bool y16 = d->format == DVSR_FRAME_U16_Y_MSB || d->format == DVSR_FRAME_U16_Y_10 || d->format == DVSR_FRAME_U16_Y_12;
+  RgbFormat rgb;
+  const bool is_rgb = frame_rgb_format(d->format, &rgb);   // frame_rgb.hip's formats
   DVSR_REQUIRE(d->format == DVSR_FRAME_F32_CHW || d->format == DVSR_FRAME_U8_HWC_RGB || d->format == DVSR_FRAME_U8_HWC_BGR ||
-                   d->format == DVSR_FRAME_U8_Y || y16,
+                   d->format == DVSR_FRAME_U8_Y || y16 || is_rgb,
                DVSR_ERR_INVALID, "frame_luma_sad: unknown frame format %d", d->format);
   DVSR_REQUIRE(d->h >= 1 && d->w >= 1 && d->h <= (1 << 20) && d->w <= (1 << 24), DVSR_ERR_INVALID,
                "frame_luma_sad: frame size h=%d w=%d outside [1, %d] x [1, %d]", d->h, d->w, 1 << 20, 1 << 24);
   DVSR_REQUIRE(pairs >= 1, DVSR_ERR_INVALID, "frame_luma_sad: pairs=%d must be positive", pairs);
   DVSR_REQUIRE(reinterpret_cast<uintptr_t>(sad) % 8 == 0, DVSR_ERR_INVALID, "frame_luma_sad: misaligned result (8 bytes)");
   int kind;
-  if (d->format == DVSR_FRAME_F32_CHW) {
+  long long po[3] = {0, 0, 0};
+  if (is_rgb) {
+    int rc = frame_rgb_check("frame_luma_sad", a, d, d->h, d->w, false);
+    if (rc == DVSR_OK) rc = frame_rgb_check("frame_luma_sad", b, d, d->h, d->w, false);
+    if (rc != DVSR_OK) return rc;
+    DVSR_REQUIRE(rgb.bytes == 1 || frame_stride % 2 == 0, DVSR_ERR_INVALID, "frame_luma_sad: odd frame stride %lld of 16-bit words",
+                 frame_stride);
+    kind = rgb.planar ? (rgb.bytes == 1 ? SAD_CHW8 : SAD_CHW16) : (d->pixel_stride == 6 ? SAD_HWC16_3 : SAD_HWC16_4);
+    if (rgb.planar) {
+      po[0] = rgb.reorder ? 2 * d->plane_stride : 0;
+      po[1] = rgb.reorder ? 0 : d->plane_stride;
+      po[2] = rgb.reorder ? d->plane_stride : 2 * d->plane_stride;
+    }
+  } else if (d->format == DVSR_FRAME_F32_CHW) {
     kind = SAD_F32;
     DVSR_REQUIRE(d->row_stride >= d->w, DVSR_ERR_INVALID, "frame_luma_sad: row stride %lld shorter than a row of %d floats",
                  d->row_stride, d->w);
@@ -283,7 +365,9 @@ extern "C" int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_fram
     const int n = pairs - first < 65535 ? pairs - first : 65535;
     const long long skip = (long long)first * frame_stride * unit;
     SadArgs args{static_cast<const char*>(a) + skip, static_cast<const char*>(b) + skip, sad + first, d->h, d->w,
-                 d->row_stride, d->plane_stride, frame_stride, d->format == DVSR_FRAME_U8_HWC_BGR};
+                 d->row_stride, d->plane_stride, frame_stride,
+                 d->format == DVSR_FRAME_U8_HWC_BGR || (is_rgb && !rgb.planar && rgb.reorder), {po[0], po[1], po[2]},
+                 is_rgb ? (1u << rgb.depth) - 1u : 0u, is_rgb ? rgb.depth - 8 : 0};
     const dim3 grid(ceil_div(ceil_div(d->w, per_thread), SAD_X), ceil_div(d->h, SAD_Y * SAD_ROWS), n);
     switch (kind) {
       case SAD_F32: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_F32>, grid, block, 0, st, args); break;
@@ -292,6 +376,10 @@ extern "C" int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_fram
       case SAD_Y16_MSB: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_Y16_MSB>, grid, block, 0, st, args); break;
       case SAD_Y16_10: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_Y16_10>, grid, block, 0, st, args); break;
       case SAD_Y16_12: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_Y16_12>, grid, block, 0, st, args); break;
+      case SAD_HWC16_3: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_HWC16_3>, grid, block, 0, st, args); break;
+      case SAD_HWC16_4: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_HWC16_4>, grid, block, 0, st, args); break;
+      case SAD_CHW8: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_CHW8>, grid, block, 0, st, args); break;
+      case SAD_CHW16: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_CHW16>, grid, block, 0, st, args); break;
       default: hipLaunchKernelGGL(frame_luma_sad_kernel<SAD_HWC4>, grid, block, 0, st, args); break;
     }
     const int rc = check_launch("frame_luma_sad_kernel");

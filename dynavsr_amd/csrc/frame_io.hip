@@ -7,6 +7,7 @@
 //   frame_ingest_*_kernel   source frame h x w -> fp32 planar [3][Hp][Wp]: v / 255.0f (a true division: v * (1/255.f) differs
 //                           from numpy on 126 of the 256 values), BGR swapped to RGB, rows / columns beyond h x w filled from
 //                           the frame itself at the bottom and right (reflect without edge repeat, or replicate)
+//   (16-bit interleaved and planar integer RGB / GBR: the same two entry points dispatch to frame_rgb.hip)
 //   frame_emit_*_kernel     fp32 planar [3][Hs][Ws] -> the top-left h x w crop as 8-bit HWC (quant_u8 of quant.h, the
 //                           quantiser of dvsr_frame_metrics) or as fp32 planar; bytes outside the crop are not touched
 // One thread = 4 consecutive pixels of a row in all three planes: three 16-byte accesses on the aligned fp32 side and 12
@@ -233,13 +234,16 @@ int frame_ingest_check(const char* what, const void* src, const dvsr_frame_desc*
                        int pad_mode) {
   int rc = frame_planar_check(what, dst, Hp, Wp, FIO_Y);
   if (rc != DVSR_OK) return rc;
-  rc = frame_desc_check(what, src, sd, Hp, Wp, false);
+  RgbFormat rgb;   // (frame_rgb.hip's formats have their own descriptor check; dvsr_frame_degrade / _imresize keep frame_desc_check alone)
+  rc = sd && frame_rgb_format(sd->format, &rgb) ? frame_rgb_check(what, src, sd, Hp, Wp, false) : frame_desc_check(what, src, sd, Hp, Wp, false);
   if (rc != DVSR_OK) return rc;
   return frame_pad_check(what, pad_mode, sd->h, sd->w, Hp, Wp);
 }
 
 // (arguments checked by frame_ingest_check)
 int frame_ingest_launch(const void* src, const dvsr_frame_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st) {
+  RgbFormat rgb;
+  if (frame_rgb_format(sd.format, &rgb)) return frame_rgb_ingest_launch(src, sd, dst, Hp, Wp, pad_mode, st);
   IngestArgs a{src, dst, sd.h, sd.w, Hp, Wp, sd.row_stride, sd.plane_stride, sd.format == DVSR_FRAME_U8_HWC_BGR, pad_mode};
   const dim3 grid(ceil_div(Wp / 4, FIO_X), ceil_div(Hp, FIO_Y)), block(FIO_X, FIO_Y);
   if (!is_u8(sd.format)) hipLaunchKernelGGL(frame_ingest_f32_kernel, grid, block, 0, st, a);
@@ -263,6 +267,13 @@ extern "C" int dvsr_frame_emit(const float* src, int Hs, int Ws, void* dst, cons
                                dvsr_stream_t stream) {
   int rc = frame_planar_check("frame_emit", src, Hs, Ws, FIO_Y);
   if (rc != DVSR_OK) return rc;
+  RgbFormat rgb;
+  if (dd && frame_rgb_format(dd->format, &rgb)) {
+    rc = frame_rgb_check("frame_emit", dst, dd, Hs, Ws, true);
+    if (rc != DVSR_OK) return rc;
+    DVSR_REQUIRE(hi > lo, DVSR_ERR_INVALID, "frame_emit: range [%g, %g]", (double)lo, (double)hi);
+    return frame_rgb_emit_launch(src, Hs, Ws, dst, *dd, lo, hi, (hipStream_t)stream);
+  }
   rc = frame_desc_check("frame_emit", dst, dd, Hs, Ws, true);
   if (rc != DVSR_OK) return rc;
   DVSR_REQUIRE(!is_u8(dd->format) || hi > lo, DVSR_ERR_INVALID, "frame_emit: range [%g, %g]", (double)lo, (double)hi);

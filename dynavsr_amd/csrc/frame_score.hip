@@ -12,6 +12,10 @@
 //   U8_Y                                     rgb: refused                            y: the byte
 //   U16_Y_MSB / _10 / _12, depth d = 10 | 12 rgb: refused                            y: the d-bit level, word >> (16 - d) (MSB)
 //                                                                                       or word & (2^d - 1) (_10 / _12)
+//   U16_HWC_RGB / _BGR, depth 16             rgb: the words, in RGB order            y: refused (no Y from RGB above 8 bits)
+//   U8_CHW_RGB / _GBR                        rgb: the bytes of the planes, as R G B  y: Y8(R, G, B)
+//   U16_CHW_RGB / _GBR, d = 10 | 12 | 16     rgb: word & (2^d - 1), as R G B         y: refused
+//   (with one of these on the other side an F32_CHW frame is quantised at its depth: quant_levels(v, lo, hi, 2^d - 1))
 // Y8 is the reference's rgb2ycbcr(only_y=True), (65.481 R + 128.553 G + 24.966 B) / 255 + 16 rounded half to even, evaluated
 // exactly in integers: num = 65481 R + 128553 G + 24966 B + 16 * 255000 (< 2^26), q = num / 255000, one more when the remainder
 // is above 127500 or equals it with q odd.  Both frames reduce to one sample domain (8-bit with 8-bit, depth d with depth d).
@@ -39,7 +43,8 @@
 namespace dvsr {
 
 constexpr int SC_W = 32, SC_H = 16, SC_IW = SC_W + 10, SC_IH = SC_H + 10;
-enum : int { SC_F32 = 0, SC_HWC = 1, SC_Y8 = 2, SC_Y16_MSB = 3, SC_Y16_LSB = 4 };
+enum : int { SC_F32 = 0, SC_HWC = 1, SC_Y8 = 2, SC_Y16_MSB = 3, SC_Y16_LSB = 4,
+             SC_HWC16 = 5, SC_CHW8 = 6, SC_CHW16 = 7 };   // frame_rgb.hip's formats (swap: BGR words / G, B, R planes)
 
 struct ScoreSide {
   const unsigned char* p;              // pixel (0, 0) of the CROP
@@ -50,8 +55,8 @@ struct ScoreSide {
 struct ScoreArgs {
   ScoreSide a, b;
   int h, w;                            // the crop
-  int luma, depth, valid;              // channel y; 8 | 10 | 12; the crop has a valid SSIM region
-  float lo, hi;
+  int luma, depth, valid;              // channel y; 8 | 10 | 12 | 16; the crop has a valid SSIM region
+  float lo, hi, top;                   // top = 2^depth - 1: an fp32 side is quantised at the depth of the comparison
   double c1, c2;
   double g[11];
   unsigned long long* sse_partials;
@@ -73,7 +78,7 @@ __device__ __forceinline__ unsigned score_sample(const ScoreSide& s, int y, int 
   if constexpr (KIND == SC_F32) {
     const unsigned char* px = row + 4ll * x;
     if constexpr (!LUMA) {
-      return (unsigned)quant_u8(*reinterpret_cast<const float*>(px + c * s.plane_bytes), A.lo, A.hi);
+      return (unsigned)quant_levels(*reinterpret_cast<const float*>(px + c * s.plane_bytes), A.lo, A.hi, A.top);
     } else {
       const float r = *reinterpret_cast<const float*>(px), g = *reinterpret_cast<const float*>(px + s.plane_bytes);
       const float b = *reinterpret_cast<const float*>(px + 2 * s.plane_bytes);
@@ -91,6 +96,18 @@ __device__ __forceinline__ unsigned score_sample(const ScoreSide& s, int y, int 
     return row[x];
   } else if constexpr (KIND == SC_Y16_MSB) {
     return (unsigned)reinterpret_cast<const unsigned short*>(row)[x] >> (16 - A.depth);
+  } else if constexpr (KIND == SC_HWC16) {          // (channel rgb alone)
+    return reinterpret_cast<const unsigned short*>(row + (long long)x * s.pixel_stride)[s.swap ? 2 - c : c];
+  } else if constexpr (KIND == SC_CHW8) {
+    const unsigned char* px = row + x;
+    if constexpr (!LUMA) {
+      return px[(s.swap ? (c + 2) % 3 : c) * s.plane_bytes];
+    } else {
+      return score_y8(px[(s.swap ? 2 : 0) * s.plane_bytes], px[(s.swap ? 0 : 1) * s.plane_bytes], px[(s.swap ? 1 : 2) * s.plane_bytes]);
+    }
+  } else if constexpr (KIND == SC_CHW16) {          // (channel rgb alone)
+    const unsigned char* px = row + 2ll * x + (s.swap ? (c + 2) % 3 : c) * s.plane_bytes;
+    return (unsigned)*reinterpret_cast<const unsigned short*>(px) & ((1u << A.depth) - 1u);
   } else {
     return (unsigned)reinterpret_cast<const unsigned short*>(row)[x] & ((1u << A.depth) - 1u);
   }
@@ -124,6 +141,12 @@ __device__ __forceinline__ void score_stage_any(const ScoreSide& s, int oy0, int
       break;
     case SC_Y8: score_stage<SC_Y8, true>(s, oy0, ox0, c, A, v); break;
     case SC_Y16_MSB: score_stage<SC_Y16_MSB, true>(s, oy0, ox0, c, A, v); break;
+    case SC_HWC16: score_stage<SC_HWC16, false>(s, oy0, ox0, c, A, v); break;
+    case SC_CHW8:
+      if (A.luma) score_stage<SC_CHW8, true>(s, oy0, ox0, c, A, v);
+      else score_stage<SC_CHW8, false>(s, oy0, ox0, c, A, v);
+      break;
+    case SC_CHW16: score_stage<SC_CHW16, false>(s, oy0, ox0, c, A, v); break;
     default: score_stage<SC_Y16_LSB, true>(s, oy0, ox0, c, A, v); break;
   }
 }
@@ -143,15 +166,15 @@ __global__ __launch_bounds__(256, 4) void score_tile_kernel(ScoreArgs A) {
     unsigned vx[NL], vy[NL];
     score_stage_any(A.a, oy0, ox0, c, A, vx);
     score_stage_any(A.b, oy0, ox0, c, A, vy);
-    unsigned own = 0;                    // <= 5 x 4095^2 < 2^27
+    unsigned long long own = 0;          // (5 x 65535^2 is beyond 32 bits)
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
       const int i = threadIdx.x + 256 * k;
       const int r = i / SC_IW, col = i - r * SC_IW;
       // a pixel this tile owns (outside the crop both samples are 0)
       if (i < SC_IH * SC_IW && (r < SC_H || last_y) && (col < SC_W || last_x)) {
-        const int d = (int)vx[k] - (int)vy[k];
-        own += (unsigned)(d * d);
+        const unsigned d = vx[k] > vy[k] ? vx[k] - vy[k] : vy[k] - vx[k];
+        own += d * d;                    // (65535^2 < 2^32)
       }
     }
     sse = own;
@@ -268,7 +291,9 @@ static int score_side(const char* which, const void* p, const dvsr_frame_desc* d
   s->plane_bytes = 0;
   switch (d->format) {
     case DVSR_FRAME_F32_CHW:
-      DVSR_REQUIRE(args->depth == 8, DVSR_ERR_INVALID, "frame_score: frame %s has 8-bit samples, depth is %d", which, args->depth);
+      // (channel rgb: quantised at the depth of the comparison; the Y8 of channel y is defined on the 8-bit image alone)
+      DVSR_REQUIRE(!luma || args->depth == 8, DVSR_ERR_INVALID, "frame_score: the Y of fp32 frame %s has 8-bit samples, depth is %d",
+                   which, args->depth);
       DVSR_REQUIRE(args->hi > args->lo, DVSR_ERR_INVALID, "frame_score: range [%g, %g] of an fp32 frame", (double)args->lo,
                    (double)args->hi);
       DVSR_REQUIRE(d->row_stride >= d->w, DVSR_ERR_INVALID, "frame_score: row stride %lld of frame %s shorter than a row of %d floats",
@@ -311,8 +336,21 @@ static int score_side(const char* which, const void* p, const dvsr_frame_desc* d
       s->pixel_stride = 2;
       break;
     }
-    default:
-      DVSR_REQUIRE(false, DVSR_ERR_INVALID, "frame_score: unknown format %d of frame %s", d->format, which);
+    default: {
+      RgbFormat f;                       // frame_rgb.hip's formats
+      DVSR_REQUIRE(frame_rgb_format(d->format, &f), DVSR_ERR_INVALID, "frame_score: unknown format %d of frame %s", d->format, which);
+      const int rc = frame_rgb_check("frame_score", p, d, d->h, d->w, false);
+      if (rc != DVSR_OK) return rc;
+      DVSR_REQUIRE(args->depth == f.depth, DVSR_ERR_INVALID, "frame_score: frame %s has %d-bit samples, depth is %d", which, f.depth,
+                   args->depth);
+      DVSR_REQUIRE(!luma || f.depth == 8, DVSR_ERR_INVALID, "frame_score: channel y on the %d-bit RGB frame %s (rgb alone)", f.depth,
+                   which);
+      s->kind = f.planar ? (f.bytes == 1 ? SC_CHW8 : SC_CHW16) : SC_HWC16;
+      s->pixel_stride = d->pixel_stride;
+      s->swap = f.reorder;
+      s->plane_bytes = f.planar ? d->plane_stride : 0;
+      break;
+    }
   }
   DVSR_REQUIRE(d->row_stride >= (long long)d->w * s->pixel_stride, DVSR_ERR_INVALID,
                "frame_score: row stride %lld of frame %s shorter than a row of %lld bytes", d->row_stride, which,
@@ -339,8 +377,8 @@ extern "C" int dvsr_frame_score(const void* a, const dvsr_frame_desc* da, const 
                "frame_score: null frame / descriptor / arguments / result / workspace");
   DVSR_REQUIRE(args->channel == DVSR_SCORE_RGB || args->channel == DVSR_SCORE_Y, DVSR_ERR_INVALID,
                "frame_score: unknown channel %d", args->channel);
-  DVSR_REQUIRE(args->depth == 8 || args->depth == 10 || args->depth == 12, DVSR_ERR_INVALID, "frame_score: depth %d (8, 10 or 12)",
-               args->depth);
+  DVSR_REQUIRE(args->depth == 8 || args->depth == 10 || args->depth == 12 || args->depth == 16, DVSR_ERR_INVALID,
+               "frame_score: depth %d (8, 10, 12 or 16)", args->depth);
   DVSR_REQUIRE(da->h >= 1 && da->w >= 1 && da->h <= SCORE_MAX_SIDE && da->w <= SCORE_MAX_SIDE, DVSR_ERR_INVALID,
                "frame_score: frame size h=%d w=%d outside [1, %d]", da->h, da->w, SCORE_MAX_SIDE);
   DVSR_REQUIRE(da->h == db->h && da->w == db->w, DVSR_ERR_INVALID, "frame_score: frame a is %d x %d, frame b is %d x %d", da->h,
@@ -361,6 +399,7 @@ extern "C" int dvsr_frame_score(const void* a, const dvsr_frame_desc* da, const 
   A.valid = A.h > 10 && A.w > 10;
   A.lo = args->lo;
   A.hi = args->hi;
+  A.top = (float)((1 << args->depth) - 1);
   const int nch = A.luma ? 1 : 3;
   const size_t need = dvsr_frame_score_workspace_bytes(nch, A.h, A.w);
   DVSR_REQUIRE(workspace_bytes >= need, DVSR_ERR_WORKSPACE, "frame_score: workspace %zu < %zu bytes", workspace_bytes, need);

@@ -59,6 +59,7 @@
 #include <cstdint>
 
 #include "frame_common.h"
+#include "frame_sample.h"
 
 namespace dvsr {
 
@@ -95,69 +96,20 @@ struct YuvEmitArgs {
   YuvCoef k;
 };
 
-template <typename T>
-__device__ __forceinline__ T ld_plain(const unsigned char* p) {
-  return __hip_atomic_load(reinterpret_cast<const T*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-template <typename T>
-__device__ __forceinline__ void st_plain(unsigned char* p, T v) {
-  __hip_atomic_store(reinterpret_cast<T*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
+// ---- a sample trait S: the groups of frame_sample.h (B bytes per sample; ld1 / ld2 / ld4, st1 / st2 / st4 in naturally aligned
+// pieces) with what a YCbCr level needs: lev(a, group, i), the level of sample i of a loaded group; word(a, level); the chroma
+// midpoint; the quotient x / d given d and its reciprocal.
 
-// ---- a sample trait S: B bytes per sample; little-endian groups of 1, 2, 4 samples at any sample-aligned address, loaded (a
-// group stays packed, G4 for four; lev(a, group, i) is the level of its sample i) and stored (from words, one per sample) in
-// naturally aligned pieces; word(a, level); the chroma midpoint; the quotient x / d given d and its reciprocal.
-
-struct Sample8 {
-  static constexpr int B = 1;
-  struct G4 { unsigned d[1]; };
+struct Sample8 : Bytes8 {
   // (a literal, as 255 is not: read from the argument struct it costs the planar ingest kernel 35 VGPRs and a wave of occupancy)
   static __device__ __forceinline__ float cm(const YuvCoef&) { return 128.0f; }
   static __device__ __forceinline__ float quot(float x, float d, float) { return x / d; }   // IEEE division
   static __device__ __forceinline__ float lev(const YuvIngestArgs&, unsigned v, int i) { return (float)((v >> (8 * i)) & 0xffu); }
   static __device__ __forceinline__ float lev(const YuvIngestArgs& a, const G4& g, int i) { return lev(a, g.d[0], i); }
   static __device__ __forceinline__ unsigned word(const YuvEmitArgs&, unsigned level) { return level; }
-  static __device__ __forceinline__ unsigned ld1(const unsigned char* p) { return ld_plain<unsigned char>(p); }
-  static __device__ __forceinline__ unsigned ld2a(const unsigned char* p) { return ld_plain<unsigned short>(p); }   // p even
-  static __device__ __forceinline__ unsigned ld2(const unsigned char* p) {
-    return (reinterpret_cast<uintptr_t>(p) & 1) ? (ld1(p) | (ld1(p + 1) << 8)) : ld2a(p);
-  }
-  static __device__ __forceinline__ G4 ld4(const unsigned char* p) {
-    const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3);
-    if (m == 0) return G4{{*reinterpret_cast<const unsigned*>(p)}};
-    if (m == 2) return G4{{ld2a(p) | (ld2a(p + 2) << 16)}};
-    return G4{{ld1(p) | (ld2a(p + 1) << 8) | (ld1(p + 3) << 24)}};
-  }
-  static __device__ __forceinline__ void st1(unsigned char* p, unsigned v) { st_plain<unsigned char>(p, (unsigned char)v); }
-  static __device__ __forceinline__ void st2a(unsigned char* p, unsigned v) { st_plain<unsigned short>(p, (unsigned short)v); }
-  static __device__ __forceinline__ void st2(unsigned char* p, const unsigned s[2]) {
-    const unsigned v = s[0] | (s[1] << 8);
-    if (reinterpret_cast<uintptr_t>(p) & 1) {
-      st1(p, v);
-      st1(p + 1, v >> 8);
-    } else {
-      st2a(p, v);
-    }
-  }
-  static __device__ __forceinline__ void st4(unsigned char* p, const unsigned s[4]) {
-    const unsigned v = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
-    const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3);
-    if (m == 0) {
-      *reinterpret_cast<unsigned*>(p) = v;
-    } else if (m == 2) {
-      st2a(p, v);
-      st2a(p + 2, v >> 16);
-    } else {
-      st1(p, v);
-      st2a(p + 1, v >> 8);
-      st1(p + 3, v >> 24);
-    }
-  }
 };
 
-struct Sample16 {
-  static constexpr int B = 2;
-  struct G4 { unsigned d[2]; };
+struct Sample16 : Words16 {
   static __device__ __forceinline__ float cm(const YuvCoef& k) { return k.cm; }
   static __device__ __forceinline__ float quot(float x, float, float inv) { return x * inv; }
   static __device__ __forceinline__ float lev(const YuvIngestArgs& a, unsigned v, int i) {   // the two words of a dword
@@ -165,53 +117,6 @@ struct Sample16 {
   }
   static __device__ __forceinline__ float lev(const YuvIngestArgs& a, const G4& g, int i) { return lev(a, g.d[i >> 1], i & 1); }
   static __device__ __forceinline__ unsigned word(const YuvEmitArgs& a, unsigned level) { return level << a.shift; }
-  static __device__ __forceinline__ unsigned ld1(const unsigned char* p) { return ld_plain<unsigned short>(p); }
-  static __device__ __forceinline__ unsigned ld2a(const unsigned char* p) { return ld_plain<unsigned>(p); }   // p 4-aligned
-  static __device__ __forceinline__ unsigned ld2(const unsigned char* p) {
-    return (reinterpret_cast<uintptr_t>(p) & 2) ? (ld1(p) | (ld1(p + 2) << 16)) : ld2a(p);
-  }
-  static __device__ __forceinline__ G4 ld4(const unsigned char* p) {
-    const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 7);
-    unsigned lo, hi;
-    if (m == 0) {
-      const unsigned long long v = ld_plain<unsigned long long>(p);
-      lo = (unsigned)v;
-      hi = (unsigned)(v >> 32);
-    } else if (m == 4) {
-      lo = ld2a(p);
-      hi = ld2a(p + 4);
-    } else {
-      const unsigned a = ld1(p), b = ld2a(p + 2), c = ld1(p + 6);
-      lo = a | (b << 16);
-      hi = (b >> 16) | (c << 16);
-    }
-    return G4{{lo, hi}};
-  }
-  static __device__ __forceinline__ void st1(unsigned char* p, unsigned v) { st_plain<unsigned short>(p, (unsigned short)v); }
-  static __device__ __forceinline__ void st2a(unsigned char* p, unsigned v) { st_plain<unsigned>(p, v); }
-  static __device__ __forceinline__ void st2(unsigned char* p, const unsigned s[2]) {
-    const unsigned v = s[0] | (s[1] << 16);
-    if (reinterpret_cast<uintptr_t>(p) & 2) {
-      st1(p, v);
-      st1(p + 2, v >> 16);
-    } else {
-      st2a(p, v);
-    }
-  }
-  static __device__ __forceinline__ void st4(unsigned char* p, const unsigned s[4]) {
-    const unsigned lo = s[0] | (s[1] << 16), hi = s[2] | (s[3] << 16);
-    const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(p) & 7);
-    if (m == 0) {
-      st_plain<unsigned long long>(p, (unsigned long long)lo | ((unsigned long long)hi << 32));
-    } else if (m == 4) {
-      st2a(p, lo);
-      st2a(p + 4, hi);
-    } else {
-      st1(p, lo);
-      st2a(p + 2, (lo >> 16) | (hi << 16));
-      st1(p + 6, hi >> 16);
-    }
-  }
 };
 
 // chroma sample (j, k) of both planes

@@ -245,6 +245,18 @@ int frame_ingest_launch(const void* src, const dvsr_frame_desc& sd, float* dst, 
 // (degrade.hip) reads a source frame through it too
 int frame_desc_check(const char* what, const void* ptr, const dvsr_frame_desc* d, int Ht, int Wt, bool emit);
 
+// frame_rgb.hip: 16-bit interleaved RGB / BGR and planar integer RGB / GBR (DVSR_FRAME_U16_HWC_* / _U8_CHW_* / _U16_CHW_*), which
+// dvsr_frame_ingest / _emit / _luma_sad / _score take beside the formats above and nothing else does.  frame_rgb_format decodes a
+// format value (false: not one of these; an unknown depth leaves depth = 0); frame_rgb_check is frame_desc_check for them.
+struct RgbFormat {
+  bool planar, reorder;     // [3][h][w] planes, else [h][w][3|4] words; BGR words / G, B, R planes
+  int bytes, depth;         // per sample: 1 or 2; bits of a level: 8, 10, 12 or 16 (0: the format names none of them)
+};
+bool frame_rgb_format(int format, RgbFormat* f);
+int frame_rgb_check(const char* what, const void* ptr, const dvsr_frame_desc* d, int Ht, int Wt, bool emit);
+int frame_rgb_ingest_launch(const void* src, const dvsr_frame_desc& sd, float* dst, int Hp, int Wp, int pad_mode, hipStream_t st);
+int frame_rgb_emit_launch(const float* src, int Hs, int Ws, void* dst, const dvsr_frame_desc& dd, float lo, float hi, hipStream_t st);
+
 // task.hip: the table of dvsr_task_degrade (degrade.hip) and dvsr_task_gather -- null, n, format, pixel stride, and every row of
 // the HOST copy: source, strides, fp32 alignment, flags (DVSR_TASK_TRANSPOSE only where `square`), kernel index (n_kernels = 0:
 // not looked at).  Launches nothing.

@@ -551,8 +551,8 @@ class StreamPlan:
     def extract_frame(self, leaves, frame, slot, cache, layout=None, pad_mode='reflect', matrix='bt601', yuv_range='limited'):
         """A decoder's frame on the GPU -- uint8 [h,w,3|4] ('hwc_rgb' / 'hwc_bgr'), fp32 [3,h,w] ('chw') or YCbCr 4:2:0
         ('nv12' / 'i420', or 'p010' / 'p012' / 'i420p10' / 'i420p12' in 16-bit words: packed or planes, frames.py; `matrix`,
-        `yuv_range`) or its 4:2:2 / 4:4:4 counterparts (frames.YUV422_LAYOUTS / YUV444_LAYOUTS), h <= H, w <= W, any offset and
-        row pitch --
+        `yuv_range`) or its 4:2:2 / 4:4:4 counterparts (frames.YUV422_LAYOUTS / YUV444_LAYOUTS), or 16-bit words / integer planes
+        of RGB (frames.RGB_LAYOUTS), h <= H, w <= W, any offset and row pitch --
         -> slot `slot` of `cache`, on the current stream: converted and padded to the plan's H x W straight into the slot
         (frames.ingest's result, without the temporary), then `extract`'s tape.  Returns the tensor(s) the launch reads."""
         from . import frames as F

@@ -42,7 +42,23 @@ frame is [3H, W] at any size and pitch.  Plane tuples are as above with those pl
 word conventions are those of the 4:2:0 layout of the same sample kind; 4:2:2 keeps the horizontal chroma filters and has no
 vertical one, 4:4:4 has none.  YUV_LAYOUTS / YUV16_LAYOUTS name the 4:2:0 layouts, YUV422_LAYOUTS / YUV444_LAYOUTS these,
 ALL_YUV_LAYOUTS all of them.  Not provided: semi-planar 4:4:4 (nv24 / p410), packed 4:2:2 (YUY2 / UYVY / v210), 4:1:1 / 4:4:0,
-planar GBR, a 'bt2020' matrix, 16-bit depth, chroma siting other than "left".
+a 'bt2020' matrix, 16-bit YCbCr, chroma siting other than "left".
+
+RGB above 8 bits and planar integer RGB (RGB_LAYOUTS; csrc/frame_rgb.hip through dvsr_frame_ingest / dvsr_frame_emit),
+never inferred from dtype or shape either -- what 16-bit PNG / TIFF / DPX, torchvision's decoders and an FFV1 archive hold:
+    'hwc_rgb16' / 'hwc_bgr16'                  uint16 / int16 [H,W,3|4]: rgb48le / bgr48le, with a fourth word rgba64le / bgra64le
+                                               (ignored on the way in; an emitted frame has three).  Depth 16.
+    'chw_rgb8' / 'chw_gbr8'                    uint8 [3,H,W]: torchvision's decoded image; ffmpeg gbrp (planes G, B, R)
+    'chw_rgb10' / 'chw_rgb12' / 'chw_rgb16',   uint16 / int16 [3,H,W]: a 16-bit PNG as torch decodes it; gbrp10le / gbrp12le /
+    'chw_gbr10' / 'chw_gbr12' / 'chw_gbr16'    gbrp16le.  The level is in the LOW d bits; higher bits are ignored in, 0 out.
+ingest: value = float32(level) / float32(2^d - 1), an IEEE division (depth 8: the v / 255 of 'hwc_rgb', the same bits); emit: the
+8-bit quantiser with 255 replaced by 2^d - 1 (clamp to min_max, rescale, x (2^d - 1), round half to even), as torch.uint8 /
+torch.uint16 of the layout's shape; emit(ingest(x)) == x.  Interleaved views (any offset, any row pitch, a pixel stride of 3 or 4
+words) and planar views (any offset, any row pitch, any plane stride that keeps the planes from overlapping) are passed by stride;
+anything else is copied once.  luma_sad takes the top 8 bits of each level; score compares the d-bit levels (channel 'rgb' alone
+above 8 bits; a float side is then quantised at that depth); degrade and imresize go through ingest(.., multiple=1) like the
+YCbCr layouts.  Not provided: separately allocated planes, rgb24-in-int32 / x2rgb10 / r210 packed words, big-endian words,
+float16 / float32 interleaved, an alpha plane or alpha out.
 
 Scene cuts (csrc/frame_cut.hip: dvsr_frame_luma_sad), for any of the layouts above:
 
@@ -125,6 +141,14 @@ _PACKED = {L.YUV_CHROMA_420: '[H*3/2, W]', L.YUV_CHROMA_422: '[2H, W]', L.YUV_CH
 _YUV_MATRIX = {'bt601': L.YUV_BT601, 'bt709': L.YUV_BT709}
 _YUV_RANGE = {'limited': L.YUV_LIMITED, 'full': L.YUV_FULL}
 _FORMAT = {'chw': L.FRAME_F32_CHW, 'hwc_rgb': L.FRAME_U8_HWC_RGB, 'hwc_bgr': L.FRAME_U8_HWC_BGR}
+# integer RGB beyond 8-bit interleaved, never inferred -> (planar, depth, the format of its descriptor, its dtypes)
+_RGB = {'hwc_rgb16': (False, 16, L.FRAME_U16_HWC_RGB, _WORDS), 'hwc_bgr16': (False, 16, L.FRAME_U16_HWC_BGR, _WORDS),
+        'chw_rgb8': (True, 8, L.FRAME_U8_CHW_RGB, _BYTES), 'chw_gbr8': (True, 8, L.FRAME_U8_CHW_GBR, _BYTES)}
+for _d in (10, 12, 16):
+    _RGB['chw_rgb%d' % _d] = (True, _d, L.frame_depth(L.FRAME_U16_CHW_RGB, _d), _WORDS)
+    _RGB['chw_gbr%d' % _d] = (True, _d, L.frame_depth(L.FRAME_U16_CHW_GBR, _d), _WORDS)
+RGB_LAYOUTS = tuple(_RGB)
+_FORMAT.update((k, v[2]) for k, v in _RGB.items())
 _PAD = {'reflect': L.FRAME_PAD_REFLECT, 'replicate': L.FRAME_PAD_REPLICATE}
 
 
@@ -150,8 +174,18 @@ def resolve_layout(frame, layout=None):
         raise ValueError("a frame must be a tensor, got %s" % type(frame).__name__)
     if layout is None:
         layout = 'hwc_rgb' if frame.dtype == torch.uint8 else 'chw'
+    if layout in _RGB:
+        planar, _, _, dtypes = _RGB[layout]
+        kind = 'uint8' if dtypes is _BYTES else 'uint16 / int16'
+        if frame.dtype not in dtypes or frame.dim() != 3 or (frame.shape[0] != 3 if planar else frame.shape[2] not in (3, 4)):
+            raise ValueError("a %s frame must be %s %s, got %s %s" % (layout, kind, '[3,H,W]' if planar else '[H,W,3] or [H,W,4]',
+                                                                      frame.dtype, tuple(frame.shape)))
+        h, w = (int(frame.shape[1]), int(frame.shape[2])) if planar else (int(frame.shape[0]), int(frame.shape[1]))
+        if h < 1 or w < 1:
+            raise ValueError("empty frame %s" % (tuple(frame.shape),))
+        return layout, h, w
     if layout not in LAYOUTS:
-        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + ALL_YUV_LAYOUTS)))
+        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + RGB_LAYOUTS + ALL_YUV_LAYOUTS)))
     if frame.dtype == torch.uint8:
         if layout == 'chw':
             raise ValueError("a uint8 frame is interleaved ('hwc_rgb' / 'hwc_bgr'), not 'chw'")
@@ -191,12 +225,34 @@ def describe(frame, layout):
             frame = frame.contiguous()
             st = frame.stride()
         return frame, L.FrameDesc(_FORMAT[layout], h, w, st[1], st[0], 1)
+    if layout in _RGB:
+        return _describe_rgb(frame, layout)
     h, w, _ = frame.shape
     st = frame.stride()
     if not (st[2] == 1 and st[1] in (3, 4) and st[0] >= w * st[1]):
         frame = frame[:, :, :3].contiguous()
         st = frame.stride()
     return frame, L.FrameDesc(_FORMAT[layout], h, w, st[0], 0, st[1])
+
+
+def _describe_rgb(frame, layout):
+    """describe() for the layouts of RGB_LAYOUTS: strides in BYTES, as for the 16-bit Y planes.  Interleaved words: any
+    sample-aligned offset and row pitch, a pixel stride of 3 or 4 words.  Planar: any sample-aligned offset, any row pitch, any
+    plane stride that keeps the planes from overlapping.  Anything else is copied once."""
+    planar, _, fmt, _ = _RGB[layout]
+    es, st = frame.element_size(), frame.stride()
+    if planar:
+        _, h, w = frame.shape
+        row = max(int(st[1]), w)
+        if not ((st[2] == 1 or w == 1) and (st[1] >= w or h == 1) and st[0] >= (h - 1) * row + w and frame.data_ptr() % es == 0):
+            frame = frame.clone(memory_format=torch.contiguous_format)
+            st, row = frame.stride(), w
+        return frame, L.FrameDesc(fmt, h, w, row * es, int(st[0]) * es, es)
+    h, w, _ = frame.shape
+    if not (st[2] == 1 and st[1] in (3, 4) and (st[0] >= w * st[1] or h == 1) and frame.data_ptr() % es == 0):
+        frame = frame[:, :, :3].clone(memory_format=torch.contiguous_format)
+        st = frame.stride()
+    return frame, L.FrameDesc(fmt, h, w, max(int(st[0]), w * int(st[1])) * es, 0, int(st[1]) * es)
 
 
 def check_yuv_names(matrix, yuv_range):
@@ -331,7 +387,8 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix=
     'nv12' / 'i420': frame is a packed uint8 [H*3/2, W] tensor or a tuple of planes (module docstring), converted with
     `matrix` / `yuv_range` to un-rounded RGB in [0,1] -- one launch, like the other layouts.  'p010' / 'p012' / 'i420p10' /
     'i420p12': the same for uint16 / int16 words of 10 or 12 bits.  The 4:2:2 and 4:4:4 layouts (module docstring): the same,
-    packed [2H, W] / [3H, W] or as planes."""
+    packed [2H, W] / [3H, W] or as planes.
+    RGB_LAYOUTS (module docstring): uint16 / int16 [H,W,3|4] words or uint8 / uint16 / int16 [3,H,W] planes, level / (2^d - 1)."""
     check_yuv_names(matrix, yuv_range)
     layout, h, w = resolve_layout(frame, layout)
     Hp, Wp = padded_size(h, w, multiple)
@@ -431,7 +488,7 @@ def degrade(frame, degradation, layout=None, *, kernel_index=0, quantise=True, o
     dev = out.device if out is not None else (first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device()))
     frame = to_device(frame, dev)
     with torch.cuda.device(dev):
-        if is_yuv(layout):
+        if is_yuv(layout) or layout in _RGB:
             # (multiple=1 pads nothing but the buffer's rows to 4 floats, which are never read here)
             frame, layout = ingest(frame, layout, 1, 'replicate', matrix=matrix, yuv_range=yuv_range), 'chw'
         frame, desc = describe(frame, layout)
@@ -538,7 +595,7 @@ def imresize(frame, scale, layout=None, *, antialiasing=True, quantise=False, mo
     dev = out.device if out is not None else (first.device if first.is_cuda else torch.device('cuda', torch.cuda.current_device()))
     frame = to_device(frame, dev)
     with torch.cuda.device(dev):
-        if is_yuv(layout):
+        if is_yuv(layout) or layout in _RGB:
             frame, layout = ingest(frame, layout, 1, 'replicate', matrix=matrix, yuv_range=yuv_range), 'chw'
         frame, desc = describe(frame, layout)
         rows, cols = _imresize_axis(h, ratio, antialiasing, dev), _imresize_axis(w, ratio, antialiasing, dev)
@@ -749,7 +806,7 @@ def tile_view(frame, layout, y, x, th, tw):
     if not (0 <= y < h and 0 <= x < w and th >= 1 and tw >= 1):
         raise ValueError("tile_view: a tile of %d x %d at (%d, %d) lies outside the %d x %d frame" % (th, tw, y, x, h, w))
     y1, x1 = min(y + th, h), min(x + tw, w)
-    if layout == 'chw':
+    if layout == 'chw' or (layout in _RGB and _RGB[layout][0]):
         return frame[:, y:y1, x:x1]
     if not is_yuv(layout):
         return frame[y:y1, x:x1]
@@ -874,10 +931,13 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     touched.  'p010' / 'p012' / 'i420p10' / 'i420p12': the same as 10- / 12-bit words, a packed torch.uint16 [h*3/2, w] tensor
     (`out`: uint16 or int16); the bits of a word that carry no level are written as 0.
     The 4:2:2 layouts: packed [2h, w], which needs an even w alone; the 4:4:4 layouts: packed [3h, w] at any size.
+    RGB_LAYOUTS: the crop as torch.uint16 [h,w,3] words ('hwc_rgb16' / 'hwc_bgr16') or as torch.uint8 / torch.uint16 [3,h,w] planes
+    of d-bit levels ('chw_*'): clamp to min_max, rescale, x (2^d - 1), round half to even; `out`: such a tensor (int16 too), any
+    offset, row pitch and plane stride.
     size = (oh, ow): the crop is first resampled to oh x ow (resize(): one more launch into a buffer of its own), and
     everything above holds for the oh x ow image -- emit(resize(sr, h, w, size), oh, ow, layout, ...), bit for bit."""
-    if layout not in LAYOUTS and not is_yuv(layout):
-        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + ALL_YUV_LAYOUTS)))
+    if layout not in LAYOUTS + RGB_LAYOUTS and not is_yuv(layout):
+        raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + RGB_LAYOUTS + ALL_YUV_LAYOUTS)))
     check_yuv_names(matrix, yuv_range)
     if size is not None:
         oh, ow = check_resize(h, w, size)
@@ -904,6 +964,17 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
                 raise ValueError("emit: out is a %d x %d frame, the crop is %d x %d" % (ho, wo, h, w))
             if planes[0].device != sr.device:
                 raise ValueError("emit: out must be on %s" % sr.device)
+    if layout in _RGB:
+        planar, _, _, dtypes = _RGB[layout]
+        shape = (3, h, w) if planar else (h, w, 3)
+        if not float(min_max[1]) > float(min_max[0]):
+            raise ValueError("emit: min_max=%r needs hi > lo" % (min_max,))
+        if out is not None:
+            if not torch.is_tensor(out) or out.dtype not in dtypes or tuple(out.shape) != shape or out.device != sr.device:
+                raise ValueError("emit: out must be %s %s on %s" % (' / '.join(str(d) for d in dtypes), list(shape), sr.device))
+            if describe(out, layout)[0] is not out or (not planar and out.stride(1) != 3):
+                raise ValueError("emit: out must have contiguous samples, a pixel stride of 3 words (an emitted frame has no "
+                                 "fourth word) and rows and planes that do not overlap")
     if not sr.is_cuda:
         raise RuntimeError("emit runs on the GPU (libdynavsr_hip); there is no CPU path")
     if sr.dtype != torch.float32:
@@ -921,7 +992,10 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
             L.check(fn(sr.data_ptr(), Hs, Ws, ctypes.byref(desc), float(min_max[0]), float(min_max[1]), L.stream()), name)
         return out
     with torch.cuda.device(sr.device):
-        if out is None:
+        if layout in _RGB:
+            if out is None:
+                out = torch.empty(shape, dtype=dtypes[0], device=sr.device)
+        elif out is None:
             out = (torch.empty((3, h, w), dtype=torch.float32, device=sr.device) if layout == 'chw' else
                    torch.empty((h, w, 3), dtype=torch.uint8, device=sr.device))
         else:
@@ -971,8 +1045,8 @@ def luma_sad(frames, layout=None):
     or the GPU, in any `layout` (None: by dtype).  Y8, the luma of a pixel, is an 8-bit integer: the Y-plane byte of an
     'nv12' / 'i420' frame as it is (`matrix` and `yuv_range` play no part), the top 8 bits of the level of a 10- / 12-bit
     Y-plane word (so that scores and thresholds mean what they mean for 8-bit video), (77 R + 150 G + 29 B + 128) >> 8 of an
-    8-bit
-    RGB / BGR pixel, and the same formula on the 8-bit values emit() would write (clamp to [0,1], x 255, round half to
+    8-bit RGB / BGR pixel or of the top 8 bits of the levels of a pixel of RGB_LAYOUTS, and the same formula on the 8-bit
+    values emit() would write (clamp to [0,1], x 255, round half to
     even) of a float frame.  The sums are exact.
     A video tensor on the GPU is one launch over all pairs; a list takes one launch per pair.  CPU frames travel as bytes
     (the Y plane alone of a 4:2:0 frame) through two staging buffers on the device, so a long video is never resident as a
@@ -1032,8 +1106,11 @@ SCORE_MAX_SIDE = 32768
 
 
 def layout_depth(layout):
-    """The bits of a sample of `layout`: 10 or 12 for the 16-bit YCbCr layouts, 8 for everything else (a float frame is scored
-    as the 8-bit image emit() would write)."""
+    """The bits of a sample of `layout`: 10 or 12 for the 16-bit YCbCr layouts, 8, 10, 12 or 16 for those of RGB_LAYOUTS, 8 for
+    everything else (a float frame is scored as the 8-bit image emit() would write, or under channel='rgb' as the image of the
+    other side's depth)."""
+    if layout in _RGB:
+        return _RGB[layout][1]
     return _YUV[layout][1] if is_yuv(layout) else 8
 
 
@@ -1060,7 +1137,12 @@ def check_score(side_a, side_b, channel='rgb', crop_border=0, min_max=(0, 1), wh
     for lay in (la, lb):
         if channel == 'rgb' and is_yuv(lay):
             raise ValueError("%s: channel='rgb' on the Y plane of a %s frame (use channel='y')" % (who, lay))
+        if channel == 'y' and lay in _RGB and layout_depth(lay) > 8:
+            raise ValueError("%s: channel='y' on a %d-bit RGB frame (%s): the reference defines no Y from RGB at that depth "
+                             "(use channel='rgb')" % (who, layout_depth(lay), lay))
     da, db = layout_depth(la), layout_depth(lb)
+    if channel == 'rgb':                               # an fp32 side is quantised at the other side's depth
+        da, db = (db if la == 'chw' else da), (da if lb == 'chw' else db)
     if da != db:
         raise ValueError("%s: %s has %d-bit samples, %s has %d-bit samples: scoring at mixed bit depths is not provided"
                          % (who, la, da, lb, db))
@@ -1091,7 +1173,9 @@ def score(a, b, layout_a=None, layout_b=None, *, channel='rgb', crop_border=0, m
     (evaluated exactly in integers), the byte of the Y plane of an 'nv12' / 'i420' frame (packed or planes), or the 10- / 12-bit
     level of the Y plane of a 16-bit layout.  Both frames must have samples of one depth.  mse is the exact integer sum of
     squared differences over the crop divided once; ssim uses L = 255 (or 2^d - 1) and is NaN when the crop has no valid region
-    (a side <= 10).  psnr(mse) converts on the host.  ValueError before the first GPU call for every bad argument."""
+    (a side <= 10).  psnr(mse) converts on the host.  ValueError before the first GPU call for every bad argument.
+    RGB_LAYOUTS: channel='rgb' compares the d-bit levels in RGB order (L = 2^d - 1; a float frame on the other side is quantised
+    at that depth), channel='y' is defined at 8 bits alone ('chw_rgb8' / 'chw_gbr8'), and both sides hold one depth."""
     la, ha, wa = resolve_layout(a, layout_a)
     lb, hb, wb = resolve_layout(b, layout_b)
     lo, hi, depth = check_score((la, ha, wa), (lb, hb, wb), channel, crop_border, min_max)

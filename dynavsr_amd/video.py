@@ -376,9 +376,9 @@ def _frame_format(who, frames, layout, out, multiple, pad_mode, matrix, yuv_rang
     the padded size, `out_size` (None where it is the SR frame's own size) and the multiple the frames are padded to
     (`multiple`, None: default_multiple; raised to a multiple of `multiple_of`).  ValueError for anything else; no GPU call."""
     lay, h, w = _video_format(frames, layout, who)
-    if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') and not fio.is_yuv(out):
+    if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') + fio.RGB_LAYOUTS and not fio.is_yuv(out):
         raise ValueError("%s: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (
-            who, out, ', '.join(fio.ALL_YUV_LAYOUTS)))
+            who, out, ', '.join(fio.RGB_LAYOUTS + fio.ALL_YUV_LAYOUTS)))
     fio.check_yuv_names(matrix, yuv_range)
     out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
     if out_size == (sr_scale * h, sr_scale * w):
@@ -400,6 +400,15 @@ def _frame_format(who, frames, layout, out, multiple, pad_mode, matrix, yuv_rang
     Hp, Wp = fio.padded_size(h, w, mult)
     fio.check_pad(h, w, Hp, -(-Wp // 4) * 4, pad_mode)
     return lay, h, w, out_fmt, Hp, Wp, out_size, mult
+
+
+def _peak(out_fmt, gt_layout=None):
+    """2^d - 1 of the samples that the scores of an `out_fmt` video against a `gt_layout` one compared: the depth of the output's
+    layout, or, for a float or 8-bit output, that of an integer ground truth (frames.check_score), else 255."""
+    for lay in (out_fmt, gt_layout):
+        if fio.is_yuv(lay) or lay in fio.RGB_LAYOUTS:
+            return 2 ** fio.layout_depth(lay) - 1
+    return 255
 
 
 _SCORES_LATER = object()      # `scores` of a check that runs ahead of the call that allocates them (evaluate_degraded)
@@ -526,6 +535,11 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     'i422p12' / 'p210' / 'p212' (packed [T, 2H, W] or planes; a packed output needs an even sW or `out_size` width alone) and the
     4:4:4 names 'i444' / 'i444p10' / 'i444p12' (packed [T, 3H, W]; any size), the 16-bit ones as the output of any input;
     everything said of the 4:2:0 layouts holds for them.
+    RGB above 8 bits and planar integer RGB (frames.RGB_LAYOUTS, csrc/frame_rgb.hip): `layout` and `out` take
+    'hwc_rgb16' / 'hwc_bgr16' (uint16 / int16 [T,H,W,3|4] words: 16-bit PNG / TIFF / DPX, rgb48le), 'chw_rgb8' / 'chw_gbr8' (uint8
+    [T,3,H,W]: torchvision's decoded images, gbrp) and 'chw_rgb10' ... 'chw_gbr16' (uint16 / int16 [T,3,H,W]: gbrp10le / 12le / 16le,
+    the level in the low bits), never inferred; `out` None yields the input's layout -- torch.uint16 (uint8 at depth 8) frames of
+    2^d levels -- and the names force such an output for any input, so an 8-bit or YCbCr source can leave as 16-bit RGB.
     A video of several scenes: `cuts` (None: one scene, the calls of before) lists the first frame of every new scene, or is
     'auto' for frames.detect_cuts(frames, layout, threshold=cut_threshold); no window then crosses a cut (video_windows), so
     every scene comes out as if it had been passed alone, and the frame cache has stream_slots' capacity.
@@ -973,7 +987,7 @@ def evaluate_frames(opt, net, frames, gt, **kw):
         pass
     if peak is None:
         o = kw.get('out') if kw.get('out') is not None else kw.get('layout')
-        peak = 2 ** fio.layout_depth(o) - 1 if fio.is_yuv(o) else 255
+        peak = _peak(o, kw.get('gt_layout'))
     return score_summary(scores, _window_length(opt, net), kw.get('cuts'), peak), scores
 
 
@@ -1116,8 +1130,9 @@ def evaluate_bicubic(opt, net, frames, gt, *, layout=None, out=None, matrix='bt6
     except (TypeError, KeyError):
         raise ValueError("%s: opt['scale'] must be 2, 3 or 4" % who)
     lay, h, w = _video_format(frames, layout, who)
-    if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') and not fio.is_yuv(out):
-        raise ValueError("%s: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (who, out, ', '.join(fio.ALL_YUV_LAYOUTS)))
+    if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') + fio.RGB_LAYOUTS and not fio.is_yuv(out):
+        raise ValueError("%s: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (
+            who, out, ', '.join(fio.RGB_LAYOUTS + fio.ALL_YUV_LAYOUTS)))
     fio.check_yuv_names(matrix, yuv_range)
     out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
     if fio.is_yuv(out_fmt) and fio.packed_needs(out_fmt, s * h, s * w):
@@ -1138,5 +1153,5 @@ def evaluate_bicubic(opt, net, frames, gt, *, layout=None, out=None, matrix='bt6
             sr = fio.imresize(frames[i], (s, 1), lay, matrix=matrix, yuv_range=yuv_range)[None]
             _finish_frame(who, sr, (s * h, s * w, s * h, s * w), out_fmt, None, 1, matrix, yuv_range, i, score_into, scores)
     if peak is None:
-        peak = 2 ** fio.layout_depth(out_fmt) - 1 if fio.is_yuv(out_fmt) else 255
+        peak = _peak(out_fmt, gt_layout)
     return score_summary(scores, n, cuts, peak), scores

@@ -394,6 +394,41 @@ int dvsr_edvr_stream_extract_frame(const dvsr_edvr_stream* stream_plan, const fl
 int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_frame_desc* desc, long long frame_stride, int pairs,
                         unsigned long long* sad, dvsr_stream_t stream);
 
+/* ---- 16-bit RGB and planar integer RGB / GBR frames -------------------------------------------------
+ * What 16-bit PNG / TIFF / DPX readers and writers, torchvision's decoders (uint8 / uint16 [3,H,W]), an FFV1 archive (gbrp,
+ * gbrp10le, gbrp12le, gbrp16le) and lossless 4:4:4 RGB codecs deliver and take: further values of dvsr_frame_desc.format for
+ * dvsr_frame_ingest, dvsr_frame_emit, dvsr_edvr_stream_extract_frame, dvsr_frame_luma_sad and dvsr_frame_score -- no new entry
+ * point, no new struct.  dvsr_frame_degrade, dvsr_frame_imresize, dvsr_task_degrade and dvsr_task_gather keep refusing them.
+ *   DVSR_FRAME_U16_HWC_RGB / _BGR   16-bit little-endian words interleaved (rgb48le / bgr48le; pixel_stride 8: rgba64le /
+ *                                   bgra64le, the fourth word ignored; an emitted frame has pixel_stride 6).  Depth 16.
+ *   DVSR_FRAME_U8_CHW_RGB / _GBR    three byte planes [3][h][w] in the order R, G, B (a decoded image) or G, B, R (gbrp)
+ *   DVSR_FRAME_U16_CHW_RGB / _GBR   three planes of 16-bit little-endian words; the level of d bits is in the LOW bits of a word,
+ *                                   higher bits are ignored on the way in and written as 0.  d is part of the format:
+ *                                   DVSR_FRAME_DEPTH(format, d), d = 10, 12 or 16 (16 is stored as 0: the bare value).
+ * Units follow the 16-bit Y planes above: row_stride and plane_stride (planar formats; ignored for interleaved ones) in BYTES,
+ * pixel_stride in bytes -- 6 or 8 for interleaved words, 1 / 2 for byte / word planes; addresses and strides of words are even.
+ * Planes may lie at any plane_stride >= (h - 1) row_stride + a row.
+ * Arithmetic, top = 2^d - 1 (exact in fp32):
+ *   ingest   level = word & top (the word itself at depth 16, the byte at depth 8); value = (float)level / (float)top, an IEEE
+ *            division (numpy's np.float32(level) / np.float32(top); depth 8: v / 255.0f, the bits of the 8-bit formats); GBR
+ *            planes and BGR words go to R, G, B; padding as for every format, on the source index
+ *   emit     t = (fminf(fmaxf(v, lo), hi) - lo) / (hi - lo), level = (int)rintf(t * (float)top): the 8-bit quantiser with 255
+ *            replaced by top, round half to even.  Nothing outside the rows of the crop is written.
+ *   luma_sad the 8-bit rule on the top 8 bits of each level: (77 R' + 150 G' + 29 B' + 128) >> 8 with X' = level >> (d - 8)
+ *   score    channel rgb alone at d > 8 (the reference defines no Y from RGB there), on the d-bit levels with L = top;
+ *            dvsr_score_args.depth = d, which then also quantises an fp32 side; both sides hold one depth
+ * Bad arguments -- an unknown depth, an odd address or stride of a word frame, a row or plane stride shorter than a row or plane,
+ * a pixel stride the format does not have (emit: 8) -- return DVSR_ERR_INVALID before any launch.
+ * Not provided: separately allocated planes, rgb24-in-int32 / x2rgb10 / r210 packed words, big-endian words, float16 / float32
+ * interleaved, an alpha plane or alpha out. */
+#define DVSR_FRAME_U16_HWC_RGB 16
+#define DVSR_FRAME_U16_HWC_BGR 17
+#define DVSR_FRAME_U8_CHW_RGB 18
+#define DVSR_FRAME_U8_CHW_GBR 19
+#define DVSR_FRAME_U16_CHW_RGB 20
+#define DVSR_FRAME_U16_CHW_GBR 21
+#define DVSR_FRAME_DEPTH(format, d) ((format) | (((d) & 15) << 8))   /* e.g. gbrp10le = DVSR_FRAME_DEPTH(DVSR_FRAME_U16_CHW_GBR, 10) */
+
 /* ---- YCbCr 4:2:0 frames in and out of the video path -----------------------------------------------
  * What a video decoder really delivers and an encoder takes: 8-bit YCbCr 4:2:0 as NV12 or planar I420 (yuv420p), every plane
  * at any address and row pitch (row_stride in BYTES), chroma planes Hc x Wc = ceil(h/2) x ceil(w/2).  Converted on the
@@ -427,7 +462,7 @@ int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_frame_desc* des
  * vertical step; emit takes the taps [1,2,1]/4 on columns 2k-1 .. 2k+1 of row y, clamped to the crop, and no vertical mean.
  * 4:4:4: a pixel's chroma is its own sample both ways.  A row stride must hold Wc samples (planar) or 2 Wc (semi-planar).
  * Not provided: semi-planar 4:4:4 (nv24 / p410: refused as an unknown format), packed 4:2:2 (YUY2 / UYVY / v210), 4:1:1 /
- * 4:4:0, planar GBR, a BT.2020 matrix, depth 16, chroma siting other than "left". */
+ * 4:4:0, a BT.2020 matrix, depth 16 (YCbCr), chroma siting other than "left".  (Planar GBR: the RGB section above.) */
 #define DVSR_YUV_NV12 0      /* plane[0] = Y [h][w], plane[1] = CbCr interleaved [Hc][Wc][2]; plane[2] ignored */
 #define DVSR_YUV_I420 1      /* plane[0] = Y, plane[1] = Cb [Hc][Wc], plane[2] = Cr [Hc][Wc] */
 #define DVSR_YUV_CHROMA_420 0

@@ -37,9 +37,18 @@
       frame is 4 bytes per pixel against 3 both ways; what comes back dominates (16 x the pixels), so the expected cost is the
       copy time of a third more bytes, where the copy is not hidden behind the network.
 
+6. 16-bit RGB and planar integer RGB / GBR (csrc/frame_rgb.hip, DESIGN 3.2w), by the method of 3 with `--rgb-repeats` repetitions;
+   the expectations are printed ahead of the figures:
+   a. with `--parent-lib PATH`: dvsr_frame_ingest (uint8 HWC 180x320) and dvsr_frame_emit (uint8 HWC 720x1280), and the NV12 / P010
+      ingest and emit kernels, of this build and of that library, alternated in this process.
+   b. every new kernel against the uint8 HWC kernel of its direction in this build, PER BYTE MOVED (fp32 bytes + sample bytes).
+   c. frames/s of a pinned hwc_rgb16 video of `--rgb-frames` frames -> hwc_rgb16 frames on the host against the same video as
+      hwc_rgb; recorded as measured.
+
 usage (GPU box): python tools/frame_io_bench.py [--h 180 --w 320 --frames 100 --repeats 5 --calls 200 --yuv-repeats 10]
                  [--parent-lib PATH] > profiles/r16_chroma_io.txt   (profiles/r12_yuv16_io.txt: parts 1 to 4;
-                 profiles/r10_yuv_io.txt: 1 to 3; profiles/r08_frame_io.txt: 1 and 2)"""
+                 profiles/r10_yuv_io.txt: 1 to 3; profiles/r08_frame_io.txt: 1 and 2)
+                 python tools/frame_io_bench.py --parts rgb --parent-lib PATH > profiles/r22_rgb_io.txt   (part 6 alone)"""
 import argparse
 import ctypes
 import os
@@ -64,7 +73,10 @@ ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--calls", type=int, default=200)
 ap.add_argument("--in-flight", type=int, default=2)
 ap.add_argument("--yuv-repeats", type=int, default=10)
-ap.add_argument("--parent-lib", default=None, help="part 5a: a libdynavsr_hip.so built from the parent commit")
+ap.add_argument("--parent-lib", default=None, help="parts 5a and 6a: a libdynavsr_hip.so built from the parent commit")
+ap.add_argument("--parts", choices=("all", "rgb"), default="all", help="rgb: part 6 alone")
+ap.add_argument("--rgb-repeats", type=int, default=11)
+ap.add_argument("--rgb-frames", type=int, default=60)
 args = ap.parse_args()
 H, W, T = args.h, args.w, args.frames
 OPT = {'scale': 4, 'network_G': {'which_model_G': 'EDVR', 'nframes': 5}}
@@ -84,6 +96,182 @@ def event_us(fn, n):
     torch.cuda.synchronize()
     return 1e3 * e0.elapsed_time(e1) / n
 
+
+from dynavsr_amd import _lib as L  # noqa: E402
+
+lib = L.lib()
+
+
+def graph_us(launch, n):
+    """Device time per launch: `n` back-to-back launches captured into one graph; returns a function that replays and times it."""
+    for _ in range(3):
+        launch()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(n):
+            launch()
+    g.replay()
+    torch.cuda.synchronize()
+
+    def timed_replay():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return 1e3 * e0.elapsed_time(e1) / n
+    return timed_replay
+
+
+def c_launch(fn, *a):
+    def go():
+        L.check(fn(*a, L.stream()), fn.__name__)
+    return go
+
+
+def compare(title, entries, reps, per_byte=False):
+    """entries: [(name, launch, algorithmic bytes)], the first one the yardstick; alternated `reps` times.  per_byte: the
+    verdict is on us per MB moved, not on us per launch."""
+    timers = [(name, graph_us(launch, args.calls), nbytes) for name, launch, nbytes in entries]
+    us = {name: [] for name, _, _ in timers}
+    for _ in range(reps):
+        for name, t, _ in timers:
+            us[name].append(t())
+    print(title)
+    base = timers[0][0]
+    mb, sb = statistics.median(us[base]), max(us[base]) - min(us[base])
+    nb = timers[0][2]
+    for name, _, nbytes in timers:
+        m, sp = statistics.median(us[name]), max(us[name]) - min(us[name])
+        if name == base:
+            verdict = "yardstick"
+        elif per_byte:
+            verdict = "%.3f us/MB against %.3f + spread %.3f of %s: %s" % (
+                1e6 * m / nbytes, 1e6 * mb / nb, 1e6 * sb / nb, base, "MET" if m / nbytes <= (mb + sb) / nb else "MISSED")
+        else:
+            verdict = "not slower than %s by more than its spread %.2f us: %s" % (base, sb, "MET" if m <= mb + sb else "MISSED")
+        print("  %-22s median %7.2f us per launch  spread %5.2f  %6.2f MB algorithmic -> %6.3f TB/s effective  (%s)" % (
+            name, m, sp, nbytes / 1e6, nbytes / m / 1e6, verdict))
+
+
+# ---- 6. 16-bit RGB and planar integer RGB / GBR (csrc/frame_rgb.hip; --parts rgb runs this part alone)
+def part_rgb():
+    reps, calls = args.rgb_repeats, args.calls
+    print("6. 16-bit RGB and planar integer RGB / GBR frames (csrc/frame_rgb.hip, DESIGN 3.2w); %d launches per replay, %d repetitions "
+          "alternated" % (calls, reps))
+    print("Expectations, written before the run:")
+    print("  1. existing kernels unchanged: dvsr_frame_ingest (uint8 HWC 180x320) and dvsr_frame_emit (uint8 HWC 720x1280) of this build "
+          "against the parent commit's library in this process, and the NV12 / P010 ingest and emit kernels (frame_yuv.hip now takes "
+          "its sample groups from frame_sample.h): each median inside the parent's own max - min spread of the parent's median.")
+    print("  2. new kernels per byte moved (fp32 bytes + sample bytes) against the uint8 HWC kernel of the same direction in this build: "
+          "no new kernel's us per MB above the yardstick's by more than the yardstick's spread -- they move wider, better-aligned "
+          "groups and have no reason to be slower.")
+    print("  3. end to end, a pinned hwc_rgb16 180x320 video of %d frames -> hwc_rgb16 720x1280 frames on the host against the same "
+          "video as hwc_rgb: twice the bytes come back, so a deficit is expected; recorded as measured, no figure fixed." % args.rgb_frames)
+    rs = np.random.RandomState(6)
+    keep = []
+    fin, fout = torch.empty((3, 180, 320), device='cuda'), torch.rand((3, 720, 1280), device='cuda')
+
+    def frame_of(lay, h, w):
+        if lay in ('hwc_rgb', 'hwc_bgr'):
+            return torch.from_numpy(rs.randint(0, 256, (h, w, 3)).astype(np.uint8)).cuda()
+        depth = frames.layout_depth(lay.rstrip('x'))
+        shape = (3, h, w) if lay.startswith('chw') else (h, w, 4 if lay.endswith('x') else 3)
+        return torch.from_numpy(rs.randint(0, 2 ** depth, shape).astype(np.uint8 if depth == 8 else np.uint16)).cuda()
+
+    def rgb_launch(lb, lay, h, w, ingest):
+        """(one launch of `lay`'s ingest or emit through library `lb`, its algorithmic bytes); 'hwc_rgb16x': four words a pixel."""
+        name = lay.rstrip('x')
+        buf = frame_of(lay, h, w)
+        t, d = frames.describe(buf, name)
+        keep.append((buf, t, d))
+        nbytes = buf.numel() * buf.element_size() + 12 * h * w
+        if ingest:
+            return c_launch(lb.dvsr_frame_ingest, t.data_ptr(), ctypes.byref(d), fin.data_ptr(), h, w, L.FRAME_PAD_REFLECT), nbytes
+        return c_launch(lb.dvsr_frame_emit, fout.data_ptr(), h, w, t.data_ptr(), ctypes.byref(d), ctypes.c_float(0.0),
+                        ctypes.c_float(1.0)), nbytes
+
+    if args.parent_lib:
+        parent = ctypes.CDLL(args.parent_lib)
+        for name in ("dvsr_frame_ingest", "dvsr_frame_emit", "dvsr_frame_ingest_yuv", "dvsr_frame_emit_yuv", "dvsr_frame_ingest_yuv16",
+                     "dvsr_frame_emit_yuv16"):
+            getattr(parent, name).argtypes, getattr(parent, name).restype = getattr(lib, name).argtypes, getattr(lib, name).restype
+        print("6a. the existing kernels of this build against those of %s" % os.path.basename(args.parent_lib))
+        for ingest, (h, w) in ((True, (180, 320)), (False, (720, 1280))):
+            what = "%s hwc_rgb %dx%d" % ("ingest" if ingest else "emit", h, w)
+            entries = [("%s %s" % (who, what),) + rgb_launch(lb, 'hwc_rgb', h, w, ingest) for who, lb in (("parent", parent), ("this build", lib))]
+            compare(what, entries, reps)
+        for lay in ('nv12', 'p010'):
+            for ingest, (h, w), plane in ((True, (180, 320), fin), (False, (720, 1280), fout)):
+                depth = frames.layout_depth(lay)
+                buf = torch.from_numpy((rs.randint(0, 2 ** depth, (h * 3 // 2, w)) << (16 - depth if depth > 8 else 0)).astype(
+                    np.uint8 if depth == 8 else np.uint16)).cuda()
+                planes, d = frames.describe_yuv(frames.yuv_planes(buf, lay)[0], lay, h, w, copy=ingest)
+                keep.append((buf, planes, d))
+                suffix = "yuv16" if depth > 8 else "yuv"
+                entries = []
+                for who, lb in (("parent", parent), ("this build", lib)):
+                    if ingest:
+                        go = c_launch(getattr(lb, "dvsr_frame_ingest_" + suffix), ctypes.byref(d), plane.data_ptr(), h, w, L.FRAME_PAD_REFLECT)
+                    else:
+                        go = c_launch(getattr(lb, "dvsr_frame_emit_" + suffix), plane.data_ptr(), h, w, ctypes.byref(d), ctypes.c_float(0.0),
+                                      ctypes.c_float(1.0))
+                    entries.append(("%s %s %s" % (who, "ingest" if ingest else "emit", lay), go,
+                                    buf.numel() * buf.element_size() + 12 * h * w))
+                compare("%s %s %dx%d" % ("ingest" if ingest else "emit", lay, h, w), entries, reps)
+    else:
+        print("6a. NOT measured: no --parent-lib")
+    print("6b. every new kernel against the uint8 HWC kernel of its direction in this build, per byte moved")
+    for ingest, (h, w), lays in ((True, (180, 320), ('hwc_rgb', 'hwc_rgb16', 'hwc_rgb16x', 'chw_rgb8', 'chw_gbr10', 'chw_rgb16')),
+                                 (False, (720, 1280), ('hwc_rgb', 'hwc_rgb16', 'chw_rgb8', 'chw_gbr10', 'chw_rgb16'))):
+        entries = [("%s %s" % ("ingest" if ingest else "emit", lay),) + rgb_launch(lib, lay, h, w, ingest) for lay in lays]
+        compare("%s %dx%d" % ("ingest" if ingest else "emit", h, w), entries, reps, per_byte=True)
+    del keep[:]
+    # 6c. end to end
+    n, hh, ww = args.rgb_frames, 180, 320
+    edvr = EDVR()
+    edvr.load_state_dict(synth.edvr_state_dict(0))
+    edvr = edvr.cuda()
+    clip = synth.clip(1, 1, 10, hh, ww, smooth=False)[0].permute(0, 2, 3, 1)                          # [10,H,W,3] in [0,1]
+    v8 = torch.cat([(clip * 255).round().to(torch.uint8)] * ((n + 9) // 10))[:n].contiguous().pin_memory()
+    v16 = torch.from_numpy(np.concatenate([(clip.numpy() * 65535).round().astype(np.uint16)] * ((n + 9) // 10))[:n].copy()).pin_memory()
+    o8 = torch.empty((n, 4 * hh, 4 * ww, 3), dtype=torch.uint8).pin_memory()
+    o16 = torch.empty((n, 4 * hh, 4 * ww, 3), dtype=torch.uint16).pin_memory()
+
+    def path(video, out, layout):
+        def go():
+            for i, sr in enumerate(adapt.super_resolve_frames(OPT, edvr, video, in_flight=args.in_flight, layout=layout)):
+                out[i].copy_(sr, non_blocking=True)
+            torch.cuda.synchronize()
+        return go
+
+    def fps(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        return n / (time.perf_counter() - t0)
+    p16, p8 = path(v16, o16, 'hwc_rgb16'), path(v8, o8, 'hwc_rgb')
+    p16()
+    p8()
+    f16, f8 = [], []
+    for _ in range(reps):
+        f16.append(fps(p16))
+        f8.append(fps(p8))
+    m16, m8 = statistics.median(f16), statistics.median(f8)
+    print("6c. video %d frames %dx%d pinned host -> %dx%d host, in_flight %d, %d repetitions alternated" % (
+        n, hh, ww, 4 * hh, 4 * ww, args.in_flight, reps))
+    print("  hwc_rgb16 in, hwc_rgb16 out (%.2f MB in, %.2f MB back per frame)  median %7.1f frames/s  spread %5.1f  (%s)" % (
+        6 * hh * ww / 1e6, 96 * hh * ww / 1e6, m16, max(f16) - min(f16), " ".join("%.1f" % v for v in f16)))
+    print("  hwc_rgb in, hwc_rgb out     (%.2f MB in, %.2f MB back per frame)  median %7.1f frames/s  spread %5.1f  (%s)" % (
+        3 * hh * ww / 1e6, 48 * hh * ww / 1e6, m8, max(f8) - min(f8), " ".join("%.1f" % v for v in f8)))
+    print("  hwc_rgb16 - hwc_rgb = %+.1f frames/s (%+.1f %%), as measured; twice the bytes travel both ways" % (
+        m16 - m8, 100 * (m16 - m8) / m8))
+
+
+if args.parts == 'rgb':
+    part_rgb()
+    sys.exit(0)
 
 r = np.random.RandomState(0)
 for (h, w) in ((180, 320), (480, 854)):
@@ -157,64 +345,6 @@ print("  new - baseline = %+.1f frames/s (%+.1f %%); baseline spread %.1f -> %s"
 
 
 # ---- 3. the YCbCr 4:2:0 pair next to the HWC kernels
-from dynavsr_amd import _lib as L  # noqa: E402
-
-lib = L.lib()
-
-
-def graph_us(launch, n):
-    """Device time per launch: `n` back-to-back launches captured into one graph; returns a function that replays and times it."""
-    for _ in range(3):
-        launch()
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(n):
-            launch()
-    g.replay()
-    torch.cuda.synchronize()
-
-    def timed_replay():
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        return 1e3 * e0.elapsed_time(e1) / n
-    return timed_replay
-
-
-def c_launch(fn, *a):
-    def go():
-        L.check(fn(*a, L.stream()), fn.__name__)
-    return go
-
-
-def compare(title, entries, reps, per_byte=False):
-    """entries: [(name, launch, algorithmic bytes)], the first one the yardstick; alternated `reps` times.  per_byte: the
-    verdict is on us per MB moved, not on us per launch."""
-    timers = [(name, graph_us(launch, args.calls), nbytes) for name, launch, nbytes in entries]
-    us = {name: [] for name, _, _ in timers}
-    for _ in range(reps):
-        for name, t, _ in timers:
-            us[name].append(t())
-    print(title)
-    base = timers[0][0]
-    mb, sb = statistics.median(us[base]), max(us[base]) - min(us[base])
-    nb = timers[0][2]
-    for name, _, nbytes in timers:
-        m, sp = statistics.median(us[name]), max(us[name]) - min(us[name])
-        if name == base:
-            verdict = "yardstick"
-        elif per_byte:
-            verdict = "%.3f us/MB against %.3f + spread %.3f of %s: %s" % (
-                1e6 * m / nbytes, 1e6 * mb / nb, 1e6 * sb / nb, base, "MET" if m / nbytes <= (mb + sb) / nb else "MISSED")
-        else:
-            verdict = "not slower than %s by more than its spread %.2f us: %s" % (base, sb, "MET" if m <= mb + sb else "MISSED")
-        print("  %-22s median %7.2f us per launch  spread %5.2f  %6.2f MB algorithmic -> %6.3f TB/s effective  (%s)" % (
-            name, m, sp, nbytes / 1e6, nbytes / m / 1e6, verdict))
-
-
 h, w = 180, 320
 rgb = torch.from_numpy(r.randint(0, 256, (h, w, 3)).astype(np.uint8)).cuda()
 packed = torch.from_numpy(r.randint(0, 256, (h * 3 // 2, w)).astype(np.uint8)).cuda()
@@ -422,3 +552,5 @@ print("  p010 in, p010 out (%.2f MB in, %.2f MB back per frame)   median %7.1f f
     3 * H * W / 1e6, 12 * H * 4 * W / 1e6, m0, s0, " ".join("%.1f" % v for v in f0)))
 print("  p210 - p010 = %+.1f frames/s (%+.1f %%); p010 spread %.1f; 4 bytes per pixel against 3 travel both ways -> %s" % (
     m2 - m0, 100 * (m2 - m0) / m0, s0, "inside the p010 spread" if m2 >= m0 - s0 else "below the p010 path by more than its spread"))
+
+part_rgb()
