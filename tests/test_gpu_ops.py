@@ -145,8 +145,18 @@ def test_mdcn_rejects_unsupported(ops):
                          1, 1, 1, 4)
 
 
-@pytest.mark.parametrize("scale,mul,h,w", [(2, 1.0, 9, 13), (2, 2.0, 4, 4), (2, 2.0, 45, 80), (2, 1.0, 11, 20), (4, 1.0, 16, 16), (4, 1.0, 7, 5)])
+@pytest.mark.parametrize("scale,mul,h,w", [
+    (2, 1.0, 9, 13), (2, 2.0, 4, 4), (2, 2.0, 45, 80), (2, 1.0, 11, 20), (4, 1.0, 16, 16), (4, 1.0, 7, 5),
+    (2, 1.0, 5, 6),    # S = 2 with W % 4 == 2: upsample_bilinear_fwd4_kernel at S = 2, and the 2x backward
+    (2, 2.0, 1, 8),    # H = 1: all three rows of the 2x forward clamp to row 0; the generic backward
+    (2, 1.0, 3, 1),    # W = 1: the scalar forward, the generic backward
+    (3, 1.0, 4, 4),    # S = 3 through the 4-wide kernel
+    (3, 0.5, 5, 3),    # S = 3, scalar
+    (1, 1.0, 3, 5),    # S = 1: the identity times mul
+])
 def test_upsample_bilinear(ops, scale, mul, h, w):
+    """upsample_bilinear_fwd (misc.hip) dispatches on S, W % 4 and the alignment, its backward on S, H >= 2 and W >= 2: every
+    branch of both (and, in a child under DVSR_UP2=4, the four-columns-per-thread 2x kernel: test_gpu_switch_arms.py)."""
     x = rnd(2, 3, h, w, seed=1).requires_grad_()
     ref = F.interpolate(x, scale_factor=scale, mode="bilinear", align_corners=False) * mul
     got = ops.upsample_bilinear(dev(x.detach()), scale, mul)
@@ -167,9 +177,33 @@ def test_pool3s2(ops, h, w):
     assert relerr(ops.pool3s2_backward(dev(x.detach()), dev(g1), dev(g2)), gref) < 1e-6
 
 
-def test_tsa_gate_and_blend(ops):
-    b, n, c, h, w = 2, 5, 64, 6, 10
-    emb = rnd(b, n, c, h, w, seed=1, scale=0.3).requires_grad_()
+@pytest.mark.parametrize("h,w", [(9, 7), (4, 4), (1, 5), (6, 1), (2, 2)])
+def test_pool3s2_ties(ops, h, w):
+    """Integer-valued inputs from {0, 1, 2}: most 3x3 windows hold several maxima, so pool3s2_bwd_kernel's rule -- the gradient
+    goes to the FIRST maximum in row-major window order -- decides where it did not with Gaussian inputs (test_pool3s2).  At
+    these five sizes with such inputs torch's CPU backward through F.max_pool2d routes each window's gradient to that same
+    element (checked on the CPU), so fp64 autograd is the reference; sizes with one row, one column and a single window."""
+    x = torch.from_numpy(np.random.RandomState(7).randint(0, 3, (2, 5, h, w)).astype(np.float64)).requires_grad_()
+    rmax, ravg = F.max_pool2d(x, 3, 2, 1), F.avg_pool2d(x, 3, 2, 1)
+    win = F.unfold(F.pad(x.detach(), (1, 1, 1, 1), value=-1.0), 3, stride=2).view(2, 5, 9, -1)
+    tied = (win == win.max(2, keepdim=True)[0]).sum(2) > 1
+    assert float(tied.double().mean()) >= 0.2, "the windows were meant to hold several maxima"   # (0.68 at 9x7 and 4x4, 0.20 at 1x5)
+    gmax, gavg = ops.pool3s2(dev(x.detach()))
+    assert gmax.shape == rmax.shape and gavg.shape == ravg.shape
+    assert relerr(gmax, rmax) == 0 and relerr(gavg, ravg) < 1e-6
+    g1, g2 = rnd(*rmax.shape, seed=2), rnd(*rmax.shape, seed=3)
+    (gref,) = torch.autograd.grad([rmax, ravg], x, [g1, g2])
+    assert relerr(ops.pool3s2_backward(dev(x.detach()), dev(g1), dev(g2)), gref) < 1e-6
+
+
+@pytest.mark.parametrize("b,n,c,h,w", [
+    (2, 5, 64, 6, 10),
+    (1, 3, 13, 5, 7),     # HW = 35 is odd: the scalar gate under every DVSR_TSA_V; C = 13 leaves a remainder in the unroll-8 loops; the blend has 455 elements: its scalar kernel
+    (1, 7, 128, 3, 6),    # EDVR-L's N and C; HW = 18: the 2-pixel kernel by default, the scalar one under DVSR_TSA_V=4
+    (2, 1, 8, 4, 4),      # N = 1
+])
+def test_tsa_gate_and_blend(ops, b, n, c, h, w):
+    emb =rnd(b, n, c, h, w, seed=1, scale=0.3).requires_grad_()
     ref_ = rnd(b, c, h, w, seed=2, scale=0.3).requires_grad_()
     al = rnd(b, n, c, h, w, seed=3).requires_grad_()
     cor = torch.sigmoid((emb * ref_.unsqueeze(1)).sum(2))
