@@ -95,6 +95,8 @@ class YuvDesc(Structure):
 
 YUV_NV12, YUV_I420 = 0, 1
 YUV_CHROMA_420, YUV_CHROMA_422, YUV_CHROMA_444 = 0, 1, 2          # format = form | chroma << 4, of both descriptors
+# the same field with a chroma siting other than "left" (DESIGN 3.2x): a pair of sub-sampling and siting
+YUV_CHROMA_420_CENTER, YUV_CHROMA_420_TOPLEFT, YUV_CHROMA_422_CENTER = 4, 5, 6
 
 
 def yuv_format(form, chroma):
@@ -103,6 +105,7 @@ def yuv_format(form, chroma):
 
 
 YUV_BT601, YUV_BT709 = 0, 1
+YUV_BT2020NC = 9                                                  # H.273's MatrixCoefficients code
 YUV_LIMITED, YUV_FULL = 0, 1
 
 

@@ -767,7 +767,7 @@ def adapt_multiple(opt):
 
 
 def _adapt_arguments(opt, model, frames, padding, layout, out, pad_mode, multiple, matrix, yuv_range, cuts, cut_threshold, out_size,
-                     gt, gt_layout, score, crop_border, scores, baseline_scores, losses, baseline):
+                     gt, gt_layout, score, crop_border, scores, baseline_scores, losses, baseline, siting='left'):
     """The first stage of adapt_frames: its arguments checked and resolved into one record.  No GPU call, except for what
     cuts='auto' (frames.detect_cuts) asks for, behind every other check."""
     from types import SimpleNamespace
@@ -788,7 +788,7 @@ def _adapt_arguments(opt, model, frames, padding, layout, out, pad_mode, multipl
     if out_size is not None:
         out_size = fio.check_size(out_size, "adapt_frames: out_size")
     lay, h, w, out_fmt, Hp, Wp, out_size, mult = _frame_format(who, frames, layout, out, multiple, pad_mode, matrix, yuv_range,
-                                                               out_size, sr_scale, M, 1)
+                                                               out_size, sr_scale, M, 1, siting)
     score_into = _frame_scoring(who, T, gt, gt_layout, scores, score, crop_border, out_fmt, out_size, sr_scale, h, w, matrix,
                                 yuv_range)
     if baseline_scores is not None:
@@ -824,7 +824,7 @@ def _adapt_arguments(opt, model, frames, padding, layout, out, pad_mode, multipl
 def adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, frames, padding='new_info', *, layout=None,
                  out=None, pad_mode='reflect', multiple=None, matrix='bt601', yuv_range='limited', cuts=None,
                  cut_threshold=10.0, out_size=None, gt=None, gt_layout=None, score='rgb', crop_border=0, scores=None,
-                 baseline_scores=None, losses=None, baseline=True, overlap=True, frames_per_batch=1):
+                 baseline_scores=None, losses=None, baseline=True, overlap=True, frames_per_batch=1, siting='left'):
     """Test-time adaptation of a decoded VIDEO (test_dynavsr.py:197-283 without the caller cutting, cropping or converting
     clips): for every frame, in order, yields (baseline frame | None, adapted frame) -- the un-adapted network's output and the
     output of the copies adapted on that frame's window, both in the format super_resolve_frames would yield for the same
@@ -854,10 +854,11 @@ def adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, f
     from . import frames as fio
     who = "adapt_frames"
     a = _adapt_arguments(opt, model, frames, padding, layout, out, pad_mode, multiple, matrix, yuv_range, cuts, cut_threshold,
-                         out_size, gt, gt_layout, score, crop_border, scores, baseline_scores, losses, baseline)
+                         out_size, gt, gt_layout, score, crop_border, scores, baseline_scores, losses, baseline, siting)
     lay, h, w, out_fmt, Hp, Wp, out_size, mult = a.lay, a.h, a.w, a.out_fmt, a.Hp, a.Wp, a.out_size, a.mult
     sr_scale, score_into, region, windows, n = a.sr_scale, a.score_into, a.region, a.windows, a.n
-    ingested = _ingest_cache(lambda j: fio.ingest(frames[j], lay, mult, pad_mode, matrix=matrix, yuv_range=yuv_range), 2 * n)
+    ingested = _ingest_cache(lambda j: fio.ingest(frames[j], lay, mult, pad_mode, matrix=matrix, yuv_range=yuv_range, siting=siting),
+                             2 * n)
 
     def clips():
         for win in windows:
@@ -865,7 +866,7 @@ def adapt_frames(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, f
 
     def finished(i, sr, into):
         return _finish_frame(who, sr, (h, w, Hp, Wp), out_fmt, out_size, sr_scale, matrix, yuv_range, i,
-                             score_into if into is not None else None, into)
+                             score_into if into is not None else None, into, siting=siting)
     results = adapt_video(opt, model, est_model, modelcp, est_modelcp, est_model_fixed, clips(), overlap=overlap,
                           frames_per_batch=frames_per_batch, region=region, baseline=baseline)
     for i, (base, r) in enumerate(results):
@@ -915,9 +916,9 @@ def evaluate_degraded(opt, model, est_model, modelcp, est_modelcp, est_model_fix
     b = dict(_ADAPT_FRAMES_DEFAULTS, gt=gt, gt_layout=lay, **check)
     _adapt_arguments(opt, model, stand_in, *[b[k] for k in (
         'padding', 'layout', 'out', 'pad_mode', 'multiple', 'matrix', 'yuv_range', 'cuts', 'cut_threshold', 'out_size', 'gt',
-        'gt_layout', 'score', 'crop_border', 'scores', 'baseline_scores', 'losses', 'baseline')])
+        'gt_layout', 'score', 'crop_border', 'scores', 'baseline_scores', 'losses', 'baseline', 'siting')])
     lr = degrade_frames(hr, degradation, layout=lay, quantise=quantise, matrix=kw.get('matrix', 'bt601'),
-                        yuv_range=kw.get('yuv_range', 'limited'))
+                        yuv_range=kw.get('yuv_range', 'limited'), siting=kw.get('siting', 'left'))
     if isinstance(kw.get('cuts'), str) and kw['cuts'] == 'auto':
         kw['cuts'] = fio.detect_cuts(lr, 'chw', threshold=kw.get('cut_threshold', 10.0))
     for name in ('scores', 'baseline_scores'):

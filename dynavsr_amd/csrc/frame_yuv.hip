@@ -15,7 +15,7 @@
 // The network computes on fp32 planar RGB [3][Hp][Wp] in [0,1].
 //
 // The arithmetic (DESIGN 3.2k and 3.2m say the same), s = 2^(d-8):
-//   matrix  BT601: Kr = 0.299, Kb = 0.114;  BT709: Kr = 0.2126, Kb = 0.0722;  Kg = 1 - Kr - Kb
+//   matrix  BT601: Kr = 0.299, Kb = 0.114;  BT709: Kr = 0.2126, Kb = 0.0722;  BT2020NC: Kr = 0.2627, Kb = 0.0593;  Kg = 1 - Kr - Kb
 //   range   H.273 at depth d.  LIMITED: y0 = 16 s, ys = 219 s, cs = 224 s;  FULL: y0 = 0, ys = cs = 2^d - 1;  chroma mid cm = 128 s
 //   BT601 + LIMITED at d = 8 are the reference's ycbcr2rgb / rgb2ycbcr ("same as matlab", data/util.py:234-299).
 //   siting  MPEG-2 / H.264 "left": chroma sample (j, k) sits on luma column 2k, midway between luma rows 2j and 2j+1.
@@ -56,6 +56,28 @@
 // chroma group is two rows of 2 samples (4:2:2 planar), two rows of two CbCr pairs (4:2:2 semi-planar) or two rows of 4 samples
 // (4:4:4), each at the same multiple of its size inside its row as the 4:2:0 group, so the choice of pieces is still the row's.
 // Every CS_420 line is the line it was: those instantiations compile to what they compiled to before the axis.
+//
+// Chroma siting is a fourth compile-time axis SITE, beside S, SEMI and CS, left by default; the chroma field of a
+// descriptor's format names a pair of sub-sampling and siting, which yuv_frame_from splits.  Chroma sample (j, k) sits at luma
+// position (4:2:2: y is the luma row itself)
+//               x          y
+//     left      2k         2j + 1/2
+//     center    2k + 1/2   2j + 1/2
+//     topleft   2k         2j
+//   ingest  linear interpolation at the luma pixel's position, indices clamped to the plane, k = x >> 1, j = y >> 1:
+//     horizontal H(j, x)   co-sited (left, topleft): Ch above
+//                          center: 0.75 C[j][k] + 0.25 C[j][max(k-1, 0)] (x even) | 0.75 C[j][k] + 0.25 C[j][min(k+1, Wc-1)] (x odd)
+//     vertical (4:2:0)     midway (left, center): 0.75 H(j) + 0.25 H(j -+ 1 clamped) above
+//                          co-sited (topleft): H(j, x) (y even) | (H(j, x) + H(min(j+1, Hc-1), x)) / 2 (y odd)
+//     (multiples of 1/16 of a level below 2^12: exact in fp32 in any evaluation order)
+//   emit    filters centred on the chroma sample's position, indices clamped to the crop, on the per-pixel cb, cr:
+//     horizontal           co-sited: [1,2,1]/4 on 2k-1, 2k, 2k+1 above;  center: the mean of columns 2k and min(2k+1, w-1)
+//     vertical (4:2:0)     midway: the mean of rows 2j and min(2j+1, h-1) above
+//                          co-sited: [1,2,1]/4 on rows max(2j-1, 0), 2j, min(2j+1, h-1)
+//   The luma plane does not depend on siting.  What a lane reads beyond the left kernels: ingest center one more chroma column,
+//   max(k0-1, 0), per chroma row; ingest topleft chroma rows j and min(j+1, Hc-1) only; emit topleft a third fp32 row,
+//   max(y0-1, 0); emit center no left neighbour.  Every SITE_LEFT line is the line it was.  The new instantiations fuse the
+//   products of the matrix step by name, as 4:2:2 and 4:4:4 do.
 #include <cstdint>
 
 #include "frame_common.h"
@@ -66,6 +88,8 @@ namespace dvsr {
 constexpr int YUV_X = 64, YUV_Y = 4;   // threads of a workgroup along a row (one wave) / block rows of a workgroup
 // the chroma sub-sampling CS of a kernel: the chroma field of a descriptor's format
 constexpr int CS_420 = DVSR_YUV_CHROMA_420, CS_422 = DVSR_YUV_CHROMA_422, CS_444 = DVSR_YUV_CHROMA_444;
+// the chroma siting SITE of a kernel (kernels.h: YuvFrame::siting)
+constexpr int SITE_LEFT = YUV_SITE_LEFT, SITE_CENTER = YUV_SITE_CENTER, SITE_TOPLEFT = YUV_SITE_TOPLEFT;
 
 // (what the 8-bit kernels read comes first and together: their scalar loads of it stay few)
 struct YuvCoef {
@@ -153,10 +177,86 @@ __device__ __forceinline__ void chroma3(const YuvIngestArgs& a, int j, int k0, i
 
 __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
+// the horizontal step of a block inside the frame, SITE_CENTER and SITE_TOPLEFT: chroma columns k0, k0 + 1, k2 (c) and
+// max(k0 - 1, 0) (cm, center alone) of one chroma row -> luma columns x0 .. x0 + 3
+template <int SITE>
+__device__ __forceinline__ void chroma_h4(const float c[3], float cm, float h[4]) {
+  if constexpr (SITE == SITE_CENTER) {
+    h[0] = 0.75f * c[0] + 0.25f * cm;
+    h[1] = 0.75f * c[0] + 0.25f * c[1];
+    h[2] = 0.75f * c[1] + 0.25f * c[0];
+    h[3] = 0.75f * c[1] + 0.25f * c[2];
+  } else {
+    h[0] = c[0];
+    h[1] = (c[0] + c[1]) * 0.5f;
+    h[2] = c[1];
+    h[3] = (c[1] + c[2]) * 0.5f;
+  }
+}
+
+// SITE_CENTER and SITE_TOPLEFT: the second chroma column / row of luma index s whose first is s >> 1 (n: of the plane), and the
+// weight of the first -- center and midway 0.75, co-sited 0.5 (an even co-sited index is its own neighbour)
+template <bool COSITED>
+__device__ __forceinline__ int chroma_other(int s, int n) {
+  const int k = s >> 1;
+  return (s & 1) ? min(k + 1, n - 1) : (COSITED ? k : max(k - 1, 0));
+}
+template <bool COSITED>
+constexpr float chroma_weight() { return COSITED ? 0.5f : 0.75f; }
+
+// 4:2:0, SITE_CENTER and SITE_TOPLEFT: the chroma of a 4 x 2 block inside the frame, on the luma grid
+template <class S, bool SEMI, int SITE>
+__device__ __forceinline__ void chroma_block_sited(const YuvIngestArgs& a, int x0, int y0, int Hc, int Wc, float Cb[2][4], float Cr[2][4]) {
+  constexpr bool TOP = SITE == SITE_TOPLEFT;
+  constexpr int NR = TOP ? 2 : 3;      // chroma rows read: j, j + 1 (co-sited) | j - 1, j, j + 1 (midway), clamped
+  const int j = y0 >> 1, k0 = x0 >> 1, k2 = min(k0 + 2, Wc - 1), km = max(k0 - 1, 0);
+  float cb[NR][3], cr[NR][3], lb[NR], lr[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    const int jr = TOP ? min(j + r, Hc - 1) : min(max(j - 1 + r, 0), Hc - 1);
+    chroma3<S, SEMI>(a, jr, k0, k2, cb[r], cr[r]);
+    if constexpr (SITE == SITE_CENTER) chroma1<S, SEMI>(a, jr, km, lb[r], lr[r]);
+    else lb[r] = lr[r] = 0.0f;         // (not read)
+  }
+  float hb[NR][4], hr[NR][4];          // the horizontal step, per chroma row
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    chroma_h4<SITE>(cb[r], lb[r], hb[r]);
+    chroma_h4<SITE>(cr[r], lr[r], hr[r]);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if constexpr (TOP) {
+      Cb[0][i] = hb[0][i];
+      Cb[1][i] = (hb[0][i] + hb[1][i]) * 0.5f;
+      Cr[0][i] = hr[0][i];
+      Cr[1][i] = (hr[0][i] + hr[1][i]) * 0.5f;
+    } else {
+      Cb[0][i] = 0.75f * hb[1][i] + 0.25f * hb[0][i];
+      Cb[1][i] = 0.75f * hb[1][i] + 0.25f * hb[2][i];
+      Cr[0][i] = 0.75f * hr[1][i] + 0.25f * hr[0][i];
+      Cr[1][i] = 0.75f * hr[1][i] + 0.25f * hr[2][i];
+    }
+  }
+}
+
 // 4:2:2 and 4:4:4: the chroma of a 4 x 2 block inside the frame, on the luma grid -- each luma row has its own chroma row
-template <class S, bool SEMI, int CS>
+template <class S, bool SEMI, int CS, int SITE>
 __device__ __forceinline__ void chroma_rows(const YuvIngestArgs& a, int x0, int y0, float Cb[2][4], float Cr[2][4]) {
-  if constexpr (CS == CS_422) {
+  if constexpr (CS == CS_422 && SITE == SITE_CENTER) {
+    const int Wc = (a.w + 1) >> 1, k0 = x0 >> 1, k2 = min(k0 + 2, Wc - 1), km = max(k0 - 1, 0);
+    float cb[2][3], cr[2][3], lb[2], lr[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      chroma3<S, SEMI>(a, y0 + r, k0, k2, cb[r], cr[r]);
+      chroma1<S, SEMI>(a, y0 + r, km, lb[r], lr[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      chroma_h4<SITE>(cb[r], lb[r], Cb[r]);
+      chroma_h4<SITE>(cr[r], lr[r], Cr[r]);
+    }
+  } else if constexpr (CS == CS_422) {
     // columns x0 .. x0 + 3 lie on chroma columns k0, k0 + 1 and reach to k0 + 2 for the last (odd) one
     const int Wc = (a.w + 1) >> 1, k0 = x0 >> 1, k2 = min(k0 + 2, Wc - 1);
     float cb[2][3], cr[2][3];
@@ -191,8 +291,9 @@ __device__ __forceinline__ void chroma_rows(const YuvIngestArgs& a, int x0, int 
   }
 }
 
-template <class S, bool SEMI, int CS>
+template <class S, bool SEMI, int CS, int SITE = SITE_LEFT>
 __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvIngestArgs a) {
+  static_assert(SITE == SITE_LEFT || CS == CS_420 || (CS == CS_422 && SITE == SITE_CENTER), "a siting of this sub-sampling");
   const int x0 = (blockIdx.x * YUV_X + threadIdx.x) * 4;
   const int y0 = (blockIdx.y * YUV_Y + threadIdx.y) * 2;
   if (x0 >= a.Wp || y0 >= a.Hp) return;
@@ -203,7 +304,7 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
       typename S::G4 yl[2];
 #pragma unroll
       for (int r = 0; r < 2; ++r) yl[r] = S::ld4(a.p[0] + (long long)(y0 + r) * a.rs[0] + S::B * x0);
-      chroma_rows<S, SEMI, CS>(a, x0, y0, Cb, Cr);
+      chroma_rows<S, SEMI, CS, SITE>(a, x0, y0, Cb, Cr);
 #pragma unroll
       for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -221,7 +322,9 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
           // 4:2:2: the two chroma columns of Ch(sy, sx); 4:4:4: the pixel's own sample, as both
           const int ka = CS == CS_422 ? sx >> 1 : sx;
           chroma1<S, SEMI>(a, sy, ka, cbv[r][i][0], crv[r][i][0]);
-          if constexpr (CS == CS_422) {
+          if constexpr (CS == CS_422 && SITE == SITE_CENTER) {
+            chroma1<S, SEMI>(a, sy, chroma_other<false>(sx, Wc), cbv[r][i][1], crv[r][i][1]);
+          } else if constexpr (CS == CS_422) {
             chroma1<S, SEMI>(a, sy, (sx & 1) ? min(ka + 1, Wc - 1) : ka, cbv[r][i][1], crv[r][i][1]);
           } else {
             cbv[r][i][1] = cbv[r][i][0];
@@ -233,8 +336,53 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
       for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          Cb[r][i] = (cbv[r][i][0] + cbv[r][i][1]) * 0.5f;   // (4:4:4: (c + c) / 2 = c, exactly)
-          Cr[r][i] = (crv[r][i][0] + crv[r][i][1]) * 0.5f;
+          if constexpr (SITE == SITE_CENTER) {
+            Cb[r][i] = 0.75f * cbv[r][i][0] + 0.25f * cbv[r][i][1];
+            Cr[r][i] = 0.75f * crv[r][i][0] + 0.25f * crv[r][i][1];
+          } else {
+            Cb[r][i] = (cbv[r][i][0] + cbv[r][i][1]) * 0.5f;   // (4:4:4: (c + c) / 2 = c, exactly)
+            Cr[r][i] = (crv[r][i][0] + crv[r][i][1]) * 0.5f;
+          }
+        }
+    }
+  } else if (SITE != SITE_LEFT && x0 + 3 < a.w && y0 + 1 < a.h) {
+    if constexpr (SITE != SITE_LEFT) {
+      typename S::G4 yl[2];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) yl[r] = S::ld4(a.p[0] + (long long)(y0 + r) * a.rs[0] + S::B * x0);
+      chroma_block_sited<S, SEMI, SITE>(a, x0, y0, Hc, Wc, Cb, Cr);
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Y[r][i] = S::lev(a, yl[r], i);
+    }
+  } else if (SITE != SITE_LEFT) {
+    // ... and its blocks with padded rows / columns or a ragged end: sample by sample, every index clamped
+    if constexpr (SITE != SITE_LEFT) {
+      constexpr bool CO_X = SITE != SITE_CENTER, CO_Y = SITE == SITE_TOPLEFT;   // co-sited with a luma column / row
+      constexpr float WX = chroma_weight<CO_X>(), WY = chroma_weight<CO_Y>();
+      float cbv[2][4][4], crv[2][4][4];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int sy = pad_index(min(y0 + r, a.Hp - 1), a.h, a.pad);
+        const int j = sy >> 1, jn = chroma_other<CO_Y>(sy, Hc);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int sx = pad_index(x0 + i, a.w, a.pad);
+          const int ka = sx >> 1, kb = chroma_other<CO_X>(sx, Wc);
+          Y[r][i] = S::lev(a, S::ld1(a.p[0] + (long long)sy * a.rs[0] + S::B * sx), 0);
+          chroma1<S, SEMI>(a, j, ka, cbv[r][i][0], crv[r][i][0]);
+          chroma1<S, SEMI>(a, j, kb, cbv[r][i][1], crv[r][i][1]);
+          chroma1<S, SEMI>(a, jn, ka, cbv[r][i][2], crv[r][i][2]);
+          chroma1<S, SEMI>(a, jn, kb, cbv[r][i][3], crv[r][i][3]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          Cb[r][i] = WY * (WX * cbv[r][i][0] + (1.0f - WX) * cbv[r][i][1]) + (1.0f - WY) * (WX * cbv[r][i][2] + (1.0f - WX) * cbv[r][i][3]);
+          Cr[r][i] = WY * (WX * crv[r][i][0] + (1.0f - WX) * crv[r][i][1]) + (1.0f - WY) * (WX * crv[r][i][2] + (1.0f - WX) * crv[r][i][3]);
         }
     }
   } else if (x0 + 3 < a.w && y0 + 1 < a.h) {
@@ -304,7 +452,7 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_ingest_yuv_kernel(YuvInge
     for (int i = 0; i < 4; ++i) {
       const float yn = S::quot(Y[r][i] - a.k.y0, a.k.ys, a.k.inv_ys), cb = S::quot(Cb[r][i] - S::cm(a.k), a.k.cs, a.k.inv_cs),
                   cr = S::quot(Cr[r][i] - S::cm(a.k), a.k.cs, a.k.inv_cs);
-      if constexpr (CS == CS_420) {
+      if constexpr (CS == CS_420 && SITE == SITE_LEFT) {
         o[r][0][i] = clamp01(yn + a.k.r_cr * cr);
         o[r][1][i] = clamp01(yn - a.k.g_cb * cb - a.k.g_cr * cr);
         o[r][2][i] = clamp01(yn + a.k.b_cb * cb);
@@ -350,31 +498,35 @@ __device__ __forceinline__ void store_chroma2(const YuvEmitArgs& a, int j, int x
   }
 }
 
-template <class S, bool SEMI, int CS>
+template <class S, bool SEMI, int CS, int SITE = SITE_LEFT>
 __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitArgs a) {
   static_assert(CS != CS_444 || !SEMI, "4:4:4 is planar");
+  static_assert(SITE == SITE_LEFT || CS == CS_420 || (CS == CS_422 && SITE == SITE_CENTER), "a siting of this sub-sampling");
+  // SITE_TOPLEFT: a third row, max(y0 - 1, 0), for the vertical taps; SITE_CENTER: no left neighbour, as 4:4:4
+  constexpr int NR = SITE == SITE_TOPLEFT ? 3 : 2;
+  constexpr bool NO_LEFT = CS == CS_444 || SITE == SITE_CENTER;
   const int x0 = (blockIdx.x * YUV_X + threadIdx.x) * 4;
   const int y0 = (blockIdx.y * YUV_Y + threadIdx.y) * 2;
   if (x0 >= a.w || y0 >= a.h) return;
   // rows y0 and min(y0 + 1, h - 1); columns max(x0 - 1, 0) and x0 .. x0 + 3 (x0 + 3 < Ws: Ws is a multiple of 4, x0 < w <= Ws)
   const long long plane = (long long)a.Hs * a.Ws;
-  const int yr[2] = {y0, min(y0 + 1, a.h - 1)}, xl = max(x0 - 1, 0);
-  f32x4 v[2][3];
-  float l[2][3];
+  const int yr[3] = {y0, min(y0 + 1, a.h - 1), max(y0 - 1, 0)}, xl = max(x0 - 1, 0);
+  f32x4 v[NR][3];
+  float l[NR][3];
 #pragma unroll
-  for (int r = 0; r < 2; ++r) {
+  for (int r = 0; r < NR; ++r) {
     const float* row = a.src + (long long)yr[r] * a.Ws;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       v[r][c] = *reinterpret_cast<const f32x4*>(row + c * plane + x0);
-      if constexpr (CS == CS_444) l[r][c] = 0.0f;   // (no filter, no left neighbour: what comes of it below is dropped)
+      if constexpr (NO_LEFT) l[r][c] = 0.0f;   // (no filter, no left neighbour: what comes of it below is dropped)
       else l[r][c] = row[c * plane + xl];
     }
   }
   const float scale = a.hi - a.lo;
-  float yv[2][4], cbv[2][5], crv[2][5];   // column index 0 of cbv / crv is the left neighbour
+  float yv[NR][4], cbv[NR][5], crv[NR][5];   // column index 0 of cbv / crv is the left neighbour (yv of the third row: dropped)
 #pragma unroll
-  for (int r = 0; r < 2; ++r)
+  for (int r = 0; r < NR; ++r)
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
       float t[3];
@@ -403,23 +555,48 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitAr
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int i = 2 * k;               // columns 2k - 1, 2k, 2k + 1 of this lane's chroma column k
-      const float fb = 0.5f * (0.25f * (cbv[0][i] + 2.0f * cbv[0][i + 1] + cbv[0][i + 2]) +
-                               0.25f * (cbv[1][i] + 2.0f * cbv[1][i + 1] + cbv[1][i + 2]));
-      const float fr = 0.5f * (0.25f * (crv[0][i] + 2.0f * crv[0][i + 1] + crv[0][i + 2]) +
-                               0.25f * (crv[1][i] + 2.0f * crv[1][i + 1] + crv[1][i + 2]));
-      cbw[0][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fb, a.k.top));
-      crw[0][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fr, a.k.top));
+      if constexpr (SITE == SITE_LEFT) {
+        const float fb = 0.5f * (0.25f * (cbv[0][i] + 2.0f * cbv[0][i + 1] + cbv[0][i + 2]) +
+                                 0.25f * (cbv[1][i] + 2.0f * cbv[1][i + 1] + cbv[1][i + 2]));
+        const float fr = 0.5f * (0.25f * (crv[0][i] + 2.0f * crv[0][i + 1] + crv[0][i + 2]) +
+                                 0.25f * (crv[1][i] + 2.0f * crv[1][i + 1] + crv[1][i + 2]));
+        cbw[0][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fb, a.k.top));
+        crw[0][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fr, a.k.top));
+      } else {
+        float fb, fr;
+        if constexpr (SITE == SITE_CENTER) {   // columns 2k, 2k + 1 of rows 2j, 2j + 1
+          fb = 0.5f * (0.5f * (cbv[0][i + 1] + cbv[0][i + 2]) + 0.5f * (cbv[1][i + 1] + cbv[1][i + 2]));
+          fr = 0.5f * (0.5f * (crv[0][i + 1] + crv[0][i + 2]) + 0.5f * (crv[1][i + 1] + crv[1][i + 2]));
+        } else {                               // the same columns of rows 2j - 1 (index 2), 2j, 2j + 1
+          float hb[3], hr[3];
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            hb[r] = 0.25f * (cbv[r][i] + 2.0f * cbv[r][i + 1] + cbv[r][i + 2]);
+            hr[r] = 0.25f * (crv[r][i] + 2.0f * crv[r][i + 1] + crv[r][i + 2]);
+          }
+          fb = 0.25f * (hb[2] + 2.0f * hb[0] + hb[1]);
+          fr = 0.25f * (hr[2] + 2.0f * hr[0] + hr[1]);
+        }
+        cbw[0][k] = S::word(a, quant_level(fmaf(a.k.cs, fb, S::cm(a.k)), a.k.top));
+        crw[0][k] = S::word(a, quant_level(fmaf(a.k.cs, fr, S::cm(a.k)), a.k.top));
+      }
     }
   } else {
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
       for (int k = 0; k < CK; ++k) {
-        // 4:2:2: the same columns, of row r alone; 4:4:4: the pixel's own
-        const float fb = CS == CS_444 ? cbv[r][k + 1] : 0.25f * (cbv[r][2 * k] + 2.0f * cbv[r][2 * k + 1] + cbv[r][2 * k + 2]);
-        const float fr = CS == CS_444 ? crv[r][k + 1] : 0.25f * (crv[r][2 * k] + 2.0f * crv[r][2 * k + 1] + crv[r][2 * k + 2]);
-        cbw[r][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fb, a.k.top));
-        crw[r][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fr, a.k.top));
+        if constexpr (SITE == SITE_CENTER) {   // 4:2:2: columns 2k, 2k + 1 of row r
+          const float fb = 0.5f * (cbv[r][2 * k + 1] + cbv[r][2 * k + 2]), fr = 0.5f * (crv[r][2 * k + 1] + crv[r][2 * k + 2]);
+          cbw[r][k] = S::word(a, quant_level(fmaf(a.k.cs, fb, S::cm(a.k)), a.k.top));
+          crw[r][k] = S::word(a, quant_level(fmaf(a.k.cs, fr, S::cm(a.k)), a.k.top));
+        } else {
+          // 4:2:2: the same columns, of row r alone; 4:4:4: the pixel's own
+          const float fb = CS == CS_444 ? cbv[r][k + 1] : 0.25f * (cbv[r][2 * k] + 2.0f * cbv[r][2 * k + 1] + cbv[r][2 * k + 2]);
+          const float fr = CS == CS_444 ? crv[r][k + 1] : 0.25f * (crv[r][2 * k] + 2.0f * crv[r][2 * k + 1] + crv[r][2 * k + 2]);
+          cbw[r][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fb, a.k.top));
+          crw[r][k] = S::word(a, quant_level(S::cm(a.k) + a.k.cs * fr, a.k.top));
+        }
       }
   }
   // ---- stores
@@ -464,10 +641,23 @@ __global__ __launch_bounds__(YUV_X * YUV_Y) void frame_emit_yuv_kernel(YuvEmitAr
 
 // ---- the host side, on the one internal frame (kernels.h: YuvFrame)
 
-// format = base | chroma << 4: a known pair (base 0 is the semi-planar form of either descriptor, 1 the planar one)?
+// format = base | chroma << 4: a known pair (base 0 is the semi-planar form of either descriptor, 1 the planar one)?  The chroma
+// field names a sub-sampling and a siting: 3, 7 and above and any bit above bit 7 name none.
 static bool yuv_format_known(int format) {
   const int base = format & 15, chroma = format >> 4;
-  return format >= 0 && base <= 1 && chroma <= DVSR_YUV_CHROMA_444;
+  return format >= 0 && base <= 1 && chroma <= DVSR_YUV_CHROMA_422_CENTER && chroma != 3;
+}
+
+// the sub-sampling / the siting of the chroma field of a known format
+static int yuv_chroma_of(int format) {
+  const int c = format >> 4;
+  if (c == DVSR_YUV_CHROMA_420_CENTER || c == DVSR_YUV_CHROMA_420_TOPLEFT) return DVSR_YUV_CHROMA_420;
+  return c == DVSR_YUV_CHROMA_422_CENTER ? DVSR_YUV_CHROMA_422 : c;
+}
+static int yuv_siting_of(int format) {
+  const int c = format >> 4;
+  if (c == DVSR_YUV_CHROMA_420_CENTER || c == DVSR_YUV_CHROMA_422_CENTER) return YUV_SITE_CENTER;
+  return c == DVSR_YUV_CHROMA_420_TOPLEFT ? YUV_SITE_TOPLEFT : YUV_SITE_LEFT;
 }
 
 int yuv_frame_from(const char* what, const dvsr_yuv_desc* d, YuvFrame* f) {
@@ -476,7 +666,7 @@ int yuv_frame_from(const char* what, const dvsr_yuv_desc* d, YuvFrame* f) {
   DVSR_REQUIRE(d->format != DVSR_YUV_FORMAT(DVSR_YUV_NV12, DVSR_YUV_CHROMA_444), DVSR_ERR_INVALID,
                "%s: YUV format %d, semi-planar 4:4:4, is not provided", what, d->format);
   *f = YuvFrame{{d->plane[0], d->plane[1], d->plane[2]}, {d->row_stride[0], d->row_stride[1], d->row_stride[2]},
-                d->h, d->w, d->matrix, d->range, (d->format & 15) == DVSR_YUV_NV12, 1, 8, d->format >> 4};
+                d->h, d->w, d->matrix, d->range, (d->format & 15) == DVSR_YUV_NV12, 1, 8, yuv_chroma_of(d->format), yuv_siting_of(d->format)};
   return DVSR_OK;
 }
 
@@ -487,14 +677,15 @@ int yuv_frame_from(const char* what, const dvsr_yuv16_desc* d, YuvFrame* f) {
                "%s: 16-bit YUV format %d, semi-planar 4:4:4, is not provided", what, d->format);
   DVSR_REQUIRE(d->depth == 10 || d->depth == 12, DVSR_ERR_INVALID, "%s: unknown depth %d (10 or 12)", what, d->depth);
   *f = YuvFrame{{d->plane[0], d->plane[1], d->plane[2]}, {d->row_stride[0], d->row_stride[1], d->row_stride[2]},
-                d->h, d->w, d->matrix, d->range, (d->format & 15) == DVSR_YUV16_SEMI_MSB, 2, d->depth, d->format >> 4};
+                d->h, d->w, d->matrix, d->range, (d->format & 15) == DVSR_YUV16_SEMI_MSB, 2, d->depth, yuv_chroma_of(d->format),
+                yuv_siting_of(d->format)};
   return DVSR_OK;
 }
 
 // (arguments checked by yuv_frame_check)
 static YuvCoef yuv_coef(const YuvFrame& f) {
-  const bool bt709 = f.matrix == DVSR_YUV_BT709, full = f.range == DVSR_YUV_FULL;
-  const double kr = bt709 ? 0.2126 : 0.299, kb = bt709 ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
+  const bool bt709 = f.matrix == DVSR_YUV_BT709, bt2020 = f.matrix == DVSR_YUV_BT2020NC, full = f.range == DVSR_YUV_FULL;
+  const double kr = bt2020 ? 0.2627 : bt709 ? 0.2126 : 0.299, kb = bt2020 ? 0.0593 : bt709 ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
   const double s = (double)(1 << (f.depth - 8)), top = (double)((1 << f.depth) - 1);
   const double y0 = full ? 0.0 : 16.0 * s, ys = full ? top : 219.0 * s, cs = full ? top : 224.0 * s, cm = 128.0 * s;
   const double r_cr = 2.0 * (1.0 - kr), b_cb = 2.0 * (1.0 - kb);
@@ -505,8 +696,8 @@ static YuvCoef yuv_coef(const YuvFrame& f) {
 
 // the frame on the "any address, any pitch" side, against the h x w it may have at most
 static int yuv_frame_check(const char* what, const YuvFrame& f, int Ht, int Wt) {
-  DVSR_REQUIRE(f.matrix == DVSR_YUV_BT601 || f.matrix == DVSR_YUV_BT709, DVSR_ERR_INVALID, "%s: unknown YUV matrix %d", what,
-               f.matrix);
+  DVSR_REQUIRE(f.matrix == DVSR_YUV_BT601 || f.matrix == DVSR_YUV_BT709 || f.matrix == DVSR_YUV_BT2020NC, DVSR_ERR_INVALID,
+               "%s: unknown YUV matrix %d", what, f.matrix);
   DVSR_REQUIRE(f.range == DVSR_YUV_LIMITED || f.range == DVSR_YUV_FULL, DVSR_ERR_INVALID, "%s: unknown YUV range %d", what,
                f.range);
   DVSR_REQUIRE(f.h >= 1 && f.w >= 1 && f.h <= Ht && f.w <= Wt, DVSR_ERR_INVALID,
@@ -528,25 +719,31 @@ static int yuv_frame_check(const char* what, const YuvFrame& f, int Ht, int Wt) 
 static dim3 yuv_grid(int h, int w) { return dim3(ceil_div(ceil_div(w, 4), YUV_X), ceil_div(ceil_div(h, 2), YUV_Y)); }
 
 // the instantiation that takes a frame
-template <int CS>
+template <int CS, int SITE = SITE_LEFT>
 static auto ingest_kernel_of(const YuvFrame& f) {
-  if (f.bytes == 2) return f.semi ? frame_ingest_yuv_kernel<Sample16, true, CS> : frame_ingest_yuv_kernel<Sample16, false, CS>;
-  return f.semi ? frame_ingest_yuv_kernel<Sample8, true, CS> : frame_ingest_yuv_kernel<Sample8, false, CS>;
+  if (f.bytes == 2)
+    return f.semi ? frame_ingest_yuv_kernel<Sample16, true, CS, SITE> : frame_ingest_yuv_kernel<Sample16, false, CS, SITE>;
+  return f.semi ? frame_ingest_yuv_kernel<Sample8, true, CS, SITE> : frame_ingest_yuv_kernel<Sample8, false, CS, SITE>;
 }
-template <int CS>
+template <int CS, int SITE = SITE_LEFT>
 static auto emit_kernel_of(const YuvFrame& f) {
-  if (f.bytes == 2) return f.semi ? frame_emit_yuv_kernel<Sample16, true, CS> : frame_emit_yuv_kernel<Sample16, false, CS>;
-  return f.semi ? frame_emit_yuv_kernel<Sample8, true, CS> : frame_emit_yuv_kernel<Sample8, false, CS>;
+  if (f.bytes == 2) return f.semi ? frame_emit_yuv_kernel<Sample16, true, CS, SITE> : frame_emit_yuv_kernel<Sample16, false, CS, SITE>;
+  return f.semi ? frame_emit_yuv_kernel<Sample8, true, CS, SITE> : frame_emit_yuv_kernel<Sample8, false, CS, SITE>;
 }
+// (the pairs of sub-sampling and siting that yuv_frame_from lets through: 4:2:0 x 3, 4:2:2 x {left, center}, 4:4:4)
 static auto ingest_kernel(const YuvFrame& f) {
   if (f.chroma == CS_444)   // (planar alone: yuv_frame_from)
     return f.bytes == 2 ? frame_ingest_yuv_kernel<Sample16, false, CS_444> : frame_ingest_yuv_kernel<Sample8, false, CS_444>;
-  return f.chroma == CS_422 ? ingest_kernel_of<CS_422>(f) : ingest_kernel_of<CS_420>(f);
+  if (f.chroma == CS_422) return f.siting == SITE_CENTER ? ingest_kernel_of<CS_422, SITE_CENTER>(f) : ingest_kernel_of<CS_422>(f);
+  if (f.siting == SITE_CENTER) return ingest_kernel_of<CS_420, SITE_CENTER>(f);
+  return f.siting == SITE_TOPLEFT ? ingest_kernel_of<CS_420, SITE_TOPLEFT>(f) : ingest_kernel_of<CS_420>(f);
 }
 static auto emit_kernel(const YuvFrame& f) {
   if (f.chroma == CS_444)
     return f.bytes == 2 ? frame_emit_yuv_kernel<Sample16, false, CS_444> : frame_emit_yuv_kernel<Sample8, false, CS_444>;
-  return f.chroma == CS_422 ? emit_kernel_of<CS_422>(f) : emit_kernel_of<CS_420>(f);
+  if (f.chroma == CS_422) return f.siting == SITE_CENTER ? emit_kernel_of<CS_422, SITE_CENTER>(f) : emit_kernel_of<CS_422>(f);
+  if (f.siting == SITE_CENTER) return emit_kernel_of<CS_420, SITE_CENTER>(f);
+  return f.siting == SITE_TOPLEFT ? emit_kernel_of<CS_420, SITE_TOPLEFT>(f) : emit_kernel_of<CS_420>(f);
 }
 
 int frame_ingest_yuv_check(const char* what, const YuvFrame& f, const float* dst, int Hp, int Wp, int pad_mode) {

@@ -273,7 +273,10 @@ struct YuvFrame {
   bool semi;                // interleaved CbCr (NV12 / NV16, P010 / P012 / P210 / P212); otherwise planar
   int bytes, depth;         // per sample: 1 or 2; bits of a level: 8, 10 or 12
   int chroma;               // DVSR_YUV_CHROMA_420 / _422 / _444 (never semi-planar)
+  int siting;               // YUV_SITE_*: where a chroma sample sits (4:4:4: left, unused)
 };
+// the chroma field of a descriptor's format names a pair: yuv_frame_from splits it into `chroma` and `siting`
+enum : int { YUV_SITE_LEFT = 0, YUV_SITE_CENTER = 1, YUV_SITE_TOPLEFT = 2 };
 int yuv_frame_from(const char* what, const dvsr_yuv_desc* d, YuvFrame* f);
 int yuv_frame_from(const char* what, const dvsr_yuv16_desc* d, YuvFrame* f);
 int frame_ingest_yuv_check(const char* what, const YuvFrame& f, const float* dst, int Hp, int Wp, int pad_mode);

@@ -548,7 +548,8 @@ class StreamPlan:
             ws.numel(), packed, L.stream()))
         self.stats['extracted'] += 1
 
-    def extract_frame(self, leaves, frame, slot, cache, layout=None, pad_mode='reflect', matrix='bt601', yuv_range='limited'):
+    def extract_frame(self, leaves, frame, slot, cache, layout=None, pad_mode='reflect', matrix='bt601', yuv_range='limited',
+                      siting='left'):
         """A decoder's frame on the GPU -- uint8 [h,w,3|4] ('hwc_rgb' / 'hwc_bgr'), fp32 [3,h,w] ('chw') or YCbCr 4:2:0
         ('nv12' / 'i420', or 'p010' / 'p012' / 'i420p10' / 'i420p12' in 16-bit words: packed or planes, frames.py; `matrix`,
         `yuv_range`) or its 4:2:2 / 4:4:4 counterparts (frames.YUV422_LAYOUTS / YUV444_LAYOUTS), or 16-bit words / integer planes
@@ -556,7 +557,7 @@ class StreamPlan:
         -> slot `slot` of `cache`, on the current stream: converted and padded to the plan's H x W straight into the slot
         (frames.ingest's result, without the temporary), then `extract`'s tape.  Returns the tensor(s) the launch reads."""
         from . import frames as F
-        F.check_yuv_names(matrix, yuv_range)
+        F.check_yuv_names(matrix, yuv_range, siting)
         layout, h, w = F.resolve_layout(frame, layout)
         if h > self.h or w > self.w:
             raise ValueError("EDVR stream of %d x %d frames got a frame of %d x %d" % (self.h, self.w, h, w))
@@ -565,7 +566,7 @@ class StreamPlan:
         if not first.is_cuda:
             raise RuntimeError("libdynavsr_hip needs a tensor on the GPU, got device %s" % first.device)
         if F.is_yuv(layout):
-            planes, desc = F.describe_yuv(F.yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range)
+            planes, desc = F.describe_yuv(F.yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range, siting=siting)
             params, arr = self._params(leaves)
             fn = F._yuv_entry(layout, 'edvr_stream_extract_frame')[0]
             self._run('extract', leaves, lambda ws, packed: fn(

@@ -21,7 +21,7 @@ and 'i420' (yuv420p), never inferred.  Such a frame is PACKED -- one uint8 tenso
 followed by the interleaved CbCr rows (NV12, any row pitch) or by the Cb and the Cr plane (I420, contiguous) -- or a tuple
 of PLANES on one device: (y [H,W], uv [Hc,Wc,2]) for NV12, (y, u [Hc,Wc], v [Hc,Wc]) for I420, Hc x Wc = ceil(H/2) x
 ceil(W/2), every plane at any offset and row pitch (passed by stride) and H, W of either parity.  `matrix` ('bt601' |
-'bt709') and `yuv_range` ('limited' | 'full') name the conversion; the defaults are the reference's ycbcr2rgb / rgb2ycbcr
+'bt709' | 'bt2020nc') and `yuv_range` ('limited' | 'full') name the conversion; the defaults are the reference's ycbcr2rgb / rgb2ycbcr
 (data/util.py:234-299).  ingest gives the un-rounded fp32 RGB, emit goes from fp32 RGB to 4:2:0 bytes in one launch; the
 arithmetic is written out in csrc/frame_yuv.hip and DESIGN 3.2k.
 
@@ -42,7 +42,16 @@ frame is [3H, W] at any size and pitch.  Plane tuples are as above with those pl
 word conventions are those of the 4:2:0 layout of the same sample kind; 4:2:2 keeps the horizontal chroma filters and has no
 vertical one, 4:4:4 has none.  YUV_LAYOUTS / YUV16_LAYOUTS name the 4:2:0 layouts, YUV422_LAYOUTS / YUV444_LAYOUTS these,
 ALL_YUV_LAYOUTS all of them.  Not provided: semi-planar 4:4:4 (nv24 / p410), packed 4:2:2 (YUY2 / UYVY / v210), 4:1:1 / 4:4:0,
-a 'bt2020' matrix, 16-bit YCbCr, chroma siting other than "left".
+16-bit YCbCr.
+
+Where the chroma samples sit, and BT.2020, never inferred: `siting` is 'left' (MPEG-2 / H.264, y4m 420mpeg2: on
+luma column 2k, midway between rows 2j and 2j+1; the default and what every call without it means), 'center' (JPEG / MPEG-1 /
+MJPEG, yuvj420p, y4m 420jpeg: midway both ways) or 'topleft' (HEVC / AV1 UHD and HDR10, chroma_sample_location=topleft: on
+column 2k and row 2j).  One siting serves input and output, as `matrix` does.  4:2:2 has no vertical position, so its 'topleft'
+is 'left'; for 4:4:4 and every layout that is not YCbCr the name is checked and has no effect.  matrix='bt2020nc' is BT.2020
+non-constant luminance (Kr = 0.2627, Kb = 0.0593; H.273 MatrixCoefficients 9), what nearly every 'p010' stream carries.  Not
+provided: constant-luminance BT.2020 and ICtCp, transfer functions (PQ / HLG: the network sees the transfer-coded R'G'B' as it
+does for SDR), a siting per direction, bottom and interlaced sitings, 420paldv.
 
 RGB above 8 bits and planar integer RGB (RGB_LAYOUTS; csrc/frame_rgb.hip through dvsr_frame_ingest / dvsr_frame_emit),
 never inferred from dtype or shape either -- what 16-bit PNG / TIFF / DPX, torchvision's decoders and an FFV1 archive hold:
@@ -138,7 +147,12 @@ YUV444_LAYOUTS = tuple(k for k, v in _YUV.items() if v[5] == L.YUV_CHROMA_444)
 ALL_YUV_LAYOUTS = YUV_LAYOUTS + YUV16_LAYOUTS + YUV422_LAYOUTS + YUV444_LAYOUTS
 # sub-sampling -> the shape of a packed frame, as the messages write it
 _PACKED = {L.YUV_CHROMA_420: '[H*3/2, W]', L.YUV_CHROMA_422: '[2H, W]', L.YUV_CHROMA_444: '[3H, W]'}
-_YUV_MATRIX = {'bt601': L.YUV_BT601, 'bt709': L.YUV_BT709}
+_YUV_MATRIX = {'bt601': L.YUV_BT601, 'bt709': L.YUV_BT709, 'bt2020nc': L.YUV_BT2020NC}
+# where the chroma samples sit, never inferred: siting -> sub-sampling -> the chroma field of a descriptor's format.
+# 4:2:2 has no vertical position, so its 'topleft' is 'left'; 4:4:4 has no siting.
+YUV_SITINGS = ('left', 'center', 'topleft')
+_YUV_SITING = {'left': {}, 'center': {L.YUV_CHROMA_420: L.YUV_CHROMA_420_CENTER, L.YUV_CHROMA_422: L.YUV_CHROMA_422_CENTER},
+               'topleft': {L.YUV_CHROMA_420: L.YUV_CHROMA_420_TOPLEFT}}
 _YUV_RANGE = {'limited': L.YUV_LIMITED, 'full': L.YUV_FULL}
 _FORMAT = {'chw': L.FRAME_F32_CHW, 'hwc_rgb': L.FRAME_U8_HWC_RGB, 'hwc_bgr': L.FRAME_U8_HWC_BGR}
 # integer RGB beyond 8-bit interleaved, never inferred -> (planar, depth, the format of its descriptor, its dtypes)
@@ -255,11 +269,13 @@ def _describe_rgb(frame, layout):
     return frame, L.FrameDesc(fmt, h, w, max(int(st[0]), w * int(st[1])) * es, 0, int(st[1]) * es)
 
 
-def check_yuv_names(matrix, yuv_range):
+def check_yuv_names(matrix, yuv_range, siting='left'):
     if matrix not in _YUV_MATRIX:
-        raise ValueError("unknown YCbCr matrix %r ('bt601' or 'bt709')" % (matrix,))
+        raise ValueError("unknown YCbCr matrix %r ('bt601', 'bt709' or 'bt2020nc', BT.2020 non-constant luminance)" % (matrix,))
     if yuv_range not in _YUV_RANGE:
         raise ValueError("unknown YCbCr range %r ('limited' or 'full')" % (yuv_range,))
+    if not isinstance(siting, str) or siting not in _YUV_SITING:
+        raise ValueError("unknown chroma siting %r ('left', 'center' or 'topleft')" % (siting,))
 
 
 def chroma_size(layout, h, w):
@@ -334,13 +350,14 @@ def yuv_planes(frame, layout):
     return planes, h, w
 
 
-def describe_yuv(planes, layout, h, w, matrix='bt601', yuv_range='limited', copy=True):
+def describe_yuv(planes, layout, h, w, matrix='bt601', yuv_range='limited', copy=True, siting='left'):
     """(planes', dvsr_yuv_desc) of what yuv_planes returned (a dvsr_yuv16_desc for the 10- / 12-bit layouts; the layout's chroma
-    sub-sampling is in the descriptor's format).  A plane that the
+    sub-sampling and `siting` are in the descriptor's format).  A plane that the
     descriptor can express -- any offset, any row pitch -- is passed by stride; any other is copied first (copy = False:
     ValueError, for a destination)."""
-    check_yuv_names(matrix, yuv_range)
-    (_, depth, fmt, _, _, _), rest = _YUV[layout], (h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
+    check_yuv_names(matrix, yuv_range, siting)
+    (_, depth, fmt, _, _, chroma), rest = _YUV[layout], (h, w, _YUV_MATRIX[matrix], _YUV_RANGE[yuv_range])
+    fmt = L.yuv_format(fmt & 15, _YUV_SITING[siting].get(chroma, chroma))
     desc = L.Yuv16Desc(fmt, depth, *rest) if depth > 8 else L.YuvDesc(fmt, *rest)
     kept = []
     for i, p in enumerate(planes):
@@ -377,7 +394,7 @@ def _planar_ok(t):
     return t.is_contiguous() and t.shape[-1] % 4 == 0 and t.data_ptr() % 16 == 0
 
 
-def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix='bt601', yuv_range='limited'):
+def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix='bt601', yuv_range='limited', siting='left'):
     """One frame -> fp32 [3,Hp,Wp] on the GPU, (Hp, Wp) = padded_size(h, w, multiple).
 
     frame: uint8 [H,W,3|4] ('hwc_rgb' / 'hwc_bgr'; a fourth byte is ignored) or float [3,H,W] ('chw'), on the CPU or the
@@ -387,9 +404,10 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix=
     'nv12' / 'i420': frame is a packed uint8 [H*3/2, W] tensor or a tuple of planes (module docstring), converted with
     `matrix` / `yuv_range` to un-rounded RGB in [0,1] -- one launch, like the other layouts.  'p010' / 'p012' / 'i420p10' /
     'i420p12': the same for uint16 / int16 words of 10 or 12 bits.  The 4:2:2 and 4:4:4 layouts (module docstring): the same,
-    packed [2H, W] / [3H, W] or as planes.
+    packed [2H, W] / [3H, W] or as planes.  `siting` ('left' | 'center' | 'topleft', module docstring) names where the chroma
+    samples of a 4:2:0 / 4:2:2 frame sit; it is checked and has no effect for every other layout.
     RGB_LAYOUTS (module docstring): uint16 / int16 [H,W,3|4] words or uint8 / uint16 / int16 [3,H,W] planes, level / (2^d - 1)."""
-    check_yuv_names(matrix, yuv_range)
+    check_yuv_names(matrix, yuv_range, siting)
     layout, h, w = resolve_layout(frame, layout)
     Hp, Wp = padded_size(h, w, multiple)
     Wb = -(-Wp // 4) * 4
@@ -406,7 +424,7 @@ def ingest(frame, layout=None, multiple=4, pad_mode='reflect', out=None, matrix=
     frame = to_device(frame, dev)
     yuv = is_yuv(layout)
     if yuv:
-        planes, desc = describe_yuv(yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range)
+        planes, desc = describe_yuv(yuv_planes(frame, layout)[0], layout, h, w, matrix, yuv_range, siting=siting)
     else:
         frame, desc = describe(frame, layout)
     with torch.cuda.device(dev):
@@ -452,7 +470,8 @@ def degradation_edge(degradation, kernel_index=0, who="degrade"):
     return degradation.shifted_edge(int(kernel_index)), int(degradation.scale)
 
 
-def degrade(frame, degradation, layout=None, *, kernel_index=0, quantise=True, out=None, matrix='bt601', yuv_range='limited'):
+def degrade(frame, degradation, layout=None, *, kernel_index=0, quantise=True, out=None, matrix='bt601', yuv_range='limited',
+            siting='left'):
     """One ground-truth frame -> its LR frame, fp32 [3,h_lr,w_lr] on the GPU ((Hc, Wc, h_lr, w_lr) = degraded_size(h, w, K,
     degradation.scale)): Degradation.apply(ingest(frame, multiple=1)[:, :Hc, :Wc].contiguous()[None], quantise)[0] bit for bit,
     in one launch that reads the frame as it is (dvsr_frame_degrade) -- no fp32 copy of the HR frame, no crop.
@@ -467,12 +486,12 @@ def degrade(frame, degradation, layout=None, *, kernel_index=0, quantise=True, o
     goes through ingest(.., multiple=1) first -- one extra fp32 HR frame -- and gives the bits of that float frame.
     out: the fp32 [3,h_lr,w_lr] GPU tensor to fill, possibly a view with contiguous columns and rows and planes that do not
     overlap.  Arguments are checked before the first GPU call (ValueError)."""
-    check_yuv_names(matrix, yuv_range)
+    check_yuv_names(matrix, yuv_range, siting)
     if isinstance(degradation, Imresize):
         if isinstance(kernel_index, bool) or not isinstance(kernel_index, numbers.Integral) or kernel_index != 0:
             raise ValueError("degrade: kernel_index=%r of an Imresize, which has no kernel set" % (kernel_index,))
         return imresize(frame, (1, degradation.scale), layout, antialiasing=degradation.antialiasing, quantise=quantise,
-                        modcrop=degradation.scale, out=out, matrix=matrix, yuv_range=yuv_range)
+                        modcrop=degradation.scale, out=out, matrix=matrix, yuv_range=yuv_range, siting=siting)
     layout, h, w = resolve_layout(frame, layout)
     K, scale = degradation_edge(degradation, kernel_index)
     Hc, Wc, hl, wl = degraded_size(h, w, K, scale)
@@ -490,7 +509,7 @@ def degrade(frame, degradation, layout=None, *, kernel_index=0, quantise=True, o
     with torch.cuda.device(dev):
         if is_yuv(layout) or layout in _RGB:
             # (multiple=1 pads nothing but the buffer's rows to 4 floats, which are never read here)
-            frame, layout = ingest(frame, layout, 1, 'replicate', matrix=matrix, yuv_range=yuv_range), 'chw'
+            frame, layout = ingest(frame, layout, 1, 'replicate', matrix=matrix, yuv_range=yuv_range, siting=siting), 'chw'
         frame, desc = describe(frame, layout)
         kernel = degradation._shifted_on(dev)[int(kernel_index)]
         if tuple(kernel.shape) != (K, K):
@@ -562,7 +581,7 @@ def _imresize_axis(n_in, ratio, antialiasing, device):
 
 
 def imresize(frame, scale, layout=None, *, antialiasing=True, quantise=False, modcrop=None, out=None, matrix='bt601',
-             yuv_range='limited'):
+             yuv_range='limited', siting='left'):
     """MATLAB's imresize(frame, scale, 'bicubic') -- the reference's data.util.imresize -- of one frame: fp32 [3,oh,ow] on the
     GPU, (oh, ow) = imresize_size(h, w, scale), in one launch that reads the frame as it is (dvsr_frame_imresize).
 
@@ -573,7 +592,7 @@ def imresize(frame, scale, layout=None, *, antialiasing=True, quantise=False, mo
     to the kernel directly, views by stride; every YCbCr layout goes through ingest(.., multiple=1) first.  out: the fp32
     [3,oh,ow] GPU tensor to fill, possibly a view with contiguous columns and rows and planes that do not overlap.
     Arguments are checked before the first GPU call (ValueError)."""
-    check_yuv_names(matrix, yuv_range)
+    check_yuv_names(matrix, yuv_range, siting)
     ratio = imresize_ratio(scale)
     layout, h, w = resolve_layout(frame, layout)
     if modcrop is not None:
@@ -596,7 +615,7 @@ def imresize(frame, scale, layout=None, *, antialiasing=True, quantise=False, mo
     frame = to_device(frame, dev)
     with torch.cuda.device(dev):
         if is_yuv(layout) or layout in _RGB:
-            frame, layout = ingest(frame, layout, 1, 'replicate', matrix=matrix, yuv_range=yuv_range), 'chw'
+            frame, layout = ingest(frame, layout, 1, 'replicate', matrix=matrix, yuv_range=yuv_range, siting=siting), 'chw'
         frame, desc = describe(frame, layout)
         rows, cols = _imresize_axis(h, ratio, antialiasing, dev), _imresize_axis(w, ratio, antialiasing, dev)
         if out is None:
@@ -920,12 +939,13 @@ def _stitch_run(tiles, ny, nx, rows, cols, out):
             "dvsr_frame_stitch")
 
 
-def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='limited', size=None):
+def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='limited', size=None, siting='left'):
     """The top-left h x w crop of sr (fp32 [3,Hs,Ws] or [1,3,Hs,Ws] on the GPU) as uint8 [h,w,3] ('hwc_rgb' / 'hwc_bgr':
     clamp to min_max, rescale, x 255, round half to even -- util.tensor2img's image, and dvsr_frame_metrics') or as fp32
     [3,h,w] ('chw').  out: the tensor to write (any offset and row pitch; what lies outside the crop is not touched).
     A source whose rows are not 16-byte aligned (Ws not a multiple of 4) is copied into one that is, first.
-    'nv12' / 'i420': the crop as YCbCr 4:2:0 bytes (`matrix`, `yuv_range`; chroma filtered inside the crop alone).  With h and
+    'nv12' / 'i420': the crop as YCbCr 4:2:0 bytes (`matrix`, `yuv_range`, `siting` -- where the chroma samples are to sit,
+    module docstring; chroma filtered inside the crop alone).  With h and
     w even and no `out` the result is a packed uint8 [h*3/2, w] tensor; otherwise `out` is a packed tensor of that shape or a
     tuple of planes (module docstring; needed for an odd h or w) and is returned; bytes outside the planes' rows are not
     touched.  'p010' / 'p012' / 'i420p10' / 'i420p12': the same as 10- / 12-bit words, a packed torch.uint16 [h*3/2, w] tensor
@@ -938,14 +958,14 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
     everything above holds for the oh x ow image -- emit(resize(sr, h, w, size), oh, ow, layout, ...), bit for bit."""
     if layout not in LAYOUTS + RGB_LAYOUTS and not is_yuv(layout):
         raise ValueError("unknown frame layout %r (one of %s)" % (layout, ', '.join(LAYOUTS + RGB_LAYOUTS + ALL_YUV_LAYOUTS)))
-    check_yuv_names(matrix, yuv_range)
+    check_yuv_names(matrix, yuv_range, siting)
     if size is not None:
         oh, ow = check_resize(h, w, size)
         if is_yuv(layout) and out is None and packed_needs(layout, oh, ow):
             raise ValueError("emit: a packed %s frame needs %s, got %d x %d: pass `out` as planes"
                              % (layout, packed_needs(layout, oh, ow), oh, ow))
         # (the whole buffer goes on: its rows are 16-byte aligned, those of resize()'s view are not when ow % 4)
-        return emit(_resize(sr, h, w, (oh, ow))[0], oh, ow, layout, min_max, out, matrix, yuv_range)
+        return emit(_resize(sr, h, w, (oh, ow))[0], oh, ow, layout, min_max, out, matrix, yuv_range, siting=siting)
     if sr.dim() == 4 and sr.shape[0] == 1:
         sr = sr[0]
     if sr.dim() != 3 or sr.shape[0] != 3:
@@ -987,7 +1007,7 @@ def emit(sr, h, w, layout, min_max=(0, 1), out=None, matrix='bt601', yuv_range='
             if out is None:
                 out = torch.empty((packed_rows(layout, h), w), dtype=_YUV[layout][4][0], device=sr.device)
                 planes = yuv_planes(out, layout)[0]
-            _, desc = describe_yuv(planes, layout, h, w, matrix, yuv_range, copy=False)
+            _, desc = describe_yuv(planes, layout, h, w, matrix, yuv_range, copy=False, siting=siting)
             fn, name = _yuv_entry(layout, 'frame_emit')
             L.check(fn(sr.data_ptr(), Hs, Ws, ctypes.byref(desc), float(min_max[0]), float(min_max[1]), L.stream()), name)
         return out

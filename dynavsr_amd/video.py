@@ -370,7 +370,7 @@ def choose_tile(net, h, w, budget, overlap=16, in_flight=2, scenes=1, flip_test=
 
 
 def _frame_format(who, frames, layout, out, multiple, pad_mode, matrix, yuv_range, out_size, sr_scale, default_multiple,
-                  multiple_of):
+                  multiple_of, siting='left'):
     """The front end's checks of a video that is taken as a decoder delivers it, shared by super_resolve_frames and
     adapt_frames: (lay, h, w, out_fmt, Hp, Wp, out_size, mult) -- the frames' layout and size, the format of the yielded frames,
     the padded size, `out_size` (None where it is the SR frame's own size) and the multiple the frames are padded to
@@ -379,7 +379,7 @@ def _frame_format(who, frames, layout, out, multiple, pad_mode, matrix, yuv_rang
     if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') + fio.RGB_LAYOUTS and not fio.is_yuv(out):
         raise ValueError("%s: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (
             who, out, ', '.join(fio.RGB_LAYOUTS + fio.ALL_YUV_LAYOUTS)))
-    fio.check_yuv_names(matrix, yuv_range)
+    fio.check_yuv_names(matrix, yuv_range, siting)
     out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
     if out_size == (sr_scale * h, sr_scale * w):
         out_size = None                           # the SR frame's own size: today's calls
@@ -460,7 +460,7 @@ def _stream_buffer(buffers, k, make):
 
 
 def _finish_frame(who, sr, geometry, out_fmt, out_size, sr_scale, matrix, yuv_range, i=None, score_into=None, into=None,
-                  resized=None):
+                  resized=None, siting='left'):
     """The back end of the two frame generators for a network output sr [1,3,s Hp,s Wp] of a frame that was padded from
     h x w to Hp x Wp (geometry): frame i as it is yielded -- the s h x s w crop, resampled to `out_size` and converted to
     `out_fmt` -- and its score, on the current stream.  `resized`: the stream's frames.resize_buffer(out_size), which then
@@ -474,13 +474,13 @@ def _finish_frame(who, sr, geometry, out_fmt, out_size, sr_scale, matrix, yuv_ra
             sr = fio.resize(sr, s * h, s * w, out_size)[None]
         elif resized is not None:
             fio.resize(sr, s * h, s * w, out_size, out=resized)
-            sr = fio.emit(resized, out_size[0], out_size[1], out_fmt, matrix=matrix, yuv_range=yuv_range)
+            sr = fio.emit(resized, out_size[0], out_size[1], out_fmt, matrix=matrix, yuv_range=yuv_range, siting=siting)
         else:
-            sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range, size=out_size)
+            sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range, size=out_size, siting=siting)
     elif out_fmt == 'float':
         sr = sr if _untouched(geometry, out_fmt, out_size) else fio.emit(sr, s * h, s * w, 'chw')[None]
     else:
-        sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range)
+        sr = fio.emit(sr, s * h, s * w, out_fmt, matrix=matrix, yuv_range=yuv_range, siting=siting)
     if score_into is not None:
         if into is None:
             score_into(i, sr)                      # (behind the conversion, on the caller's stream like it)
@@ -492,7 +492,7 @@ def _finish_frame(who, sr, geometry, out_fmt, out_size, sr_scale, matrix, yuv_ra
 def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, layout=None, out=None, pad_mode='reflect',
                          multiple=None, matrix='bt601', yuv_range='limited', cuts=None, cut_threshold=10.0, out_size=None,
                          flip_test=False, gt=None, gt_layout=None, score='rgb', crop_border=0, scores=None,
-                         tile=None, tile_overlap=16, tile_budget=None):
+                         tile=None, tile_overlap=16, tile_budget=None, siting='left'):
     """Super-resolves a VIDEO: `frames` is a [T,3,H,W] tensor or a list of [3,H,W] frames (CPU or GPU); yields the SR frame
     [1,3,sH,sW] of every frame, in order -- what `net(frames[index_generation(i, T, nframes, padding)][None])` gives, the
     sliding-window test of the reference's video datasets (video_test_dataset_int.py:219, `padding: new_info` in the
@@ -523,7 +523,8 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     buffer).
     What a VIDEO decoder delivers is YCbCr 4:2:0 (frames.py, csrc/frame_yuv.hip): with `layout` 'nv12' or 'i420' (never
     inferred) `frames` is a uint8 [T, H*3/2, W] tensor or a list of packed frames or of plane tuples, converted with `matrix`
-    ('bt601' | 'bt709') and `yuv_range` ('limited' | 'full') in the launch that fills the frame cache; `out` None then
+    ('bt601' | 'bt709' | 'bt2020nc'), `yuv_range` ('limited' | 'full') and `siting` ('left' | 'center' | 'topleft': where the
+    chroma samples sit, frames.py; one name for input and output) in the launch that fills the frame cache; `out` None then
     yields packed uint8 [sH*3/2, sW] frames of the input's layout on the device, written from the fp32 SR frame in one launch,
     and 'nv12' / 'i420' force such an output for RGB and float inputs too (sH and sW must be even).
     High-bit-depth video (HEVC Main10, AV1, VP9 profile 2): `layout` 'p010' / 'p012' (semi-planar, the level in the top bits of a
@@ -590,7 +591,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
     Arguments are checked before the first GPU call (ValueError)."""
     a = _frame_arguments(opt, net, frames, padding, in_flight, layout, out, pad_mode, multiple, matrix, yuv_range, cuts,
                          cut_threshold, out_size, flip_test, gt, gt_layout, score, crop_border, scores, tile, tile_overlap,
-                         tile_budget)
+                         tile_budget, siting)
     if a.is_edvr:
         yield from _stream_frames(net, frames, a)
     else:
@@ -599,7 +600,7 @@ def super_resolve_frames(opt, net, frames, padding='new_info', in_flight=2, *, l
 
 def _frame_arguments(opt, net, frames, padding, in_flight, layout, out, pad_mode, multiple, matrix, yuv_range, cuts,
                      cut_threshold, out_size, flip_test, gt, gt_layout, score, crop_border, scores, tile, tile_overlap,
-                     tile_budget):
+                     tile_budget, siting='left'):
     """The first stage of super_resolve_frames: its arguments checked and resolved into one record, which the two paths read.
     No GPU call, except for what cuts='auto' (frames.detect_cuts) and tile='auto' (the device's free memory) ask for, behind
     every check that can be made without them.  Fields beside the arguments themselves: T; is_edvr; lay, h, w, the frames'
@@ -635,7 +636,7 @@ def _frame_arguments(opt, net, frames, padding, in_flight, layout, out, pad_mode
     else:
         lay, h, w, out_fmt, Hp, Wp, out_size, mult = _frame_format(
             "super_resolve_frames", frames, layout, out, multiple, pad_mode, matrix, yuv_range, out_size, sr_scale,
-            4 if is_edvr else 1, 4 if is_edvr or tile is not None else 1)
+            4 if is_edvr else 1, 4 if is_edvr or tile is not None else 1, siting)
     score_into = _frame_scoring("super_resolve_frames", T, gt, gt_layout, scores, score, crop_border, out_fmt, out_size,
                                 sr_scale, h, w, matrix, yuv_range)
     n = _window_length(opt, net)
@@ -655,7 +656,7 @@ def _frame_arguments(opt, net, frames, padding, in_flight, layout, out, pad_mode
             fio.check_pad(h - ys[-1], w - xs[-1], th, tw, pad_mode)     # the tile at the bottom right is padded from itself
     direct = plain or (grid is None and lay == 'chw' and _untouched((h, w, Hp, Wp), out_fmt, out_size))
     return SimpleNamespace(T=T, is_edvr=is_edvr, padding=padding, in_flight=in_flight, flip_test=flip_test, lay=lay, h=h, w=w,
-                           Hp=Hp, Wp=Wp, mult=mult, pad_mode=pad_mode, matrix=matrix, yuv_range=yuv_range, out_fmt=out_fmt,
+                           Hp=Hp, Wp=Wp, mult=mult, pad_mode=pad_mode, matrix=matrix, yuv_range=yuv_range, siting=siting, out_fmt=out_fmt,
                            out_size=out_size, sr_scale=sr_scale, n=n, cuts=cuts, grid=grid, tile_overlap=tile_overlap,
                            score_into=score_into, direct=direct)
 
@@ -726,11 +727,11 @@ def _clip_frames(opt, net, frames, a):
         return
 
     def ingest(x):
-        return fio.ingest(x, a.lay, a.mult, a.pad_mode, matrix=a.matrix, yuv_range=a.yuv_range)
+        return fio.ingest(x, a.lay, a.mult, a.pad_mode, matrix=a.matrix, yuv_range=a.yuv_range, siting=a.siting)
 
     def finished(i, sr):
         return _finish_frame("super_resolve_frames", sr, (a.h, a.w, a.Hp, a.Wp), a.out_fmt, a.out_size, a.sr_scale, a.matrix,
-                             a.yuv_range, i, a.score_into)
+                             a.yuv_range, i, a.score_into, siting=a.siting)
     if a.grid is None:
         ingested = _ingest_cache(lambda j: ingest(frames[j]), 2 * a.n)
         for i, sr in enumerate(run(clips_of(ingested))):
@@ -815,11 +816,13 @@ def _extract_frame(st, a, x, k, slot, s, main):
             if a.direct:
                 padded = xt if xt.data_ptr() % 16 == 0 else flipped[0].copy_(xt)
             else:
-                padded = fio.ingest(xt, a.lay, a.mult, a.pad_mode, out=flipped[0], matrix=a.matrix, yuv_range=a.yuv_range)
+                padded = fio.ingest(xt, a.lay, a.mult, a.pad_mode, out=flipped[0], matrix=a.matrix, yuv_range=a.yuv_range,
+                                    siting=a.siting)
         if a.direct:
             plan.extract(st.leaves, xt, ids.sid(t, 0, slot), st.cache)
         else:
-            xt = plan.extract_frame(st.leaves, xt, ids.sid(t, 0, slot), st.cache, a.lay, a.pad_mode, a.matrix, a.yuv_range)
+            xt = plan.extract_frame(st.leaves, xt, ids.sid(t, 0, slot), st.cache, a.lay, a.pad_mode, a.matrix, a.yuv_range,
+                                    a.siting)
         read += [xt] if torch.is_tensor(xt) else list(xt)
         for v in range(1, nv):
             plan.extract(st.leaves, fio.flip(padded, v, out=flipped[1]), ids.sid(t, v, slot), st.cache)
@@ -918,7 +921,7 @@ def _stream_frames(net, frames, a):
                     buf = _stream_buffer(st.resized, k, lambda: fio.resize_buffer(a.out_size, dev))
                 # (the score: behind the launch that wrote sr; the event below covers the row too)
                 sr = _finish_frame("super_resolve_frames", dst, geometry, a.out_fmt, a.out_size, a.sr_scale, a.matrix,
-                                   a.yuv_range, centre, a.score_into, resized=buf)
+                                   a.yuv_range, centre, a.score_into, resized=buf, siting=a.siting)
                 ev = torch.cuda.Event()
                 ev.record(s)
             st.ids.mark_read(wslots, ev)
@@ -1019,7 +1022,7 @@ def _degraded_geometry(who, hr, degradation, layout):
     return lay, h, w, per_frame, K, scale, sizes
 
 
-def degrade_frames(hr, degradation, *, layout=None, quantise=True, matrix='bt601', yuv_range='limited', out=None):
+def degrade_frames(hr, degradation, *, layout=None, quantise=True, matrix='bt601', yuv_range='limited', out=None, siting='left'):
     """A ground-truth video -> its LR video, fp32 [T,3,h_lr,w_lr] on the GPU: what super_resolve_frames / adapt_frames take.
 
     hr: a [T,...] tensor or a list of frames of one kind and size, in any `layout` frames.ingest takes (None: by dtype; the
@@ -1036,7 +1039,7 @@ def degrade_frames(hr, degradation, *, layout=None, quantise=True, matrix='bt601
     nframes different blurs: here a frame is degraded once.
     out: the fp32 [T,3,h_lr,w_lr] GPU tensor to fill.  Arguments are checked before the first GPU call (ValueError)."""
     who = "degrade_frames"
-    fio.check_yuv_names(matrix, yuv_range)
+    fio.check_yuv_names(matrix, yuv_range, siting)
     lay, h, w, per_frame, K, scale, (Hc, Wc, hl, wl) = _degraded_geometry(who, hr, degradation, layout)
     T = len(hr)
     if out is not None:
@@ -1050,7 +1053,7 @@ def degrade_frames(hr, degradation, *, layout=None, quantise=True, matrix='bt601
         lr = out if out is not None else torch.empty((T, 3, hl, wl), dtype=torch.float32, device=dev)
         for j in range(T):
             fio.degrade(hr[j], degradation, lay, kernel_index=j if per_frame else 0, quantise=quantise, out=lr[j], matrix=matrix,
-                        yuv_range=yuv_range)
+                        yuv_range=yuv_range, siting=siting)
     return lr
 
 
@@ -1109,12 +1112,12 @@ def evaluate_degraded(opt, net, hr, degradation, *, hr_layout=None, quantise=Tru
     a = _frame_arguments(opt, net, stand_in, *[b[k] for k in list(inspect.signature(_frame_arguments).parameters)[3:]])
     video_windows(a.T, a.n, a.padding, a.cuts)              # (the padding mode and the window length, which the paths check later)
     lr = degrade_frames(hr, degradation, layout=lay, quantise=quantise, matrix=kw.get('matrix', 'bt601'),
-                        yuv_range=kw.get('yuv_range', 'limited'))
+                        yuv_range=kw.get('yuv_range', 'limited'), siting=kw.get('siting', 'left'))
     return evaluate_frames(opt, net, lr, gt, gt_layout=lay, **kw)
 
 
 def evaluate_bicubic(opt, net, frames, gt, *, layout=None, out=None, matrix='bt601', yuv_range='limited', cuts=None,
-                     cut_threshold=10.0, gt_layout=None, score='rgb', crop_border=0, scores=None, peak=None):
+                     cut_threshold=10.0, gt_layout=None, score='rgb', crop_border=0, scores=None, peak=None, siting='left'):
     """The "Bicubic" row of an SR table for one video: frame i is frames.imresize(frames[i], opt['scale'], layout) -- MATLAB's
     imresize(lr, s) on the device -- in place of the network's output, then converted to `out` and scored against gt[i] exactly
     as evaluate_frames does it, so that the two summaries compare row for row: (score_summary(scores, nframes, cuts, peak),
@@ -1133,7 +1136,7 @@ def evaluate_bicubic(opt, net, frames, gt, *, layout=None, out=None, matrix='bt6
     if out not in (None, 'float', 'hwc_rgb', 'hwc_bgr') + fio.RGB_LAYOUTS and not fio.is_yuv(out):
         raise ValueError("%s: out=%r (None, 'float', 'hwc_rgb', 'hwc_bgr' or one of %s)" % (
             who, out, ', '.join(fio.RGB_LAYOUTS + fio.ALL_YUV_LAYOUTS)))
-    fio.check_yuv_names(matrix, yuv_range)
+    fio.check_yuv_names(matrix, yuv_range, siting)
     out_fmt = out if out is not None else ('float' if lay == 'chw' else lay)
     if fio.is_yuv(out_fmt) and fio.packed_needs(out_fmt, s * h, s * w):
         raise ValueError("%s: a packed %s output of %d x %d needs %s" % (who, out_fmt, s * h, s * w,
@@ -1150,8 +1153,9 @@ def evaluate_bicubic(opt, net, frames, gt, *, layout=None, out=None, matrix='bt6
         if scores is None:
             scores = torch.zeros((T, 2), dtype=torch.float64, device=dev)
         for i in range(T):
-            sr = fio.imresize(frames[i], (s, 1), lay, matrix=matrix, yuv_range=yuv_range)[None]
-            _finish_frame(who, sr, (s * h, s * w, s * h, s * w), out_fmt, None, 1, matrix, yuv_range, i, score_into, scores)
+            sr = fio.imresize(frames[i], (s, 1), lay, matrix=matrix, yuv_range=yuv_range, siting=siting)[None]
+            _finish_frame(who, sr, (s * h, s * w, s * h, s * w), out_fmt, None, 1, matrix, yuv_range, i, score_into, scores,
+                          siting=siting)
     if peak is None:
         peak = _peak(out_fmt, gt_layout)
     return score_summary(scores, n, cuts, peak), scores

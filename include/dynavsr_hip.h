@@ -462,15 +462,41 @@ int dvsr_frame_luma_sad(const void* a, const void* b, const dvsr_frame_desc* des
  * vertical step; emit takes the taps [1,2,1]/4 on columns 2k-1 .. 2k+1 of row y, clamped to the crop, and no vertical mean.
  * 4:4:4: a pixel's chroma is its own sample both ways.  A row stride must hold Wc samples (planar) or 2 Wc (semi-planar).
  * Not provided: semi-planar 4:4:4 (nv24 / p410: refused as an unknown format), packed 4:2:2 (YUY2 / UYVY / v210), 4:1:1 /
- * 4:4:0, a BT.2020 matrix, depth 16 (YCbCr), chroma siting other than "left".  (Planar GBR: the RGB section above.) */
+ * 4:4:0, depth 16 (YCbCr).  (Planar GBR: the RGB section above.)
+ *
+ * Chroma siting and BT.2020.  The chroma field of `format` names a pair of sub-sampling and siting:
+ *   DVSR_YUV_CHROMA_420 (0), _422 (1)   "left": MPEG-2 / H.264 / y4m 420mpeg2, as always
+ *   DVSR_YUV_CHROMA_420_CENTER (4), DVSR_YUV_CHROMA_422_CENTER (6)   JPEG / MPEG-1 / MJPEG, ffmpeg's yuvj420p, y4m 420jpeg
+ *   DVSR_YUV_CHROMA_420_TOPLEFT (5)     HEVC / AV1 UHD and HDR10, chroma_sample_location=topleft (BT.2100)
+ * Value 3, values above 6 and any bit above bit 7 are refused as an unknown format; plane sizes, forms and everything else are
+ * those of the sub-sampling.  Chroma sample (j, k) sits at luma position (4:2:2: y is the luma row itself)
+ *             x          y
+ *   left      2k         2j + 1/2
+ *   center    2k + 1/2   2j + 1/2
+ *   topleft   2k         2j
+ * ingest: linear interpolation at the luma pixel's position, indices clamped to the plane, k = x >> 1, j = y >> 1.  Horizontal
+ *   step H(j, x): co-sited (left, topleft) as above; center: 0.75 C[j][k] + 0.25 C[j][max(k-1, 0)] (x even) |
+ *   0.75 C[j][k] + 0.25 C[j][min(k+1, Wc-1)] (x odd).  Vertical step (4:2:0): midway (left, center) as above; co-sited
+ *   (topleft): H(j, x) (y even) | (H(j, x) + H(min(j+1, Hc-1), x)) / 2 (y odd).
+ * emit: filters centred on the chroma sample's position, indices clamped to the crop.  Horizontal: co-sited [1,2,1]/4 on
+ *   2k-1, 2k, 2k+1 as above; center: the mean of columns 2k and min(2k+1, w-1).  Vertical (4:2:0): midway the mean of rows 2j
+ *   and min(2j+1, h-1) as above; co-sited: [1,2,1]/4 on rows max(2j-1, 0), 2j, min(2j+1, h-1).  Luma does not depend on siting.
+ * DVSR_YUV_BT2020NC (9, H.273's MatrixCoefficients code; 2 .. 8 stay refused): BT.2020 non-constant luminance, Kr = 0.2627,
+ * Kb = 0.0593, with the ranges and level scales of the other two.  Not provided: constant-luminance BT.2020, ICtCp, transfer
+ * functions (PQ / HLG: the network sees the transfer-coded R'G'B' as it does for SDR), a siting per direction, bottom and
+ * interlaced sitings, 420paldv. */
 #define DVSR_YUV_NV12 0      /* plane[0] = Y [h][w], plane[1] = CbCr interleaved [Hc][Wc][2]; plane[2] ignored */
 #define DVSR_YUV_I420 1      /* plane[0] = Y, plane[1] = Cb [Hc][Wc], plane[2] = Cr [Hc][Wc] */
 #define DVSR_YUV_CHROMA_420 0
 #define DVSR_YUV_CHROMA_422 1
 #define DVSR_YUV_CHROMA_444 2
+#define DVSR_YUV_CHROMA_420_CENTER 4
+#define DVSR_YUV_CHROMA_420_TOPLEFT 5
+#define DVSR_YUV_CHROMA_422_CENTER 6
 #define DVSR_YUV_FORMAT(form, chroma) ((form) | ((chroma) << 4))   /* e.g. nv16 = DVSR_YUV_FORMAT(DVSR_YUV_NV12, DVSR_YUV_CHROMA_422) */
 #define DVSR_YUV_BT601 0
 #define DVSR_YUV_BT709 1
+#define DVSR_YUV_BT2020NC 9  /* Kr = 0.2627, Kb = 0.0593 */
 #define DVSR_YUV_LIMITED 0
 #define DVSR_YUV_FULL 1
 typedef struct dvsr_yuv_desc {
@@ -501,13 +527,14 @@ int dvsr_edvr_stream_extract_frame_yuv(const dvsr_edvr_stream* stream_plan, cons
  * between, no temporary and no device copy on the way into the frame cache.
  * Bad arguments (null descriptor / plane, unknown format / depth / matrix / range / pad mode, h or w < 1 or beyond the target, a
  * row stride shorter than a row or odd, an odd plane address, a reflect pad not smaller than the dimension, a misaligned fp32
- * side) return DVSR_ERR_INVALID before any launch.  depth 16, a BT.2020 matrix and transfer functions are not provided. */
+ * side) return DVSR_ERR_INVALID before any launch.  The sitings and DVSR_YUV_BT2020NC of the section above apply as they are.
+ * depth 16 and transfer functions are not provided. */
 #define DVSR_YUV16_SEMI_MSB 0     /* plane[0] = Y [h][w], plane[1] = CbCr interleaved [Hc][Wc][2]; plane[2] ignored */
 #define DVSR_YUV16_PLANAR_LSB 1   /* plane[0] = Y, plane[1] = Cb [Hc][Wc], plane[2] = Cr [Hc][Wc] */
 typedef struct dvsr_yuv16_desc {
   int format, depth;         /* DVSR_YUV16_*, or DVSR_YUV_FORMAT(one of them, DVSR_YUV_CHROMA_*); depth 10 or 12 */
   int h, w;                  /* the frame's own (luma) size */
-  int matrix, range;         /* DVSR_YUV_BT601 / _BT709, DVSR_YUV_LIMITED / _FULL */
+  int matrix, range;         /* DVSR_YUV_BT601 / _BT709 / _BT2020NC, DVSR_YUV_LIMITED / _FULL */
   void* plane[3];
   long long row_stride[3];   /* bytes, even */
 } dvsr_yuv16_desc;

@@ -45,10 +45,20 @@
    c. frames/s of a pinned hwc_rgb16 video of `--rgb-frames` frames -> hwc_rgb16 frames on the host against the same video as
       hwc_rgb; recorded as measured.
 
+7. chroma siting and BT.2020 NCL (the SITE axis of csrc/frame_yuv.hip), by the method of 3 with `--rgb-repeats`
+   repetitions; the expectations are printed ahead of the figures:
+   a. with `--parent-lib PATH`: the left-sited ingest (180x320) and emit (720x1280) kernels of nv12, i420, p010, nv16 and i444 of
+      this build and of that library, alternated in this process.
+   b. every new ingest instantiation against the left kernel of the same layout in this build.
+   c. every new emit instantiation against the left kernel of the same layout; topleft reads 1.5 x the fp32 rows: recorded.
+   d. frames/s of a pinned p010 video of `--rgb-frames` frames -> p010 frames on the host with siting='topleft',
+      matrix='bt2020nc' against the same call with the defaults.
+
 usage (GPU box): python tools/frame_io_bench.py [--h 180 --w 320 --frames 100 --repeats 5 --calls 200 --yuv-repeats 10]
                  [--parent-lib PATH] > profiles/r16_chroma_io.txt   (profiles/r12_yuv16_io.txt: parts 1 to 4;
                  profiles/r10_yuv_io.txt: 1 to 3; profiles/r08_frame_io.txt: 1 and 2)
-                 python tools/frame_io_bench.py --parts rgb --parent-lib PATH > profiles/r22_rgb_io.txt   (part 6 alone)"""
+                 python tools/frame_io_bench.py --parts rgb --parent-lib PATH > profiles/r22_rgb_io.txt   (part 6 alone)
+                 python tools/frame_io_bench.py --parts siting --parent-lib PATH > profiles/r23_yuv_siting.txt   (part 7 alone)"""
 import argparse
 import ctypes
 import os
@@ -74,7 +84,7 @@ ap.add_argument("--calls", type=int, default=200)
 ap.add_argument("--in-flight", type=int, default=2)
 ap.add_argument("--yuv-repeats", type=int, default=10)
 ap.add_argument("--parent-lib", default=None, help="parts 5a and 6a: a libdynavsr_hip.so built from the parent commit")
-ap.add_argument("--parts", choices=("all", "rgb"), default="all", help="rgb: part 6 alone")
+ap.add_argument("--parts", choices=("all", "rgb", "siting"), default="all", help="rgb: part 6 alone; siting: part 7 alone")
 ap.add_argument("--rgb-repeats", type=int, default=11)
 ap.add_argument("--rgb-frames", type=int, default=60)
 args = ap.parse_args()
@@ -130,9 +140,9 @@ def c_launch(fn, *a):
     return go
 
 
-def compare(title, entries, reps, per_byte=False):
+def compare(title, entries, reps, per_byte=False, recorded=()):
     """entries: [(name, launch, algorithmic bytes)], the first one the yardstick; alternated `reps` times.  per_byte: the
-    verdict is on us per MB moved, not on us per launch."""
+    verdict is on us per MB moved, not on us per launch.  recorded: names whose ratio to the yardstick is printed, not judged."""
     timers = [(name, graph_us(launch, args.calls), nbytes) for name, launch, nbytes in entries]
     us = {name: [] for name, _, _ in timers}
     for _ in range(reps):
@@ -146,6 +156,8 @@ def compare(title, entries, reps, per_byte=False):
         m, sp = statistics.median(us[name]), max(us[name]) - min(us[name])
         if name == base:
             verdict = "yardstick"
+        elif name in recorded:
+            verdict = "%.3f x %s, recorded" % (m / mb, base)
         elif per_byte:
             verdict = "%.3f us/MB against %.3f + spread %.3f of %s: %s" % (
                 1e6 * m / nbytes, 1e6 * mb / nb, 1e6 * sb / nb, base, "MET" if m / nbytes <= (mb + sb) / nb else "MISSED")
@@ -269,8 +281,106 @@ def part_rgb():
         m16 - m8, 100 * (m16 - m8) / m8))
 
 
+# ---- 7. chroma siting and BT.2020 NCL (the SITE axis of csrc/frame_yuv.hip; --parts siting runs this part alone)
+def part_siting():
+    reps, calls = args.rgb_repeats, args.calls
+    print("7. chroma siting and BT.2020 NCL (the SITE axis of csrc/frame_yuv.hip, DESIGN 3.2x); %d launches per replay, %d repetitions "
+          "alternated" % (calls, reps))
+    print("Expectations, written before the run:")
+    print("  1. the existing left kernels are not slower than the parent's beyond the parent's own spread: ingest 180x320 and emit "
+          "720x1280 for nv12, i420, p010, nv16 and i444.  A miss means the new axis leaked into the old instantiations, by "
+          "registers or occupancy.")
+    print("  2. each new ingest instantiation is not slower than the left kernel of the same layout and build beyond that kernel's "
+          "spread: center reads one more chroma sample per row, topleft one chroma row fewer.")
+    print("  3. center emit is not slower than left emit (no left-neighbour loads); topleft emit reads 1.5 x the fp32 rows, and its "
+          "ratio to left is recorded, not bounded.")
+    print("  Also recorded: frames/s of a pinned p010 180x320 video -> p010 720x1280 frames on the host with siting='topleft', "
+          "matrix='bt2020nc' against the same call with the defaults.")
+    rs = np.random.RandomState(7)
+    keep = []
+    fin, fout = torch.empty((3, 180, 320), device='cuda'), torch.rand((3, 720, 1280), device='cuda')
+
+    def yuv_launch(lb, lay, siting, ingest):
+        """(one launch of `lay`'s ingest 180x320 or emit 720x1280 with `siting` through library `lb`, its algorithmic bytes)"""
+        h, w = (180, 320) if ingest else (720, 1280)
+        depth = frames.layout_depth(lay)
+        msb = 16 - depth if lay.startswith('p') else 0
+        buf = torch.from_numpy((rs.randint(0, 2 ** depth, (frames.packed_rows(lay, h), w)) << msb).astype(
+            np.uint8 if depth == 8 else np.uint16)).cuda()
+        planes, d = frames.describe_yuv(frames.yuv_planes(buf, lay)[0], lay, h, w, copy=ingest, siting=siting)
+        keep.append((buf, planes, d))
+        suffix = "yuv16" if depth > 8 else "yuv"
+        nbytes = buf.numel() * buf.element_size() + 12 * h * w
+        if ingest:
+            return c_launch(getattr(lb, "dvsr_frame_ingest_" + suffix), ctypes.byref(d), fin.data_ptr(), h, w, L.FRAME_PAD_REFLECT), nbytes
+        return c_launch(getattr(lb, "dvsr_frame_emit_" + suffix), fout.data_ptr(), h, w, ctypes.byref(d), ctypes.c_float(0.0),
+                        ctypes.c_float(1.0)), nbytes
+
+    def title(ingest, lay):
+        return "%s %s %s" % ("ingest" if ingest else "emit", lay, "180x320" if ingest else "720x1280")
+
+    if args.parent_lib:
+        parent = ctypes.CDLL(args.parent_lib)
+        for name in ("dvsr_frame_ingest_yuv", "dvsr_frame_emit_yuv", "dvsr_frame_ingest_yuv16", "dvsr_frame_emit_yuv16"):
+            getattr(parent, name).argtypes, getattr(parent, name).restype = getattr(lib, name).argtypes, getattr(lib, name).restype
+        print("7a. the left kernels of this build against those of %s" % os.path.basename(args.parent_lib))
+        for lay in ('nv12', 'i420', 'p010', 'nv16', 'i444'):
+            for ingest in (True, False):
+                compare(title(ingest, lay), [("%s %s" % (who, title(ingest, lay)),) + yuv_launch(lb, lay, 'left', ingest)
+                                             for who, lb in (("parent", parent), ("this build", lib))], reps)
+    else:
+        print("7a. NOT measured: no --parent-lib")
+    sited = [(lay, ('left', 'center', 'topleft')) for lay in ('nv12', 'i420', 'p010', 'i420p10')] + \
+            [(lay, ('left', 'center')) for lay in ('nv16', 'i422', 'p210', 'i422p10')]
+    for ingest, part in ((True, "7b. every new ingest instantiation against the left kernel of its layout in this build"),
+                         (False, "7c. every new emit instantiation against the left kernel of its layout in this build")):
+        print(part)
+        for lay, sitings in sited:
+            compare(title(ingest, lay), [("%s %s" % (title(ingest, lay), s),) + yuv_launch(lib, lay, s, ingest) for s in sitings], reps,
+                    recorded=() if ingest else ("%s topleft" % title(ingest, lay),))
+    del keep[:]
+    # 7d. end to end
+    n, hh, ww = args.rgb_frames, 180, 320
+    edvr = EDVR()
+    edvr.load_state_dict(synth.edvr_state_dict(0))
+    edvr = edvr.cuda()
+    video = torch.from_numpy((rs.randint(0, 1024, (n, hh * 3 // 2, ww)) << 6).astype(np.uint16)).pin_memory()
+    out = torch.empty((n, 4 * hh * 3 // 2, 4 * ww), dtype=torch.uint16).pin_memory()
+
+    def path(**kw):
+        def go():
+            for i, sr in enumerate(adapt.super_resolve_frames(OPT, edvr, video, in_flight=args.in_flight, layout='p010', **kw)):
+                out[i].copy_(sr, non_blocking=True)
+            torch.cuda.synchronize()
+        return go
+
+    def fps(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        return n / (time.perf_counter() - t0)
+    new, old = path(siting='topleft', matrix='bt2020nc'), path()
+    new()
+    old()
+    fn, fo = [], []
+    for _ in range(reps):
+        fn.append(fps(new))
+        fo.append(fps(old))
+    mn, mo = statistics.median(fn), statistics.median(fo)
+    print("7d. p010 video %d frames %dx%d pinned host -> p010 %dx%d host, in_flight %d, %d repetitions alternated" % (
+        n, hh, ww, 4 * hh, 4 * ww, args.in_flight, reps))
+    print("  siting='topleft', matrix='bt2020nc'  median %7.1f frames/s  spread %5.1f  (%s)" % (
+        mn, max(fn) - min(fn), " ".join("%.1f" % v for v in fn)))
+    print("  the defaults (left, bt601)           median %7.1f frames/s  spread %5.1f  (%s)" % (
+        mo, max(fo) - min(fo), " ".join("%.1f" % v for v in fo)))
+    print("  topleft bt2020nc - defaults = %+.1f frames/s (%+.1f %%), as measured" % (mn - mo, 100 * (mn - mo) / mo))
+
+
 if args.parts == 'rgb':
     part_rgb()
+    sys.exit(0)
+if args.parts == 'siting':
+    part_siting()
     sys.exit(0)
 
 r = np.random.RandomState(0)
