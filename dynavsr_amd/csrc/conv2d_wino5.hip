@@ -38,9 +38,15 @@
 // image and the LDS-DMA fetches raw(k + 2) into the raw buffer raw(k) has left; ONE barrier per chunk.
 //
 // Epilogue.  Y = A^T M A.  The six nu of a row are in one wave: the column transform (6 -> 4 values) is done in registers,
-// then per cout half one exchange round through the LDS ([xi][j][register quad][lane] x 16 B = 96 KB), eight reader waves
-// (tile, 2 couts) apply the row transform, bias, activation, residual and store 16-byte output rows (PixelShuffle(2): 32);
-// a ragged last tile row stores only its rows inside the image.
+// then two exchange rounds through the LDS (wino5_exchange.h).  A 16-byte record holds the four j of ONE cout; a unit
+// (cout half, register quad) = [xi 6][register 4][lane 64] records = 24 KB; round t carries the quads 2 t and 2 t + 1 of BOTH
+// cout halves (96 KB), so all twelve consumer waves store in both rounds (eight records each: the VGPR-to-LDS path wants stores
+// from many waves on both SIMD halves).  Sixteen reader waves (tile, one cout; PixelShuffle(2): eight, a cout pair) fetch
+// six conflict-free records per cout, apply the row transform on whole records -- its result IS the 16-byte output row --, bias,
+// activation, residual and store (PixelShuffle(2): 32-byte rows); a ragged last tile row stores only its rows inside the
+// image.  Up to round 6 a round was one cout half, a record four couts of one j, and a reader picked 4 or 8 bytes out of each
+// of 24 records (4- and 2-way bank conflicts); same values, same arithmetic per output, same bits:
+// profiles/r24_wino5_epilogue.txt.
 //
 // Who runs it.  Launches that pass ALLOW_WINO_F4 to conv2_choose: the engine's NO-GRAD forward slot (engine.hip: Op::fwd[1]; a
 // training tape keeps F(2x2)) and the op-level packed entries (dvsr_conv2d_forward_packed / _dgrad_packed), which pass it for
@@ -50,6 +56,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "small_grid.h"
+#include "wino5_exchange.h"
 
 namespace dvsr {
 
@@ -149,10 +156,9 @@ int pack_weights_wino5_run(const PackTable& t, hipStream_t st) {
   return check_launch("pack_weights_wino5_kernel");
 }
 
-// RES: the epilogue adds a residual tensor (a.res != nullptr; plain stores only).  R16 (instantiated with RES): all sixteen
-// waves read the exchange image, one cout each; otherwise eight consumer waves read a cout PAIR each -- what PixelShuffle(2)
-// needs for 16-byte rows of the shuffled image, and what measures faster without a residual -- and the producers leave after
-// the loop.
+// RES: the epilogue adds a residual tensor (a.res != nullptr; plain stores only).  R16 (every launch without a PixelShuffle):
+// all sixteen waves read the exchange image, one cout each; otherwise eight consumer waves read a cout PAIR each -- what
+// PixelShuffle(2) needs for 16-byte rows of the shuffled image -- and the producers only attend the epilogue's barriers.
 // PRE (with R16, without RES): the epilogue adds a.pre[n / a.pre_bdiv][cout][oy][ox] BEFORE the activation -- the half of a
 // two-input convolution whose input pre_bdiv batch items share, convolved once by a launch of its own (engine.hip: Op::hoist).
 // Its 16-byte rows are fetched like the residual's -- the four rows of a cout together, ahead of the stores, none past a cut last
@@ -195,22 +201,22 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
   if (a.trace && threadIdx.x == 0) a.trace[(size_t)blockIdx.x * 64 + 60] = __builtin_amdgcn_s_memrealtime();
 #endif
 
-  // R16 epilogue, one round: every wave reads the exchange image [xi 6][j 4][rq 4][lane 64] x 16 B -- lane' = the writer's lane
-  // (tile, hi), register quad rq' = wave & 3, cout wave >> 2 of the quad --, applies the row transform, bias, activation and
-  // residual and stores four 16-byte output rows.  (Eight readers with a cout pair each took 3.1-3.7 k cycles per round,
-  // sixteen take 1.8 k.)
-  auto read16 = [&](int m) __attribute__((always_inline)) {
+  // R16 epilogue, round t: every wave reads one cout of one unit of the exchange image (wino5_exchange.h) -- lane' = the
+  // writer's lane (tile, hi), cout half wave >> 3, register quad 2 t + ((wave >> 2) & 1), register wave & 3 of the quad: six
+  // 16-byte records {Z_0 .. Z_3}, one per xi --, applies the row transform, bias, activation and residual and stores four
+  // 16-byte output rows.
+  auto read16 = [&](int t) __attribute__((always_inline)) {
     int le = lane;
     asm volatile("" : "+v"(le));   // (nothing of this addressing may be hoisted above the chunk loop)
-    const int rq_r = wave & 3, cp_r = wave >> 2;
-    const float* const xr = smem + (rq_r * 64 + le) * 4 + cp_r;
+    const int m_r = w5x::r16_mh(wave), rq_r = w5x::r16_rq(wave, t), c_r = w5x::r16_c(wave);
+    const float* const xr = smem + w5x::rec(m_r, rq_r, 0, c_r, le);
     const int lo_e = le & 31, hi_e = le >> 5;
     const int trow_e = lo_e / TC, tcol_e = lo_e - trow_e * TC;
     const int oy = oy0 + 4 * trow_e, ox = ox0 + 4 * tcol_e;
     const size_t HWo = (size_t)a.Ho * a.Wo;
     const float slope = a.act == ACT_LRELU ? 0.1f : (a.act == ACT_RELU ? 0.f : 1.f);
     const float* bias = wset_ptr(a.bias, a.b_gs, n, a.wdiv);
-    const int co0 = cbi * 64 + m * 32 + 8 * rq_r + 4 * hi_e + cp_r;   // this thread's cout
+    const int co0 = cbi * 64 + w5x::cout_of(m_r, rq_r, hi_e, c_r);   // this thread's cout
     f32x4 pr[4];
     if constexpr (PRE) {
       // the addend's four rows go out FIRST: the exchange reads and the row transform below cover their latency.  Nothing is
@@ -221,18 +227,18 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
       for (int i = 0; i < 4; ++i)
         pr[i] = (live && oy + i < a.Ho) ? *reinterpret_cast<const f32x4*>(pre + (size_t)i * a.Wo) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    float y[4][4];
+    f32x4 z[6];   // (components: j)
+#pragma unroll
+    for (int x = 0; x < 6; ++x) z[x] = *reinterpret_cast<const f32x4*>(xr + x * (w5x::NC * w5x::NLANE * w5x::REC_F));
+    float y[4][4];   // y[i]: output row i
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float z[6];
-#pragma unroll
-      for (int x = 0; x < 6; ++x) z[x] = xr[(x * 16 + j * 4) * 256];
-      const float sa = z[1] + z[2], da = z[1] - z[2];
-      const float sb = z[3] + z[4], db = z[3] - z[4];
-      y[0][j] = z[0] + sa + sb;
+      const float sa = z[1][j] + z[2][j], da = z[1][j] - z[2][j];
+      const float sb = z[3][j] + z[4][j], db = z[3][j] - z[4][j];
+      y[0][j] = z[0][j] + sa + sb;
       y[1][j] = __builtin_fmaf(2.f, db, da);
       y[2][j] = __builtin_fmaf(4.f, sb, sa);
-      y[3][j] = __builtin_fmaf(8.f, db, da) + z[5];
+      y[3][j] = __builtin_fmaf(8.f, db, da) + z[5][j];
     }
     const bool px_ok = oy < a.Ho && ox < a.Wo;   // (Wo is a multiple of 4: whole tile columns; the last tile row may be cut)
     const int nrow = a.Ho - oy < 4 ? a.Ho - oy : 4;
@@ -521,8 +527,8 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
 
   // ---- epilogue.  A^T = [[1,1,1,1,1,0],[0,1,-1,2,-2,0],[0,1,1,4,4,0],[0,1,-1,8,-8,1]].  Column transform in registers:
   // Z_j = sum_nu M[nu] A^T[j][nu]
-  int lane_e = lane;
-  asm volatile("" : "+v"(lane_e));   // (nothing of the epilogue's addressing may be hoisted above the chunk loop)
+  // (register quad by register quad: the exchange stores {Z[0][r] .. Z[3][r]} from four consecutive registers, and a quad's
+  // sixteen results fit where its 24 accumulators were -- let the scheduler mix the quads and the allocator spills)
   f32x16 Z[4];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -532,12 +538,23 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
     Z[1][r] = __builtin_fmaf(2.f, db, da);
     Z[2][r] = __builtin_fmaf(4.f, sb, sa);
     Z[3][r] = __builtin_fmaf(8.f, db, da) + acc[5][r];
+    if ((r & 3) == 3 && r < 15) {
+      // (the quad's four records exist here, and the next quad's sums and differences -- all of them start from the points 1
+      // and 3 -- only after it)
+      auto rec = [&](int q) __attribute__((always_inline)) { return f32x4{Z[0][q], Z[1][q], Z[2][q], Z[3][q]}; };
+      asm volatile("" : "+v"(acc[1][r + 1]), "+v"(acc[1][r + 2]), "+v"(acc[1][r + 3]), "+v"(acc[1][r + 4]),
+                        "+v"(acc[3][r + 1]), "+v"(acc[3][r + 2]), "+v"(acc[3][r + 3]), "+v"(acc[3][r + 4])
+                   : "v"(rec(r - 3)), "v"(rec(r - 2)), "v"(rec(r - 1)), "v"(rec(r)));
+    }
   }
-  // exchange image: [xi 6][j 4][rq 4][lane 64] x 16 B; reader (waves 0-7): lane' = writer lane (tile, hi), rq' = wave & 3,
-  // cout pair cp = wave >> 2 of the register quad
-  float* const xw = smem + (cxi * 16 * 64 + lane_e) * 4;
-  const int rq_r = wave & 3, cp_r = wave >> 2;
-  const float* const xr = smem + (rq_r * 64 + lane_e) * 4 + cp_r * 2;
+  int lane_e = lane;
+  asm volatile("" : "+v"(lane_e));   // (nothing of the epilogue's addressing may be hoisted above the chunk loop or the transform)
+  // exchange image (wino5_exchange.h): round t holds the units (mh, 2 t), (mh, 2 t + 1) of both cout halves, a record the four
+  // j of one cout.  Every consumer wave writes its eight records of the round; reader (waves 0-7): lane' = writer lane
+  // (tile, hi), cout half wave >> 2, register quad 2 t + ((wave >> 1) & 1), the cout pair 2 (wave & 1), + 1 of the quad
+  static_assert(Sh::XCH == w5x::IMG_F, "the exchange image is one round's four units");
+  float* const xw = smem + w5x::rec(cmh, 0, cxi, 0, lane_e);
+  const int m_r = w5x::r8_mh(wave), c_r = w5x::r8_c(wave);
   const int lo_e = lane_e & 31, hi_e = lane_e >> 5;
   const int trow_e = lo_e / TC, tcol_e = lo_e - trow_e * TC;
   const int oy = oy0 + 4 * trow_e, ox = ox0 + 4 * tcol_e;
@@ -547,35 +564,44 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
   W5_STAMP(50);
   lds_barrier();   // every wave is past its last V read
   W5_STAMP(51);
+  // the eight records of round T: register quads 2 T and 2 T + 1 (Z keeps its compile-time indices)
+  auto xwrite = [&](auto t_) __attribute__((always_inline)) {
+    constexpr int T = decltype(t_)::value;
+#pragma unroll
+    for (int rqb = 0; rqb < 2; ++rqb)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int r = 4 * (2 * T + rqb) + c;
+        *reinterpret_cast<f32x4*>(xw + rqb * w5x::UNIT_F + c * (w5x::NLANE * w5x::REC_F)) = f32x4{Z[0][r], Z[1][r], Z[2][r], Z[3][r]};
+      }
+  };
+  // (one copy of the reader for both rounds; round 1's writes sit behind round 0's reads inside the loop, so that neither
+  // xwrite turns into 32 selects between the two rounds' registers)
+  xwrite(std::integral_constant<int, 0>{});
 #pragma unroll 1
-  for (int m = 0; m < 2; ++m) {
-    if (cmh == m) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int rq = 0; rq < 4; ++rq)
-          *reinterpret_cast<f32x4*>(xw + (j * 4 + rq) * 256) = f32x4{Z[j][4 * rq], Z[j][4 * rq + 1], Z[j][4 * rq + 2], Z[j][4 * rq + 3]};
-    }
+  for (int m = 0; m < 2; ++m) {   // m: the round
     W5_STAMP(52 + 4 * m);
     lds_barrier();
     W5_STAMP(53 + 4 * m);
     if constexpr (R16) read16(m);
     else if (wave < 8) {
-      const int co0 = cbi * 64 + m * 32 + 8 * rq_r + 4 * hi_e + 2 * cp_r;   // this thread's two couts: co0, co0 + 1
+      const int rq_r = w5x::r8_rq(wave, m);
+      const float* const xr = smem + w5x::rec(m_r, rq_r, 0, c_r, lane_e);
+      const int co0 = cbi * 64 + w5x::cout_of(m_r, rq_r, hi_e, c_r);   // this thread's two couts: co0, co0 + 1
       float y[2][4][4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        w5f2 z[6];
+      for (int c = 0; c < 2; ++c) {
+        f32x4 z[6];   // (components: j)
 #pragma unroll
-        for (int x = 0; x < 6; ++x) z[x] = *reinterpret_cast<const w5f2*>(xr + (x * 16 + j * 4) * 256);
+        for (int x = 0; x < 6; ++x) z[x] = *reinterpret_cast<const f32x4*>(xr + (x * w5x::NC + c) * (w5x::NLANE * w5x::REC_F));
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const float sa = z[1][c] + z[2][c], da = z[1][c] - z[2][c];
-          const float sb = z[3][c] + z[4][c], db = z[3][c] - z[4][c];
-          y[c][0][j] = z[0][c] + sa + sb;
+        for (int j = 0; j < 4; ++j) {
+          const float sa = z[1][j] + z[2][j], da = z[1][j] - z[2][j];
+          const float sb = z[3][j] + z[4][j], db = z[3][j] - z[4][j];
+          y[c][0][j] = z[0][j] + sa + sb;
           y[c][1][j] = __builtin_fmaf(2.f, db, da);
           y[c][2][j] = __builtin_fmaf(4.f, sb, sa);
-          y[c][3][j] = __builtin_fmaf(8.f, db, da) + z[5][c];
+          y[c][3][j] = __builtin_fmaf(8.f, db, da) + z[5][j];
         }
       }
       const bool px_ok = oy < a.Ho && ox < a.Wo;   // (Wo is a multiple of 4: whole tile columns; the last tile row may be cut)
@@ -622,7 +648,7 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
             }
           }
         } else {
-          // PixelShuffle(2): couts 4 q + 2 dy + dx; this thread holds dy = cp_r, dx = 0, 1 of channel q = co0 >> 2
+          // PixelShuffle(2): couts 4 q + 2 dy + dx; this thread holds dy = wave & 1, dx = 0, 1 of channel q = co0 >> 2
           const int cq = co0 >> 2, dy = (co0 >> 1) & 1;
           float* dst = a.y + (((size_t)n * (a.Cout >> 2) + cq) * (2 * a.Ho) + (2 * oy + dy)) * (size_t)(2 * a.Wo) + 2 * ox;
 #pragma unroll
@@ -638,6 +664,7 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
     W5_STAMP(54 + 4 * m);
     if (m == 0) lds_barrier();   // the reads of the first round are done
     W5_STAMP(55 + 4 * m);
+    if (m == 0) xwrite(std::integral_constant<int, 1>{});
   }
 #ifdef DVSR_CONV_TRACE
   W5_STAMP(41);
@@ -655,15 +682,20 @@ __global__ __launch_bounds__(1024) void conv2d_wino5_kernel(ConvK2 a) {
 template <int TC>
 static int launch_wino5(ConvK2 k, hipStream_t st) {
   using Sh = Wino5Shape<TC>;
-  // Sixteen readers only where the epilogue also fetches a residual (fe_rb_b 96-99 -> 91-92 us on one box); without one the
-  // eight pair readers measure 2-3 % FASTER per launch (L1_om 238 against 243 us, HRconv 222-226 against 229-233), and a
-  // PixelShuffle(2) launch (never with a residual: conv2_prepare) needs the pairs for its 16-byte rows.
+  // Sixteen readers (one cout each) everywhere but in a PixelShuffle(2) launch (never with a residual: conv2_prepare), which
+  // needs the cout PAIRS of the eight-reader form for the 16-byte rows of the shuffled image.  With the round-6 exchange records
+  // (four couts of one j) the pair readers were 2-3 % faster per launch where no residual is fetched (L1_om 238 against 243 us);
+  // with records of one cout (six conflict-free 16-byte reads per cout) the sixteen are, in every alternating run of
+  // profiles/r24_wino5_epilogue.txt C: the five fe_rb_a 387.9 / 386.1 -> 383.3 / 381.9 us, L1_om 228.6 / 229.4 -> 226.0 / 226.7,
+  // cas_om 229.1 / 228.9 -> 226.8 / 226.3, HRconv 217.8 / 215.0 -> 211.7 / 213.3.
   // The addend (k.pre; never with a residual or a PixelShuffle: conv2d_packed_prepare) is one more fetch in the epilogue, as the
-  // residual is: sixteen readers.
+  // residual is; each form is an instantiation of its own, so none carries another's registers (see the pair reader).
   auto kern = k.pre ? conv2d_wino5_kernel<TC, false, true, true>
-                    : (k.res ? conv2d_wino5_kernel<TC, true, true, false> : conv2d_wino5_kernel<TC, false, false, false>);
-  static PerDeviceOnce attr_once, attr_once_r, attr_once_p;
+                    : (k.res ? conv2d_wino5_kernel<TC, true, true, false>
+                             : (k.ps ? conv2d_wino5_kernel<TC, false, false, false> : conv2d_wino5_kernel<TC, false, true, false>));
+  static PerDeviceOnce attr_once, attr_once_r, attr_once_p, attr_once_16;
   set_dyn_lds_once(attr_once, (const void*)conv2d_wino5_kernel<TC, false, false, false>, Sh::LDS_BYTES);
+  set_dyn_lds_once(attr_once_16, (const void*)conv2d_wino5_kernel<TC, false, true, false>, Sh::LDS_BYTES);
   set_dyn_lds_once(attr_once_r, (const void*)conv2d_wino5_kernel<TC, true, true, false>, Sh::LDS_BYTES);
   set_dyn_lds_once(attr_once_p, (const void*)conv2d_wino5_kernel<TC, false, true, true>, Sh::LDS_BYTES);
   k.tiles_x = ceil_div(k.Wo, Sh::OW); k.tiles_y = ceil_div(k.Ho, Sh::OH); k.ntiles = k.tiles_x * k.tiles_y * k.N;
